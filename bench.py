@@ -7,11 +7,15 @@ BASELINE config "10k-atom periodic water box, l_max=2, 64 features, 3 interactio
 15^3 H2O = 10 125 atoms, r_max 4.5 A, parity=False, radial MLP 128x1).  With N>1 every rank evaluates its own
 copy of the box (frames are independent; replicas, no data-path collective) and the value is the aggregate.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` (dominant hand-written
-kernel: algorithmic bytes / HIP-event duration on the launching stream) and `cpu_baseline` (the CPU oracle,
-``oracle/``, timed on a bounded sample of the same workload on this host).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (the result line:
+`metric`, `value`, `unit`, `ms_per_step`, ...).  `--dump-outputs DIR` writes what the timed path returned in its last
+step as DIR/<name>.npy (float32 / float64; inputs are seeded, so two builds can be compared output for output).
+`--full` adds everything else to the line: `roofline` (dominant hand-written kernel: algorithmic bytes / HIP-event
+duration on the launching stream, traffic from live rocprofv3 --pmc passes), the clocks, the exact-fp32 and MD-step
+variants, the other BASELINE workloads and `cpu_baseline` (the CPU oracle, ``oracle/``, timed on a bounded sample of
+the same workload on this host).
 """
 
 from __future__ import annotations
@@ -28,7 +32,7 @@ if ROOT not in sys.path:
 
 import torch  # noqa: E402
 
-HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA peak (MI355X_MICROARCH.md)
 MFMA_F32_PEAK_TFLOPS = 157.3  # dense fp32 MFMA peak (v_mfma_f32_32x32x2_f32), same guide
 # committed PMC summary (scripts/profile.sh): only used for `roofline.traffic` when the live measurement below is
@@ -114,6 +118,44 @@ def build_model(cfg, names, device, seed=0):
     return model.to(device).eval()
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as ``out_dir/<name>.npy``, float64 kept, every other dtype as float32.  Past
+    DUMP_MAX_BYTES in all, every array keeps a fixed sample of its rows (sorted, numpy default_rng(0)), the same in every run."""
+    import numpy as np
+
+    arrs = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        arrs[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrs.items():
+        if total > DUMP_MAX_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_MAX_BYTES / total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def host_cpus() -> int:
+    """CPUs this process may use: the affinity mask, capped by a cgroup CPU quota and by OMP_NUM_THREADS when set
+    (os.cpu_count() counts the whole host; a thread pool sized by it oversubscribes a container's share)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, int(quota) // int(period))
+    except Exception:
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
 def cpu_baseline(workload_name: str, max_seconds: float = 60.0, full_box: bool = True):
     """Time the CPU oracle (reference op order, PyTorch CPU ops) beside the GPU number, protocol of SURVEY.md 8(d).
 
@@ -141,7 +183,7 @@ def cpu_baseline(workload_name: str, max_seconds: float = 60.0, full_box: bool =
     model = build_model(cfg, names, torch.device("cpu"))
     weights = {k.replace("model.func.", ""): v.detach() for k, v in model.state_dict().items()}
     specs = omodel.build_specs(cfg)
-    ncpu = os.cpu_count() or 1
+    ncpu = host_cpus()
     t_start = time.perf_counter()
 
     def one(d=data, c=cfg):
@@ -641,9 +683,14 @@ def train_bench(args, world, rank, device, distributed):
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # the loss of the last timed step and the parameters it left behind
+        dump_outputs(args.dump_outputs, {
+            "loss": loss.detach().reshape(1),
+            "parameters": torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]),
+        })
     roofline = step_roofline = None
     kernels = {}
-    if args.kernel_steps > 0 and (rank == 0 or distributed):
+    if args.full and args.kernel_steps > 0 and (rank == 0 or distributed):
         # (the instrumented steps contain the gradient all-reduce: with more than one rank EVERY rank has to run them,
         # only rank 0 records -- rank 0 alone would wait for its peers forever)
         if rank == 0:
@@ -704,7 +751,7 @@ def other_workloads(timeout_s: float = 420.0):
             continue
         env = dict(os.environ, NQA_BENCH_NO_CLOCKS="1", NQA_BENCH_NO_EXACT_FP32="1", NQA_BENCH_NO_MD_STEP="1", NQA_BENCH_NO_OTHER="1")
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", str(steps), "--warmup", str(warm),
-               "--no-cpu-baseline", "--no-pmc", "--no-other-workloads", "--kernel-steps", "2"]
+               "--full", "--no-cpu-baseline", "--no-pmc", "--no-other-workloads", "--kernel-steps", "2"]
         t0 = time.perf_counter()
         try:
             res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=left)
@@ -727,17 +774,25 @@ def other_workloads(timeout_s: float = 420.0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without a launcher bench.py starts them itself")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure (clocks, exact-fp32 and MD-step variants, "
+                         "per-kernel roofline with live PMC traffic, other workloads, CPU baseline); the --no-* / "
+                         "--kernel-steps options below trim a --full run")
     ap.add_argument("--workload", default="water10k", choices=sorted(WORKLOADS) + sorted(TRAIN_WORKLOADS))
     ap.add_argument("--no-graph", action="store_true", help="time eager launches instead of hipGraph replay")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes behind `roofline.traffic`")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # 1 warm-up + 2 eager steps, no output
-    ap.add_argument("--kernel-steps", type=int, default=3, help="eager steps instrumented with HIP events for `roofline`")
+    ap.add_argument("--kernel-steps", type=int, default=3, help="--full: eager steps instrumented with HIP events for `roofline`")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="default run only: skip the short child runs of the other BASELINE configs (`config.other_workloads`)")
+                    help="default workload only: skip the short child runs of the other BASELINE configs (`config.other_workloads`)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         raise SystemExit(relaunch_distributed(args.gpus))
@@ -828,20 +883,21 @@ def main():
             torch.cuda.synchronize()
             if not torch.allclose(g_f, f2, atol=1e-5, rtol=1e-5):
                 raise RuntimeError("graph replay disagrees with eager")
-            return g
+            return g, (g_e, g_f)
         except Exception as exc:  # pragma: no cover
             if rank == 0:
                 print(f"[bench] hipGraph capture unavailable ({type(exc).__name__}: {exc}); timing eager", file=sys.stderr)
             topology_cache.clear()
-            return None
+            return None, None
 
-    graph = capture() if use_graph else None
+    graph, graph_out = capture() if use_graph else (None, None)
 
     def step():
+        """One evaluation; returns (total_energy, forces) -- for a replay, the graph's output tensors."""
         if graph is not None:
             graph.replay()
-        else:
-            step_eager()
+            return graph_out
+        return step_eager()
 
     for _ in range(args.warmup):
         step()
@@ -852,7 +908,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -862,10 +918,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:  # (before anything below replays the graph again)
+        dump_outputs(args.dump_outputs, {"total_energy": last[0], "forces": last[1]})
 
     # ---- what the clocks were while the device ran this very step (rank 0; outside the timed region) ----
     gpu_state = None
-    if rank == 0 and os.environ.get("NQA_BENCH_NO_CLOCKS", "") in ("", "0"):
+    if args.full and rank == 0 and os.environ.get("NQA_BENCH_NO_CLOCKS", "") in ("", "0"):
         sampler = GpuClockSampler(dev_index).start()
         t1 = time.perf_counter()
         n_busy = 0
@@ -886,7 +944,7 @@ def main():
 
     # ---- the same step with every GEMM on the exact-fp32 MFMA pipe (the default splits fp32 operands into fp16 planes) ----
     exact_ms = None
-    if rank == 0 and world == 1 and os.environ.get("NQA_BENCH_NO_EXACT_FP32", "") in ("", "0"):
+    if args.full and rank == 0 and world == 1 and os.environ.get("NQA_BENCH_NO_EXACT_FP32", "") in ("", "0"):
         saved = {k: os.environ.get(k) for k in ("NQA_MLP_EXACT_FP32", "NQA_NODE_EXACT_FP32")}
         try:
             os.environ["NQA_MLP_EXACT_FP32"] = "1"
@@ -894,7 +952,7 @@ def main():
             for _ in range(3):
                 step_eager()
             torch.cuda.synchronize()
-            g2 = capture() if use_graph else None
+            g2 = capture()[0] if use_graph else None
             run = (g2.replay if g2 is not None else step_eager)
             for _ in range(3):
                 run()
@@ -921,7 +979,7 @@ def main():
     # evaluation (list -> pairing -> model) replayed as one hipGraph (integrations/graphed_step.py).  Reported next to the
     # headline, never as `value`: the headline's list is static, as BASELINE.json's metric is.
     md_step = None
-    if (rank == 0 and world == 1 and use_graph and args.workload == "water10k" and "cell" in data
+    if (args.full and rank == 0 and world == 1 and use_graph and args.workload == "water10k" and "cell" in data
             and os.environ.get("NQA_BENCH_NO_MD_STEP", "") in ("", "0")):
         try:
             from nequip_amd.integrations.graphed_step import GraphedStep
@@ -952,7 +1010,7 @@ def main():
     # ---- per-kernel HIP-event timing of the hand-written kernels (eager, on the launching stream) ------
     roofline = step_roofline = None
     kernels = {}
-    if rank == 0 and args.kernel_steps > 0:
+    if args.full and rank == 0 and args.kernel_steps > 0:
         # (per-kernel durations are taken back to back on one stream: the side-stream overlap of the radial backward
         # would make concurrent kernels stretch each other's event intervals)
         prev_ov = os.environ.get("NQA_NO_OVERLAP")
@@ -1018,14 +1076,14 @@ def main():
             "kernels_gbps": {k: v["gbps"] for k, v in kernels.items()},
             "kernels_tflops": {k: v["tflops"] for k, v in kernels.items() if v.get("tflops", 0) > 0},
         }
-        if (world == 1 and args.workload == "water10k" and not args.no_other_workloads
+        if (args.full and world == 1 and args.workload == "water10k" and not args.no_other_workloads
                 and os.environ.get("NQA_BENCH_NO_OTHER", "") in ("", "0")):
             # free this process's device memory first: cu100k needs most of what the cfg-3 model + graphs hold
-            graph = None
+            graph = graph_out = last = None
             topology_cache.clear()
             torch.cuda.empty_cache()
             result["config"]["other_workloads"] = other_workloads()
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             result["cpu_baseline"] = cpu_baseline(args.workload)
             result["gpu_over_cpu"] = value / result["cpu_baseline"]["value"]
         print(json.dumps(result))

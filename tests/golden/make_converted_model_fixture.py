@@ -2,9 +2,9 @@
 """A model that the REFERENCE's builder produced and the REFERENCE's `modify` converted with `enable_NequipAMD_full`, saved so
 that the GPU box (which has no reference tree) can evaluate it: `tests/golden/converted_reference_model.pt`.
 
-    python tests/golden/make_converted_model_fixture.py      # needs /root/reference
+    NEQUIP_REFERENCE=<mir-group/nequip source tree> python tests/golden/make_converted_model_fixture.py
 
-The build and the conversion are exactly those of tests/test_reference_full_modifier.py (nequip's real `NequIPGNNModel`
+The build and the conversion are exactly those of tests/golden/make_full_modifier_fixture.py (nequip's real `NequIPGNNModel`
 builder and `modify`, e3nn served by functional stand-ins).  The converted chain consists of nequip_amd modules only; the two
 reference CONTAINERS around it (`SequentialGraphNetwork`, `GraphModel`: no arithmetic) cannot be unpickled without nequip,
 so the chain's modules -- the very objects the modifier produced, not rebuilt ones -- are re-seated in this package's
@@ -20,20 +20,17 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..", "..")))
-sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..")))
+sys.path.insert(0, HERE)
 
 
 def main():
-    import pytest  # noqa: F401  (the fixture generator of the test module is reused as is)
-    import test_reference_full_modifier as T
+    import make_full_modifier_fixture as T
 
-    gen = T.ref.__wrapped__() if hasattr(T.ref, "__wrapped__") else T.ref.__pytest_wrapped__.obj()
-    ref = next(gen)
-    try:
+    with T.reference() as ref:
         from nequip_amd.integrations import nequip_full
         from nequip_amd.nn import ForceStressOutput, GraphModel, SequentialGraphNetwork
 
-        model = T._build_reference(ref)
+        model = T.build_reference(ref, T.HYPER)
         nequip_full.register_full()
         torch.cuda.is_available = lambda: True
         torch.version.hip = torch.version.hip or "7.0"
@@ -46,11 +43,6 @@ def main():
         path = os.path.join(HERE, "converted_reference_model.pt")
         torch.save({"model": out, "hyper": T.HYPER}, path)
         print("wrote", path, os.path.getsize(path), "bytes")
-    finally:
-        try:
-            next(gen)
-        except StopIteration:
-            pass
 
 
 if __name__ == "__main__":
