@@ -477,6 +477,40 @@ int nqa_energy_head(int32_t backward, const void* h, const void* readout_weight,
                     int32_t dim, int32_t act, double cst, int64_t num_nodes, nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * ZBL core-repulsion pair term (nequip/nn/pair_potential.py:230-389, _ZBL / ZBL; LAMMPS pair_style zbl).  Per edge
+ *   e = (i <- j), r = |edge_vec_e|, u = r * rmax_recip(e):
+ *     E_e = qqr2e_half Z_i Z_j / r * psi((Z_i^0.23 + Z_j^0.23) r / 0.46850) * cutoff_p(u),  psi = the four-exponential
+ *     screening function, cutoff_p = the PolynomialCutoff polynomial masked by u < 1 (E_e and all its derivatives are an
+ *     exact zero for u >= 1).
+ *   nqa_zbl_fwd:     pe_out[n] = pe_in[n] (NULL: 0) + sum_{e: centre(e) = n} E_e
+ *   nqa_zbl_bwd:     g_edge_vec[e] = g_pe[centre(e)] * E'(r) v_e / r          (every row of [E, 3] written)
+ *   nqa_zbl_bwd_bwd: given a cotangent c [E, 3] of g_edge_vec, h = v / r:
+ *                      gg_pe[n] = sum_{e: centre(e) = n} E'(r) (h . c_e)                      (may be NULL)
+ *                      g_edge_vec2[e] = g_pe[centre] (E'' h (h . c) + E'/r (c - h (h . c)))   (may be NULL)
+ *   edge_vec float64 [E, 3]; (rowptr_dst, edge_id_dst, src_sorted) the centre-atom CSR of nqa_csr_build(key = edge_dst);
+ *   atom_types int64 [num_nodes]; z_table float64 [T, 2] = (Z, Z^0.23) holding model-dtype values; rmax_recip_edge
+ *   float64 [E] or NULL (then the scalar rmax_recip); p >= 2; round_f32 != 0: the float32 model's roundings (the sum
+ *   Z_i^0.23 + Z_j^0.23, the cutoff value and, in nqa_zbl_bwd, its cotangent are rounded to float32, as the reference
+ *   and its autograd do); qqr2e_half: ONE float64 in device memory, 0.5 qqr2e (the module's `_qqr2exesquare` buffer:
+ *   no host read, capturable).
+ *   Rows n >= num_out (num_out <= num_nodes: a local-ghost list) have no per-atom energy: their edges contribute nothing.
+ *   16 lanes per centre atom, fixed-order sums: no atomics, bit-identical repeated evaluations.  No allocation.
+ * ------------------------------------------------------------------------------------------- */
+int nqa_zbl_fwd(const double* edge_vec, const int32_t* rowptr_dst, const int32_t* edge_id_dst, const int32_t* src_sorted,
+                const int64_t* atom_types, const double* z_table, const double* rmax_recip_edge, double rmax_recip, double p,
+                int32_t round_f32, const double* qqr2e_half, int64_t num_nodes, int64_t num_out, const double* pe_in,
+                double* pe_out, nqa_stream stream);
+int nqa_zbl_bwd(const double* edge_vec, const int32_t* rowptr_dst, const int32_t* edge_id_dst, const int32_t* src_sorted,
+                const int64_t* atom_types, const double* z_table, const double* rmax_recip_edge, double rmax_recip, double p,
+                int32_t round_f32, const double* qqr2e_half, int64_t num_nodes, int64_t num_out, const double* g_pe,
+                double* g_edge_vec, nqa_stream stream);
+int nqa_zbl_bwd_bwd(const double* edge_vec, const int32_t* rowptr_dst, const int32_t* edge_id_dst,
+                    const int32_t* src_sorted, const int64_t* atom_types, const double* z_table,
+                    const double* rmax_recip_edge, double rmax_recip, double p, int32_t round_f32, const double* qqr2e_half,
+                    int64_t num_nodes, int64_t num_out, const double* g_pe, const double* cot_edge_vec, double* gg_pe,
+                    double* g_edge_vec2, nqa_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Paired radial weights.  InteractionBlock.edge_mlp (nequip/nn/interaction_block.py:119-127,190-192) is a function of
  *   the edge length alone, and a neighbour list holds every interaction as (i <- j, S) and (j <- i, -S): the reference
  *   evaluates the MLP twice per pair.  nqa_edge_pairs finds the pairs of a list:

@@ -42,6 +42,12 @@
  *   energy_head_bwd(Tensor g_e, Tensor h, Tensor w, Tensor? scales, Tensor types, int act, float cst) -> Tensor
  *   force_virial(Tensor g_vec, Tensor edge_vec, Tensor edge_index, Tensor? batch, Tensor? cell, SymInt num_nodes,
  *                SymInt num_frames) -> (Tensor, Tensor, Tensor)      forces, virial, stress from dE/d(edge vectors)
+ *   zbl_fwd(Tensor edge_vec, Tensor? pe_in, Tensor edge_index, Tensor atom_types, Tensor z_table, Tensor qqr2e_half,
+ *           Tensor? rmax_recip_edge, float rmax_recip, float p, bool f32) -> Tensor
+ *       per-atom energies pe_in (or 0) + the ZBL pair term of each centre atom's edges (nn/_pair_potential_ops.py,
+ *       nqa_zbl_fwd; z_table [T, 2] = (Z, Z^0.23), qqr2e_half the module's float64 buffer)
+ *   zbl_bwd(Tensor g_pe, Tensor edge_vec, Tensor edge_index, Tensor atom_types, Tensor z_table, Tensor qqr2e_half,
+ *           Tensor? rmax_recip_edge, float rmax_recip, float p, bool f32) -> Tensor      dE/d(edge vectors), [E, 3]
  * Derived weight images (packed fp16-split fragments, transposed copies, the radial MLP's split second layer) are built
  * once per CONSTANT weight tensor: the cache is keyed on the identity of the tensor's storage, which an AOTInductor
  * package's constant buffers keep from call to call (NQA_OP_CONSTANT_CACHE=0 switches it off; a weight buffer rewritten

@@ -249,6 +249,21 @@ SIGNATURES = {
         [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
          c_double, c_int64, c_void_p],
     ),
+    "nqa_zbl_fwd": (
+        c_int32,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int32, c_void_p, c_int64,
+         c_int64, c_void_p, c_void_p, c_void_p],
+    ),
+    "nqa_zbl_bwd": (
+        c_int32,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int32, c_void_p, c_int64,
+         c_int64, c_void_p, c_void_p, c_void_p],
+    ),
+    "nqa_zbl_bwd_bwd": (
+        c_int32,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int32, c_void_p, c_int64,
+         c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     "nqa_neighbor_list_workspace_bytes": (c_int64, [c_int64]),
     "nqa_neighbor_list_count": (
         c_int32,

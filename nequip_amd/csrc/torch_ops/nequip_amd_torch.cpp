@@ -1504,6 +1504,69 @@ Tensor energy_head_bwd(const Tensor& g_e, const Tensor& h_, const Tensor& w_, co
   return gh;
 }
 
+// ---- zbl_fwd / zbl_bwd (nequip_amd/nn/_pair_potential_ops.py) --------------------------------------------------------
+struct ZblGeometry {
+  Tensor vec, types, zt, qq;
+  OptTensor rmax_edge;
+  std::shared_ptr<Topology> topo;
+};
+
+ZblGeometry zbl_geometry(const Tensor& edge_vec, const Tensor& edge_index, const Tensor& atom_types, const Tensor& z_table,
+                         const Tensor& qq, const OptTensor& rmax_edge, int64_t num_out, const char* op) {
+  require_gpu(edge_vec, op);
+  TORCH_CHECK(edge_vec.scalar_type() == at::kDouble && edge_vec.dim() == 2 && edge_vec.size(1) == 3, "nequip_amd::", op,
+              ": edge_vec must be float64 [E, 3]");
+  TORCH_CHECK(edge_index.scalar_type() == at::kLong && edge_index.dim() == 2 && edge_index.size(0) == 2 &&
+                  edge_index.size(1) == edge_vec.size(0),
+              "nequip_amd::", op, ": edge_index must be int64 [2, E]");
+  TORCH_CHECK(z_table.dim() == 2 && z_table.size(1) == 2 && qq.numel() == 1, "nequip_amd::", op,
+              ": z_table [T, 2], qqr2e_half one value");
+  ZblGeometry g;
+  g.vec = edge_vec.contiguous();
+  const Tensor t = atom_types.reshape({-1});
+  g.types = (t.scalar_type() == at::kLong ? t : t.to(at::kLong)).contiguous();
+  TORCH_CHECK(num_out >= 0 && num_out <= g.types.size(0), "nequip_amd::", op, ": more per-atom energies than atoms");
+  g.zt = as_f64(z_table);
+  g.qq = as_f64(qq);
+  g.rmax_edge = rmax_edge.has_value() && rmax_edge->defined() ? OptTensor(as_f64(rmax_edge->reshape({-1}))) : OptTensor();
+  g.topo = topology_of(edge_index.select(0, 0), edge_index.select(0, 1), g.types.size(0));
+  return g;
+}
+
+Tensor zbl_fwd(const Tensor& edge_vec, const OptTensor& pe_in, const Tensor& edge_index, const Tensor& atom_types,
+               const Tensor& z_table, const Tensor& qq, const OptTensor& rmax_edge, double rmax_recip, double p, bool f32) {
+  c10::DeviceGuard guard(edge_vec.device());
+  const bool has_pe = pe_in.has_value() && pe_in->defined();
+  const int64_t n_out = has_pe ? pe_in->size(0) : atom_types.numel();
+  ZblGeometry g = zbl_geometry(edge_vec, edge_index, atom_types, z_table, qq, rmax_edge, n_out, "zbl_fwd");
+  const Csr& cd = by_dst(*g.topo);
+  const OptTensor pe = has_pe ? OptTensor(as_f64(pe_in->reshape({-1}))) : OptTensor();
+  Tensor out = at::empty({n_out, 1}, edge_vec.options().dtype(at::kDouble));
+  NQA_CALL(nqa_zbl_fwd(static_cast<const double*>(g.vec.data_ptr()), i32(cd.rowptr), i32(cd.edge_id), i32(cd.other),
+                       static_cast<const int64_t*>(g.types.data_ptr()), static_cast<const double*>(g.zt.data_ptr()),
+                       static_cast<const double*>(ptr(g.rmax_edge)), rmax_recip, p, f32 ? 1 : 0,
+                       static_cast<const double*>(g.qq.data_ptr()), g.types.size(0), n_out,
+                       static_cast<const double*>(ptr(pe)), static_cast<double*>(out.data_ptr()), stream_of(edge_vec)),
+           "nqa_zbl_fwd");
+  return out;
+}
+
+Tensor zbl_bwd(const Tensor& g_pe, const Tensor& edge_vec, const Tensor& edge_index, const Tensor& atom_types,
+               const Tensor& z_table, const Tensor& qq, const OptTensor& rmax_edge, double rmax_recip, double p, bool f32) {
+  c10::DeviceGuard guard(edge_vec.device());
+  const Tensor gp = as_f64(g_pe.reshape({-1}));
+  ZblGeometry g = zbl_geometry(edge_vec, edge_index, atom_types, z_table, qq, rmax_edge, gp.size(0), "zbl_bwd");
+  const Csr& cd = by_dst(*g.topo);
+  Tensor out = at::empty({edge_vec.size(0), 3}, edge_vec.options().dtype(at::kDouble));
+  NQA_CALL(nqa_zbl_bwd(static_cast<const double*>(g.vec.data_ptr()), i32(cd.rowptr), i32(cd.edge_id), i32(cd.other),
+                       static_cast<const int64_t*>(g.types.data_ptr()), static_cast<const double*>(g.zt.data_ptr()),
+                       static_cast<const double*>(ptr(g.rmax_edge)), rmax_recip, p, f32 ? 1 : 0,
+                       static_cast<const double*>(g.qq.data_ptr()), g.types.size(0), gp.size(0),
+                       static_cast<const double*>(gp.data_ptr()), static_cast<double*>(out.data_ptr()), stream_of(edge_vec)),
+           "nqa_zbl_bwd");
+  return out;
+}
+
 const char* const kEdgeCfg = "int lmax, bool want_sh, bool want_emb, int nb, float rmax_recip, float p, float factor, bool f32";
 
 bool already_registered() {
@@ -1547,6 +1610,10 @@ TORCH_LIBRARY_FRAGMENT(nequip_amd, m) {
   m.def("energy_head_bwd(Tensor g_e, Tensor h, Tensor w, Tensor? scales, Tensor types, int act, float cst) -> Tensor");
   m.def("gate(Tensor x, str key) -> Tensor");
   m.def("gate_bwd(Tensor x, Tensor g, str key) -> Tensor");
+  m.def("zbl_fwd(Tensor edge_vec, Tensor? pe_in, Tensor edge_index, Tensor atom_types, Tensor z_table, Tensor qqr2e_half, "
+        "Tensor? rmax_recip_edge, float rmax_recip, float p, bool f32) -> Tensor");
+  m.def("zbl_bwd(Tensor g_pe, Tensor edge_vec, Tensor edge_index, Tensor atom_types, Tensor z_table, Tensor qqr2e_half, "
+        "Tensor? rmax_recip_edge, float rmax_recip, float p, bool f32) -> Tensor");
   m.impl("tp_scatter_fwd", c10::DispatchKey::CUDA, TORCH_FN(tp_scatter_fwd));
   m.impl("tp_scatter_bwd", c10::DispatchKey::CUDA, TORCH_FN(tp_scatter_bwd));
   m.impl("edge_vectors", c10::DispatchKey::CUDA, TORCH_FN(edge_vectors));
@@ -1565,6 +1632,8 @@ TORCH_LIBRARY_FRAGMENT(nequip_amd, m) {
   m.impl("energy_head_bwd", c10::DispatchKey::CUDA, TORCH_FN(energy_head_bwd));
   m.impl("gate", c10::DispatchKey::CUDA, TORCH_FN(gate));
   m.impl("gate_bwd", c10::DispatchKey::CUDA, TORCH_FN(gate_bwd));
+  m.impl("zbl_fwd", c10::DispatchKey::CUDA, TORCH_FN(zbl_fwd));
+  m.impl("zbl_bwd", c10::DispatchKey::CUDA, TORCH_FN(zbl_bwd));
 }
 
 // ---- host-side introspection (tests: the tables built here against the Python host's, no GPU needed) -------------------

@@ -22,6 +22,7 @@ Reference class (attributes read)                                        -> mirr
         ``conv.{use_sc, is_first_layer, edge_mlp.dims, avg_num_neighbors_norm.norm_const}``)        ``ConvNetLayer`` (+ ``InteractionBlock``)
     ``ScalarMLP`` (``field``, ``out_field``, ``mlp_module.{dims, bias/has_bias, mlp}``)             ``ScalarMLP``
     ``PerTypeScaleShift`` (``type_names``, ``field``, ``out_field``, ``scales``, ``shifts``)        ``PerTypeScaleShift``
+    ``ZBL`` (``atomic_numbers``, ``_qqr2exesquare``, ``cutoff.p``, ``per_atom_energy_field``)          ``nn.pair_potential.ZBL``
     ``AtomwiseReduce`` (``field``, ``out_field``, ``reduce``, ``constant``)                         ``AtomwiseReduce``
     ``ForceStressOutput`` (``func``, ``do_derivatives``)                                           ``ForceStressOutput``
 
@@ -294,6 +295,18 @@ def _factories(model) -> Dict[str, Callable]:
                                      scales=val(old.scales, old.has_scales), shifts=val(old.shifts, old.has_shifts),
                                      irreps_in=_irreps_dict(old.irreps_in))
 
+    def zbl(old):
+        from ..data.chemistry import chemical_symbols
+        from ..nn.pair_potential import _QQR2E, ZBL
+
+        z = [int(round(float(v))) for v in old.atomic_numbers.detach().reshape(-1).tolist()]
+        q = float(old._qqr2exesquare)
+        # (the buffers themselves are carried over by name below: a rescaled prefactor survives whichever units are named)
+        units = next((u for u, v in _QQR2E.items() if abs(v * 0.5 - q) <= 1e-9 * v), "metal")
+        return ZBL(type_names=_type_names(model, len(z)), chemical_species=[chemical_symbols[v] for v in z], units=units,
+                   polynomial_cutoff_p=float(old.cutoff.p), per_atom_energy_field=old.per_atom_energy_field,
+                   irreps_in=_irreps_dict(old.irreps_in))
+
     def reduce_(old):
         avg = None
         if getattr(old, "constant", 1.0) != 1.0:
@@ -313,6 +326,7 @@ def _factories(model) -> Dict[str, Callable]:
         "ConvNetLayer": under_dtype(convnet),
         "ScalarMLP": under_dtype(scalar_mlp),
         "PerTypeScaleShift": under_dtype(scale_shift),
+        "ZBL": under_dtype(zbl),
         "AtomwiseReduce": under_dtype(reduce_),
         "ForceStressOutput": under_dtype(force_stress),
     }

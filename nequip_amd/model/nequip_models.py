@@ -1,7 +1,8 @@
 """NequIP GNN model builders (mirror of ``nequip/model/nequip_models.py:116-399`` and the ``@model_builder``
 wrapper ``nequip/model/utils.py:104-216``): same arguments, same module names/ordering
 (``type_embed -> spharm -> edge_norm -> bessel_encode -> factor -> layer{i}_convnet -> per_atom_energy_readout
--> per_type_energy_scale_shift -> total_energy_sum``), wrapped in ``ForceStressOutput`` and ``GraphModel``.
+-> per_type_energy_scale_shift [-> pair_potential] -> total_energy_sum``), wrapped in ``ForceStressOutput`` and
+``GraphModel``; ``ZBLPairPotential`` mirrors ``nequip/model/pair_potential.py``.
 The modules on the hot path are the HIP-backed ones of ``nequip_amd.nn``.
 """
 
@@ -23,6 +24,7 @@ from ..nn import (
     PerTypeScaleShift,
     ScalarMLP,
     SequentialGraphNetwork,
+    ZBL,
 )
 from ..nn.embedding import (
     BesselEdgeLengthEncoding,
@@ -149,6 +151,7 @@ def _full_nequip_energy_model(
     convnet_nonlinearity_type: str = "gate",
     convnet_nonlinearity_scalars: Dict[str, str] = {"e": "silu", "o": "tanh"},
     convnet_nonlinearity_gates: Dict[str, str] = {"e": "silu", "o": "tanh"},
+    pair_potential: Optional[Dict] = None,
 ):
     if not all(name.isalnum() for name in type_names):
         raise AssertionError("type names must be alphanumeric")
@@ -191,12 +194,49 @@ def _full_nequip_energy_model(
     scale_shift = chain.add("per_type_energy_scale_shift", lambda prev: PerTypeScaleShift(
         type_names=type_names, field=energy, out_field=energy, scales=per_type_energy_scales,
         shifts=per_type_energy_shifts, irreps_in=prev))
+    if pair_potential is not None:  # (nequip/model/energy_modules.py:10-35)
+        chain.add("pair_potential", lambda prev: _instantiate_pair_potential(pair_potential, type_names, prev))
     chain.add("total_energy_sum", lambda prev: AtomwiseReduce(irreps_in=prev, reduce="sum", field=energy,
                                                              out_field=AtomicDataDict.TOTAL_ENERGY_KEY))
 
     _plan_fusions(convnets, edge_norm, readout, scale_shift, readout_mlp_hidden_layers_depth)
     _plan_embedding_fusion(chain.modules["spharm"], edge_norm, bessel)
     return ForceStressOutput(SequentialGraphNetwork(chain.modules), do_derivatives)
+
+
+_PAIR_POTENTIAL_TARGETS = ("nequip.nn.pair_potential.ZBL", "nequip_amd.nn.pair_potential.ZBL")
+
+
+def _instantiate_pair_potential(config: Dict, type_names: Sequence[str], irreps_in) -> torch.nn.Module:
+    """``hydra.utils.instantiate(config, type_names=..., irreps_in=...)`` for the pair terms this package implements (the
+    call arguments win over the config's, as in hydra).  Other targets -- ``LennardJones``, third-party terms -- raise."""
+    config = dict(config)
+    target = config.pop("_target_", None)
+    if target not in _PAIR_POTENTIAL_TARGETS:
+        raise NotImplementedError(f"pair_potential `_target_: {target}` has no nequip_amd implementation (supported: "
+                                  f"{', '.join(_PAIR_POTENTIAL_TARGETS)})")
+    config.update(type_names=list(type_names), irreps_in=irreps_in)
+    return ZBL(**config)
+
+
+def ZBLPairPotential(seed: int = 0, model_dtype="float32", **kwargs) -> GraphModel:
+    """A force field of the ZBL term alone (``nequip/model/pair_potential.py``): ``edge_norm -> pair_potential ->
+    total_energy_sum`` in ``ForceStressOutput``."""
+    return _build(_zbl_pair_potential, seed, model_dtype, **kwargs)
+
+
+def _zbl_pair_potential(r_max: float, type_names: Sequence[str], chemical_species: Sequence[str], units: str,
+                        polynomial_cutoff_p: int = 6,
+                        per_edge_type_cutoff: Optional[Dict[str, Union[float, Dict[str, float]]]] = None):
+    chain = _Chain()
+    chain.add("edge_norm", lambda prev: EdgeLengthNormalizer(r_max=r_max, type_names=type_names,
+                                                             per_edge_type_cutoff=per_edge_type_cutoff))
+    chain.add("pair_potential", lambda prev: ZBL(type_names=type_names, chemical_species=chemical_species, units=units,
+                                                 polynomial_cutoff_p=polynomial_cutoff_p, irreps_in=prev))
+    chain.add("total_energy_sum", lambda prev: AtomwiseReduce(irreps_in=prev, reduce="sum",
+                                                             field=AtomicDataDict.PER_ATOM_ENERGY_KEY,
+                                                             out_field=AtomicDataDict.TOTAL_ENERGY_KEY))
+    return ForceStressOutput(SequentialGraphNetwork(chain.modules))
 
 
 class _Chain:

@@ -14,4 +14,5 @@ from .interaction_block import InteractionBlock  # noqa: F401
 from .misc import ApplyFactor  # noqa: F401
 from .mlp import ScalarMLP, ScalarMLPFunction  # noqa: F401
 from .norm import AvgNumNeighborsNorm  # noqa: F401
+from .pair_potential import ZBL  # noqa: F401
 from .utils import scatter, tp_path_exists, with_edge_vectors_  # noqa: F401
