@@ -629,7 +629,8 @@ int nqa_tp_scatter_bwd_pairs_dual(const nqa_plan* plan, const void* plan_image, 
 /* Forward-mode companion of the same second-order backward: the gradient w.r.t. grad_out of <cotangents, backward outputs>,
  *   out = F(x_cot, y, w) + F(x, y_cot, w) + F(x, y, w_cot)      (F = nqa_tp_scatter_fwd; the op is trilinear)
  *   in one pass over the edges instead of three forward launches and two additions.  A NULL cotangent drops its term (at
- *   least one is required); w / w_cot hold one row per edge, or per pair when weight_rows (dst-CSR slot order, as
+ *   least one is required when there are edges: the operands of an edge-free graph are empty, so their pointers may
+ *   all be NULL, and out is zeros); w / w_cot hold one row per edge, or per pair when weight_rows (dst-CSR slot order, as
  *   nqa_tp_scatter_fwd_paired) is given.  Structure-specialised float32 plans (nqa_tp_fwd_jvp_supported). */
 int32_t nqa_tp_fwd_jvp_supported(const nqa_plan* plan, int32_t dtype);
 int nqa_tp_scatter_fwd_jvp(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x, const void* y,

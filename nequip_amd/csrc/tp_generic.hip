@@ -1003,13 +1003,20 @@ int nqa_tp_scatter_fwd_jvp(const nqa_plan* plan, const void* plan_image, int32_t
     return NQA_ERR_UNSUPPORTED;
   }
   if (num_nodes < 0 || num_edges < 0 || (num_nodes > 0 && (!out || !rowptr_dst)) ||
-      (num_edges > 0 && (!x || !y || !w || !edge_id_dst || !src_sorted)) || (!x_cot && !y_cot && !w_cot) ||
+      (num_edges > 0 && (!x || !y || !w || !edge_id_dst || !src_sorted || (!x_cot && !y_cot && !w_cot))) ||
       (weight_rows != nullptr && (num_pairs <= 0 || num_pairs > 1073741823))) {
     set_error("nqa_tp_scatter_fwd_jvp: NULL operand (at least one cotangent is required)");
     return NQA_ERR_INVALID;
   }
   if (num_nodes == 0) return NQA_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (num_edges == 0) {  // no terms: the edge operands (cotangents included) are empty and may be NULL
+    if (hipMemsetAsync(out, 0, (size_t)num_nodes * plan->dim_out * 4, s) != hipSuccess) {
+      set_error("nqa_tp_scatter_fwd_jvp: hipMemsetAsync failed");
+      return NQA_ERR_LAUNCH;
+    }
+    return NQA_OK;
+  }
   SpecArgs<float> a{};
   spec_fill(a, plan, num_nodes);
   a.x = static_cast<const float*>(x);
@@ -1049,6 +1056,13 @@ int nqa_tp_scatter_bwd_x_dual(const nqa_plan* plan, const void* plan_image, int3
   }
   if (num_nodes == 0) return NQA_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (num_edges == 0) {  // no terms: the edge operands (cotangents included) are empty and may be NULL
+    if (hipMemsetAsync(grad_x, 0, (size_t)num_nodes * plan->dim_in1 * 4, s) != hipSuccess) {
+      set_error("nqa_tp_scatter_bwd_x_dual: hipMemsetAsync failed");
+      return NQA_ERR_LAUNCH;
+    }
+    return NQA_OK;
+  }
   SpecArgs<float> a{};
   spec_fill(a, plan, num_nodes);
   a.y = static_cast<const float*>(y);
