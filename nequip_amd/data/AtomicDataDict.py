@@ -7,6 +7,7 @@ import torch
 
 from ._keys import *  # noqa: F401,F403
 from . import _keys
+from ._key_registry import _GRAPH_FIELDS
 
 Type = Dict[str, torch.Tensor]
 
@@ -60,6 +61,13 @@ def batched_from_list(frames: List[Type]) -> Type:
         out[_keys.EDGE_CELL_SHIFT_KEY] = torch.cat(shift)
     if cells:
         out[_keys.CELL_KEY] = torch.cat(cells)
+    # the other registered per-frame fields (charge, spin, dataset, custom ones): one row per frame.  Per-frame targets
+    # (energy, stress, virial) and pbc stay out, as before: this builds model inputs.
+    done = {_keys.CELL_KEY, _keys.NUM_NODES_KEY, _keys.PBC_KEY, _keys.TOTAL_ENERGY_KEY, _keys.STRESS_KEY, _keys.VIRIAL_KEY}
+    for key in sorted(k for k in _GRAPH_FIELDS if k not in done and all(k in d for d in frames)):
+        vals = [d[key] for d in frames]
+        if all(isinstance(v, torch.Tensor) for v in vals):
+            out[key] = torch.cat([v.reshape(1, -1) for v in vals])
     return out
 
 

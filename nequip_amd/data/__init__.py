@@ -1,1 +1,2 @@
 from . import AtomicDataDict  # noqa: F401
+from ._key_registry import register_fields  # noqa: F401

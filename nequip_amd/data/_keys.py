@@ -21,6 +21,10 @@ _INPUTS: Dict[str, str] = dict(
     NUM_NODES_KEY="num_atoms",
     LMP_MLIAP_DATA_KEY="lmp_mliap_data",
     NUM_LOCAL_GHOST_NODES_KEY="num_local_ghost_atoms",
+    # integer per-frame labels a model may be conditioned on (categorical graph-field embeddings, nn/embedding/node.py)
+    DATASET_KEY="dataset",
+    TOTAL_CHARGE_KEY="charge",
+    TOTAL_SPIN_KEY="spin",
 )
 
 # per-edge quantities written by the embedding modules (an edge-vector based caller provides `edge_vectors` itself)

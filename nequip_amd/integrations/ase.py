@@ -107,6 +107,10 @@ class NequIPCalculator(Calculator):
         self._graphed = None  # (identity of the atoms, GraphedStep, cell as last written)
         if self.graphed_md and self.transforms:
             raise ValueError("graphed_md replays a fixed pipeline: it cannot run user transforms")
+        if self.graphed_md:
+            from ..nn.embedding.node import refuse_categorical_graph_fields
+
+            refuse_categorical_graph_fields(model, "NequIPCalculator(graphed_md=True)")
         if self.graphed_md and type(model).__name__ == "DictInputOutputWrapper":
             raise ValueError("graphed_md needs the eager nequip_amd model: a compiled package's graph is fixed at export time")
         # chemical symbol -> atom type index (`ChemicalSpeciesToAtomTypeMapper`, nequip/data/transforms): a list means

@@ -41,6 +41,9 @@ class GraphedStep:
         if not atom_types.is_cuda:
             raise RuntimeError("GraphedStep runs on the GPU only (HIP kernels; there is no CPU path)")
         assert not model.training, "call .eval() on the model before building a GraphedStep"
+        from ..nn.embedding.node import refuse_categorical_graph_fields
+
+        refuse_categorical_graph_fields(model, "GraphedStep (graphed_md)")
         if headroom < 1.0:
             raise ValueError("headroom must be >= 1")
         self.model = model

@@ -42,6 +42,9 @@ class NequIPLAMMPSMLIAPWrapper(_Base):
 
     def __init__(self, model: torch.nn.Module, device: Optional[str] = None, sync_inputs: bool = True):
         super().__init__()
+        from ..nn.embedding.node import refuse_categorical_graph_fields
+
+        refuse_categorical_graph_fields(model, "NequIPLAMMPSMLIAPWrapper (LAMMPS ML-IAP)")
         r_max = getattr(model, "r_max", None)
         if r_max is None:
             md = getattr(model, "metadata", None) or {}

@@ -13,7 +13,7 @@ under their old names, so ``state_dict()`` keys are the same before and after --
 ``enable_OpenEquivariance`` keeps ``new.tp = old.tp``).
 
 Reference class (attributes read)                                        -> mirror
-    ``NodeTypeEmbed`` (``num_types``, ``set_features``, ``embed_module``)                        ``nn.embedding.NodeTypeEmbed``
+    ``NodeTypeEmbed`` (``num_types``, ``set_features``, ``embed_module``, categorical graph-field tables) ``nn.embedding.NodeTypeEmbed``
     ``SphericalHarmonicEdgeAttrs`` (``irreps_edge_sh``, ``out_field``, ``sh.normalize/normalization``)  ``SphericalHarmonicEdgeAttrs``
     ``EdgeLengthNormalizer`` (``r_max``, ``num_types``, ``_per_edge_type``, ``_rmax_recip``, fields)    ``EdgeLengthNormalizer``
     ``BesselEdgeLengthEncoding`` (``num_bessels``, ``trainable``, ``cutoff.p``, fields)             ``BesselEdgeLengthEncoding``
@@ -220,10 +220,35 @@ def _factories(model) -> Dict[str, Callable]:
         return wrapped
 
     def node_type_embed(old):
-        if getattr(old, "categorical_graph_field_embed", None) or len(getattr(old, "categorical_embeds", [])) > 0:
-            raise NotImplementedError(f"{FULL_MODIFIER_NAME}: categorical graph field embeddings")
-        return aemb.NodeTypeEmbed(type_names=_type_names(model, old.num_types), num_features=old.embed_module.embedding_dim,
-                                  set_features=old.set_features, irreps_in=_irreps_dict(old.irreps_in))
+        # categorical graph-field embeddings (nequip/nn/embedding/node.py:78-118): one Embedding per field under
+        # `categorical_graph_field_embed_modules`, shifted by `categorical_graph_field_embed_shifts[field]` (its `min`)
+        fields = None
+        if getattr(old, "do_categorical_graph_field_embed", False):
+            fields = []
+            shifts = dict(getattr(old, "categorical_graph_field_embed_shifts", {}))
+            for field, mod in old.categorical_graph_field_embed_modules.items():
+                if not isinstance(mod, torch.nn.Embedding) or field not in shifts:
+                    raise NotImplementedError(f"{FULL_MODIFIER_NAME}: categorical graph field `{field}` is not an "
+                                              f"Embedding with a shift ({type(mod).__name__})")
+                fields.append({"field": field, "num_features": mod.embedding_dim, "min": int(shifts[field]),
+                               "max": int(shifts[field]) + mod.num_embeddings - 1})
+        else:
+            for name in ("categorical_graph_field_embed_modules", "categorical_embeds"):
+                if len(getattr(old, name, None) or []) > 0:
+                    raise NotImplementedError(f"{FULL_MODIFIER_NAME}: `{name}` present but "
+                                              f"`do_categorical_graph_field_embed` is not set")
+        new = aemb.NodeTypeEmbed(type_names=_type_names(model, old.num_types), num_features=old.embed_module.embedding_dim,
+                                 type_embed_init=getattr(old, "type_embed_init", None), set_features=old.set_features,
+                                 categorical_graph_field_embed=fields, irreps_in=_irreps_dict(old.irreps_in))
+        # every entry of the old state must have a home: nothing is re-attached as an inert buffer here
+        extra = sorted(set(old.state_dict()) - set(new.state_dict()))
+        if extra:
+            raise NotImplementedError(f"{FULL_MODIFIER_NAME}: NodeTypeEmbed entries without a counterpart: {extra}")
+        if str(new.irreps_out[AtomicDataDict.NODE_ATTRS_KEY]) != str(old.irreps_out[AtomicDataDict.NODE_ATTRS_KEY]):
+            raise RuntimeError(f"{FULL_MODIFIER_NAME}: rebuilt NodeTypeEmbed produces "
+                               f"{new.irreps_out[AtomicDataDict.NODE_ATTRS_KEY]}, the reference one "
+                               f"{old.irreps_out[AtomicDataDict.NODE_ATTRS_KEY]}")
+        return new
 
     def spharm(old):
         sh = getattr(old, "sh", None)

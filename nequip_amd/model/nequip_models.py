@@ -135,6 +135,7 @@ def _full_nequip_energy_model(
     feature_irreps_hidden: Sequence[Union[str, Irreps]],
     irreps_edge_sh: Union[int, str, Irreps],
     type_embed_num_features: int,
+    categorical_graph_field_embed: Optional[List[Dict[str, int]]] = None,
     readout_mlp_hidden_layers_depth: int = 0,
     readout_mlp_hidden_layers_width: Optional[int] = None,
     readout_mlp_nonlinearity: Optional[str] = "silu",
@@ -163,7 +164,9 @@ def _full_nequip_energy_model(
 
     chain = _Chain()
     # ---- geometry: type embedding, spherical harmonics, normalised lengths, Bessel x cutoff (x 2 pi / r_max^2, folded) ----
-    chain.add("type_embed", lambda prev: NodeTypeEmbed(type_names=type_names, num_features=type_embed_num_features))
+    # (categorical graph fields -- charge, spin, dataset: per-frame integers embedded next to the type, nn/embedding/node.py)
+    chain.add("type_embed", lambda prev: NodeTypeEmbed(type_names=type_names, num_features=type_embed_num_features,
+                                                       categorical_graph_field_embed=categorical_graph_field_embed))
     chain.add("spharm", lambda prev: SphericalHarmonicEdgeAttrs(irreps_edge_sh=irreps_edge_sh, irreps_in=prev))
     edge_norm = chain.add("edge_norm", lambda prev: EdgeLengthNormalizer(
         r_max=r_max, type_names=type_names, per_edge_type_cutoff=per_edge_type_cutoff, irreps_in=prev))

@@ -27,6 +27,12 @@ class GraphModel(GraphModuleMixin, torch.nn.Module):
             # local / ghost bookkeeping of a domain-decomposed caller (nequip/nn/graph_model.py:70-75)
             AtomicDataDict.LMP_MLIAP_DATA_KEY, AtomicDataDict.NUM_LOCAL_GHOST_NODES_KEY,
         ]  # fmt: skip
+        # graph fields the model declares as inputs (categorical graph-field embeddings register theirs in irreps_in, the
+        # reference derives its input fields from model.irreps_in the same way: nequip/nn/graph_model.py:61-85)
+        from ..data._key_registry import _GRAPH_FIELDS
+
+        self.model_input_fields += [k for k in self.model.irreps_in
+                                    if k in _GRAPH_FIELDS and k not in self.model_input_fields]
         self._init_irreps(irreps_in=self.model.irreps_in, irreps_out=self.model.irreps_out)
 
     @property

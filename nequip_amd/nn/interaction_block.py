@@ -121,8 +121,8 @@ class InteractionBlock(GraphModuleMixin, torch.nn.Module):
                 or differentiable_parameters(self.training, self.linear_1.weight)):
             return None
         table = data.get("_nqa_node_attrs_table")
-        if table is None or table.shape[0] > 16:
-            return None
+        if table is None or table.shape[0] > 16 or "_nqa_node_attrs_classes" in data:
+            return None  # (a batch with categorical graph fields: the unfused typed launches, see forward)
         types = data[AtomicDataDict.ATOM_TYPE_KEY].view(-1)[: h.shape[0]].contiguous()
         if traceable():  # the same launch as a dispatcher-op pair (o3/_node_ops.py::node_stage)
             from ..o3 import _node_ops
@@ -220,8 +220,16 @@ class InteractionBlock(GraphModuleMixin, torch.nn.Module):
                 x.record_stream(sc_stream)
             # (no side stream -- always the case while a compiler traces -- means no stream context at all: Dynamo
             # rejects `torch.cuda.stream(None)`)
+            classes = data.get("_nqa_node_attrs_classes")
             with (torch.cuda.stream(sc_stream) if sc_stream is not None else contextlib.nullcontext()):
-                if table is not None and table.shape[0] <= 16:
+                if classes is not None:
+                    # a batch with categorical graph fields: node_attrs = cat(type row, the rows of the atom's frame)
+                    types = data[AtomicDataDict.ATOM_TYPE_KEY].view(-1)[: x.shape[0]]
+                    if x.is_cuda and not traceable() and table is not None and table.shape[0] <= 16:
+                        sc = self.sc.forward_classes(x, types, table, classes)
+                    else:
+                        sc = self.sc(x, node_attrs)
+                elif table is not None and table.shape[0] <= 16:
                     sc = self.sc.forward_typed(x, data[AtomicDataDict.ATOM_TYPE_KEY].view(-1)[: x.shape[0]], table)
                 else:
                     sc = self.sc(x, node_attrs)

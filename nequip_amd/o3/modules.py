@@ -171,6 +171,8 @@ class FullyConnectedTensorProduct(_WeightCacheMixin, torch.nn.Module):
       K = T*mul1 over one-hot-expanded features -- mul2/T times fewer FLOPs.
     """
 
+    _weight_cache_attrs = _WeightCacheMixin._weight_cache_attrs + ("_eval_wp_classes",)
+
     def __init__(self, irreps_in1, irreps_in2, irreps_out):
         super().__init__()
         self.irreps_in1 = Irreps(irreps_in1)
@@ -273,6 +275,46 @@ class FullyConnectedTensorProduct(_WeightCacheMixin, torch.nn.Module):
             cached = (key, wp.contiguous())
             self._eval_wp = cached
         return cached[1]
+
+    def _contract_cols(self, weight: torch.Tensor, table: torch.Tensor, v0: int) -> torch.Tensor:
+        """``W_r[u, w] = sum_v table[r, v] W[u, v0 + v, w]`` for all instructions, ``[R, wstride]``: the contraction of
+        ``forward_typed`` restricted to the ``table.shape[1]`` columns of the second operand that start at ``v0``."""
+        perm, scale = self._contract_index(weight.device, weight.dtype)
+        wm = weight.index_select(0, perm).view(self.irreps_in2[0].mul, -1)
+        return _skinny_mm(table, wm[v0 : v0 + table.shape[1]] * scale)
+
+    def _eval_weights_cols(self, table: torch.Tensor, v0: int, dtype) -> torch.Tensor:
+        """``_contract_cols`` as constants (eval mode), one cache entry per (table, column offset)."""
+        key = (v0, id(self.weight), self.weight.data_ptr(), self.weight._version, table._version, table.data_ptr(),
+               tuple(table.shape), table.device, dtype)
+        cache = self.__dict__.setdefault("_eval_wp_classes", {})
+        hit = cache.get(key)
+        if hit is None:
+            if len(cache) >= 16:
+                cache.clear()
+            hit = cache[key] = self._contract_cols(self.weight.detach(), table.detach(), v0).contiguous()
+        return hit
+
+    def forward_classes(self, x: torch.Tensor, types: torch.Tensor, table: torch.Tensor, classes) -> torch.Tensor:
+        """``sc(x, a)`` for ``a[z] = cat(table[types[z]], tb_1[idx_1[z]], ...)``, where ``classes`` lists ``(idx_k, tb_k,
+        v0_k)`` and ``tb_k`` fills columns ``[v0_k, v0_k + tb_k.shape[1])`` of ``a`` (categorical graph fields of a batch:
+        ``idx_k`` = the row of the atom's frame).  The map is linear in ``a``, so it is the sum of one typed map per table,
+        each with its own pre-contracted weights -- ``T + sum_k R_k`` weight sets, independent of the number of frames --
+        chained through the ``addend`` of the fused launch (fixed order: deterministic)."""
+        if not (x.is_cuda and not traceable() and self._meta is not None and x.dtype in (torch.float32, torch.float64)):
+            raise NotImplementedError("forward_classes: float32 / float64 CUDA features and a single scalar attribute "
+                                      "block only")
+        n = x.shape[0]
+        out = None
+        for idx, tb, v0 in [(types, table, 0)] + list(classes):
+            if differentiable_parameters(self.training, self.weight):
+                with parameter_side(x.device, tb):
+                    wp = self._contract_cols(self.weight, tb, v0)
+                publish(x.device, wp)
+            else:
+                wp = self._eval_weights_cols(tb, v0, x.dtype)
+            out = _node_linear(x, wp, idx.view(-1)[:n].contiguous(), self._meta, addend=out)
+        return out
 
     def forward_typed(self, x: torch.Tensor, types: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
         if x.is_cuda and not traceable() and self._meta is not None and x.dtype in (torch.float32, torch.float64):
