@@ -18,9 +18,11 @@ prebuilt (the BASELINE model shapes); plans whose structure is not listed run on
 from __future__ import annotations
 
 import hashlib
+import itertools
 import os
 import sys
-from typing import List, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..", "..")))
@@ -103,10 +105,6 @@ def baseline_irreps() -> List[Tuple[str, str, int, str]]:
                 for k in range(1, lmax + 1):
                     out.append((f"{tag}_mid_k{k}", "+".join(hs[:k]), lmax, hidden))
                     out.append((f"{tag}_last_k{k}", "+".join(hs[:k]), lmax, "1x0e"))
-    # experiments: NQA_GEN_EXTRA="name:irreps_in:lmax:irreps_out;..." adds structures (scripts/r2_split_probe.py)
-    for rec in filter(None, os.environ.get("NQA_GEN_EXTRA", "").split(";")):
-        name, f_in, lmax, f_out = rec.split(":")
-        out.append((name, f_in, int(lmax), f_out))
     return out
 
 
@@ -122,147 +120,547 @@ def baseline_structures() -> List[Structure]:
 
 
 # --------------------------------------------------------------------------------------------------------------
+# Decisions.  Everything the emitters need to know about a structure is settled here, before any code is written.
+
+PAIR_BUDGET = 110  # register estimate 2 OD + 3 XD + NP of the pair kernel (l2p_second at 144 spills 127 registers)
+RING_BUDGET = 180  # register estimate of the LDS-ring pair kernel at two wavefronts per SIMD (see plan_structure)
+RING_WAVE_BYTES = 20480  # one wavefront's LDS ring: the CU's 160 KB at two wavefronts per SIMD
+RING_MAX_CHUNKS = 6
+COPY_BYTES = 16  # bytes per lane of one LDS-DMA copy (dword-per-lane reads reach 4.0 TB/s on this part, 16-byte ones 6.7)
+SPLIT_MERGE_BUDGET = 70  # merging l_1 = 0 and 1 into one part (budget 102) spilled 82 registers
+SPLIT_NOHOIST = 64  # owner-side intermediates above which a split part keeps them per pair (l_1 = 3: 79 spilled registers)
 
 
-def _emit(st: Structure) -> str:
-    NB, NY, NS, NP = len(st.in1_ls), len(st.in2_ls), len(st.out_ls), len(st.instr)
-    xpre = [sum(2 * l + 1 for l in st.in1_ls[:b]) for b in range(NB)]
-    ypre = [sum(2 * l + 1 for l in st.in2_ls[:j]) for j in range(NY)]
-    opre = [sum(2 * l + 1 for l in st.out_ls[:s]) for s in range(NS)]
-    XD = sum(2 * l + 1 for l in st.in1_ls)  # dim_in1 / mul
+def _cg(l1: int, l2: int, l3: int) -> np.ndarray:
+    return np.array(wigner_3j(l1, l2, l3), dtype=np.float64)
+
+
+def n_owner_terms(st: Structure, paths: Sequence[int]) -> int:
+    """Owner-side intermediates T_ij = sum_k C_ijk g_k of the pair kernels: one per (path, i, j) with a non-zero 3j row."""
+    n = 0
+    for pth in paths:
+        b, j, s = st.instr[pth]
+        n += int((np.abs(_cg(st.in1_ls[b], st.in2_ls[j], st.out_ls[s])).sum(axis=2) != 0).sum())
+    return n
+
+
+def ring_plan(st: Structure, paths: Sequence[int]):
+    """Chunks of one pair's ring image for `paths`: contiguous path ranges plus the chunk of every input block's x row (not
+    later than its first use) with the smallest largest chunk, for the fewest chunks (at most RING_MAX_CHUNKS) whose ring of
+    chunks + 1 slots fits RING_WAVE_BYTES.  Returns (chunks, slot bytes, path bounds, {block: chunk}), or None.  Sizes are in
+    16-byte units: one component of 64 fp32 channels is 16 of them."""
+    n = len(paths)
+    blocks = sorted({st.instr[p_][0] for p_ in paths})
+    units = [16 + 16 * (2 * st.out_ls[st.instr[p_][2]] + 1) for p_ in paths]  # weight + grad_out segments of each path
+    xunits = {b_: 16 * (2 * st.in1_ls[b_] + 1) for b_ in blocks}
+    yrow_units = (sum(2 * l + 1 for l in st.in2_ls) * 4 + COPY_BYTES - 1) // COPY_BYTES
+    first_of = {}
+    for k_, p_ in enumerate(paths):
+        first_of.setdefault(st.instr[p_][0], k_)
+    for C in range(1, min(n, RING_MAX_CHUNKS) + 1):
+        best = None
+        for cuts in itertools.combinations(range(1, n), C - 1):
+            bounds = [0] + list(cuts) + [n]
+            chunk_of = [0] * n
+            for c_ in range(C):
+                for k_ in range(bounds[c_], bounds[c_ + 1]):
+                    chunk_of[k_] = c_
+            base = [sum(units[bounds[c_]:bounds[c_ + 1]]) for c_ in range(C)]
+            base[0] += 2 * yrow_units
+            for place in itertools.product(*[range(chunk_of[first_of[b_]] + 1) for b_ in blocks]):
+                tot = list(base)
+                for b_, c_ in zip(blocks, place):
+                    tot[c_] += xunits[b_]
+                key = (max(tot), sum(place))
+                if best is None or key < best[0]:
+                    best = (key, bounds, dict(zip(blocks, place)))
+        slot_bytes = best[0][0] * COPY_BYTES
+        if RING_WAVE_BYTES // slot_bytes >= C + 1:
+            return C, slot_bytes, best[1], best[2]
+    return None
+
+
+@dataclass
+class Ring:
+    """Layout of one LDS ring: chunk c of a pair holds the paths cpaths[c] (and the x rows of the blocks placed in it)."""
+    chunks: int
+    slot_bytes: int
+    blocks: List[int]
+    xplace: Dict[int, int]
+    cpaths: List[List[int]]
+    lds_off: List[dict]  # per chunk: (kind, id) -> byte offset inside the slot
+    dma: List[list]  # per chunk: (kind, lds byte offset, lanes, [(lane_lo, lane_hi, id, unit of the segment at lane_lo)])
+    Sgw: List[int]  # stores a chunk is certain to issue: grad_w per path,
+    Sgx: List[int]  # the grad_x row components of the blocks that end in it (+ the unwritten components, in the last chunk)
+    Sgx_atom: List[int]  # (ATOM: the components no path writes are not touched at all)
+
+    @property
+    def slots(self) -> int:
+        return self.chunks + 1
+
+    @property
+    def copies(self) -> int:
+        return sum(len(ins) for ins in self.dma)
+
+
+def ring_layout(st: Structure, paths: Sequence[int], n_unused: int, last_path: Dict[int, int]) -> Optional[Ring]:
+    """Chunk images [w segments][x segments][g segments][y_in][y_out] of the ring planned for `paths` (None: no plan)."""
+    plan = ring_plan(st, paths)
+    if plan is None:
+        return None
+    RC, RSLOT, bounds, xplace = plan
     S = sum(2 * l + 1 for l in st.in2_ls)
-    OD = sum(2 * l + 1 for l in st.out_ls)  # dim_out / mul
+    yrow_units = (S * 4 + COPY_BYTES - 1) // COPY_BYTES
+    blocks = sorted({st.instr[p_][0] for p_ in paths})
+    cpaths = [[paths[k_] for k_ in range(bounds[c_], bounds[c_ + 1])] for c_ in range(RC)]
+    lds_off, dma = [], []
+    for c_ in range(RC):
+        streams = {"w": [(p_, 16) for p_ in cpaths[c_]],
+                   "x": [(b_, 16 * (2 * st.in1_ls[b_] + 1)) for b_ in blocks if xplace[b_] == c_],
+                   "g": [(st.instr[p_][2], 16 * (2 * st.out_ls[st.instr[p_][2]] + 1)) for p_ in cpaths[c_]]}
+        offs, ins, pos = {}, [], 0
+        for kind in ("w", "x", "g"):
+            segs, start = [], 0
+            for ident, units in streams[kind]:
+                offs[(kind, ident)] = (pos + start) * COPY_BYTES
+                segs.append((ident, start, units))
+                start += units
+            for i0 in range(0, start, 64):
+                nl = min(64, start - i0)
+                pieces = []
+                for ident, sstart, units in segs:
+                    lo, hi = max(sstart, i0), min(sstart + units, i0 + nl)
+                    if lo < hi:
+                        pieces.append((lo - i0, hi - i0, ident, lo - sstart))
+                ins.append((kind, (pos + i0) * COPY_BYTES, nl, pieces))
+            pos += start
+        if c_ == 0:
+            offs[("y", "I")] = pos * COPY_BYTES
+            ins.append(("yI", pos * COPY_BYTES, S, None))
+            pos += yrow_units
+            offs[("y", "X")] = pos * COPY_BYTES
+            ins.append(("yX", pos * COPY_BYTES, S, None))
+            pos += yrow_units
+        assert pos * COPY_BYTES <= RSLOT, (st.name, c_, pos * COPY_BYTES, RSLOT)
+        lds_off.append(offs)
+        dma.append(ins)
+    # (the two grad_y stores of the last chunk are not counted: an under-count only shortens the look-ahead by two operations)
+    Sgw = [len(cpaths[c_]) for c_ in range(RC)]
+    Sgx = [sum(2 * st.in1_ls[b_] + 1 for b_ in blocks if last_path[b_] in cpaths[c_]) for c_ in range(RC)]
+    Sgx_atom = list(Sgx)
+    Sgx[RC - 1] += n_unused
+    ring = Ring(RC, RSLOT, blocks, xplace, cpaths, lds_off, dma, Sgw, Sgx, Sgx_atom)
+    assert sum(Sgw) + sum(Sgx) + ring.copies < 64, "vmcnt range"
+    return ring
+
+
+@dataclass
+class Plan:
+    st: Structure
+    NB: int
+    NS: int
+    NP: int
+    XD: int  # dim_in1 / mul
+    S: int
+    OD: int  # dim_out / mul
+    xpre: List[int]
+    ypre: List[int]
+    opre: List[int]
+    coeff: List[float]  # path normalisation
+    slot_coeff: List[Optional[float]]  # per output slot (None: no path writes it)
+    used_blocks: List[int]
+    used_y: List[int]
+    used_slots: List[int]
+    unused_comps: List[int]  # grad_x components of the input blocks no path reads
+    first_path: Dict[int, int]  # input block -> its first / last path (paths are created input-block major)
+    last_path: Dict[int, int]
+    big: bool
+    pair_ok: bool
+    ring: Optional[Ring]  # bwd_pair_ring_kernel
+    part_paths: List[List[int]]  # bwd_pair_split_kernel: the paths of each part
+    pair_parts: int  # 0: no pair kernel, 1: bwd_pair_kernel, > 1: bwd_pair_split_kernel
+    split_rings: List[Ring]  # bwd_pair_split_ring_kernel, per part
+    ring_flag: int  # registered: 0 no ring kernel, 1 bwd_pair_ring_kernel, 2 bwd_pair_split_ring_kernel
+
+
+def plan_structure(st: Structure) -> Plan:
+    NB, NS, NP = len(st.in1_ls), len(st.out_ls), len(st.instr)
+    xpre = [sum(2 * l + 1 for l in st.in1_ls[:b]) for b in range(NB)]
+    ypre = [sum(2 * l + 1 for l in st.in2_ls[:j]) for j in range(len(st.in2_ls))]
+    opre = [sum(2 * l + 1 for l in st.out_ls[:s]) for s in range(NS)]
+    XD = sum(2 * l + 1 for l in st.in1_ls)
+    S = sum(2 * l + 1 for l in st.in2_ls)
+    OD = sum(2 * l + 1 for l in st.out_ls)
     n_into = [0] * NS
     for _, _, s in st.instr:
         n_into[s] += 1
     coeff = [((2 * st.out_ls[s] + 1) / n_into[s]) ** 0.5 for _, _, s in st.instr]
-    used_blocks = sorted({b for b, _, _ in st.instr})
-    used_y = sorted({j for _, j, _ in st.instr})
-    tag = st.tag()
-    # streamed per-edge / per-pair result rows (grad_w, grad_x rows) leave through nontemporal stores: they are read long
-    # after the caches have turned over and should not displace the gathered node rows (same-box A/B: cfg-3 edge backward
-    # 0.24 -> 0.22 ms, cu20k step 22.2 -> 21.8 ms; NQA_GEN_NT=0 at build time restores plain stores)
-    nt_stores = os.environ.get("NQA_GEN_NT", "1") != "0"
-    # weight rows through nontemporal LOADS: measured worse (cfg-3 tp_fwd 0.36 -> 0.39 ms, edge backward 0.21 -> 0.25)
-    nt_loads = os.environ.get("NQA_GEN_NT_LOADS", "0") != "0"
-
-    def emit_store(ptr, val):
-        return f"__builtin_nontemporal_store({val}, {ptr})" if nt_stores else f"*{ptr} = {val}"
+    # slots shared by several instructions have equal coeff per slot (same l3, same n_into)
+    slot_coeff = [None] * NS
+    for p, (_, _, s) in enumerate(st.instr):
+        slot_coeff[s] = coeff[p]
+    first_path, last_path = {}, {}
+    for p, (b, _, _) in enumerate(st.instr):
+        first_path.setdefault(b, p)
+        last_path[b] = p
+    blocks_in_order = [b for b, _, _ in st.instr]
+    assert all(blocks_in_order[first_path[b]:last_path[b] + 1] == [b] * (last_path[b] - first_path[b] + 1) for b in first_path), \
+        "paths are created input-block major (interaction_block.py:89-109)"
+    unused_comps = [i for b in range(NB) if b not in first_path for i in range(xpre[b], xpre[b] + 2 * st.in1_ls[b] + 1)]
     # register-heavy structures (l_max = 3 middle layer): ask for two wavefronts per SIMD so that the compiler does not
     # spend the whole register file on load hoisting at occupancy 1
     big = (OD + 2 * (XD + NP + S)) > 160
-    lb = "__launch_bounds__(256, 2)" if big else "__launch_bounds__(256)"
+    # pair kernel: two grad_out rows, three x rows, the weights in registers.  Measured on cu20k (l_max 3, 269): 298 spilled
+    # registers, fused backward 10 -> 70 ms -- the big structures stay with the per-edge kernels or the split form
+    pair_ok = (2 * OD + 3 * XD + NP) <= PAIR_BUDGET
+    # ring kernel: the owner's grad_out row and the products of it the compiler hoists out of the pair loop, both y rows and
+    # both grad_y accumulators, the owner's x row / its gradient / one block's row gradient (l2n_mid: 177 -> 247 registers;
+    # l3n_mid_k2: 192 -> 27 spilled, whose scratch loads draw hipcc's own vmcnt waits into the loop --
+    # scripts/check_ring_waits.py).  Structures beyond it keep bwd_pair_kernel.
+    ring = None
+    if pair_ok and OD + n_owner_terms(st, range(NP)) + 4 * S + 3 * XD <= RING_BUDGET:
+        ring = ring_layout(st, list(range(NP)), len(unused_comps), last_path)
+    # split form: greedy merge of consecutive input blocks while a (conservative) register budget holds -- the l_max = 3
+    # parts carry 32 grad_y accumulators and up to 49 intermediates per path on top of what `budget` counts
+    part_paths: List[List[int]] = []
+    if not pair_ok:
+        by_block = {}
+        for pth, (b, _, _) in enumerate(st.instr):
+            by_block.setdefault(b, []).append(pth)
+
+        def budget(paths):
+            od = sum(2 * st.out_ls[st.instr[p_][2]] + 1 for p_ in paths)
+            xd = sum(2 * st.in1_ls[b_] + 1 for b_ in {st.instr[p_][0] for p_ in paths})
+            return 2 * od + 3 * xd + len(paths)
+
+        for b in sorted(by_block):
+            if part_paths and budget(part_paths[-1] + by_block[b]) <= SPLIT_MERGE_BUDGET:
+                part_paths[-1] = part_paths[-1] + by_block[b]
+            else:
+                part_paths.append(list(by_block[b]))
+        if not (all(budget(pp) <= PAIR_BUDGET for pp in part_paths) and 1 < len(part_paths) <= 8):
+            part_paths = []
+    pair_parts = len(part_paths) if part_paths else (1 if pair_ok else 0)
+    split_rings = []
+    for part_i, paths in enumerate(part_paths):
+        sr = ring_layout(st, paths, len(unused_comps) if part_i == 0 else 0, last_path)
+        if sr is None:
+            # (the host zeroes grad_y and asks for atomic adds for flag 2, which only the split ring kernel implements)
+            raise ValueError(f"{st.name}: no LDS-ring plan for pair part {part_i} (paths {paths})")
+        split_rings.append(sr)
+    ring_flag = 2 if pair_parts > 1 else (1 if ring is not None else 0)
+    return Plan(st, NB, NS, NP, XD, S, OD, xpre, ypre, opre, coeff, slot_coeff, sorted(first_path),
+                sorted({j for _, j, _ in st.instr}), sorted({s for _, _, s in st.instr}), unused_comps, first_path, last_path,
+                big, pair_ok, ring, part_paths, pair_parts, split_rings, ring_flag)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# Shared pieces of the emitters.
+
+def emit_store(ptr, val):
+    # streamed per-edge / per-pair result rows (grad_w, grad_x rows) leave through nontemporal stores: they are read long after
+    # the caches have turned over (same-box A/B: cfg-3 edge backward 0.24 -> 0.22 ms, cu20k step 22.2 -> 21.8 ms)
+    return f"__builtin_nontemporal_store({val}, {ptr})"
+
+
+def decl_x(p: Plan, indent, sfx=""):
+    return [f"{indent}T xb{b}{sfx}[{2 * p.st.in1_ls[b] + 1}];" for b in p.used_blocks]
+
+
+def decl_y(p: Plan, indent, sfx=""):
+    return [f"{indent}T yb{j}{sfx}[{2 * p.st.in2_ls[j] + 1}];" for j in p.used_y]
+
+
+# Addressing: every row base (x[src], w[e], y[e], g[dst]) is wave-uniform (scalar registers); the per-lane part is a
+# loop-invariant 32-bit element offset computed once from the *clamped* channel uc = min(u, mul-1), so loads need
+# no predication (lanes with u >= mul read channel mul-1 and never store).
+def lane_offsets(p: Plan, indent, want_x=True, want_g=False):
+    st = p.st
+    out = [f"{indent}const unsigned ucb = (unsigned)(u < mul ? u : mul - 1) * (unsigned)sizeof(T);"]
+    if want_x:
+        for b in p.used_blocks:
+            out.append(f"{indent}const unsigned xo{b} = (unsigned)(mul * {p.xpre[b]}) * (unsigned)sizeof(T) + ucb * {2 * st.in1_ls[b] + 1}u;")
+    if want_g:
+        for sl in p.used_slots:
+            out.append(f"{indent}const unsigned go{sl} = (unsigned)(mul * {p.opre[sl]}) * (unsigned)sizeof(T) + ucb * {2 * st.out_ls[sl] + 1}u;")
+    return out
+
+
+def load_x(p: Plan, indent, row, sfx="", decl=True):
+    out = decl_x(p, indent, sfx) if decl else []
+    for b in p.used_blocks:
+        for i in range(2 * p.st.in1_ls[b] + 1):
+            out.append(f"{indent}xb{b}{sfx}[{i}] = spec_at({row}, xo{b})[{i}];")
+    return out
+
+
+def load_y(p: Plan, indent, row, sfx="", decl=True):
+    out = decl_y(p, indent, sfx) if decl else []
+    for j in p.used_y:
+        for i in range(2 * p.st.in2_ls[j] + 1):
+            out.append(f"{indent}yb{j}{sfx}[{i}] = {row}[{p.ypre[j] + i}];")
+    return out
+
+
+def load_w(p: Plan, indent, row, scale=False, sfx="", decl=True):
+    # plain loads: nontemporal weight loads measured worse (cfg-3 tp_fwd 0.36 -> 0.39 ms, edge backward 0.21 -> 0.25)
+    out = [f"{indent}T wv{sfx}[kNP];"] if decl else []
+    for pth in range(p.NP):
+        c = f"T({p.coeff[pth]!r}) * " if scale else ""
+        out.append(f"{indent}wv{sfx}[{pth}] = {c}*spec_at({row} + (unsigned)(mul * {pth}), ucb);")
+    return out
+
+
+def load_g(p: Plan, indent, rowexpr, name):
+    """A grad_out row, scaled by the path coefficients and zeroed on inactive lanes, into `name`."""
+    out = [f"{indent}{{ const T* __restrict__ gb = {rowexpr};"]
+    for s_ in range(p.NS):
+        for k in range(2 * p.st.out_ls[s_] + 1):
+            if p.slot_coeff[s_] is None:
+                out.append(f"{indent}  {name}[{p.opre[s_] + k}] = T(0);")
+            else:
+                out.append(f"{indent}  {name}[{p.opre[s_] + k}] = spec_at(gb, go{s_})[{k}];")
+    for s_ in range(p.NS):
+        if p.slot_coeff[s_] is None:
+            continue
+        for k in range(2 * p.st.out_ls[s_] + 1):
+            out.append(f"{indent}  {name}[{p.opre[s_] + k}] = act ? T({p.slot_coeff[s_]!r}) * {name}[{p.opre[s_] + k}] : T(0);")
+    out.append(f"{indent}}}")
+    return out
+
+
+def path_terms(p: Plan, out, pth, xs, gname, ys, tag_, ind, dual):
+    """One path of one directed edge of the pair kernels: B{tag}{jj} (-> grad_w, grad_y) into `out`; returns the live jj and
+    the grad_x terms per input component.  dual: also the D{tag}{jj} of DUAL (B from the cotangent rows x2, D from x)."""
+    b_, j, s_ = p.st.instr[pth]
+    l1, l2, l3 = p.st.in1_ls[b_], p.st.in2_ls[j], p.st.out_ls[s_]
+    d1, d2, d3 = 2 * l1 + 1, 2 * l2 + 1, 2 * l3 + 1
+    C = _cg(l1, l2, l3)
+    started = [False] * d2
+    gx_terms = []
+    for i in range(d1):
+        a_terms = []
+        for jj in range(d2):
+            ks = [k for k in range(d3) if C[i, jj, k] != 0.0]
+            if not ks:
+                continue
+            expr = " + ".join(f"T({float(C[i, jj, k])!r}) * {gname}[{p.opre[s_] + k}]" for k in ks)
+            out.append(f"{ind}const T t{tag_}{i}_{jj} = {expr};")
+            xa = f"(DUAL ? xb{b_}{xs}2[{i}] : xb{b_}{xs}[{i}])" if dual else f"xb{b_}{xs}[{i}]"
+            if started[jj]:
+                out.append(f"{ind}B{tag_}{jj} += {xa} * t{tag_}{i}_{jj};")
+                if dual:
+                    out.append(f"{ind}if (DUAL) D{tag_}{jj} += xb{b_}{xs}[{i}] * t{tag_}{i}_{jj};")
+            else:
+                out.append(f"{ind}T B{tag_}{jj} = {xa} * t{tag_}{i}_{jj};")
+                if dual:
+                    out.append(f"{ind}T D{tag_}{jj} = DUAL ? xb{b_}{xs}[{i}] * t{tag_}{i}_{jj} : T(0);")
+                started[jj] = True
+            a_terms.append(f"yb{j}{ys}[{jj}] * t{tag_}{i}_{jj}")
+        gx_terms.append((p.xpre[b_] + i, " + ".join(a_terms) if a_terms else None))
+    return [jj for jj in range(d2) if started[jj]], gx_terms
+
+
+def src_base(p: Plan, kind, ident):
+    """Byte offset of a ring copy's segment from its row base (weight column / x block / grad_out slot of this chunk)."""
+    if kind == "w":
+        return f"(unsigned)(mul * {ident} + chunk * 64) * 4u"
+    if kind == "x":
+        return f"(unsigned)(mul * {p.xpre[ident]} + chunk * {64 * (2 * p.st.in1_ls[ident] + 1)}) * 4u"
+    return f"(unsigned)(mul * {p.opre[ident]} + chunk * {64 * (2 * p.st.out_ls[ident] + 1)}) * 4u"
+
+
+def ring_lane_offsets(p: Plan, r: Ring, ind, ro):
+    """Per-lane source offsets of the copies that span several segments (one segment: its uniform offset goes into the
+    scalar base, the lanes share l16)."""
+    out = []
+    for c_ in range(r.chunks):
+        for i_, (kind, loff, nl, pieces) in enumerate(r.dma[c_]):
+            if pieces is None or len(pieces) == 1:
+                continue
+            expr = None
+            for lo, hi, ident, seg_unit in reversed(pieces):
+                e_ = f"{src_base(p, kind, ident)} + (unsigned)({(seg_unit - lo) * COPY_BYTES})"
+                expr = e_ if expr is None else f"(lane < {hi} ? {e_} : {expr})"
+            out.append(f"{ind}const unsigned {ro}{c_}_{i_} = ({expr}) + l16;")
+    return out
+
+
+def ring_copies(p: Plan, r: Ring, ind, c_, sfx, slotexpr, slot_bytes, ro, lgkm_note, lgkm=True):
+    """Copies of chunk c_ of the pair whose indices are in jn{sfx} / pr{sfx} / ei{sfx} / eo{sfx} into LDS slot `slotexpr`.
+    Only the weight rows are copied nontemporally: they are read once (lab: 545 -> 533 us; x / g too: slower)."""
+    out = [f"{ind}{{ const unsigned sb_ = wbase + (unsigned)({slotexpr}) * {slot_bytes};"]
+    if lgkm:
+        out.append(f"{ind}  spec_wait_lgkm();{lgkm_note}")
+    kinds = {k_ for k_, _, _, _ in r.dma[c_]}
+    if "w" in kinds:
+        out.append(f"{ind}  const T* __restrict__ wr_ = a.w + (int64_t)pr{sfx} * a.wn;")
+    if "x" in kinds:
+        out.append(f"{ind}  const T* __restrict__ xr_ = a.x + (int64_t)jn{sfx} * a.din;")
+    if "g" in kinds:
+        out.append(f"{ind}  const T* __restrict__ gr_ = a.g + (int64_t)jn{sfx} * a.dout;")
+    for i_, (kind, loff, nl, pieces) in enumerate(r.dma[c_]):
+        if kind == "yI":
+            out.append(f"{ind}  spec_glds4<{nl}>(sb_ + {loff}u, a.y + (int64_t)ei{sfx} * kS, l4);")
+        elif kind == "yX":
+            out.append(f"{ind}  spec_glds4<{nl}>(sb_ + {loff}u, a.y + (int64_t)eo{sfx} * kS, l4);")
+        else:
+            nt_ = ", true" if kind == "w" else ""
+            if len(pieces) == 1:
+                lo_, _, ident_, seg_unit_ = pieces[0]
+                uoff = f"{src_base(p, kind, ident_)} + (unsigned)({(seg_unit_ - lo_) * COPY_BYTES})"
+                out.append(f"{ind}  spec_glds16<{nl}{nt_}>(sb_ + {loff}u, reinterpret_cast<const char*>({kind}r_) + ({uoff}), l16);")
+            else:
+                out.append(f"{ind}  spec_glds16<{nl}{nt_}>(sb_ + {loff}u, {kind}r_, {ro}{c_}_{i_});")
+    out.append(f"{ind}}}")
+    return out
+
+
+def ring_waits(r: Ring, c_, ind):
+    """Counted wait before chunk c_ is read: the copies and stores issued since its own copies (tp_spec.h spec_wait_vm)."""
+    nfirst = r.copies + sum(r.Sgw[:c_])
+    nfirst_gx = f"(ATOM ? {nfirst + sum(r.Sgx_atom[:c_])} : {nfirst + sum(r.Sgx[:c_])})"
+    nsteady = r.copies + sum(r.Sgw)
+    nsteady_gx = f"(ATOM ? {nsteady + sum(r.Sgx_atom)} : {nsteady + sum(r.Sgx)})"
+    return [f"{ind}if (!hasB) spec_wait_vm<0>();",
+            f"{ind}else if (first) spec_wait_vm<GX ? {nfirst_gx} : {nfirst}>();",
+            f"{ind}else spec_wait_vm<GX ? {nsteady_gx} : {nsteady}>();"]
+
+
+def ring_operand_reads(p: Plan, r: Ring, c_, ys, ind):
+    """The y rows (chunk 0) and the x blocks placed in chunk c_, from its LDS image into registers."""
+    lo, out = r.lds_off[c_], []
+    if c_ == 0:
+        for j in ys:
+            for i in range(2 * p.st.in2_ls[j] + 1):
+                out.append(f"{ind}yb{j}I[{i}] = *reinterpret_cast<const T*>(cb + {lo[('y', 'I')] + 4 * (p.ypre[j] + i)});")
+                out.append(f"{ind}yb{j}X[{i}] = *reinterpret_cast<const T*>(cb + {lo[('y', 'X')] + 4 * (p.ypre[j] + i)});")
+    for b_ in r.blocks:
+        if r.xplace[b_] == c_:
+            d1 = 2 * p.st.in1_ls[b_] + 1
+            for i in range(d1):
+                out.append(f"{ind}xb{b_}J[{i}] = *reinterpret_cast<const T*>(cb + {lo[('x', b_)]} + l4 * {d1}u + {4 * i});")
+    return out
+
+
+def wave_reduce_lines(n, acc):
+    """WPN > 1: the wavefronts of a node add their `n` accumulators through the LDS into wavefront 0's."""
+    return ["  if (WPN > 1) {",
+            "    extern __shared__ __align__(16) unsigned char nqa_smem[];",
+            "    T* red = reinterpret_cast<T*>(nqa_smem);",
+            "    if (wsub > 0) {",
+            "#pragma unroll",
+            f"      for (int k = 0; k < {n}; ++k) red[((wsub - 1) * {n} + k) * 64 + lane] = {acc}[k];",
+            "    }",
+            "    __syncthreads();",
+            "    if (wsub > 0) return;",
+            "#pragma unroll",
+            f"    for (int k = 0; k < {n}; ++k) {{",
+            "#pragma unroll",
+            f"      for (int w2 = 0; w2 < WPN - 1; ++w2) {acc}[k] += red[(w2 * {n} + k) * 64 + lane];",
+            "    }",
+            "  }"]
+
+
+def store_x_rows(p: Plan, ind, blocks, uvar, val):
+    """One node's grad_x row in the irreps layout; val(component) gives the value."""
+    out = []
+    for b in blocks:
+        d = 2 * p.st.in1_ls[b] + 1
+        for i in range(d):
+            out.append(f"{ind}ob[(int64_t)mul * {p.xpre[b]} + (int64_t){uvar} * {d} + {i}] = {val(p.xpre[b] + i)};")
+    return out
+
+
+# --------------------------------------------------------------------------------------------------------------
+# Emitters: one per kernel family, each returns its lines.
+
+def emit_header(p: Plan) -> List[str]:
+    st = p.st
+    return [f"// GENERATED by gen_spec.py for structure '{st.name}': {st.key()}",
+            "// Edge-outer specialised TensorProductScatter kernels (see gen_spec.py docstring).",
+            '#include <hip/hip_runtime.h>',
+            '#include <cstdint>',
+            '#include "../generated/cg_generated.h"',
+            '#include "../tp_spec.h"',
+            "namespace nqa {",
+            "namespace {",
+            f"constexpr int kXD = {p.XD}, kS = {p.S}, kOD = {p.OD}, kNP = {p.NP};",
+            "typedef float f2 __attribute__((ext_vector_type(2)));  // one v_pk_*_f32 operand: two fp32 values in a register pair"]
+
+
+def _node_kernel_prologue(L):
+    """Item / node / chunk of fwd_kernel and bwd_x_kernel (WPN == 1: four nodes per workgroup, else one)."""
+    L += ["  const int lane = threadIdx.x & 63;",
+          "  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
+          "  const int mul = a.mul;",
+          "  const int nchunk = (mul + 63) >> 6;",
+          "  int64_t item; int wsub;",
+          "  const unsigned bid = spec_xcd_remap(blockIdx.x, gridDim.x);",
+          "  if (WPN == 1) { item = (int64_t)bid * 4 + wid; wsub = 0; } else { item = bid; wsub = wid; }",
+          "  const bool valid = item < (int64_t)a.N * nchunk;",
+          "  if (WPN == 1 && !valid) return;",
+          "  const int node = spec_uniform(valid ? (int)(item / nchunk) : 0);",
+          "  const int chunk = (int)(item - (int64_t)node * nchunk);",
+          "  const int u = chunk * 64 + lane;",
+          "  const bool act = valid && (u < mul);"]
+
+
+def _edge_kernel_prologue(L):
+    """Item / node / chunk of the kernels that spread WPN wavefronts over a node (four wavefronts per workgroup)."""
+    L += ["  const int lane = threadIdx.x & 63;",
+          "  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));",
+          "  const int mul = a.mul;",
+          "  const int nchunk = (mul + 63) >> 6;",
+          "  const int64_t witem = (int64_t)spec_xcd_remap(blockIdx.x, gridDim.x) * 4 + wid;",
+          "  const int64_t item = witem / WPN;",
+          "  const int wsub = (int)(witem - item * WPN);"]
+
+
+def emit_fwd(p: Plan) -> List[str]:
+    st = p.st
+    lb = "__launch_bounds__(256, 2)" if p.big else "__launch_bounds__(256)"
     L = []
     A = L.append
-    A(f"// GENERATED by gen_spec.py for structure '{st.name}': {st.key()}")
-    A("// Edge-outer specialised TensorProductScatter kernels (see gen_spec.py docstring).")
-    A('#include <hip/hip_runtime.h>')
-    A('#include <cstdint>')
-    A('#include "../generated/cg_generated.h"')
-    A('#include "../tp_spec.h"')
-    A("namespace nqa {")
-    A("namespace {")
-    A(f"constexpr int kXD = {XD}, kS = {S}, kOD = {OD}, kNP = {NP};")
-    if os.environ.get("NQA_GEN_PAIR_TIMING", "0") != "0":
-        A("__device__ unsigned long long nqa_lab_tm[8];")
-    A("typedef float f2 __attribute__((ext_vector_type(2)));  // one v_pk_*_f32 operand: two fp32 values in a register pair")
-
-    def decl_x(indent, sfx=""):
-        return [f"{indent}T xb{b}{sfx}[{2 * st.in1_ls[b] + 1}];" for b in used_blocks]
-
-    def decl_y(indent, sfx=""):
-        return [f"{indent}T yb{j}{sfx}[{2 * st.in2_ls[j] + 1}];" for j in used_y]
-
-    # Addressing: every row base (x[src], w[e], y[e], g[dst]) is wave-uniform (scalar registers); the per-lane part is a
-    # loop-invariant 32-bit element offset computed once from the *clamped* channel uc = min(u, mul-1), so loads need
-    # no predication (lanes with u >= mul read channel mul-1 and never store).
-    def lane_offsets(indent, want_x=True, want_g=False):
-        out = [f"{indent}const unsigned ucb = (unsigned)(u < mul ? u : mul - 1) * (unsigned)sizeof(T);"]
-        if want_x:
-            for b in used_blocks:
-                out.append(f"{indent}const unsigned xo{b} = (unsigned)(mul * {xpre[b]}) * (unsigned)sizeof(T) + ucb * {2 * st.in1_ls[b] + 1}u;")
-        if want_g:
-            for sl in sorted({s_ for _, _, s_ in st.instr}):
-                out.append(f"{indent}const unsigned go{sl} = (unsigned)(mul * {opre[sl]}) * (unsigned)sizeof(T) + ucb * {2 * st.out_ls[sl] + 1}u;")
-        return out
-
-    def load_x(indent, row, sfx="", decl=True):
-        out = decl_x(indent, sfx) if decl else []
-        for b in used_blocks:
-            d = 2 * st.in1_ls[b] + 1
-            for i in range(d):
-                out.append(f"{indent}xb{b}{sfx}[{i}] = spec_at({row}, xo{b})[{i}];")
-        return out
-
-    def load_y(indent, row, sfx="", decl=True):
-        out = decl_y(indent, sfx) if decl else []
-        for j in used_y:
-            d = 2 * st.in2_ls[j] + 1
-            for i in range(d):
-                out.append(f"{indent}yb{j}{sfx}[{i}] = {row}[{ypre[j] + i}];")
-        return out
-
-    def load_w(indent, row, scale=False, sfx="", decl=True):
-        out = [f"{indent}T wv{sfx}[kNP];"] if decl else []
-        for p in range(NP):
-            c = f"T({coeff[p]!r}) * " if scale else ""
-            ld = (f"__builtin_nontemporal_load(spec_at({row} + (unsigned)(mul * {p}), ucb))" if nt_loads
-                  else f"*spec_at({row} + (unsigned)(mul * {p}), ucb)")
-            out.append(f"{indent}wv{sfx}[{p}] = {c}{ld};")
-        return out
-
-    # ------------------------------------------------------------------ forward
     A("// JVP (second-order backward of training: the gradient w.r.t. grad_out): out = F(x2, y, w) + F(x, y2, w) + F(x, y, w2) in")
     A("// one pass over the edges; a term whose cotangent pointer (a.x2 / a.y2 / a.w2) is NULL is skipped (wave-uniform).")
     A("template <typename T, int WPN, bool JVP = false>")
     # (four wavefronts per SIMD would need 128 registers: 19-48 spills in the pipelined loop, measured 2.2x slower)
     A(f"__global__ {lb} void fwd_kernel(const SpecArgs<T> a) {{")
-    A("  const int lane = threadIdx.x & 63;")
-    A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
-    A("  const int mul = a.mul;")
-    A("  const int nchunk = (mul + 63) >> 6;")
-    A("  int64_t item; int wsub;")
-    A("  const unsigned bid = spec_xcd_remap(blockIdx.x, gridDim.x);")
-    A("  if (WPN == 1) { item = (int64_t)bid * 4 + wid; wsub = 0; } else { item = bid; wsub = wid; }")
-    A("  const bool valid = item < (int64_t)a.N * nchunk;")
-    A("  if (WPN == 1 && !valid) return;")
-    A("  const int node = spec_uniform(valid ? (int)(item / nchunk) : 0);")
-    A("  const int chunk = (int)(item - (int64_t)node * nchunk);")
-    A("  const int u = chunk * 64 + lane;")
-    A("  const bool act = valid && (u < mul);")
-    L.extend(lane_offsets("  "))
+    _node_kernel_prologue(L)
+    L.extend(lane_offsets(p, "  "))
     A(f"  T acc[kOD];")
     A("#pragma unroll")
     A("  for (int k = 0; k < kOD; ++k) acc[k] = T(0);")
     A("  const int beg = a.rowptr[node], end = valid ? a.rowptr[node + 1] : beg;")
     # register budget: accumulators + two operand sets; big structures (l_max = 3 middle layer: 99 accumulators, 23
     # paths) would hit the 256-VGPR wall at one wavefront per SIMD, so they run the plain loop at twice the occupancy
-    pipelined = not big
+    pipelined = not p.big
     if pipelined:
         A("  // Two register sets (A/B): the operands of edge i+1 are requested before edge i is evaluated, the indices of")
         A("  // edge i+2 before that -- every HBM/L2 round trip of an edge hides behind the arithmetic of the previous one.")
-        L.extend(["  T wvA[kNP], wvB[kNP];"] + decl_x("  ", "A") + decl_x("  ", "B") + decl_y("  ", "A") + decl_y("  ", "B"))
-        L.extend(["  T wv2A[kNP], wv2B[kNP];"] + decl_x("  ", "A2") + decl_x("  ", "B2") + decl_y("  ", "A2") + decl_y("  ", "B2"))
+        L.extend(["  T wvA[kNP], wvB[kNP];"] + decl_x(p, "  ", "A") + decl_x(p, "  ", "B") + decl_y(p, "  ", "A") + decl_y(p, "  ", "B"))
+        L.extend(["  T wv2A[kNP], wv2B[kNP];"] + decl_x(p, "  ", "A2") + decl_x(p, "  ", "B2") + decl_y(p, "  ", "A2") + decl_y(p, "  ", "B2"))
     else:
-        L.extend(["  T wvA[kNP];"] + decl_x("  ", "A") + decl_y("  ", "A"))
-        L.extend(["  T wv2A[kNP];"] + decl_x("  ", "A2") + decl_y("  ", "A2"))
+        L.extend(["  T wvA[kNP];"] + decl_x(p, "  ", "A") + decl_y(p, "  ", "A"))
+        L.extend(["  T wv2A[kNP];"] + decl_x(p, "  ", "A2") + decl_y(p, "  ", "A2"))
 
     def fwd_loads(sfx, e, sv, r):
         out = [f"    {{ const T* __restrict__ xr = a.x + (int64_t){sv} * a.din;",
                f"      const T* __restrict__ wr = a.w + (int64_t){r} * a.wn;",
                f"      const T* __restrict__ yr = a.y + (int64_t){e} * kS;"]
-        out += load_w("      ", "wr", sfx=sfx, decl=False)
-        out += load_x("      ", "xr", sfx=sfx, decl=False)
-        out += load_y("      ", "yr", sfx=sfx, decl=False)
+        out += load_w(p, "      ", "wr", sfx=sfx, decl=False)
+        out += load_x(p, "      ", "xr", sfx=sfx, decl=False)
+        out += load_y(p, "      ", "yr", sfx=sfx, decl=False)
         out.append("      if (JVP) {")
         out.append("        if (a.x2 != nullptr) {")
-        out += load_x("          ", f"(a.x2 + (int64_t){sv} * a.din)", sfx=sfx + "2", decl=False)
+        out += load_x(p, "          ", f"(a.x2 + (int64_t){sv} * a.din)", sfx=sfx + "2", decl=False)
         out.append("        }")
         out.append("        if (a.y2 != nullptr) {")
-        out += load_y("          ", f"(a.y2 + (int64_t){e} * kS)", sfx=sfx + "2", decl=False)
+        out += load_y(p, "          ", f"(a.y2 + (int64_t){e} * kS)", sfx=sfx + "2", decl=False)
         out.append("        }")
         out.append("        if (a.w2 != nullptr) {")
-        out += load_w("          ", f"(a.w2 + (int64_t){r} * a.wn)", sfx="2" + sfx, decl=False)
+        out += load_w(p, "          ", f"(a.w2 + (int64_t){r} * a.wn)", sfx="2" + sfx, decl=False)
         out.append("        }")
         out.append("      }")
         out.append("    }")
@@ -270,20 +668,20 @@ def _emit(st: Structure) -> str:
 
     def fwd_compute(sfx):
         out = []
-        for p, (b, j, sl) in enumerate(st.instr):
+        for pth, (b, j, sl) in enumerate(st.instr):
             l1, l2, l3 = st.in1_ls[b], st.in2_ls[j], st.out_ls[sl]
             d3 = 2 * l3 + 1
             out.append("    if (!JVP) {")
             out.append(f"      T t[{d3}]; CGT<{l1},{l2},{l3}>::template ab_c<T>(xb{b}{sfx}, yb{j}{sfx}, t);")
             for k in range(d3):
-                out.append(f"      acc[{opre[sl] + k}] += wv{sfx}[{p}] * t[{k}];")
+                out.append(f"      acc[{p.opre[sl] + k}] += wv{sfx}[{pth}] * t[{k}];")
             out.append("    } else {")
-            for cond, xa, ya, wa in ((f"a.w2 != nullptr", f"xb{b}{sfx}", f"yb{j}{sfx}", f"wv2{sfx}[{p}]"),
-                                     (f"a.x2 != nullptr", f"xb{b}{sfx}2", f"yb{j}{sfx}", f"wv{sfx}[{p}]"),
-                                     (f"a.y2 != nullptr", f"xb{b}{sfx}", f"yb{j}{sfx}2", f"wv{sfx}[{p}]")):
+            for cond, xa, ya, wa in ((f"a.w2 != nullptr", f"xb{b}{sfx}", f"yb{j}{sfx}", f"wv2{sfx}[{pth}]"),
+                                     (f"a.x2 != nullptr", f"xb{b}{sfx}2", f"yb{j}{sfx}", f"wv{sfx}[{pth}]"),
+                                     (f"a.y2 != nullptr", f"xb{b}{sfx}", f"yb{j}{sfx}2", f"wv{sfx}[{pth}]")):
                 out.append(f"      if ({cond}) {{ T t[{d3}]; CGT<{l1},{l2},{l3}>::template ab_c<T>({xa}, {ya}, t);")
                 for k in range(d3):
-                    out.append(f"        acc[{opre[sl] + k}] += {wa} * t[{k}];")
+                    out.append(f"        acc[{p.opre[sl] + k}] += {wa} * t[{k}];")
                 out.append("      }")
             out.append("    }")
         return out
@@ -326,69 +724,40 @@ def _emit(st: Structure) -> str:
         L.extend(fwd_compute("A"))
         A("    idx = nidx; e0 = e_n; s0 = s_n; r0 = r_n;")
         A("  }")
-    # scale by path coefficient: slots shared by several instructions have equal coeff per slot (same l3, same n_into)
-    slot_coeff = [None] * NS
-    for p, (_, _, s) in enumerate(st.instr):
-        slot_coeff[s] = coeff[p]
-    A("  if (WPN > 1) {")
-    A("    extern __shared__ __align__(16) unsigned char nqa_smem[];")
-    A("    T* red = reinterpret_cast<T*>(nqa_smem);")
-    A("    if (wsub > 0) {")
-    A("#pragma unroll")
-    A("      for (int k = 0; k < kOD; ++k) red[((wsub - 1) * kOD + k) * 64 + lane] = acc[k];")
-    A("    }")
-    A("    __syncthreads();")
-    A("    if (wsub > 0) return;")
-    A("#pragma unroll")
-    A("    for (int k = 0; k < kOD; ++k) {")
-    A("#pragma unroll")
-    A("      for (int w2 = 0; w2 < WPN - 1; ++w2) acc[k] += red[(w2 * kOD + k) * 64 + lane];")
-    A("    }")
-    A("  }")
+    L.extend(wave_reduce_lines("kOD", "acc"))
     A("  if (act) {")
     A("    T* __restrict__ ob = a.out + (int64_t)node * a.dout;")
-    for s in range(NS):
+    for s in range(p.NS):
         d3 = 2 * st.out_ls[s] + 1
-        if slot_coeff[s] is None:
-            for k in range(d3):
-                A(f"    ob[(int64_t)mul * {opre[s]} + (int64_t)u * {d3} + {k}] = T(0);")
-        else:
-            for k in range(d3):
-                A(f"    ob[(int64_t)mul * {opre[s]} + (int64_t)u * {d3} + {k}] = T({slot_coeff[s]!r}) * acc[{opre[s] + k}];")
+        for k in range(d3):
+            val = "T(0)" if p.slot_coeff[s] is None else f"T({p.slot_coeff[s]!r}) * acc[{p.opre[s] + k}]"
+            A(f"    ob[(int64_t)mul * {p.opre[s]} + (int64_t)u * {d3} + {k}] = {val};")
     A("  }")
     A("}")
+    return L
 
-    # ------------------------------------------------------------------ backward (edge operands)
+
+def emit_bwd_edge(p: Plan) -> List[str]:
     # One contraction serves both edge gradients:  B^p_j = sum_ik C^p_ijk x_i g_k  gives  gw_p = sum_j y_j B^p_j  and
     # gy_j += w_p B^p_j.  FUSED additionally forms A^p_i = sum_jk C^p_ijk y_j g_k and emits the edge's contribution
     # w_p A^p_i to grad_x[src] (grad_out[dst] is already in registers), summed per source node afterwards.
     # FULL: mul is a multiple of 64, every lane owns a channel -- `act` is a compile-time true, so the per-path stores
     # inside the edge loop are plain stores instead of one exec-mask branch region each (16 of them split the loop body
     # of the l_max = 2 middle layer into as many scheduling regions)
+    st = p.st
+    L = []
+    A = L.append
     A("template <typename T, int WPN, bool FUSED, bool GW, bool GY, bool FULL>")
-    # l_max <= 2 structures sit at ~130 VGPRs: asking for four wavefronts per SIMD (128 registers) costs a couple of
-    # spills and buys a third more loads in flight; the big l_max = 3 structures spill heavily under any bound
-    # generator switch (build time): pipe3 = two operand sets at three wavefronts per SIMD (default; same-box cfg-3:
-    # fused backward 0.80 ms vs 0.86 for occ4 = plain loop at four wavefronts and 0.91 for plain = plain loop at three)
-    be_mode = os.environ.get("NQA_GEN_BWD_EDGE", "pipe3")
-    # big structures (l_max = 3 middle layer: 99 accumulators, 23 paths) run at one wavefront per SIMD whatever is asked
-    # (forcing two costs 28 spilled registers and 20 % of the kernel, measured), so nothing hides an edge's load latency
-    # but the wavefront itself.  Giving them the two operand sets as well, out of the 512 registers (VGPR + AGPR) a lone
-    # wavefront owns (NQA_GEN_BIG_PIPE=1), was measured too: 357 registers, no gain on cu20k (9.98 vs 9.36 ms), and the
-    # 312-accumulator parity structure then spills 800 registers -- the plain loop stays
-    big_pipe = os.environ.get("NQA_GEN_BIG_PIPE", "0") != "0"
-    be_pipelined = be_mode == "pipe3" and (not big or big_pipe)
-    fused_occ = os.environ.get("NQA_GEN_FUSED_OCC", "3")  # wavefronts per SIMD asked for the fused instantiation
-    be_lb = ("__launch_bounds__(256)" if (big or be_mode == "plain")
-             else (f"__launch_bounds__(256, FUSED ? {fused_occ} : 3)" if be_pipelined else "__launch_bounds__(256, 4)"))
+    # two operand sets at three wavefronts per SIMD (same-box cfg-3: fused backward 0.80 ms vs 0.86 for a plain loop at four
+    # wavefronts and 0.91 for a plain loop at three).  Big structures (l_max = 3 middle layer: 99 accumulators, 23 paths)
+    # run the plain loop at one wavefront per SIMD: forcing two costs 28 spilled registers and 20 % of the kernel; two
+    # operand sets out of a lone wavefront's 512 registers gained nothing on cu20k (9.98 vs 9.36 ms)
+    # (the emitted text is pinned by generated_spec.manifest.json: the redundant `FUSED ? 3 : 3`, the never-read `rr` and
+    # `probe_sink` stay until a change that re-pins the manifest)
+    pipelined = not p.big
+    be_lb = "__launch_bounds__(256)" if p.big else "__launch_bounds__(256, FUSED ? 3 : 3)"
     A(f"__global__ {be_lb} void bwd_edge_kernel(const SpecArgs<T> a) {{")
-    A("  const int lane = threadIdx.x & 63;")
-    A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
-    A("  const int mul = a.mul;")
-    A("  const int nchunk = (mul + 63) >> 6;")
-    A("  const int64_t witem = (int64_t)spec_xcd_remap(blockIdx.x, gridDim.x) * 4 + wid;")
-    A("  const int64_t item = witem / WPN;")
-    A("  const int wsub = (int)(witem - item * WPN);")
+    _edge_kernel_prologue(L)
     A("  if (item >= (int64_t)a.N * nchunk) return;")
     A("  const int node = spec_uniform((int)(item / nchunk));")
     A("  const int chunk = (int)(item - (int64_t)node * nchunk);")
@@ -396,79 +765,46 @@ def _emit(st: Structure) -> str:
     A("  const bool act = FULL || (u < mul);")
     A("  const int beg = a.rowptr[node], end = a.rowptr[node + 1];")
     A("  if (beg + wsub >= end) return;")
-    L.extend(lane_offsets("  ", want_x=True, want_g=True))
+    L.extend(lane_offsets(p, "  ", want_x=True, want_g=True))
     A("  T gv[kOD];")
     A("  {")
     A("    // unpredicated loads from the clamped channel (all requests in flight at once, contiguous components merge into")
     A("    // wide loads), masked afterwards: `act ? load : 0` per element compiles into one branch + load + wait per value,")
     A("    // i.e. kOD serial memory round trips before the first edge")
     A("    const T* __restrict__ gb = a.g + (int64_t)node * a.dout;")
-    for s_ in range(NS):
-        d3 = 2 * st.out_ls[s_] + 1
-        if slot_coeff[s_] is None:
-            for k in range(d3):
-                A(f"    gv[{opre[s_] + k}] = T(0);")
+    for s_ in range(p.NS):
+        for k in range(2 * st.out_ls[s_] + 1):
+            A(f"    gv[{p.opre[s_] + k}] = T(0);" if p.slot_coeff[s_] is None else f"    gv[{p.opre[s_] + k}] = spec_at(gb, go{s_})[{k}];")
+    for s_ in range(p.NS):
+        if p.slot_coeff[s_] is None:
             continue
-        for k in range(d3):
-            A(f"    gv[{opre[s_] + k}] = spec_at(gb, go{s_})[{k}];")
-    for s_ in range(NS):
-        d3 = 2 * st.out_ls[s_] + 1
-        if slot_coeff[s_] is None:
-            continue
-        for k in range(d3):
-            A(f"    gv[{opre[s_] + k}] = act ? T({slot_coeff[s_]!r}) * gv[{opre[s_] + k}] : T(0);")
+        for k in range(2 * st.out_ls[s_] + 1):
+            A(f"    gv[{p.opre[s_] + k}] = act ? T({p.slot_coeff[s_]!r}) * gv[{p.opre[s_] + k}] : T(0);")
     A("  }")
 
     def be_loads(sfx, e, sv, rg):
         out = [f"    {{ const T* __restrict__ xr = a.x + (int64_t){sv} * a.din;",
                f"      const T* __restrict__ yr = a.y + (int64_t){e} * kS;",
                f"      const T* __restrict__ wr = a.w + (int64_t)spec_wrow_of(a, {rg}) * a.wn;"]
-        if probe & 8:
-            out.append("      if (!FUSED) {")
-            out += load_x("        ", "xr", sfx=sfx, decl=False)
-            out.append("      } else {")
-            for b in used_blocks:
-                for i in range(2 * st.in1_ls[b] + 1):
-                    out.append(f"        xb{b}{sfx}[{i}] = T(0.5) + T({i}) * probe_sink;")
-            out.append("      }")
-        else:
-            out += load_x("      ", "xr", sfx=sfx, decl=False)
+        out += load_x(p, "      ", "xr", sfx=sfx, decl=False)
         out.append("      if (GY || FUSED) {")
-        if probe & 2:
-            out.append("        if (!FUSED) {")
-            out += load_w("          ", "wr", sfx=sfx, decl=False)
-            out.append("        } else {")
-            for p in range(NP):
-                out.append(f"          wv{sfx}[{p}] = T({0.3 + 0.01 * p!r}) + probe_sink;")
-            out.append("        }")
-        else:
-            out += load_w("        ", "wr", sfx=sfx, decl=False)
+        out += load_w(p, "        ", "wr", sfx=sfx, decl=False)
         out.append("      }")
         out.append("      if (GW || FUSED) {")
-        out += load_y("        ", "yr", sfx=sfx, decl=False)
+        out += load_y(p, "        ", "yr", sfx=sfx, decl=False)
         out.append("      }")
         out.append("    }")
         return out
-
-    # timing probes of the fused backward (wrong results, never shipped): bit 1 no grad_w stores, 2 no weight loads,
-    # 4 no per-edge grad_x rows, 8 no x gather
-    probe = int(os.environ.get("NQA_GEN_PROBE", "0"))
 
     def be_compute(sfx, e, rg):
         # every path's weight gradient is stored as soon as it is formed, and an input block's grad_x components as soon
         # as its last path is done: keeps up to kNP + kXD values out of the live set (the fused form has to fit 168
         # registers for three wavefronts per SIMD; 28 spilled registers doubled its time)
-        early_gw = True
         out = ["    {", "    T rr[kNP];", "    T q[kS];", "#pragma unroll", "    for (int j = 0; j < kS; ++j) q[j] = T(0);"]
-        if early_gw:
-            out.append(f"    T* __restrict__ gwr_e = (GW || FUSED) ? a.gw + (int64_t){rg} * a.wn : nullptr;")
+        out.append(f"    T* __restrict__ gwr_e = (GW || FUSED) ? a.gw + (int64_t){rg} * a.wn : nullptr;")
 
-        def emit_gw(p, expr, ind):
-            if early_gw and (probe & 1):
-                return [f"{ind}{{ const T r_ = {expr}; if (FUSED) probe_sink += r_; else if (act) {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {p}), ucb)', 'r_')}; }}"]
-            if early_gw:
-                return [f"{ind}{{ const T r_ = {expr}; if (act) {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {p}), ucb)', 'r_')}; }}"]
-            return [f"{ind}rr[{p}] = {expr};"]
+        def emit_gw(pth, expr, ind):
+            return [f"{ind}{{ const T r_ = {expr}; if (act) {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'r_')}; }}"]
 
         # ---- fused form (all three gradients): one intermediate serves both contractions.  Per path and input component i,
         #   T_ij = sum_k C_ijk g_k   (nnz(C) fused multiply-adds with literal coefficients)
@@ -479,23 +815,15 @@ def _emit(st: Structure) -> str:
         # instead of 1625 for l_max = 3 -- the kernel is bound by its vector-ALU work.
         out.append("    if (FUSED) {")
         out.append(f"      T* __restrict__ gxr = a.gxe + (int64_t){e} * a.din;")
-        last_path_of_block = {b_: p for p, (b_, _, _) in enumerate(st.instr)}
-        first_path_of_block = {}
-        for p, (b_, _, _) in enumerate(st.instr):
-            first_path_of_block.setdefault(b_, p)
-        contiguous = all(
-            [bb for bb, _, _ in st.instr][first_path_of_block[b_]:last_path_of_block[b_] + 1] == [b_] * (last_path_of_block[b_] - first_path_of_block[b_] + 1)
-            for b_ in first_path_of_block)
-        assert contiguous, "paths are created input-block major (interaction_block.py:89-109)"
         out.append("      T gxa[kXD];")
-        for p, (b_, j, s_) in enumerate(st.instr):
+        for pth, (b_, j, s_) in enumerate(st.instr):
             l1, l2, l3 = st.in1_ls[b_], st.in2_ls[j], st.out_ls[s_]
             d1, d2, d3 = 2 * l1 + 1, 2 * l2 + 1, 2 * l3 + 1
-            C = np.array(wigner_3j(l1, l2, l3), dtype=np.float64)
-            if first_path_of_block[b_] == p:
+            C = _cg(l1, l2, l3)
+            if p.first_path[b_] == pth:
                 for i in range(d1):
-                    out.append(f"      gxa[{xpre[b_] + i}] = T(0);")
-            out.append(f"      {{  // path {p}: {l1} x {l2} -> {l3}")
+                    out.append(f"      gxa[{p.xpre[b_] + i}] = T(0);")
+            out.append(f"      {{  // path {pth}: {l1} x {l2} -> {l3}")
             bj_started = [False] * d2
             for i in range(d1):
                 a_terms = []
@@ -503,7 +831,7 @@ def _emit(st: Structure) -> str:
                     ks = [k for k in range(d3) if C[i, jj, k] != 0.0]
                     if not ks:
                         continue
-                    expr = " + ".join(f"T({float(C[i, jj, k])!r}) * gv[{opre[s_] + k}]" for k in ks)
+                    expr = " + ".join(f"T({float(C[i, jj, k])!r}) * gv[{p.opre[s_] + k}]" for k in ks)
                     out.append(f"        const T t{i}_{jj} = {expr};")
                     if bj_started[jj]:
                         out.append(f"        B{jj} += xb{b_}{sfx}[{i}] * t{i}_{jj};")
@@ -512,51 +840,39 @@ def _emit(st: Structure) -> str:
                         bj_started[jj] = True
                     a_terms.append(f"yb{j}{sfx}[{jj}] * t{i}_{jj}")
                 if a_terms:
-                    out.append(f"        gxa[{xpre[b_] + i}] += wv{sfx}[{p}] * ({' + '.join(a_terms)});")
+                    out.append(f"        gxa[{p.xpre[b_] + i}] += wv{sfx}[{pth}] * ({' + '.join(a_terms)});")
             live = [jj for jj in range(d2) if bj_started[jj]]
             gw_expr = " + ".join(f"yb{j}{sfx}[{jj}] * B{jj}" for jj in live) if live else "T(0)"
-            out.extend(emit_gw(p, gw_expr, "        "))
+            out.extend(emit_gw(pth, gw_expr, "        "))
             for jj in live:
-                out.append(f"        q[{ypre[j] + jj}] += wv{sfx}[{p}] * B{jj};")
+                out.append(f"        q[{p.ypre[j] + jj}] += wv{sfx}[{pth}] * B{jj};")
             out.append("      }")
-            if last_path_of_block[b_] == p and (probe & 4):
-                for i in range(d1):
-                    out.append(f"      probe_sink += gxa[{xpre[b_] + i}];")
-            elif last_path_of_block[b_] == p:
+            if p.last_path[b_] == pth:
                 out.append("      if (act) {")
                 for i in range(d1):
-                    out.append(f"        {emit_store(f'spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb)', f'gxa[{xpre[b_] + i}]')};")
+                    out.append(f"        {emit_store(f'spec_at(gxr + (unsigned)(mul * {p.xpre[b_] + i}), ucb)', f'gxa[{p.xpre[b_] + i}]')};")
                 out.append("      }")
-        unused = [i for b in range(NB) if b not in first_path_of_block for i in range(xpre[b], xpre[b] + 2 * st.in1_ls[b] + 1)]
-        if unused:
+        if p.unused_comps:
             out.append("      if (act) {")
-            for i in unused:
+            for i in p.unused_comps:
                 out.append(f"        *spec_at(gxr + (unsigned)(mul * {i}), ucb) = T(0);")
             out.append("      }")
         out.append("    } else {")
         # ---- edge operands only: B^p_j = sum_ik C^p_ijk x_i g_k through the shared pair products of cg_generated.h
-        for p, (b_, j, s_) in enumerate(st.instr):
+        for pth, (b_, j, s_) in enumerate(st.instr):
             l1, l2, l3 = st.in1_ls[b_], st.in2_ls[j], st.out_ls[s_]
             d2 = 2 * l2 + 1
-            out.append(f"    {{ T t[{d2}]; CGT<{l1},{l2},{l3}>::template ac_b<T>(xb{b_}{sfx}, gv + {opre[s_]}, t);")
+            out.append(f"    {{ T t[{d2}]; CGT<{l1},{l2},{l3}>::template ac_b<T>(xb{b_}{sfx}, gv + {p.opre[s_]}, t);")
             terms = " + ".join(f"t[{i}] * yb{j}{sfx}[{i}]" for i in range(d2))
             out.append("      if (GW) {")
-            out.extend(emit_gw(p, terms, "        "))
+            out.extend(emit_gw(pth, terms, "        "))
             out.append("      }")
             out.append("      if (GY) {")
             for i in range(d2):
-                out.append(f"        q[{ypre[j] + i}] += wv{sfx}[{p}] * t[{i}];")
+                out.append(f"        q[{p.ypre[j] + i}] += wv{sfx}[{pth}] * t[{i}];")
             out.append("      }")
             out.append("    }")
         out.append("    }")
-        if not early_gw:
-            out.append("    if (GW || FUSED) {")
-            out.append("      if (act) {")
-            out.append(f"        T* __restrict__ gwr = a.gw + (int64_t){rg} * a.wn;")
-            for p in range(NP):
-                out.append(f"        *spec_at(gwr + (unsigned)(mul * {p}), ucb) = rr[{p}];")
-            out.append("      }")
-            out.append("    }")
         out.append("    if (GY || FUSED) {")
         out.append(f"      T* __restrict__ gyr = a.gy + (int64_t){e} * a.gy_stride + chunk * kS;")
         out.append("      spec_mask_dup<T, kS>(q, u < mul);")
@@ -567,10 +883,10 @@ def _emit(st: Structure) -> str:
 
     A("  T probe_sink = T(0);")
     A("  int idx = beg + wsub;")
-    if be_pipelined:
+    if pipelined:
         A("  // Two operand sets (A/B) as in the forward kernel: the rows of edge i+1 are requested before edge i is")
         A("  // evaluated and its gradients stored, so every wavefront keeps two edges' worth of loads in flight.")
-        L.extend(["  T wvA[kNP], wvB[kNP];"] + decl_x("  ", "A") + decl_x("  ", "B") + decl_y("  ", "A") + decl_y("  ", "B"))
+        L.extend(["  T wvA[kNP], wvB[kNP];"] + decl_x(p, "  ", "A") + decl_x(p, "  ", "B") + decl_y(p, "  ", "A") + decl_y(p, "  ", "B"))
         A("  int e0 = spec_uniform(a.eid[idx]), s0 = spec_uniform(a.nbr[idx]), r0 = spec_gwrow(a, idx);")
         A("  int e1 = 0, s1 = 0, r1 = 0;")
         L.extend(be_loads("A", "e0", "s0", "r0"))
@@ -592,7 +908,7 @@ def _emit(st: Structure) -> str:
         A("    idx = nidx;")
         A("  }")
     else:
-        L.extend(["  T wvA[kNP];"] + decl_x("  ", "A") + decl_y("  ", "A"))
+        L.extend(["  T wvA[kNP];"] + decl_x(p, "  ", "A") + decl_y(p, "  ", "A"))
         A("  int e = spec_uniform(a.eid[idx]), s = spec_uniform(a.nbr[idx]);")
         A("  int rg = spec_gwrow(a, idx);  // row of grad_w written by this edge; its weights are row spec_wrow_of(a, rg)")
         A("  while (idx < end) {")
@@ -603,28 +919,20 @@ def _emit(st: Structure) -> str:
         L.extend(be_compute("A", "e", "rg"))
         A("    idx = nidx; e = e_n; s = s_n; rg = rg_n;")
         A("  }")
-    if probe:
-        A("  if (probe_sink == T(12345.678)) a.gy[0] = probe_sink;")
     A("}")
+    return L
 
-    # ------------------------------------------------------------------ backward (node features)
+
+def emit_bwd_x(p: Plan) -> List[str]:
+    st = p.st
+    lb = "__launch_bounds__(256, 2)" if p.big else "__launch_bounds__(256)"
+    L = []
+    A = L.append
     A("// DUAL (second-order backward of training): out = Bx(y2, w, g) + Bx(y, w2, g) in one pass (a.y2 / a.w2 = the cotangents)")
     A("template <typename T, int WPN, bool DUAL = false>")
     A(f"__global__ {lb} void bwd_x_kernel(const SpecArgs<T> a) {{")
-    A("  const int lane = threadIdx.x & 63;")
-    A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
-    A("  const int mul = a.mul;")
-    A("  const int nchunk = (mul + 63) >> 6;")
-    A("  int64_t item; int wsub;")
-    A("  const unsigned bid = spec_xcd_remap(blockIdx.x, gridDim.x);")
-    A("  if (WPN == 1) { item = (int64_t)bid * 4 + wid; wsub = 0; } else { item = bid; wsub = wid; }")
-    A("  const bool valid = item < (int64_t)a.N * nchunk;")
-    A("  if (WPN == 1 && !valid) return;")
-    A("  const int node = spec_uniform(valid ? (int)(item / nchunk) : 0);")
-    A("  const int chunk = (int)(item - (int64_t)node * nchunk);")
-    A("  const int u = chunk * 64 + lane;")
-    A("  const bool act = valid && (u < mul);")
-    L.extend(lane_offsets("  ", want_x=False, want_g=True))
+    _node_kernel_prologue(L)
+    L.extend(lane_offsets(p, "  ", want_x=False, want_g=True))
     A("  T acc[kXD];")
     A("#pragma unroll")
     A("  for (int i = 0; i < kXD; ++i) acc[i] = T(0);")
@@ -639,1577 +947,713 @@ def _emit(st: Structure) -> str:
     A("    const T* __restrict__ gr = a.g + (int64_t)d * a.dout;")
     A("    const T* __restrict__ wr = a.w + (int64_t)r * a.wn;")
     A("    const T* __restrict__ yr = a.y + (int64_t)e * kS;")
-    L.extend(load_w("    ", "wr", scale=True))
+    L.extend(load_w(p, "    ", "wr", scale=True))
     A("    T wv2[kNP];")
-    L.extend(decl_y("    ", "2"))
+    L.extend(decl_y(p, "    ", "2"))
     A("    if (DUAL) {")
-    L.extend(load_w("      ", "(a.w2 + (int64_t)r * a.wn)", scale=True, sfx="2", decl=False))
-    L.extend(load_y("      ", "(a.y2 + (int64_t)e * kS)", sfx="2", decl=False))
+    L.extend(load_w(p, "      ", "(a.w2 + (int64_t)r * a.wn)", scale=True, sfx="2", decl=False))
+    L.extend(load_y(p, "      ", "(a.y2 + (int64_t)e * kS)", sfx="2", decl=False))
     A("    }")
-    used_slots = sorted({s for _, _, s in st.instr})
-    for s in used_slots:
+    for s in p.used_slots:
         d3 = 2 * st.out_ls[s] + 1
         A(f"    T gs{s}[{d3}];")
         for k in range(d3):
             A(f"    gs{s}[{k}] = spec_at(gr, go{s})[{k}];")
-    L.extend(load_y("    ", "yr"))
-    for p, (b, j, s) in enumerate(st.instr):
+    L.extend(load_y(p, "    ", "yr"))
+    for pth, (b, j, s) in enumerate(st.instr):
         l1, l2, l3 = st.in1_ls[b], st.in2_ls[j], st.out_ls[s]
         d1 = 2 * l1 + 1
         A("    if (!DUAL) {")
         A(f"      T t[{d1}]; CGT<{l1},{l2},{l3}>::template bc_a<T>(yb{j}, gs{s}, t);")
         for i in range(d1):
-            A(f"      acc[{xpre[b] + i}] += wv[{p}] * t[{i}];")
+            A(f"      acc[{p.xpre[b] + i}] += wv[{pth}] * t[{i}];")
         A("    } else {")
         A(f"      T t[{d1}], t2[{d1}]; CGT<{l1},{l2},{l3}>::template bc_a<T>(yb{j}2, gs{s}, t); CGT<{l1},{l2},{l3}>::template bc_a<T>(yb{j}, gs{s}, t2);")
         for i in range(d1):
-            A(f"      acc[{xpre[b] + i}] += wv[{p}] * t[{i}] + wv2[{p}] * t2[{i}];")
+            A(f"      acc[{p.xpre[b] + i}] += wv[{pth}] * t[{i}] + wv2[{pth}] * t2[{i}];")
         A("    }")
     A("    idx = nidx; e = e_n; d = d_n; r = r_n;")
     A("  }")
+    L.extend(wave_reduce_lines("kXD", "acc"))
+    A("  if (act) {")
+    A("    T* __restrict__ ob = a.out + (int64_t)node * a.din;")
+    L.extend(store_x_rows(p, "    ", range(p.NB), "u", lambda c: f"acc[{c}]"))
+    A("  }")
+    A("}")
+    return L
+
+
+# ------------------------------------------------------------------ backward, pair-centric (paired radial weights)
+# A reverse-edge pair p = {j -> o, o -> j} shares one weight row.  Walking the edges by destination, the two directed
+# edges of a pair are evaluated by different wavefronts at different times: the weight row is read twice, the two
+# halves of its gradient are written to separate rows (summed later by the radial backward), and every directed edge
+# writes a per-edge row of grad_x contributions for its source.  Here every pair has an OWNER node o (half of each
+# node's pairs, see EdgePairing.owner_csr); the wavefront of o holds x[o], grad_out[o] and the grad_x[o] accumulators
+# in registers and, per owned pair, gathers x[j] and grad_out[j] and evaluates BOTH directed edges:
+#   in  = j -> o  (x = x[j], g = grad_out[o]):  grad_w half, grad_y[in],  grad_x[j] contribution -> row of the pair
+#   out = o -> j  (x = x[o], g = grad_out[j]):  grad_w half, grad_y[out], grad_x[o] contribution -> registers
+# so the weight row is read once, grad_w leaves already summed ([P, W] instead of [2P, W]) and only one grad_x row per
+# pair is written: per pair 2 W + dim_in1 floats of HBM traffic instead of 2 (2 W + dim_in1), in exchange for a second
+# gathered node row (grad_out[j]) that comes out of the cache hierarchy.  Same arithmetic per directed edge as the
+# fused kernel above (shared intermediate T_ij).
+def emit_pair(p: Plan) -> List[str]:
+    st = p.st
+    pair_lb = "__launch_bounds__(256)" if p.big else "__launch_bounds__(256, 2)"
+    L = []
+    A = L.append
+    A("// GX = false: grad_w (summed over the pair) and grad_y only -- layers whose grad_x is not needed or comes from bwd_x")
+    A("// DUAL (with GX = false; second-order backward of training): two operand sets in one pass,")
+    A("//   grad_w = Bw(x2, y, g) + Bw(x, y2, g),  grad_y = By(x2, w, g)   (x2 = a.x2, y2 = a.y2: the cotangents of grad_x /")
+    A("//   grad_y of the first-order backward) -- the intermediate T_ij = sum_k C_ijk g_k serves both products")
+    A("template <typename T, int WPN, bool FULL, bool GX, bool DUAL = false>")
+    A(f"__global__ {pair_lb} void bwd_pair_kernel(const SpecArgs<T> a) {{")
+    _edge_kernel_prologue(L)
+    A("  if (item >= (int64_t)a.N * nchunk) return;  // (WPN == 4: the whole workgroup)")
+    A("  const int node = spec_uniform((int)(item / nchunk));")
+    A("  const int chunk = (int)(item - (int64_t)node * nchunk);")
+    A("  const int u = chunk * 64 + lane;")
+    A("  const bool act = FULL || (u < mul);")
+    A("  const int beg = a.rowptr[node], end = a.rowptr[node + 1];")
+    L.extend(lane_offsets(p, "  ", want_x=True, want_g=True))
+    A("  T gvO[kOD], gxO[kXD];")
+    L.extend(load_g(p, "  ", "a.g + (int64_t)node * a.dout", "gvO"))
+    L.extend(load_x(p, "  ", "(a.x + (int64_t)node * a.din)", sfx="O"))
+    L.extend(decl_x(p, "  ", "O2"))
+    A("  if (DUAL) {")
+    L.extend(load_x(p, "    ", "(a.x2 + (int64_t)node * a.din)", sfx="O2", decl=False))
+    A("  }")
+    A("#pragma unroll")
+    A("  for (int i = 0; i < kXD; ++i) gxO[i] = T(0);")
+    A("  int idx = beg + wsub;")
+    A("  T gvJ[kOD];")
+    L += (["  T wvA[kNP], wv2A[kNP];", "  int jnA = 0, prA = 0, eiA = 0, eoA = 0;"]
+          + decl_x(p, "  ", "JA") + decl_y(p, "  ", "IA") + decl_y(p, "  ", "XA")
+          + decl_x(p, "  ", "JA2") + decl_y(p, "  ", "IA2") + decl_y(p, "  ", "XA2"))
+    # the next pair's weight row (the one stream that comes from HBM) is touched while this pair is evaluated -- plain loads
+    # into a sink value, so that the row is in the L2 when the real loads ask for it (same-box cfg-3: 2.930 -> 2.912 ms)
+    A("  T pf_sink = T(0);")
+    A("  for (; idx < end; idx += WPN) {")
+    # operands of the pair in owner slot idx (the indices are wave-uniform)
+    A("    {")
+    A("      jnA = spec_uniform(a.nbr[idx]); prA = spec_uniform(a.wid[idx]);")
+    A("      eiA = spec_uniform(a.eid[idx]); eoA = spec_uniform(a.eid2[idx]);")
+    A("      const T* __restrict__ xr = a.x + (int64_t)jnA * a.din;")
+    A("      const T* __restrict__ wr = a.w + (int64_t)prA * a.wn;")
+    A("      const T* __restrict__ yi = a.y + (int64_t)eiA * kS;")
+    A("      const T* __restrict__ yo = a.y + (int64_t)eoA * kS;")
+    L.extend(load_w(p, "      ", "wr", sfx="A", decl=False))
+    L.extend(load_x(p, "      ", "xr", sfx="JA", decl=False))
+    L.extend(load_g(p, "      ", "a.g + (int64_t)jnA * a.dout", "gvJ"))
+    L.extend(load_y(p, "      ", "yi", sfx="IA", decl=False))
+    L.extend(load_y(p, "      ", "yo", sfx="XA", decl=False))
+    A("      if (DUAL && a.w2 != nullptr) {")
+    L.extend(load_w(p, "        ", "(a.w2 + (int64_t)prA * a.wn)", sfx="2A", decl=False))
+    A("      }")
+    A("      if (DUAL) {")
+    L.extend(load_x(p, "        ", "(a.x2 + (int64_t)jnA * a.din)", sfx="JA2", decl=False))
+    L.extend(load_y(p, "        ", "(a.y2 + (int64_t)eiA * kS)", sfx="IA2", decl=False))
+    L.extend(load_y(p, "        ", "(a.y2 + (int64_t)eoA * kS)", sfx="XA2", decl=False))
+    A("      }")
+    A("    }")
+    A("    T pf[kNP];")
+    A("    {")
+    A("      const int nidx_ = idx + WPN < end ? idx + WPN : idx;")
+    A("      const int prn_ = spec_uniform(a.wid[nidx_]);")
+    A("      const T* __restrict__ wn_ = a.w + (int64_t)prn_ * a.wn;")
+    for pth in range(p.NP):
+        A(f"      pf[{pth}] = *spec_at(wn_ + (unsigned)(mul * {pth}), ucb);")
+    A("    }")
+    # both directed edges of the pair
+    A("    {")
+    A("    T qI[kS], qX[kS], gxa[kXD];")
+    A("#pragma unroll")
+    A("    for (int j = 0; j < kS; ++j) { qI[j] = T(0); qX[j] = T(0); }")
+    A("    T* __restrict__ gwr_e = a.gw + (int64_t)prA * a.wn;")
+    A("    T* __restrict__ gxr = a.gxe + (int64_t)(idx) * a.din;")
+    for pth, (b_, j, s_) in enumerate(st.instr):
+        d1 = 2 * st.in1_ls[b_] + 1
+        if p.first_path[b_] == pth:
+            for i in range(d1):
+                A(f"      gxa[{p.xpre[b_] + i}] = T(0);")
+        A(f"      {{  // path {pth}")
+        live_i, gx_i = path_terms(p, L, pth, "JA", "gvO", "IA", "i", "        ", dual=True)
+        for comp, expr in gx_i:
+            if expr:
+                A(f"        if (GX) gxa[{comp}] += wvA[{pth}] * ({expr});")
+        live_x, gx_x = path_terms(p, L, pth, "O", "gvJ", "XA", "x", "        ", dual=True)
+        for comp, expr in gx_x:
+            if expr:
+                A(f"        if (GX) gxO[{comp}] += wvA[{pth}] * ({expr});")
+        terms = [f"yb{j}IA[{jj}] * Bi{jj}" for jj in live_i] + [f"yb{j}XA[{jj}] * Bx{jj}" for jj in live_x]
+        gw_expr = " + ".join(terms) if terms else "T(0)"
+        dterms = [f"yb{j}IA2[{jj}] * Di{jj}" for jj in live_i] + [f"yb{j}XA2[{jj}] * Dx{jj}" for jj in live_x]
+        dual_expr = " + ".join(dterms) if dterms else "T(0)"
+        A(f"        {{ T r_ = {gw_expr}; if (DUAL) r_ += {dual_expr}; if (act) {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'r_')}; }}")
+        for jj in live_i:
+            A(f"        qI[{p.ypre[j] + jj}] += wvA[{pth}] * Bi{jj};")
+        for jj in live_x:
+            A(f"        qX[{p.ypre[j] + jj}] += wvA[{pth}] * Bx{jj};")
+        # DUAL with a weight cotangent (a.w2): grad_y += By(x, w2, g) rides on the D intermediates
+        A("        if (DUAL && a.w2 != nullptr) {")
+        for jj in live_i:
+            A(f"          qI[{p.ypre[j] + jj}] += wv2A[{pth}] * Di{jj};")
+        for jj in live_x:
+            A(f"          qX[{p.ypre[j] + jj}] += wv2A[{pth}] * Dx{jj};")
+        A("        }")
+        A("      }")
+        if p.last_path[b_] == pth:
+            A("      if (GX && act) {")
+            for i in range(d1):
+                A(f"        {emit_store(f'spec_at(gxr + (unsigned)(mul * {p.xpre[b_] + i}), ucb)', f'gxa[{p.xpre[b_] + i}]')};")
+            A("      }")
+    if p.unused_comps:
+        A("      if (GX && act) {")
+        for i in p.unused_comps:
+            A(f"        *spec_at(gxr + (unsigned)(mul * {i}), ucb) = T(0);")
+        A("      }")
+    A("      spec_mask_dup<T, kS>(qI, u < mul);")
+    A("      spec_mask_dup<T, kS>(qX, u < mul);")
+    A("      spec_wave_reduce_store<T, kS>(qI, a.gy + (int64_t)eiA * a.gy_stride + chunk * kS, lane);")
+    A("      spec_wave_reduce_store<T, kS>(qX, a.gy + (int64_t)eoA * a.gy_stride + chunk * kS, lane);")
+    A("    }")
+    A("#pragma unroll")
+    A("    for (int p_ = 0; p_ < kNP; ++p_) pf_sink += pf[p_];")
+    A("  }")
+    A("  if (pf_sink == T(12345.678)) a.gy[0] = pf_sink;")
+    A("  // grad_x[owner]: the owner-side contributions of all its pairs (the other side arrives through the rows)")
+    A("  if (!GX) return;")
+    L.extend(wave_reduce_lines("kXD", "gxO"))
+    A("  if (act) {")
+    A("    const int uc = u < mul ? u : mul - 1;")
+    A("    T* __restrict__ ob = a.out + (int64_t)node * a.din;")
+    L.extend(store_x_rows(p, "    ", range(p.NB), "uc", lambda c: f"gxO[{c}]"))
+    A("  }")
+    A("}")
+    return L
+
+
+# ------------------------------------------------------------------ pair-centric backward, LDS ring
+# What held bwd_pair_kernel at half of the HBM roof (profiles/r6_pair_*.txt, r6_lab_call4.txt ... call7.txt; index: profiles/README_r6.md): one pair in flight per
+# wavefront at two wavefronts per SIMD.  The same loop WITHOUT its arithmetic takes 85 % of the kernel's time, with every
+# stream pointed at cache-hot rows still 42 % -- it is the serial chain indices -> row loads -> arithmetic -> stores of
+# each pair, 8 of them per CU, not bandwidth and not the vector ALU; a second operand set in registers spills (254 used).
+# (A packed-fp32 form that evaluated both directed edges of a pair as v_pk_* pairs measured 561 vs 575 us: a v_pk_fma_f32
+# takes twice the passes of a v_fma_f32, profiles/r6_pk_rate_and_packed_pair_call2.txt.)
+# Here the rows of the NEXT pair travel global -> LDS by LDS-DMA (no registers) while the current pair is evaluated out
+# of the LDS: every wavefront owns a ring of kRingSlots slots in the CU's 160 KB (20 KB per wavefront at two per SIMD);
+# a pair's rows (w, x[other], grad_out[other], the two y rows: 14 KB for the l_max = 2 middle layer) are cut into
+# kRingChunks = kRingSlots - 1 chunks in the order the paths consume them, so that one whole pair is always in flight
+# behind the one being evaluated.  After chunk q is evaluated its slot is refilled with chunk q + kRingSlots.  The copies
+# are 16 bytes per lane (dword-per-lane reads reach 4.0 TB/s on this part, 16-byte ones 6.7: scripts/micro/store_bw.hip);
+# lane l of an instruction lands at slot + 16 l, the LDS image of a segment is the 64 channels' values in row order, and
+# the evaluation reads its operands with ds_read (4 u + component) right where it uses them -- no operand arrays in
+# registers.  Ordering: the issuing wavefront's counted s_waitcnt vmcnt(N), N = the copies and stores issued since
+# (static: one pair's worth of each in the steady state, tp_spec.h spec_wait_vm); the first pair of a wavefront counts
+# its own shorter history, the last one waits for everything.  scripts/check_ring_waits.py re-counts N in the ISA.
+def emit_pair_ring(p: Plan) -> List[str]:
+    st, r = p.st, p.ring
+    RC, RN, RSLOT = r.chunks, r.slots, r.slot_bytes
+    L = []
+    A = L.append
+
+    def copies(ind, c_, sfx, slotexpr, lgkm=True):
+        return ring_copies(p, r, ind, c_, sfx, slotexpr, "(unsigned)kRingSlotBytes", "ro", "  // the slot's last reads have returned", lgkm)
+
+    A(f"constexpr int kRingChunks = {RC}, kRingSlots = {RN}, kRingSlotBytes = {RSLOT}, kRingWaveBytes = {RN * RSLOT};")
+    A("// ring chunks: " + "; ".join(
+        f"{c_}: paths {r.cpaths[c_][0]}-{r.cpaths[c_][-1]}" + "".join(f" +x{b_}" for b_ in r.blocks if r.xplace[b_] == c_)
+        + f", {len(r.dma[c_])} copies, {r.Sgw[c_]}+{r.Sgx[c_]} stores" for c_ in range(RC)))
+    A("// ATOM: the other node's grad_x contribution goes into a zeroed [N, dim_in1] accumulator (a.gxe, component rows of 64")
+    A("// channels as the per-pair rows) by floating-point atomics instead of one row per pair: no [P, dim_in1] round trip")
+    A("// through HBM and no row sum -- gx_acc_finish_kernel folds the accumulator into a.out.  (Sums in arrival order: the")
+    A("// low bits of grad_x differ from run to run; ATOM = false keeps the fixed-order rows.)")
+    A("template <int WPN, bool GX, bool ATOM>")
+    A("__global__ __launch_bounds__(256, 2) void bwd_pair_ring_kernel(const SpecArgs<float> a) {")
+    A("  typedef float T;")
+    A("  extern __shared__ __align__(16) unsigned char nqa_smem[];")
+    A("  const int lane = threadIdx.x & 63;")
+    A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
+    A("  const int mul = a.mul;  // a multiple of 64 (the launcher sends other multiplicities to bwd_pair_kernel)")
+    A("  const int nchunk = mul >> 6;")
+    A("  const int64_t witem = (int64_t)spec_xcd_remap(blockIdx.x, gridDim.x) * 4 + wid;")
+    A("  const int64_t item = witem / WPN;")
+    A("  const int wsub = (int)(witem - item * WPN);")
+    A("  const bool valid = item < (int64_t)a.N * nchunk;  // (WPN < 4: the last workgroup may hold idle wavefronts)")
+    A("  const int node = spec_uniform(valid ? (int)(item / nchunk) : 0);")
+    A("  const int chunk = valid ? (int)(item - (int64_t)node * nchunk) : 0;")
+    A("  const int u = chunk * 64 + lane;")
+    A("  constexpr bool act = true, DUAL = false;")
+    A("  const int beg = a.rowptr[node], end = valid ? a.rowptr[node + 1] : beg;")
+    L.extend(lane_offsets(p, "  ", want_x=True, want_g=True))
+    A("  const unsigned wbase = (unsigned)wid * (unsigned)kRingWaveBytes;  // this wavefront's ring (LDS byte address)")
+    A("  const unsigned l4 = (unsigned)lane * 4u, l16 = (unsigned)lane * 16u;")
+    A("  // per-lane source offsets of the copies (bytes from the row base; lane l moves 16 bytes)")
+    L.extend(ring_lane_offsets(p, r, "  ", "ro"))
+    A("  T gvO[kOD], gxO[kXD];")
+    L.extend(load_g(p, "  ", "a.g + (int64_t)node * a.dout", "gvO"))
+    L.extend(load_x(p, "  ", "(a.x + (int64_t)node * a.din)", sfx="O"))
+    A("#pragma unroll")
+    A("  for (int i = 0; i < kXD; ++i) gxO[i] = T(0);")
+
+    # The pair indices (other node, weight row, the two edges) of up to 64 of this wavefront's pairs sit in four vector
+    # registers, lane l = the wavefront's l-th pair, fetched by ONE vector load per list before the loop; a pair's
+    # indices are then a v_readlane away.  (Per-pair scalar loads, as bwd_pair_kernel has them, are not available here:
+    # behind the "memory" clobbers of the copy / wait statements hipcc turns them into vector loads followed by vmcnt(0).)
+    def block_load(ind, first_pair):
+        return [f"{ind}{{ const int i_ = beg + wsub + (({first_pair}) + lane) * WPN; const int ic_ = i_ < end ? i_ : end - 1;",
+                f"{ind}  jnV = a.nbr[ic_]; prV = a.wid[ic_]; eiV = a.eid[ic_]; eoV = a.eid2[ic_]; }}"]
+
+    A("  int idx = beg + wsub;")
+    A("  int kk = 0;  // this wavefront's pair counter: pair kk sits in owner slot beg + wsub + kk * WPN")
+    A("  int jnA = 0, prA = 0, eiA = 0, eoA = 0, jnB = 0, prB = 0, eiB = 0, eoB = 0, jnC = 0, prC = 0, eiC = 0, eoC = 0;")
+    A("  int jnV = 0, prV = 0, eiV = 0, eoV = 0;")
+    A("  bool hasA = idx < end, hasB = idx + WPN < end, hasC = false;")
+    A("  if (hasA) {")
+    L.extend(block_load("    ", "0"))
+    L.extend(_ring_index_get("A", "0", "    "))
+    L.extend(_ring_index_get("B", "1", "    "))
+    A("  }")
+    A("  // prologue: the whole first pair and the first chunk of the second fill the ring")
+    A("  if (hasA) {")
+    for c_ in range(RC):
+        L.extend(copies("    ", c_, "A", str(c_), lgkm=False))
+    A("  }")
+    A("  if (hasB) {")
+    L.extend(copies("    ", 0, "B", str(RC), lgkm=False))
+    A("  }")
+    A("  // the owner's rows are in their registers before the loop starts: hipcc, which does not see the copies, would")
+    A("  // otherwise wait for them inside the loop with a small vmcnt(n) of ITS count -- every iteration, draining the ring")
+    A("#pragma unroll")
+    A("  for (int k = 0; k < kOD; ++k) asm volatile(\"\" : \"+v\"(gvO[k]));")
+    for b in p.used_blocks:
+        for i in range(2 * st.in1_ls[b] + 1):
+            A(f"  asm volatile(\"\" : \"+v\"(xb{b}O[{i}]));")
+    A("  int rot = 0;       // slot of chunk 0 of pair A")
+    A("  bool first = true;")
+    A("  T qI[kS], qX[kS], gxa[kXD], gvJ[kOD];")
+    L.extend(decl_y(p, "  ", "I") + decl_y(p, "  ", "X") + decl_x(p, "  ", "J"))
+    L.extend(decl_x(p, "  ", "J2") + decl_x(p, "  ", "O2"))  # (names the shared path emitter mentions under DUAL, never read)
+    A("  while (hasA) {")
+    A("    hasC = idx + 2 * WPN < end;")
+    A("    if (hasC) {")
+    A("      if (((kk + 2) & 63) == 0) {  // (a wavefront with more than 64 pairs: the next block of indices)")
+    L.extend(block_load("        ", "kk + 2"))
+    A("      }")
+    L.extend(_ring_index_get("C", "kk + 2", "      "))
+    A("    }")
+    A("    T* __restrict__ gwr_e = a.gw + (int64_t)prA * a.wn;")
+    A("    T* __restrict__ gxr = a.gxe + (int64_t)(ATOM ? jnA : idx) * a.din;")
+    A("#pragma unroll")
+    A("    for (int j = 0; j < kS; ++j) { qI[j] = T(0); qX[j] = T(0); }")
+    for c_ in range(RC):
+        lo = r.lds_off[c_]
+        A(f"    {{  // ---- chunk {c_}: paths {r.cpaths[c_][0]}..{r.cpaths[c_][-1]}")
+        A(f"      int s_ = rot + {c_}; s_ = s_ >= kRingSlots ? s_ - kRingSlots : s_;")
+        A("      const unsigned sb = wbase + (unsigned)s_ * (unsigned)kRingSlotBytes;")
+        A("      const unsigned char* __restrict__ cb = nqa_smem + sb;")
+        L.extend(ring_waits(r, c_, "      "))
+        L.extend(ring_operand_reads(p, r, c_, p.used_y, "      "))
+        for pth in r.cpaths[c_]:
+            b_, j, s_ = st.instr[pth]
+            d1, d3 = 2 * st.in1_ls[b_] + 1, 2 * st.out_ls[s_] + 1
+            if p.first_path[b_] == pth:
+                for i in range(d1):
+                    A(f"      gxa[{p.xpre[b_] + i}] = T(0);")
+            A(f"      {{  // path {pth}")
+            A(f"        const T wv_ = *reinterpret_cast<const T*>(cb + {lo[('w', pth)]} + l4);")
+            for k in range(d3):
+                A(f"        gvJ[{p.opre[s_] + k}] = T({p.slot_coeff[s_]!r}) * *reinterpret_cast<const T*>(cb + {lo[('g', s_)]} + l4 * {d3}u + {4 * k});")
+            live_i, gx_i = path_terms(p, L, pth, "J", "gvO", "I", "i", "        ", dual=True)
+            for comp, expr in gx_i:
+                if expr:
+                    A(f"        if (GX) gxa[{comp}] += wv_ * ({expr});")
+            live_x, gx_x = path_terms(p, L, pth, "O", "gvJ", "X", "x", "        ", dual=True)
+            for comp, expr in gx_x:
+                if expr:
+                    A(f"        if (GX) gxO[{comp}] += wv_ * ({expr});")
+            terms = [f"yb{j}I[{jj}] * Bi{jj}" for jj in live_i] + [f"yb{j}X[{jj}] * Bx{jj}" for jj in live_x]
+            gw_expr = " + ".join(terms) if terms else "T(0)"
+            A(f"        {{ const T r_ = {gw_expr}; {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'r_')}; }}")
+            for jj in live_i:
+                A(f"        qI[{p.ypre[j] + jj}] += wv_ * Bi{jj};")
+            for jj in live_x:
+                A(f"        qX[{p.ypre[j] + jj}] += wv_ * Bx{jj};")
+            A("      }")
+            if p.last_path[b_] == pth:
+                A("      if (GX) {")
+                for i in range(d1):
+                    st_ = emit_store(f'spec_at(gxr + (unsigned)(mul * {p.xpre[b_] + i}), ucb)', f'gxa[{p.xpre[b_] + i}]')
+                    A(f"        if (ATOM) unsafeAtomicAdd(spec_at(gxr + (unsigned)(mul * {p.xpre[b_] + i}), ucb), gxa[{p.xpre[b_] + i}]); else {st_};")
+                A("      }")
+        if c_ == RC - 1:
+            if p.unused_comps:
+                A("      if (GX && !ATOM) {")
+                for i in p.unused_comps:
+                    A(f"        *spec_at(gxr + (unsigned)(mul * {i}), ucb) = T(0);")
+                A("      }")
+            A("      // refill this slot with chunk 0 of the pair after next")
+            A("      if (hasC) {")
+            L.extend(copies("        ", 0, "C", "s_"))
+            A("      }")
+            A("      // (a.gy_atomic: more than one channel chunk per edge -- the chunks add into grad_y itself instead of partial rows)")
+            A("      spec_wave_reduce_store<T, kS>(qI, a.gy + (int64_t)eiA * a.gy_stride + (a.gy_atomic ? 0 : chunk * kS), lane, a.gy_atomic != 0);")
+            A("      spec_wave_reduce_store<T, kS>(qX, a.gy + (int64_t)eoA * a.gy_stride + (a.gy_atomic ? 0 : chunk * kS), lane, a.gy_atomic != 0);")
+        else:
+            A(f"      // refill this slot with chunk {c_ + 1} of the next pair")
+            A("      if (hasB) {")
+            L.extend(copies("        ", c_ + 1, "B", "s_"))
+            A("      }")
+        A("    }")
+    A("    jnA = jnB; prA = prB; eiA = eiB; eoA = eoB; jnB = jnC; prB = prC; eiB = eiC; eoB = eoC;")
+    A("    hasA = hasB; hasB = hasC; idx += WPN; ++kk; first = false;")
+    A(f"    rot += {RC}; rot = rot >= kRingSlots ? rot - kRingSlots : rot;")
+    A("  }")
+    A("  if (!GX) return;")
+    A("  // grad_x[owner]: the owner-side contributions of all its pairs (the other side arrives through the rows)")
     A("  if (WPN > 1) {")
-    A("    extern __shared__ __align__(16) unsigned char nqa_smem[];")
-    A("    T* red = reinterpret_cast<T*>(nqa_smem);")
+    A("    T* red = reinterpret_cast<T*>(nqa_smem);  // (the rings are idle: every copy was waited for)")
+    A("    __syncthreads();")
     A("    if (wsub > 0) {")
     A("#pragma unroll")
-    A("      for (int k = 0; k < kXD; ++k) red[((wsub - 1) * kXD + k) * 64 + lane] = acc[k];")
+    A("      for (int k = 0; k < kXD; ++k) red[(((wid / WPN) * (WPN - 1) + wsub - 1) * kXD + k) * 64 + lane] = gxO[k];")
     A("    }")
     A("    __syncthreads();")
     A("    if (wsub > 0) return;")
     A("#pragma unroll")
     A("    for (int k = 0; k < kXD; ++k) {")
     A("#pragma unroll")
-    A("      for (int w2 = 0; w2 < WPN - 1; ++w2) acc[k] += red[(w2 * kXD + k) * 64 + lane];")
+    A("      for (int w2 = 0; w2 < WPN - 1; ++w2) gxO[k] += red[(((wid / WPN) * (WPN - 1) + w2) * kXD + k) * 64 + lane];")
     A("    }")
     A("  }")
-    A("  if (act) {")
+    A("  if (valid) {")
     A("    T* __restrict__ ob = a.out + (int64_t)node * a.din;")
-    for b in range(NB):
-        d = 2 * st.in1_ls[b] + 1
-        for i in range(d):
-            A(f"    ob[(int64_t)mul * {xpre[b]} + (int64_t)u * {d} + {i}] = acc[{xpre[b] + i}];")
+    L.extend(store_x_rows(p, "    ", range(p.NB), "u", lambda c: f"gxO[{c}]"))
     A("  }")
     A("}")
+    return L
 
-    # ------------------------------------------------------------------ backward, pair-centric (paired radial weights)
-    # A reverse-edge pair p = {j -> o, o -> j} shares one weight row.  Walking the edges by destination, the two directed
-    # edges of a pair are evaluated by different wavefronts at different times: the weight row is read twice, the two
-    # halves of its gradient are written to separate rows (summed later by the radial backward), and every directed edge
-    # writes a per-edge row of grad_x contributions for its source.  Here every pair has an OWNER node o (half of each
-    # node's pairs, see EdgePairing.owner_csr); the wavefront of o holds x[o], grad_out[o] and the grad_x[o] accumulators
-    # in registers and, per owned pair, gathers x[j] and grad_out[j] and evaluates BOTH directed edges:
-    #   in  = j -> o  (x = x[j], g = grad_out[o]):  grad_w half, grad_y[in],  grad_x[j] contribution -> row of the pair
-    #   out = o -> j  (x = x[o], g = grad_out[j]):  grad_w half, grad_y[out], grad_x[o] contribution -> registers
-    # so the weight row is read once, grad_w leaves already summed ([P, W] instead of [2P, W]) and only one grad_x row per
-    # pair is written: per pair 2 W + dim_in1 floats of HBM traffic instead of 2 (2 W + dim_in1), in exchange for a second
-    # gathered node row (grad_out[j]) that comes out of the cache hierarchy.  Same arithmetic per directed edge as the
-    # fused kernel above (shared intermediate T_ij).
-    # register budget: two grad_out rows, three x rows, the weights.  Measured on cu20k (l_max 3, 269): 298 spilled
-    # registers, fused backward 10 -> 70 ms -- the big structures stay with the per-edge kernels
-    pair_ok = (2 * OD + 3 * XD + NP) <= 110  # (larger structures spill: l2p_second at 144 spills 127 registers)
-    if os.environ.get("NQA_GEN_PAIR_FORCE_SPLIT", "0") != "0":  # lab: the split-by-input-block form for small structures too
-        pair_ok = False
-    pair_occ = os.environ.get("NQA_GEN_PAIR_OCC", "2")
-    pair_lb = "__launch_bounds__(256)" if big else f"__launch_bounds__(256, {pair_occ})"
-    if pair_ok:
-        A("// GX = false: grad_w (summed over the pair) and grad_y only -- layers whose grad_x is not needed or comes from bwd_x")
-        A("// DUAL (with GX = false; second-order backward of training): two operand sets in one pass,")
-        A("//   grad_w = Bw(x2, y, g) + Bw(x, y2, g),  grad_y = By(x2, w, g)   (x2 = a.x2, y2 = a.y2: the cotangents of grad_x /")
-        A("//   grad_y of the first-order backward) -- the intermediate T_ij = sum_k C_ijk g_k serves both products")
-        A("template <typename T, int WPN, bool FULL, bool GX, bool DUAL = false>")
-        A(f"__global__ {pair_lb} void bwd_pair_kernel(const SpecArgs<T> a) {{")
-        A("  const int lane = threadIdx.x & 63;")
-        A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
-        A("  const int mul = a.mul;")
-        A("  const int nchunk = (mul + 63) >> 6;")
-        A("  const int64_t witem = (int64_t)spec_xcd_remap(blockIdx.x, gridDim.x) * 4 + wid;")
-        A("  const int64_t item = witem / WPN;")
-        A("  const int wsub = (int)(witem - item * WPN);")
-        A("  if (item >= (int64_t)a.N * nchunk) return;  // (WPN == 4: the whole workgroup)")
-        A("  const int node = spec_uniform((int)(item / nchunk));")
-        A("  const int chunk = (int)(item - (int64_t)node * nchunk);")
-        A("  const int u = chunk * 64 + lane;")
-        A("  const bool act = FULL || (u < mul);")
-        A("  const int beg = a.rowptr[node], end = a.rowptr[node + 1];")
-        L.extend(lane_offsets("  ", want_x=True, want_g=True))
 
-        def load_g(indent, rowexpr, name):
-            out = [f"{indent}{{ const T* __restrict__ gb = {rowexpr};"]
-            for s_ in range(NS):
-                d3 = 2 * st.out_ls[s_] + 1
-                for k in range(d3):
-                    if slot_coeff[s_] is None:
-                        out.append(f"{indent}  {name}[{opre[s_] + k}] = T(0);")
-                    else:
-                        out.append(f"{indent}  {name}[{opre[s_] + k}] = spec_at(gb, go{s_})[{k}];")
-            for s_ in range(NS):
-                d3 = 2 * st.out_ls[s_] + 1
-                if slot_coeff[s_] is None:
-                    continue
-                for k in range(d3):
-                    out.append(f"{indent}  {name}[{opre[s_] + k}] = act ? T({slot_coeff[s_]!r}) * {name}[{opre[s_] + k}] : T(0);")
-            out.append(f"{indent}}}")
-            return out
+def _ring_index_get(sfx, k, ind):
+    return [f"{ind}jn{sfx} = __builtin_amdgcn_readlane(jnV, ({k}) & 63); pr{sfx} = __builtin_amdgcn_readlane(prV, ({k}) & 63);",
+            f"{ind}ei{sfx} = __builtin_amdgcn_readlane(eiV, ({k}) & 63); eo{sfx} = __builtin_amdgcn_readlane(eoV, ({k}) & 63);"]
 
-        A("  T gvO[kOD], gxO[kXD];")
-        L.extend(load_g("  ", "a.g + (int64_t)node * a.dout", "gvO"))
-        L.extend(load_x("  ", "(a.x + (int64_t)node * a.din)", sfx="O"))
-        L.extend(decl_x("  ", "O2"))
-        A("  if (DUAL) {")
-        L.extend(load_x("    ", "(a.x2 + (int64_t)node * a.din)", sfx="O2", decl=False))
-        A("  }")
-        A("#pragma unroll")
-        A("  for (int i = 0; i < kXD; ++i) gxO[i] = T(0);")
 
-        pair_nohoist = os.environ.get("NQA_GEN_PAIR_NOHOIST", "0") != "0"  # measured: more spills, not fewer
-        # lab only (scripts/micro/pair_lab.hip): ablations that keep every instruction and point a stream at ONE hot row (a
-        # scalar select on a.N < 0, never true): 1: grad_w stores, 2: grad_x row stores, 4: the gathered rows are the
-        # owner's own rows, 8: weight loads, 16: grad_y stores
-        pair_abl = int(os.environ.get("NQA_GEN_PAIR_ABL", "0"))
-        # lab: the other node's grad_x contribution as atomic adds into a [N, dim_in1] accumulator (a.gxe, zeroed by the
-        # caller, lane-contiguous component rows) instead of one row per pair -- no [P, dim_in1] round trip through HBM
-        pair_gx_atomic = os.environ.get("NQA_GEN_PAIR_GX_ATOMIC", "0") != "0"
+def _split_part_sets(st: Structure, paths):
+    return (sorted({st.instr[p_][0] for p_ in paths}), sorted({st.instr[p_][2] for p_ in paths}),
+            sorted({st.instr[p_][1] for p_ in paths}))
 
-        def pair_path(out, pth, xs, gname, ys, tag_):
-            """One path of one directed edge: B{tag}{jj} (-> grad_w, grad_y) and the grad_x terms per input component."""
-            b_, j, s_ = st.instr[pth]
-            l1, l2, l3 = st.in1_ls[b_], st.in2_ls[j], st.out_ls[s_]
-            d1, d2, d3 = 2 * l1 + 1, 2 * l2 + 1, 2 * l3 + 1
-            C = np.array(wigner_3j(l1, l2, l3), dtype=np.float64)
-            started = [False] * d2
-            gx_terms = []
-            for i in range(d1):
-                a_terms = []
-                for jj in range(d2):
-                    ks = [k for k in range(d3) if C[i, jj, k] != 0.0]
-                    if not ks:
-                        continue
-                    expr = " + ".join(f"T({float(C[i, jj, k])!r}) * {gname}[{opre[s_] + k}]" for k in ks)
-                    out.append(f"        const T t{tag_}{i}_{jj} = {expr};")
-                    # DUAL: B from the cotangent rows x2 (pairs with y and w), D from x (pairs with y2)
-                    xa = f"(DUAL ? xb{b_}{xs}2[{i}] : xb{b_}{xs}[{i}])"
-                    if started[jj]:
-                        out.append(f"        B{tag_}{jj} += {xa} * t{tag_}{i}_{jj};")
-                        out.append(f"        if (DUAL) D{tag_}{jj} += xb{b_}{xs}[{i}] * t{tag_}{i}_{jj};")
-                    else:
-                        out.append(f"        T B{tag_}{jj} = {xa} * t{tag_}{i}_{jj};")
-                        out.append(f"        T D{tag_}{jj} = DUAL ? xb{b_}{xs}[{i}] * t{tag_}{i}_{jj} : T(0);")
-                        started[jj] = True
-                    a_terms.append(f"yb{j}{ys}[{jj}] * t{tag_}{i}_{jj}")
-                gx_terms.append((xpre[b_] + i, " + ".join(a_terms) if a_terms else None))
-            live = [jj for jj in range(d2) if started[jj]]
-            return live, gx_terms
 
-        def pair_index_loads(sfx, idx, ind="    "):
-            return [f"{ind}jn{sfx} = spec_uniform(a.nbr[{idx}]); pr{sfx} = spec_uniform(a.wid[{idx}]);",
-                    f"{ind}ei{sfx} = spec_uniform(a.eid[{idx}]); eo{sfx} = spec_uniform(a.eid2[{idx}]);"]
+def _split_load_g(p: Plan, ind, rowexpr, name, slots):
+    out = [f"{ind}{{ const T* __restrict__ gb = {rowexpr};"]
+    for s_ in slots:
+        for k in range(2 * p.st.out_ls[s_] + 1):
+            out.append(f"{ind}  {name}[{p.opre[s_] + k}] = spec_at(gb, go{s_})[{k}];")
+    for s_ in slots:
+        for k in range(2 * p.st.out_ls[s_] + 1):
+            out.append(f"{ind}  {name}[{p.opre[s_] + k}] = act ? T({p.slot_coeff[s_]!r}) * {name}[{p.opre[s_] + k}] : T(0);")
+    out.append(f"{ind}}}")
+    return out
 
-        def pair_y_loads(sfx, ind="    "):
-            return (load_y(ind, f"(a.y + (int64_t)ei{sfx} * kS)", sfx="I" + sfx, decl=False)
-                    + load_y(ind, f"(a.y + (int64_t)eo{sfx} * kS)", sfx="X" + sfx, decl=False))
 
-        def pair_rotate(dst, src, ind="    "):
-            out = [f"{ind}jn{dst} = jn{src}; pr{dst} = pr{src}; ei{dst} = ei{src}; eo{dst} = eo{src};"]
-            for j in used_y:
-                for i in range(2 * st.in2_ls[j] + 1):
-                    out.append(f"{ind}yb{j}I{dst}[{i}] = yb{j}I{src}[{i}]; yb{j}X{dst}[{i}] = yb{j}X{src}[{i}];")
-            return out
+def _split_load_x(p: Plan, ind, rowexpr, sfx, blocks):
+    return [f"{ind}xb{b}{sfx}[{i}] = spec_at({rowexpr}, xo{b})[{i}];" for b in blocks for i in range(2 * p.st.in1_ls[b] + 1)]
 
-        def pair_loads(sfx, idx, with_g=True, scalars=True):
-            """Operands of the pair in owner slot `idx` into register set `sfx` (the indices are wave-uniform).  The
-            gathered grad_out row goes to the single array gvJ (with_g) or is requested later by pair_load_g.
-            scalars=False: the indices and the y rows are in place already (scalar prefetch, NQA_GEN_PAIR_SPF)."""
-            out = ["    {"] + (pair_index_loads(sfx, idx, "      ") if scalars else [])
-            if pair_abl & 4:
-                out.append(f"      if (a.N >= 0) jn{sfx} = node;")
-            out += [f"      const T* __restrict__ xr = a.x + (int64_t)jn{sfx} * a.din;",
-                   (f"      const T* __restrict__ wr = a.w + (int64_t)(a.N < 0 ? pr{sfx} : 0) * a.wn;" if pair_abl & 8 else
-                    f"      const T* __restrict__ wr = a.w + (int64_t)pr{sfx} * a.wn;"),
-                   f"      const T* __restrict__ yi = a.y + (int64_t)ei{sfx} * kS;",
-                   f"      const T* __restrict__ yo = a.y + (int64_t)eo{sfx} * kS;"]
-            out += load_w("      ", "wr", sfx=sfx, decl=False)
-            out += load_x("      ", "xr", sfx="J" + sfx, decl=False)
-            if with_g:
-                out += load_g("      ", f"a.g + (int64_t)jn{sfx} * a.dout", "gvJ")
-            if scalars:
-                out += load_y("      ", "yi", sfx="I" + sfx, decl=False)
-                out += load_y("      ", "yo", sfx="X" + sfx, decl=False)
-            out.append("      if (DUAL && a.w2 != nullptr) {")
-            out += load_w("        ", f"(a.w2 + (int64_t)pr{sfx} * a.wn)", sfx="2" + sfx, decl=False)
-            out.append("      }")
-            out.append("      if (DUAL) {")
-            out += load_x("        ", f"(a.x2 + (int64_t)jn{sfx} * a.din)", sfx="J" + sfx + "2", decl=False)
-            out += load_y("        ", f"(a.y2 + (int64_t)ei{sfx} * kS)", sfx="I" + sfx + "2", decl=False)
-            out += load_y("        ", f"(a.y2 + (int64_t)eo{sfx} * kS)", sfx="X" + sfx + "2", decl=False)
-            out.append("      }")
-            out.append("    }")
-            return out
 
-        def pair_load_g(sfx):
-            return load_g("    ", f"a.g + (int64_t)jn{sfx} * a.dout", "gvJ")
+def _split_part_registers(p: Plan, blocks, ys):
+    return ([f"      T xb{b}O[{2 * p.st.in1_ls[b] + 1}], xb{b}J[{2 * p.st.in1_ls[b] + 1}];" for b in blocks]
+            + [f"      T yb{j}I[{2 * p.st.in2_ls[j] + 1}], yb{j}X[{2 * p.st.in2_ls[j] + 1}];" for j in ys])
 
-        def pair_decls(sfx):
-            return ([f"  T wv{sfx}[kNP], wv2{sfx}[kNP];", f"  int jn{sfx} = 0, pr{sfx} = 0, ei{sfx} = 0, eo{sfx} = 0;"]
-                    + decl_x("  ", "J" + sfx) + decl_y("  ", "I" + sfx) + decl_y("  ", "X" + sfx)
-                    + decl_x("  ", "J" + sfx + "2") + decl_y("  ", "I" + sfx + "2") + decl_y("  ", "X" + sfx + "2"))
 
-        def pair_compute(sfx, slot):
-            if pair_abl & 32:  # lab: the memory streams of a pair without its arithmetic (every loaded value is consumed once)
-                out = ["    {", "    T s_ = T(0);", "#pragma unroll", "    for (int k = 0; k < kOD; ++k) s_ += gvJ[k] + gvO[k];"]
-                for b in used_blocks:
-                    for i in range(2 * st.in1_ls[b] + 1):
-                        out.append(f"    s_ += xb{b}J{sfx}[{i}] + xb{b}O[{i}];")
-                for j in used_y:
-                    for i in range(2 * st.in2_ls[j] + 1):
-                        out.append(f"    s_ += yb{j}I{sfx}[{i}] + yb{j}X{sfx}[{i}];")
-                out += [(f"    T* __restrict__ gwr_e = a.gw + (int64_t)(a.N < 0 ? pr{sfx} : 0) * a.wn;" if pair_abl & 1 else
-                         f"    T* __restrict__ gwr_e = a.gw + (int64_t)pr{sfx} * a.wn;"),
-                        (f"    T* __restrict__ gxr = a.gxe + (int64_t)(a.N < 0 ? ({slot}) : 0) * a.din;" if pair_abl & 2 else
-                         f"    T* __restrict__ gxr = a.gxe + (int64_t)({slot}) * a.din;")]
-                for pth in range(NP):
-                    out.append(f"    {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', f'wv{sfx}[{pth}] + s_')};")
-                for i in range(XD):
-                    out.append(f"    if (GX) {emit_store(f'spec_at(gxr + (unsigned)(mul * {i}), ucb)', 's_')};")
-                    out.append(f"    gxO[{i}] += s_;")
-                out.append(f"    if (lane < kS) {{ a.gy[(int64_t)ei{sfx} * a.gy_stride + chunk * kS + lane] = s_; a.gy[(int64_t)eo{sfx} * a.gy_stride + chunk * kS + lane] = s_; }}")
-                out.append("    }")
-                return out
-            out = ["    {"]
-            if pair_nohoist:
-                # T_ij = sum_k C_ijk g_k of the owner's grad_out is the same for all its pairs: the compiler hoists those
-                # (hundreds of) products out of the pair loop and keeps them in registers -- 254 registers, nothing left
-                # for a second operand set.  An empty asm that "modifies" the row makes them per-pair values again.
-                out += ["#pragma unroll", "    for (int k = 0; k < kOD; ++k) asm volatile(\"\" : \"+v\"(gvO[k]));"]
-            out += ["    T qI[kS], qX[kS], gxa[kXD];", "#pragma unroll",
-                   "    for (int j = 0; j < kS; ++j) { qI[j] = T(0); qX[j] = T(0); }",
-                   (f"    T* __restrict__ gwr_e = a.gw + (int64_t)(a.N < 0 ? pr{sfx} : 0) * a.wn;" if pair_abl & 1 else
-                    f"    T* __restrict__ gwr_e = a.gw + (int64_t)pr{sfx} * a.wn;"),
-                   (f"    T* __restrict__ gxr = a.gxe + (int64_t)(a.N < 0 ? ({slot}) : 0) * a.din;" if pair_abl & 2 else
-                    f"    T* __restrict__ gxr = a.gxe + (int64_t)jn{sfx} * a.din;" if pair_gx_atomic else
-                    f"    T* __restrict__ gxr = a.gxe + (int64_t)({slot}) * a.din;")]
-            last_path_of_block = {b_: p_ for p_, (b_, _, _) in enumerate(st.instr)}
-            first_path_of_block = {}
-            for p_, (b_, _, _) in enumerate(st.instr):
-                first_path_of_block.setdefault(b_, p_)
-            for pth, (b_, j, s_) in enumerate(st.instr):
-                d1 = 2 * st.in1_ls[b_] + 1
-                if first_path_of_block[b_] == pth:
-                    for i in range(d1):
-                        out.append(f"      gxa[{xpre[b_] + i}] = T(0);")
-                out.append(f"      {{  // path {pth}")
-                live_i, gx_i = pair_path(out, pth, "J" + sfx, "gvO", "I" + sfx, "i")
-                for comp, expr in gx_i:
-                    if expr:
-                        out.append(f"        if (GX) gxa[{comp}] += wv{sfx}[{pth}] * ({expr});")
-                live_x, gx_x = pair_path(out, pth, "O", "gvJ", "X" + sfx, "x")
-                for comp, expr in gx_x:
-                    if expr:
-                        out.append(f"        if (GX) gxO[{comp}] += wv{sfx}[{pth}] * ({expr});")
-                terms = [f"yb{j}I{sfx}[{jj}] * Bi{jj}" for jj in live_i] + [f"yb{j}X{sfx}[{jj}] * Bx{jj}" for jj in live_x]
-                gw_expr = " + ".join(terms) if terms else "T(0)"
-                dterms = [f"yb{j}I{sfx}2[{jj}] * Di{jj}" for jj in live_i] + [f"yb{j}X{sfx}2[{jj}] * Dx{jj}" for jj in live_x]
-                dual_expr = " + ".join(dterms) if dterms else "T(0)"
-                out.append(f"        {{ T r_ = {gw_expr}; if (DUAL) r_ += {dual_expr}; if (act) {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'r_')}; }}")
-                for jj in live_i:
-                    out.append(f"        qI[{ypre[j] + jj}] += wv{sfx}[{pth}] * Bi{jj};")
-                for jj in live_x:
-                    out.append(f"        qX[{ypre[j] + jj}] += wv{sfx}[{pth}] * Bx{jj};")
-                # DUAL with a weight cotangent (a.w2): grad_y += By(x, w2, g) rides on the D intermediates
-                out.append("        if (DUAL && a.w2 != nullptr) {")
-                for jj in live_i:
-                    out.append(f"          qI[{ypre[j] + jj}] += wv2{sfx}[{pth}] * Di{jj};")
-                for jj in live_x:
-                    out.append(f"          qX[{ypre[j] + jj}] += wv2{sfx}[{pth}] * Dx{jj};")
-                out.append("        }")
-                out.append("      }")
-                if last_path_of_block[b_] == pth:
-                    out.append("      if (GX && act) {")
-                    for i in range(d1):
-                        if pair_gx_atomic:
-                            out.append(f"        unsafeAtomicAdd(spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb), gxa[{xpre[b_] + i}]);")
-                        else:
-                            out.append(f"        {emit_store(f'spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb)', f'gxa[{xpre[b_] + i}]')};")
-                    out.append("      }")
-            unused = [i for b in range(NB) if b not in first_path_of_block for i in range(xpre[b], xpre[b] + 2 * st.in1_ls[b] + 1)]
-            if unused and not pair_gx_atomic:
-                out.append("      if (GX && act) {")
-                for i in unused:
-                    out.append(f"        *spec_at(gxr + (unsigned)(mul * {i}), ucb) = T(0);")
-                out.append("      }")
-            out.append("      spec_mask_dup<T, kS>(qI, u < mul);")
-            out.append("      spec_mask_dup<T, kS>(qX, u < mul);")
-            gy_i, gy_x = (f"(a.N < 0 ? ei{sfx} : 0)", f"(a.N < 0 ? eo{sfx} : 0)") if pair_abl & 16 else (f"ei{sfx}", f"eo{sfx}")
-            out.append(f"      spec_wave_reduce_store<T, kS>(qI, a.gy + (int64_t){gy_i} * a.gy_stride + chunk * kS, lane);")
-            out.append(f"      spec_wave_reduce_store<T, kS>(qX, a.gy + (int64_t){gy_x} * a.gy_stride + chunk * kS, lane);")
-            out.append("    }")
-            return out
+def _split_item(L):
+    L += ["  const int64_t item = (int64_t)spec_xcd_remap(blockIdx.x, gridDim.x) * 4 + wid;",
+          "  if (item >= (int64_t)a.N * nchunk * kPairParts) return;",
+          "  const int node = spec_uniform((int)(item / (nchunk * kPairParts)));",
+          "  const int rem = (int)(item - (int64_t)node * (nchunk * kPairParts));",
+          "  const int chunk = spec_uniform(rem / kPairParts);",
+          "  const int part = spec_uniform(rem - chunk * kPairParts);",
+          "  const int u = chunk * 64 + lane;"]
 
-        # NQA_GEN_PAIR_PIPE=1: two operand sets for the streamed rows (w, x[other], y); the gathered grad_out[other] row
-        # of the CURRENT pair is requested first (single buffer), then the next pair's rows, then the pair is evaluated
-        pair_pipe = os.environ.get("NQA_GEN_PAIR_PIPE", "0") != "0" and not big
-        A("  int idx = beg + wsub;")
-        A("  T gvJ[kOD];")
-        if pair_pipe:
-            L.extend(pair_decls("A") + pair_decls("B"))
-            A("  if (idx < end) {")
-            L.extend(pair_loads("A", "idx", with_g=False))
-            A("  }")
-            A("  while (idx < end) {")
-            L.extend(pair_load_g("A"))
-            A("    int nidx = idx + WPN;")
-            A("    if (nidx < end) {")
-            L.extend(pair_loads("B", "nidx", with_g=False))
-            A("    }")
-            L.extend(pair_compute("A", "idx"))
-            A("    idx = nidx;")
-            A("    if (idx >= end) break;")
-            L.extend(pair_load_g("B"))
-            A("    nidx = idx + WPN;")
-            A("    if (nidx < end) {")
-            L.extend(pair_loads("A", "nidx", with_g=False))
-            A("    }")
-            L.extend(pair_compute("B", "idx"))
-            A("    idx = nidx;")
-            A("  }")
-        else:
-            # NQA_GEN_PAIR_PREFETCH=1: touch the next pair's weight row (the one stream that comes from HBM) while this pair
-            # is evaluated -- plain loads into a sink value, so that the row is in the L2 when the real loads ask for it
-            pair_prefetch = os.environ.get("NQA_GEN_PAIR_PREFETCH", "1") != "0"  # same-box cfg-3: 2.930 -> 2.912 ms
-            # NQA_GEN_PAIR_SPF=1: the wave-uniform operands (four indices, two y rows) of the NEXT pair and the indices of the
-            # one after it are requested while this pair's rows are in flight -- one dependent scalar round trip less per pair
-            pair_spf = int(os.environ.get("NQA_GEN_PAIR_SPF", "0"))  # 2: the indices only (y rows: 36 more scalar registers)
-            spf_y = pair_spf == 1
-            L.extend(pair_decls("A"))
-            if pair_prefetch:
-                A("  T pf_sink = T(0);")
-            if pair_spf:
-                L.extend(pair_decls("N"))
-                A("  int jnM = 0, prM = 0, eiM = 0, eoM = 0;")
-                A("  if (idx < end) {")
-                L.extend(pair_index_loads("A", "idx"))
-                if spf_y:
-                    L.extend(pair_y_loads("A"))
-                A("  }")
-                if spf_y:
-                    A("  if (idx + WPN < end) {")
-                    L.extend(pair_index_loads("N", "idx + WPN"))
-                    A("  }")
-            pair_timing = os.environ.get("NQA_GEN_PAIR_TIMING", "0") != "0"  # lab: where a pair's cycles go (s_memtime)
-            if pair_timing:
-                A("  unsigned long long tm_[5] = {0, 0, 0, 0, 0};")
-                A("  const unsigned long long tk0_ = __builtin_amdgcn_s_memtime();")
-            A("  for (; idx < end; idx += WPN) {")
-            if pair_timing:
-                A("    const unsigned long long t0_ = __builtin_amdgcn_s_memtime();")
-                A("    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");")
-            L.extend(pair_loads("A", "idx", scalars=not pair_spf))
-            if pair_timing:
-                A("    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");  // indices + y rows are here, the row loads are issued")
-                A("    const unsigned long long t1_ = __builtin_amdgcn_s_memtime();")
-                A("    asm volatile(\"s_waitcnt vmcnt(0) lgkmcnt(0)\" ::: \"memory\");  // every row has arrived")
-                A("    const unsigned long long t2_ = __builtin_amdgcn_s_memtime();")
-                A("    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");")
-            if pair_spf and not spf_y:
-                L.extend(pair_y_loads("A"))
-                A("    if (idx + WPN < end) {")
-                L.extend(pair_index_loads("N", "idx + WPN", "      "))
-                A("    }")
-            elif pair_spf:
-                A("    if (idx + WPN < end) {")
-                L.extend(pair_y_loads("N", "      "))
-                A("    }")
-                A("    if (idx + 2 * WPN < end) {")
-                L.extend(pair_index_loads("M", "idx + 2 * WPN", "      "))
-                A("    }")
-            if pair_prefetch:
-                A("    T pf[kNP];")
-                A("    {")
-                if pair_spf:
-                    A("      const int prn_ = idx + WPN < end ? prN : prA;")
-                else:
-                    A("      const int nidx_ = idx + WPN < end ? idx + WPN : idx;")
-                    A("      const int prn_ = spec_uniform(a.wid[nidx_]);")
-                if pair_abl & 8:
-                    A("      const T* __restrict__ wn_ = a.w + (int64_t)(a.N < 0 ? prn_ : 0) * a.wn;")
-                else:
-                    A("      const T* __restrict__ wn_ = a.w + (int64_t)prn_ * a.wn;")
-                for pth in range(NP):
-                    A(f"      pf[{pth}] = *spec_at(wn_ + (unsigned)(mul * {pth}), ucb);")
-                A("    }")
-            L.extend(pair_compute("A", "idx"))
-            if pair_prefetch:
-                A("#pragma unroll")
-                A("    for (int p_ = 0; p_ < kNP; ++p_) pf_sink += pf[p_];")
-            if pair_timing:
-                A("    const unsigned long long t3_ = __builtin_amdgcn_s_memtime();")
-                A("    asm volatile(\"s_waitcnt vmcnt(0) lgkmcnt(0)\" ::: \"memory\");  // the stores have left")
-                A("    const unsigned long long t4_ = __builtin_amdgcn_s_memtime();")
-                A("    asm volatile(\"s_waitcnt lgkmcnt(0)\" ::: \"memory\");")
-                A("    tm_[0] += t1_ - t0_; tm_[1] += t2_ - t1_; tm_[2] += t3_ - t2_; tm_[3] += t4_ - t3_; tm_[4] += 1;")
-            if pair_spf and spf_y:
-                L.extend(pair_rotate("A", "N"))
-                A("    jnN = jnM; prN = prM; eiN = eiM; eoN = eoM;")
-            elif pair_spf:
-                A("    jnA = jnN; prA = prN; eiA = eiN; eoA = eoN;")
-            A("  }")
-            if pair_prefetch:
-                A("  if (pf_sink == T(12345.678)) a.gy[0] = pf_sink;")
-        if not pair_pipe and os.environ.get("NQA_GEN_PAIR_TIMING", "0") != "0":
-            A("  if (lane == 0) { for (int k = 0; k < 5; ++k) atomicAdd(&nqa_lab_tm[k], tm_[k]);")
-            A("    atomicAdd(&nqa_lab_tm[5], (unsigned long long)(__builtin_amdgcn_s_memtime() - tk0_)); atomicAdd(&nqa_lab_tm[6], 1ull); }")
-        A("  // grad_x[owner]: the owner-side contributions of all its pairs (the other side arrives through the rows)")
-        A("  if (!GX) return;")
-        A("  if (WPN > 1) {")
-        A("    extern __shared__ __align__(16) unsigned char nqa_smem[];")
-        A("    T* red = reinterpret_cast<T*>(nqa_smem);")
-        A("    if (wsub > 0) {")
-        A("#pragma unroll")
-        A("      for (int k = 0; k < kXD; ++k) red[((wsub - 1) * kXD + k) * 64 + lane] = gxO[k];")
-        A("    }")
-        A("    __syncthreads();")
-        A("    if (wsub > 0) return;")
-        A("#pragma unroll")
-        A("    for (int k = 0; k < kXD; ++k) {")
-        A("#pragma unroll")
-        A("      for (int w2 = 0; w2 < WPN - 1; ++w2) gxO[k] += red[(w2 * kXD + k) * 64 + lane];")
-        A("    }")
-        A("  }")
-        A("  if (act) {")
-        A("    const int uc = u < mul ? u : mul - 1;")
-        A("    T* __restrict__ ob = a.out + (int64_t)node * a.din;")
-        for b in range(NB):
-            d = 2 * st.in1_ls[b] + 1
-            for i in range(d):
-                A(f"    ob[(int64_t)mul * {xpre[b]} + (int64_t)uc * {d} + {i}] = gxO[{xpre[b] + i}];")
-        A("  }")
-        A("}")
 
-    # ------------------------------------------------------------------ pair-centric backward, PACKED fp32
-    # Round 6.  Counters and ablations of bwd_pair_kernel (profiles/r6_pair_counters.txt, r6_pair_ablations_call1.txt): with
-    # every memory stream pointed at one hot row the kernel still takes 72 % of its time -- it sits on its ~820 vector
-    # instructions per pair (4 cycles each; the vector ALU is busy for half of the kernel's duration at two wavefronts per
-    # SIMD), not on HBM.  gfx950 issues two fp32 operations per lane and instruction as v_pk_{mul,add,fma}_f32 on register
-    # PAIRS, and the two directed edges of a pair run the SAME instruction stream on different operands:
-    #     in  (j -> o):  x = x[j], g = grad_out[o], y = y[e_in]   -> grad_x row of j,  grad_y[e_in]
-    #     out (o -> j):  x = x[o], g = grad_out[j], y = y[e_out]  -> grad_x[o] (registers), grad_y[e_out]
-    # so every value becomes a pair (.x = in, .y = out): G[k] = (g_o[k], g_j[k]), X[i] = (x_j[i], x_o[i]), Y = (y_in, y_out),
-    # the weight is shared.  One packed stream evaluates both edges; the owner-side intermediates T_ij(g_o) that the scalar
-    # kernel hoisted out of the pair loop (~115 registers) are recomputed for free in the .x halves.
-    # OUTCOME (profiles/r6_pk_rate_and_packed_pair_call2.txt): 561 vs 575 us -- a v_pk_fma_f32 takes twice the passes of a
-    # v_fma_f32 (5.1 vs 2.6 cycles per wavefront instruction), the part reaches its fp32 rate without packing, and the first
-    # reading above was wrong about what bounds the kernel (see the LDS-ring section below).  Lab only: NQA_GEN_PAIR_PK=1.
-    if pair_ok and os.environ.get("NQA_GEN_PAIR_PK", "0") != "0":
-        pk_occ = os.environ.get("NQA_GEN_PAIR_PK_OCC", "2")
-        pk_prefetch = os.environ.get("NQA_GEN_PAIR_PK_PREFETCH", "0") != "0"
-        A("template <typename T, int WPN, bool FULL, bool GX>")
-        A(f"__global__ __launch_bounds__(256, {pk_occ}) void bwd_pair_pk_kernel(const SpecArgs<T> a) {{")
-        A("  static_assert(sizeof(T) == 4, \"packed fp32 only\");")
-        A("  const int lane = threadIdx.x & 63;")
-        A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
-        A("  const int mul = a.mul;")
-        A("  const int nchunk = (mul + 63) >> 6;")
-        A("  const int64_t witem = (int64_t)spec_xcd_remap(blockIdx.x, gridDim.x) * 4 + wid;")
-        A("  const int64_t item = witem / WPN;")
-        A("  const int wsub = (int)(witem - item * WPN);")
-        A("  if (item >= (int64_t)a.N * nchunk) return;  // (WPN == 4: the whole workgroup)")
-        A("  const int node = spec_uniform((int)(item / nchunk));")
-        A("  const int chunk = (int)(item - (int64_t)node * nchunk);")
-        A("  const int u = chunk * 64 + lane;")
-        A("  const bool act = FULL || (u < mul);")
-        A("  const int beg = a.rowptr[node], end = a.rowptr[node + 1];")
-        L.extend(lane_offsets("  ", want_x=True, want_g=True))
-        A("  f2 G[kOD], X[kXD];  // .x: the in edge's operand, .y: the out edge's")
-        A("  T gxO[kXD];")
+def _nohoist(p: Plan, slots, ind):
+    # the owner-side intermediates T_ij = sum_k C_ijk grad_out[owner]_k are the same for all pairs; hoisted out of the pair
+    # loop they are ~150 live values for the l_1 = 3 block (79 spilled registers).  An empty asm that "modifies" the
+    # owner's slots makes them per-pair values.
+    return [f"{ind}asm volatile(\"\" : \"+v\"(gvO[{p.opre[s_] + k}]));" for s_ in slots for k in range(2 * p.st.out_ls[s_] + 1)]
 
-        def pk_load_g(indent, rowexpr, comp):
-            out = [f"{indent}{{ const T* __restrict__ gb = {rowexpr};"]
-            for s_ in range(NS):
-                d3 = 2 * st.out_ls[s_] + 1
-                for k in range(d3):
-                    if slot_coeff[s_] is None:
-                        out.append(f"{indent}  G[{opre[s_] + k}].{comp} = T(0);")
-                    else:
-                        out.append(f"{indent}  G[{opre[s_] + k}].{comp} = spec_at(gb, go{s_})[{k}];")
-            # (the path normalisation sqrt((2 l3 + 1) / n_paths) is folded into the 3j constants below: no multiply per value)
-            out.append(f"{indent}  if (!FULL) {{")
-            for s_ in range(NS):
-                d3 = 2 * st.out_ls[s_] + 1
-                if slot_coeff[s_] is None:
-                    continue
-                for k in range(d3):
-                    out.append(f"{indent}    G[{opre[s_] + k}].{comp} = act ? G[{opre[s_] + k}].{comp} : T(0);")
-            out.append(f"{indent}  }}")
-            out.append(f"{indent}}}")
-            return out
 
-        def pk_load_x(indent, rowexpr, comp):
-            out = []
-            for b in range(NB):
-                d = 2 * st.in1_ls[b] + 1
-                for i in range(d):
-                    if b in used_blocks:
-                        out.append(f"{indent}X[{xpre[b] + i}].{comp} = spec_at({rowexpr}, xo{b})[{i}];")
-                    else:
-                        out.append(f"{indent}X[{xpre[b] + i}].{comp} = T(0);")
-            return out
-
-        L.extend(pk_load_g("  ", "a.g + (int64_t)node * a.dout", "x"))
-        L.extend(pk_load_x("  ", "(a.x + (int64_t)node * a.din)", "y"))
-        A("#pragma unroll")
-        A("  for (int i = 0; i < kXD; ++i) gxO[i] = T(0);")
-        A("  T wv[kNP];")
-        A("  f2 Y[kS];")
-        if pk_prefetch:
-            A("  T pf_sink = T(0);")
-        A("  for (int idx = beg + wsub; idx < end; idx += WPN) {")
-        A("    const int jn_ = spec_uniform(a.nbr[idx]), pr = spec_uniform(a.wid[idx]);")
-        A("    const int ei = spec_uniform(a.eid[idx]), eo = spec_uniform(a.eid2[idx]);")
-        A("    const int jn = " + ("(a.N < 0 ? jn_ : node);" if pair_abl & 4 else "jn_;"))
-        A("    const T* __restrict__ wr = a.w + (int64_t)" + ("(a.N < 0 ? pr : 0)" if pair_abl & 8 else "pr") + " * a.wn;")
-        A("    const T* __restrict__ yi = a.y + (int64_t)ei * kS;")
-        A("    const T* __restrict__ yo = a.y + (int64_t)eo * kS;")
-        for pth in range(NP):
-            A(f"    wv[{pth}] = *spec_at(wr + (unsigned)(mul * {pth}), ucb);")
-        L.extend(pk_load_x("    ", "(a.x + (int64_t)jn * a.din)", "x"))
-        L.extend(pk_load_g("    ", "a.g + (int64_t)jn * a.dout", "y"))
-        for j in used_y:
+# ------------------------------------------------------------------ pair-centric backward, split by input block
+# Structures whose two grad_out rows do not fit one wavefront's registers (l_max = 3: 99 values each): every input
+# block l_1 owns its paths, its output slots, its weight columns and its grad_x components, so the pair kernel splits
+# over PS wavefronts per (node, channel chunk) with no exchange -- wavefront `part` holds only its blocks' slice of
+# grad_out[owner] / grad_out[other] / x / w.  Shared by the parts: the two y rows and the pair indices (scalar loads).
+# grad_y: every part reduces its own partial sums into a [chunk, part] slot of the partial buffer (summed by
+# spec_gy_reduce_kernel, as the chunk partials are).
+def emit_pair_split(p: Plan) -> List[str]:
+    st = p.st
+    L = []
+    A = L.append
+    A(f"constexpr int kPairParts = {p.pair_parts};")
+    A("// ATOM (multiples of 64 channels): the other node's grad_x by atomics into the zeroed [N, dim_in1] accumulator a.gxe")
+    A("// (see bwd_pair_ring_kernel) instead of one row per pair")
+    A("template <typename T, bool FULL, bool GX, bool ATOM = false>")
+    A("__global__ __launch_bounds__(256, 2) void bwd_pair_split_kernel(const SpecArgs<T> a) {")
+    A("  const int lane = threadIdx.x & 63;")
+    A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
+    A("  const int mul = a.mul;")
+    A("  const int nchunk = (mul + 63) >> 6;")
+    _split_item(L)
+    A("  const bool act = FULL || (u < mul);")
+    A("  const int beg = a.rowptr[node], end = a.rowptr[node + 1];")
+    L.extend(lane_offsets(p, "  ", want_x=True, want_g=True))
+    A("  switch (part) {")
+    for part_i, paths in enumerate(p.part_paths):
+        blocks, slots, ys = _split_part_sets(st, paths)
+        A(f"    case {part_i}: {{  // input blocks {blocks}: paths {paths}")
+        A("      T gvO[kOD], gvJ[kOD], gxO[kXD], wv[kNP];")
+        L.extend(_split_part_registers(p, blocks, ys))
+        L.extend(_split_load_g(p, "      ", "a.g + (int64_t)node * a.dout", "gvO", slots))
+        L.extend(_split_load_x(p, "      ", "(a.x + (int64_t)node * a.din)", "O", blocks))
+        for b in blocks:
+            for i in range(2 * st.in1_ls[b] + 1):
+                A(f"      gxO[{p.xpre[b] + i}] = T(0);")
+        A("      for (int idx = beg; idx < end; ++idx) {")
+        A("        const int j_ = spec_uniform(a.nbr[idx]), pr = spec_uniform(a.wid[idx]);")
+        A("        const int ei = spec_uniform(a.eid[idx]), eo = spec_uniform(a.eid2[idx]);")
+        A("        const T* __restrict__ xr = a.x + (int64_t)j_ * a.din;")
+        A("        const T* __restrict__ wr = a.w + (int64_t)pr * a.wn;")
+        A("        const T* __restrict__ yi = a.y + (int64_t)ei * kS;")
+        A("        const T* __restrict__ yo = a.y + (int64_t)eo * kS;")
+        for pth in paths:
+            A(f"        wv[{pth}] = *spec_at(wr + (unsigned)(mul * {pth}), ucb);")
+        L.extend(_split_load_x(p, "        ", "xr", "J", blocks))
+        L.extend(_split_load_g(p, "        ", "a.g + (int64_t)j_ * a.dout", "gvJ", slots))
+        for j in ys:
             for i in range(2 * st.in2_ls[j] + 1):
-                A(f"    Y[{ypre[j] + i}] = f2{{yi[{ypre[j] + i}], yo[{ypre[j] + i}]}};")
-        if pk_prefetch:
-            A("    T pf[kNP];")
-            A("    {")
-            A("      const int nidx_ = idx + WPN < end ? idx + WPN : idx;")
-            A("      const T* __restrict__ wn_ = a.w + (int64_t)" + ("(a.N < 0 ? spec_uniform(a.wid[nidx_]) : 0)" if pair_abl & 8 else "spec_uniform(a.wid[nidx_])") + " * a.wn;")
-            for pth in range(NP):
-                A(f"      pf[{pth}] = *spec_at(wn_ + (unsigned)(mul * {pth}), ucb);")
-            A("    }")
-        A("    f2 Q[kS];")
+                A(f"        yb{j}I[{i}] = yi[{p.ypre[j] + i}]; yb{j}X[{i}] = yo[{p.ypre[j] + i}];")
+        if n_owner_terms(st, paths) > SPLIT_NOHOIST:
+            L.extend(_nohoist(p, slots, "        "))
+        A("        T qI[kS], qX[kS], gxa[kXD];")
         A("#pragma unroll")
-        A("    for (int j = 0; j < kS; ++j) Q[j] = f2{T(0), T(0)};")
-        A("    T* __restrict__ gwr_e = a.gw + (int64_t)" + ("(a.N < 0 ? pr : 0)" if pair_abl & 1 else "pr") + " * a.wn;")
-        A("    T* __restrict__ gxr = a.gxe + (int64_t)" + ("(a.N < 0 ? idx : 0)" if pair_abl & 2 else "idx") + " * a.din;")
-        pk_last = {b_: p_ for p_, (b_, _, _) in enumerate(st.instr)}
-        pk_first = {}
-        for p_, (b_, _, _) in enumerate(st.instr):
-            pk_first.setdefault(b_, p_)
-        for b in sorted(pk_first):
-            A(f"    f2 ga{b}[{2 * st.in1_ls[b] + 1}];  // sum over the block's paths of w_p A^p_i: .x -> the pair's row, .y -> grad_x[owner]")
-        for pth, (b_, j, s_) in enumerate(st.instr):
-            l1, l2, l3 = st.in1_ls[b_], st.in2_ls[j], st.out_ls[s_]
-            d1, d2, d3 = 2 * l1 + 1, 2 * l2 + 1, 2 * l3 + 1
-            C = np.array(wigner_3j(l1, l2, l3), dtype=np.float64)
-            A(f"    {{  // path {pth}: l1 {l1} x l2 {l2} -> l3 {l3}")
-            started = [False] * d2
-            for i in range(d1):
-                a_started = False
-                for jj in range(d2):
-                    ks = [k for k in range(d3) if C[i, jj, k] != 0.0]
-                    if not ks:
-                        continue
-                    expr = " + ".join(f"T({float(C[i, jj, k]) * float(slot_coeff[s_])!r}) * G[{opre[s_] + k}]" for k in ks)
-                    A(f"      const f2 t{i}_{jj} = {expr};")
-                    if started[jj]:
-                        A(f"      B{jj} += X[{xpre[b_] + i}] * t{i}_{jj};")
-                    else:
-                        A(f"      f2 B{jj} = X[{xpre[b_] + i}] * t{i}_{jj};")
-                        started[jj] = True
-                    if a_started:
-                        A(f"      if (GX) A{i} += Y[{ypre[j] + jj}] * t{i}_{jj};")
-                    else:
-                        A(f"      f2 A{i} = Y[{ypre[j] + jj}] * t{i}_{jj};")
-                        a_started = True
-                if a_started:
-                    if pk_first[b_] == pth:
-                        A(f"      if (GX) ga{b_}[{i}] = wv[{pth}] * A{i};")
-                    else:
-                        A(f"      if (GX) ga{b_}[{i}] += wv[{pth}] * A{i};")
-                elif pk_first[b_] == pth:
-                    A(f"      if (GX) ga{b_}[{i}] = f2{{T(0), T(0)}};")
-            live = [jj for jj in range(d2) if started[jj]]
-            if live:
-                terms = " + ".join(f"Y[{ypre[j] + jj}] * B{jj}" for jj in live)
-                A(f"      {{ const f2 r2 = {terms}; const T r_ = r2.x + r2.y; if (act) {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'r_')}; }}")
-            else:
-                A(f"      if (act) {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'T(0)')};")
-            for jj in live:
-                A(f"      Q[{ypre[j] + jj}] += wv[{pth}] * B{jj};")
-            A("    }")
-            if pk_last[b_] == pth:
-                A("    if (GX) {")
+        A("        for (int j = 0; j < kS; ++j) { qI[j] = T(0); qX[j] = T(0); }")
+        A("        T* __restrict__ gwr_e = a.gw + (int64_t)pr * a.wn;")
+        A("        T* __restrict__ gxr = a.gxe + (int64_t)(ATOM ? j_ : idx) * a.din;")
+        for pth in paths:
+            b_, j, s_ = st.instr[pth]
+            d1 = 2 * st.in1_ls[b_] + 1
+            if p.first_path[b_] == pth:
                 for i in range(d1):
-                    A(f"      if (act) {emit_store(f'spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb)', f'ga{b_}[{i}].x')};")
-                    A(f"      gxO[{xpre[b_] + i}] += ga{b_}[{i}].y;")
-                A("    }")
-        pk_unused = [i for b in range(NB) if b not in pk_first for i in range(xpre[b], xpre[b] + 2 * st.in1_ls[b] + 1)]
-        if pk_unused:
-            A("    if (GX && act) {")
-            for i in pk_unused:
-                A(f"      *spec_at(gxr + (unsigned)(mul * {i}), ucb) = T(0);")
-            A("    }")
-        A("    T qI[kS], qX[kS];")
-        A("#pragma unroll")
-        A("    for (int j = 0; j < kS; ++j) { qI[j] = Q[j].x; qX[j] = Q[j].y; }")
-        A("    spec_mask_dup<T, kS>(qI, u < mul);")
-        A("    spec_mask_dup<T, kS>(qX, u < mul);")
-        gy_i, gy_x = ("(a.N < 0 ? ei : 0)", "(a.N < 0 ? eo : 0)") if pair_abl & 16 else ("ei", "eo")
-        A(f"    spec_wave_reduce_store<T, kS>(qI, a.gy + (int64_t){gy_i} * a.gy_stride + chunk * kS, lane);")
-        A(f"    spec_wave_reduce_store<T, kS>(qX, a.gy + (int64_t){gy_x} * a.gy_stride + chunk * kS, lane);")
-        if pk_prefetch:
-            A("#pragma unroll")
-            A("    for (int p_ = 0; p_ < kNP; ++p_) pf_sink += pf[p_];")
-        A("  }")
-        if pk_prefetch:
-            A("  if (pf_sink == T(12345.678)) a.gy[0] = pf_sink;")
-        A("  if (!GX) return;")
-        A("  if (WPN > 1) {")
-        A("    extern __shared__ __align__(16) unsigned char nqa_smem[];")
-        A("    T* red = reinterpret_cast<T*>(nqa_smem);")
-        A("    if (wsub > 0) {")
-        A("#pragma unroll")
-        A("      for (int k = 0; k < kXD; ++k) red[((wsub - 1) * kXD + k) * 64 + lane] = gxO[k];")
-        A("    }")
-        A("    __syncthreads();")
-        A("    if (wsub > 0) return;")
-        A("#pragma unroll")
-        A("    for (int k = 0; k < kXD; ++k) {")
-        A("#pragma unroll")
-        A("      for (int w2 = 0; w2 < WPN - 1; ++w2) gxO[k] += red[(w2 * kXD + k) * 64 + lane];")
-        A("    }")
-        A("  }")
-        A("  if (act) {")
-        A("    const int uc = u < mul ? u : mul - 1;")
-        A("    T* __restrict__ ob = a.out + (int64_t)node * a.din;")
-        for b in range(NB):
-            d = 2 * st.in1_ls[b] + 1
-            for i in range(d):
-                A(f"    ob[(int64_t)mul * {xpre[b]} + (int64_t)uc * {d} + {i}] = gxO[{xpre[b] + i}];")
-        A("  }")
-        A("}")
+                    A(f"        gxa[{p.xpre[b_] + i}] = T(0);")
+            A(f"        {{  // path {pth}")
+            live_i, gx_i = path_terms(p, L, pth, "J", "gvO", "I", "i", "          ", dual=False)
+            for comp, expr in gx_i:
+                if expr:
+                    A(f"          if (GX) gxa[{comp}] += wv[{pth}] * ({expr});")
+            live_x, gx_x = path_terms(p, L, pth, "O", "gvJ", "X", "x", "          ", dual=False)
+            for comp, expr in gx_x:
+                if expr:
+                    A(f"          if (GX) gxO[{comp}] += wv[{pth}] * ({expr});")
+            terms = [f"yb{j}I[{jj}] * Bi{jj}" for jj in live_i] + [f"yb{j}X[{jj}] * Bx{jj}" for jj in live_x]
+            gw_expr = " + ".join(terms) if terms else "T(0)"
+            A(f"          {{ const T r_ = {gw_expr}; if (act) {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'r_')}; }}")
+            for jj in live_i:
+                A(f"          qI[{p.ypre[j] + jj}] += wv[{pth}] * Bi{jj};")
+            for jj in live_x:
+                A(f"          qX[{p.ypre[j] + jj}] += wv[{pth}] * Bx{jj};")
+            A("        }")
+            if p.last_path[b_] == pth:
+                A("        if (GX && act) {")
+                for i in range(d1):
+                    st_ = emit_store(f'spec_at(gxr + (unsigned)(mul * {p.xpre[b_] + i}), ucb)', f'gxa[{p.xpre[b_] + i}]')
+                    A(f"          if (ATOM) unsafeAtomicAdd(spec_at(gxr + (unsigned)(mul * {p.xpre[b_] + i}), ucb), gxa[{p.xpre[b_] + i}]); else {st_};")
+                A("        }")
+        if part_i == 0 and p.unused_comps:
+            A("        if (GX && act && !ATOM) {")
+            for i in p.unused_comps:
+                A(f"          *spec_at(gxr + (unsigned)(mul * {i}), ucb) = T(0);")
+            A("        }")
+        A("        spec_mask_dup<T, kS>(qI, u < mul);")
+        A("        spec_mask_dup<T, kS>(qX, u < mul);")
+        A(f"        spec_wave_reduce_store<T, kS>(qI, a.gy + (int64_t)ei * a.gy_stride + (chunk * kPairParts + {part_i}) * kS, lane);")
+        A(f"        spec_wave_reduce_store<T, kS>(qX, a.gy + (int64_t)eo * a.gy_stride + (chunk * kPairParts + {part_i}) * kS, lane);")
+        A("      }")
+        A("      if (GX && act) {")
+        A("        const int uc = u < mul ? u : mul - 1;")
+        A("        T* __restrict__ ob = a.out + (int64_t)node * a.din;")
+        L.extend(_split_part_x_rows(p, part_i, blocks, "uc"))
+        A("      }")
+        A("    } break;")
+    A("    default: break;")
+    A("  }")
+    A("}")
+    return L
 
-    # ------------------------------------------------------------------ pair-centric backward, LDS ring (round 6)
-    # What held bwd_pair_kernel at half of the HBM roof (profiles/r6_pair_*.txt, r6_lab_call4.txt ... call7.txt; index: profiles/README_r6.md): one pair in flight per
-    # wavefront at two wavefronts per SIMD.  The same loop WITHOUT its arithmetic takes 85 % of the kernel's time, with every
-    # stream pointed at cache-hot rows still 42 % -- it is the serial chain indices -> row loads -> arithmetic -> stores of
-    # each pair, 8 of them per CU, not bandwidth and not the vector ALU; a second operand set in registers spills (254 used).
-    # Here the rows of the NEXT pair travel global -> LDS by LDS-DMA (no registers) while the current pair is evaluated out
-    # of the LDS: every wavefront owns a ring of kRingSlots slots in the CU's 160 KB (20 KB per wavefront at two per SIMD);
-    # a pair's rows (w, x[other], grad_out[other], the two y rows: 14 KB for the l_max = 2 middle layer) are cut into
-    # kRingChunks = kRingSlots - 1 chunks in the order the paths consume them, so that one whole pair is always in flight
-    # behind the one being evaluated.  After chunk q is evaluated its slot is refilled with chunk q + kRingSlots.  The copies
-    # are 16 bytes per lane (dword-per-lane reads reach 4.0 TB/s on this part, 16-byte ones 6.7: scripts/micro/store_bw.hip);
-    # lane l of an instruction lands at slot + 16 l, the LDS image of a segment is the 64 channels' values in row order, and
-    # the evaluation reads its operands with ds_read (4 u + component) right where it uses them -- no operand arrays in
-    # registers.  Ordering: the issuing wavefront's counted s_waitcnt vmcnt(N), N = the copies and stores issued since
-    # (static: one pair's worth of each in the steady state, tp_spec.h spec_wait_vm); the first pair of a wavefront counts
-    # its own shorter history, the last one waits for everything.  scripts/check_ring_waits.py re-counts N in the ISA.
-    ring_ok = pair_ok and os.environ.get("NQA_GEN_PAIR_RING", "1") != "0"
-    if ring_ok:
-        # register budget at two wavefronts per SIMD: the owner's grad_out row and the products of it the compiler hoists out
-        # of the pair loop, both y rows and both grad_y accumulators, the owner's x row / its gradient / one block's row
-        # gradient (l2n_mid: 177 -> 247 registers; l3n_mid_k2: 192 -> 27 spilled, whose scratch loads draw hipcc's own
-        # vmcnt waits into the loop -- scripts/check_ring_waits.py).  Structures beyond it keep bwd_pair_kernel.
-        n_hoist = sum(int((np.abs(np.array(wigner_3j(st.in1_ls[b_], st.in2_ls[j_], st.out_ls[s_]))).sum(axis=2) > 0).sum())
-                      for (b_, j_, s_) in st.instr)
-        ring_ok = OD + n_hoist + 4 * S + 3 * XD <= 180
-    if ring_ok:
-        import itertools
-        RING_WAVE = int(os.environ.get("NQA_GEN_RING_WAVE_BYTES", "20480"))
-        U = 16  # bytes per lane of a copy
-        # sizes per 64-channel chunk, in 16-byte units (64 channels x 4 B = 16 units per component)
-        w_units = 16
-        yrow_units = (S * 4 + U - 1) // U
-        first_path_of_block_r = {}
-        last_path_of_block_r = {}
-        for p_, (b_, _, _) in enumerate(st.instr):
-            first_path_of_block_r.setdefault(b_, p_)
-            last_path_of_block_r[b_] = p_
-        path_units = [w_units + 16 * (2 * st.out_ls[s_] + 1) for (_, _, s_) in st.instr]
-        xblk_units = {b_: 16 * (2 * st.in1_ls[b_] + 1) for b_ in used_blocks}
 
-        def ring_partition(C):
-            """Contiguous path ranges + the chunk of every x block (not later than its first use): minimal largest chunk."""
-            best = None
-            for cuts in itertools.combinations(range(1, NP), C - 1):
-                bounds = [0] + list(cuts) + [NP]
-                chunk_of_path = [0] * NP
-                for c_ in range(C):
-                    for p_ in range(bounds[c_], bounds[c_ + 1]):
-                        chunk_of_path[p_] = c_
-                base = [sum(path_units[bounds[c_]:bounds[c_ + 1]]) for c_ in range(C)]
-                base[0] += 2 * yrow_units
-                choices = [range(chunk_of_path[first_path_of_block_r[b_]] + 1) for b_ in used_blocks]
-                for place in itertools.product(*choices):
-                    tot = list(base)
-                    for b_, c_ in zip(used_blocks, place):
-                        tot[c_] += xblk_units[b_]
-                    key = (max(tot), sum(place))
-                    if best is None or key < best[0]:
-                        best = (key, bounds, dict(zip(used_blocks, place)))
-            return best
+def _split_part_x_rows(p: Plan, part_i, blocks, uvar):
+    """A part's grad_x[owner] components; part 0 also zeroes the components of the blocks no path reads."""
+    out = store_x_rows(p, "        ", blocks, uvar, lambda c: f"gxO[{c}]")
+    if part_i == 0:
+        out += store_x_rows(p, "        ", [b for b in range(p.NB) if b not in p.first_path], uvar, lambda c: "T(0)")
+    return out
 
-        ring_plan = None
-        for C in range(1, min(NP, 6) + 1):
-            cand = ring_partition(C) if NP >= C else None
-            if cand is None:
-                continue
-            slot_bytes = cand[0][0] * U
-            if RING_WAVE // slot_bytes >= C + 1:
-                ring_plan = (C, slot_bytes, cand[1], cand[2])
-                break
-        if ring_plan is None:
-            ring_ok = False
-    if ring_ok:
-        # lab only: 1 = no result stores (never-true guard), 2 = no copies (stale LDS), 4 = no arithmetic (operands summed)
-        ring_abl = int(os.environ.get("NQA_GEN_RING_ABL", "0"))
-        # kinds of copies that are non-temporal (w, x, g): the weight rows are read once (lab: 545 -> 533 us; x / g too: slower)
-        ring_nt = set(os.environ.get("NQA_GEN_RING_NT", "w").replace("+", ",").split(","))
-        RC, RSLOT, rbounds, xplace = ring_plan
-        RN = RC + 1
-        # chunk images: [w segments][x segments][g segments][y_in][y_out]; a segment = (kind, id, units)
-        chunk_paths = [list(range(rbounds[c_], rbounds[c_ + 1])) for c_ in range(RC)]
-        lds_off = []  # per chunk: dict (kind, id) -> byte offset inside the slot
-        dma = []      # per chunk: list of (kind, lds_byte_off, nlanes, [(lane_lo, lane_hi, id, unit_in_segment_at_lane_lo)])
-        for c_ in range(RC):
-            streams = {"w": [(p_, w_units) for p_ in chunk_paths[c_]],
-                       "x": [(b_, xblk_units[b_]) for b_ in used_blocks if xplace[b_] == c_],
-                       "g": [(st.instr[p_][2], 16 * (2 * st.out_ls[st.instr[p_][2]] + 1)) for p_ in chunk_paths[c_]]}
-            offs, ins, pos = {}, [], 0
-            for kind in ("w", "x", "g"):
-                segs, start = [], 0
-                for ident, units in streams[kind]:
-                    offs[(kind, ident)] = (pos + start) * U
-                    segs.append((ident, start, units))
-                    start += units
-                for i0 in range(0, start, 64):
-                    nl = min(64, start - i0)
-                    pieces = []
-                    for ident, sstart, units in segs:
-                        lo, hi = max(sstart, i0), min(sstart + units, i0 + nl)
-                        if lo < hi:
-                            pieces.append((lo - i0, hi - i0, ident, lo - sstart))
-                    ins.append((kind, (pos + i0) * U, nl, pieces))
-                pos += start
-            if c_ == 0:
-                offs[("y", "I")] = pos * U
-                ins.append(("yI", pos * U, S, None))
-                pos += yrow_units
-                offs[("y", "X")] = pos * U
-                ins.append(("yX", pos * U, S, None))
-                pos += yrow_units
-            assert pos * U <= RSLOT, (st.name, c_, pos * U, RSLOT)
-            lds_off.append(offs)
-            dma.append(ins)
-        STG = "if (a.N < 0) " if ring_abl & 1 else ""
-        D_chunk = [len(ins) for ins in dma]
-        D_pair = sum(D_chunk)
-        # stores a chunk is certain to issue (grad_w per path, the grad_x row components of the blocks that end in it); the two
-        # grad_y stores of the last chunk are not counted (an under-count only shortens the look-ahead by two operations)
-        Sgw = [len(chunk_paths[c_]) for c_ in range(RC)]
-        Sgx = [sum(2 * st.in1_ls[b_] + 1 for b_ in used_blocks if rbounds[c_] <= last_path_of_block_r[b_] < rbounds[c_ + 1])
-               for c_ in range(RC)]
-        unused_r = [i for b in range(NB) if b not in first_path_of_block_r for i in range(xpre[b], xpre[b] + 2 * st.in1_ls[b] + 1)]
-        Sgx_atom = list(Sgx)  # (ATOM: the components no path writes are not touched at all)
-        Sgx[RC - 1] += len(unused_r)
-        if ring_abl & 1:
-            Sgw, Sgx, Sgx_atom = [0] * RC, [0] * RC, [0] * RC
-        assert sum(Sgw) + sum(Sgx) + D_pair < 64, "vmcnt range"
 
-        def src_base(kind, ident):
-            if kind == "w":
-                return f"(unsigned)(mul * {ident} + chunk * 64) * 4u"
-            if kind == "x":
-                return f"(unsigned)(mul * {xpre[ident]} + chunk * {64 * (2 * st.in1_ls[ident] + 1)}) * 4u"
-            return f"(unsigned)(mul * {opre[ident]} + chunk * {64 * (2 * st.out_ls[ident] + 1)}) * 4u"
+# ------------------------------------------------------------------ split pair kernel on the LDS ring
+# The l_max = 3 structures' pair kernel (one wavefront per (node, chunk, input block)) walked its pairs with a plain loop:
+# indices -> rows -> arithmetic -> stores, nothing of the next pair requested (the registers hold two grad_out slices).
+# The same ring as bwd_pair_ring_kernel, per part: the part's slice of w / x[other] / grad_out[other] and the two y rows
+# of the NEXT pair travel by LDS-DMA while this pair is evaluated out of the LDS.
+def emit_split_ring(p: Plan) -> List[str]:
+    st = p.st
+    L = []
+    A = L.append
+    A("// (see bwd_pair_ring_kernel for the ring, the counted waits and ATOM; parts as in bwd_pair_split_kernel)")
+    A("template <bool GX, bool ATOM>")
+    A("__global__ __launch_bounds__(256, 2) void bwd_pair_split_ring_kernel(const SpecArgs<float> a) {")
+    A("  typedef float T;")
+    A("  extern __shared__ __align__(16) unsigned char nqa_smem[];")
+    A("  const int lane = threadIdx.x & 63;")
+    A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
+    A("  const int mul = a.mul;  // a multiple of 64")
+    A("  const int nchunk = mul >> 6;")
+    _split_item(L)
+    A("  constexpr bool act = true;")
+    A("  const int beg = a.rowptr[node], end = a.rowptr[node + 1];")
+    L.extend(lane_offsets(p, "  ", want_x=True, want_g=True))
+    A(f"  const unsigned wbase = (unsigned)wid * {RING_WAVE_BYTES}u;  // this wavefront's ring (LDS byte address)")
+    A("  const unsigned l4 = (unsigned)lane * 4u, l16 = (unsigned)lane * 16u;")
+    A("  switch (part) {")
+    for part_i, paths in enumerate(p.part_paths):
+        blocks, slots, ys = _split_part_sets(st, paths)
+        r = p.split_rings[part_i]
+        RC, RN, RSLOT = r.chunks, r.slots, r.slot_bytes
+        pfx = f"p{part_i}"
 
-        A(f"constexpr int kRingChunks = {RC}, kRingSlots = {RN}, kRingSlotBytes = {RSLOT}, kRingWaveBytes = {RN * RSLOT};")
-        A("// ring chunks: " + "; ".join(
-            f"{c_}: paths {chunk_paths[c_][0]}-{chunk_paths[c_][-1]}" + "".join(f" +x{b_}" for b_ in used_blocks if xplace[b_] == c_)
-            + f", {D_chunk[c_]} copies, {Sgw[c_]}+{Sgx[c_]} stores" for c_ in range(RC)))
-        A("// ATOM: the other node's grad_x contribution goes into a zeroed [N, dim_in1] accumulator (a.gxe, component rows of 64")
-        A("// channels as the per-pair rows) by floating-point atomics instead of one row per pair: no [P, dim_in1] round trip")
-        A("// through HBM and no row sum -- gx_acc_finish_kernel folds the accumulator into a.out.  (Sums in arrival order: the")
-        A("// low bits of grad_x differ from run to run; ATOM = false keeps the fixed-order rows.)")
-        A("template <int WPN, bool GX, bool ATOM>")
-        A("__global__ __launch_bounds__(256, 2) void bwd_pair_ring_kernel(const SpecArgs<float> a) {")
-        A("  typedef float T;")
-        A("  extern __shared__ __align__(16) unsigned char nqa_smem[];")
-        A("  const int lane = threadIdx.x & 63;")
-        A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
-        A("  const int mul = a.mul;  // a multiple of 64 (the launcher sends other multiplicities to bwd_pair_kernel)")
-        A("  const int nchunk = mul >> 6;")
-        if os.environ.get("NQA_GEN_RING_NO_XCD_REMAP", "0") != "0":  # lab: workgroups in dispatch order (round-robin over the XCDs)
-            A("  const int64_t witem = (int64_t)blockIdx.x * 4 + wid;")
-        else:
-            A("  const int64_t witem = (int64_t)spec_xcd_remap(blockIdx.x, gridDim.x) * 4 + wid;")
-        A("  const int64_t item = witem / WPN;")
-        A("  const int wsub = (int)(witem - item * WPN);")
-        A("  const bool valid = item < (int64_t)a.N * nchunk;  // (WPN < 4: the last workgroup may hold idle wavefronts)")
-        A("  const int node = spec_uniform(valid ? (int)(item / nchunk) : 0);")
-        A("  const int chunk = valid ? (int)(item - (int64_t)node * nchunk) : 0;")
-        A("  const int u = chunk * 64 + lane;")
-        A("  constexpr bool act = true, DUAL = false;")
-        A("  const int beg = a.rowptr[node], end = valid ? a.rowptr[node + 1] : beg;")
-        L.extend(lane_offsets("  ", want_x=True, want_g=True))
-        A("  const unsigned wbase = (unsigned)wid * (unsigned)kRingWaveBytes;  // this wavefront's ring (LDS byte address)")
-        A("  const unsigned l4 = (unsigned)lane * 4u, l16 = (unsigned)lane * 16u;")
-        A("  // per-lane source offsets of the copies (bytes from the row base; lane l moves 16 bytes)")
-        for c_ in range(RC):
-            for i_, (kind, loff, nl, pieces) in enumerate(dma[c_]):
-                if pieces is None or len(pieces) == 1:
-                    continue  # (one segment: its uniform offset goes into the scalar base, the lanes share l16)
-                expr = None
-                for lo, hi, ident, seg_unit in reversed(pieces):
-                    e_ = f"{src_base(kind, ident)} + (unsigned)({(seg_unit - lo) * U})"
-                    expr = e_ if expr is None else f"(lane < {hi} ? {e_} : {expr})"
-                A(f"  const unsigned ro{c_}_{i_} = ({expr}) + l16;")
-        A("  T gvO[kOD], gxO[kXD];")
-        L.extend(load_g("  ", "a.g + (int64_t)node * a.dout", "gvO"))
-        L.extend(load_x("  ", "(a.x + (int64_t)node * a.din)", sfx="O"))
-        A("#pragma unroll")
-        A("  for (int i = 0; i < kXD; ++i) gxO[i] = T(0);")
+        def copies(ind, c_, sfx, slotexpr, lgkm=True):
+            return ring_copies(p, r, ind, c_, sfx, slotexpr, f"{RSLOT}u", f"{pfx}ro", "", lgkm)
 
-        def ring_issue(ind, c_, sfx, slotexpr, lgkm=True):
-            """Copies of chunk c_ of the pair whose indices are in jn{sfx} / pr{sfx} / ei{sfx} / eo{sfx} into LDS slot `slotexpr`."""
-            if ring_abl & 2:
-                return []
-            out = [f"{ind}{{ const unsigned sb_ = wbase + (unsigned)({slotexpr}) * (unsigned)kRingSlotBytes;"]
-            if lgkm:
-                out.append(f"{ind}  spec_wait_lgkm();  // the slot's last reads have returned")
-            kinds = {k_ for k_, _, _, _ in dma[c_]}
-            if "w" in kinds:
-                out.append(f"{ind}  const T* __restrict__ wr_ = a.w + (int64_t)pr{sfx} * a.wn;")
-            if "x" in kinds:
-                out.append(f"{ind}  const T* __restrict__ xr_ = a.x + (int64_t)jn{sfx} * a.din;")
-            if "g" in kinds:
-                out.append(f"{ind}  const T* __restrict__ gr_ = a.g + (int64_t)jn{sfx} * a.dout;")
-            for i_, (kind, loff, nl, pieces) in enumerate(dma[c_]):
-                if kind == "yI":
-                    out.append(f"{ind}  spec_glds4<{nl}>(sb_ + {loff}u, a.y + (int64_t)ei{sfx} * kS, l4);")
-                elif kind == "yX":
-                    out.append(f"{ind}  spec_glds4<{nl}>(sb_ + {loff}u, a.y + (int64_t)eo{sfx} * kS, l4);")
-                else:
-                    nt_ = ", true" if kind in ring_nt else ""
-                    if len(pieces) == 1:
-                        lo_, _, ident_, seg_unit_ = pieces[0]
-                        uoff = f"{src_base(kind, ident_)} + (unsigned)({(seg_unit_ - lo_) * U})"
-                        out.append(f"{ind}  spec_glds16<{nl}{nt_}>(sb_ + {loff}u, reinterpret_cast<const char*>({kind}r_) + ({uoff}), l16);")
-                    else:
-                        out.append(f"{ind}  spec_glds16<{nl}{nt_}>(sb_ + {loff}u, {kind}r_, ro{c_}_{i_});")
-            out.append(f"{ind}}}")
-            return out
-
-        # The pair indices (other node, weight row, the two edges) of up to 64 of this wavefront's pairs sit in four vector
-        # registers, lane l = the wavefront's l-th pair, fetched by ONE vector load per list before the loop; a pair's
-        # indices are then a v_readlane away.  (Per-pair scalar loads, as bwd_pair_kernel has them, are not available here:
-        # behind the "memory" clobbers of the copy / wait statements hipcc turns them into vector loads followed by vmcnt(0).)
-        def ring_block_load(ind, first_pair):
-            return [f"{ind}{{ const int i_ = beg + wsub + (({first_pair}) + lane) * WPN; const int ic_ = i_ < end ? i_ : end - 1;",
+        def blk_load(ind, first_pair):
+            return [f"{ind}{{ const int i_ = beg + ({first_pair}) + lane; const int ic_ = i_ < end ? i_ : end - 1;",
                     f"{ind}  jnV = a.nbr[ic_]; prV = a.wid[ic_]; eiV = a.eid[ic_]; eoV = a.eid2[ic_]; }}"]
 
-        def ring_index_get(sfx, k, ind="    "):
-            return [f"{ind}jn{sfx} = __builtin_amdgcn_readlane(jnV, ({k}) & 63); pr{sfx} = __builtin_amdgcn_readlane(prV, ({k}) & 63);",
-                    f"{ind}ei{sfx} = __builtin_amdgcn_readlane(eiV, ({k}) & 63); eo{sfx} = __builtin_amdgcn_readlane(eoV, ({k}) & 63);"]
-
-        A("  int idx = beg + wsub;")
-        A("  int kk = 0;  // this wavefront's pair counter: pair kk sits in owner slot beg + wsub + kk * WPN")
-        A("  int jnA = 0, prA = 0, eiA = 0, eoA = 0, jnB = 0, prB = 0, eiB = 0, eoB = 0, jnC = 0, prC = 0, eiC = 0, eoC = 0;")
-        A("  int jnV = 0, prV = 0, eiV = 0, eoV = 0;")
-        A("  bool hasA = idx < end, hasB = idx + WPN < end, hasC = false;")
-        A("  if (hasA) {")
-        L.extend(ring_block_load("    ", "0"))
-        L.extend(ring_index_get("A", "0"))
-        L.extend(ring_index_get("B", "1"))
-        A("  }")
-        A("  // prologue: the whole first pair and the first chunk of the second fill the ring")
-        A("  if (hasA) {")
-        for c_ in range(RC):
-            L.extend(ring_issue("    ", c_, "A", str(c_), lgkm=False))
-        A("  }")
-        A("  if (hasB) {")
-        L.extend(ring_issue("    ", 0, "B", str(RC), lgkm=False))
-        A("  }")
-        A("  // the owner's rows are in their registers before the loop starts: hipcc, which does not see the copies, would")
-        A("  // otherwise wait for them inside the loop with a small vmcnt(n) of ITS count -- every iteration, draining the ring")
-        A("#pragma unroll")
-        A("  for (int k = 0; k < kOD; ++k) asm volatile(\"\" : \"+v\"(gvO[k]));")
-        for b in used_blocks:
+        A(f"    case {part_i}: {{  // input blocks {blocks}: paths {paths}; ring of {RN} slots of {RSLOT} bytes, {RC} chunk(s) per pair, {r.copies} copies")
+        L.extend(ring_lane_offsets(p, r, "      ", f"{pfx}ro"))
+        A("      T gvO[kOD], gvJ[kOD], gxO[kXD], qI[kS], qX[kS], gxa[kXD];")
+        L.extend(_split_part_registers(p, blocks, ys))
+        L.extend(_split_load_g(p, "      ", "a.g + (int64_t)node * a.dout", "gvO", slots))
+        L.extend(_split_load_x(p, "      ", "(a.x + (int64_t)node * a.din)", "O", blocks))
+        for b in blocks:
             for i in range(2 * st.in1_ls[b] + 1):
-                A(f"  asm volatile(\"\" : \"+v\"(xb{b}O[{i}]));")
-        A("  int rot = 0;       // slot of chunk 0 of pair A")
-        A("  bool first = true;")
-        A("  T qI[kS], qX[kS], gxa[kXD], gvJ[kOD];")
-        L.extend(decl_y("  ", "I") + decl_y("  ", "X") + decl_x("  ", "J"))
-        L.extend(decl_x("  ", "J2") + decl_x("  ", "O2"))  # (names the shared path emitter mentions under DUAL, never read)
-        A("  while (hasA) {")
-        A("    hasC = idx + 2 * WPN < end;")
-        A("    if (hasC) {")
-        A("      if (((kk + 2) & 63) == 0) {  // (a wavefront with more than 64 pairs: the next block of indices)")
-        L.extend(ring_block_load("        ", "kk + 2"))
-        A("      }")
-        L.extend(ring_index_get("C", "kk + 2", "      "))
-        A("    }")
-        A("    T* __restrict__ gwr_e = a.gw + (int64_t)prA * a.wn;")
-        A("    T* __restrict__ gxr = a.gxe + (int64_t)(ATOM ? jnA : idx) * a.din;")
-        A("#pragma unroll")
-        A("    for (int j = 0; j < kS; ++j) { qI[j] = T(0); qX[j] = T(0); }")
+                A(f"      gxO[{p.xpre[b] + i}] = T(0);")
+        A("      int idx = beg, kk = 0;")
+        A("      int jnA = 0, prA = 0, eiA = 0, eoA = 0, jnB = 0, prB = 0, eiB = 0, eoB = 0, jnC = 0, prC = 0, eiC = 0, eoC = 0;")
+        A("      int jnV = 0, prV = 0, eiV = 0, eoV = 0;")
+        A("      bool hasA = idx < end, hasB = idx + 1 < end, hasC = false;")
+        A("      if (hasA) {")
+        L.extend(blk_load("        ", "0"))
+        L.extend(_ring_index_get("A", "0", "        "))
+        L.extend(_ring_index_get("B", "1", "        "))
         for c_ in range(RC):
-            lo = lds_off[c_]
-            nfirst = D_pair + sum(Sgw[:c_])
-            nfirst_gx = f"(ATOM ? {nfirst + sum(Sgx_atom[:c_])} : {nfirst + sum(Sgx[:c_])})"
-            nsteady = D_pair + sum(Sgw)
-            nsteady_gx = f"(ATOM ? {nsteady + sum(Sgx_atom)} : {nsteady + sum(Sgx)})"
-            A(f"    {{  // ---- chunk {c_}: paths {chunk_paths[c_][0]}..{chunk_paths[c_][-1]}")
-            A(f"      int s_ = rot + {c_}; s_ = s_ >= kRingSlots ? s_ - kRingSlots : s_;")
-            A("      const unsigned sb = wbase + (unsigned)s_ * (unsigned)kRingSlotBytes;")
-            A("      const unsigned char* __restrict__ cb = nqa_smem + sb;")
-            if not (ring_abl & 2):
-                A("      if (!hasB) spec_wait_vm<0>();")
-                A(f"      else if (first) spec_wait_vm<GX ? {nfirst_gx} : {nfirst}>();")
-                A(f"      else spec_wait_vm<GX ? {nsteady_gx} : {nsteady}>();")
-            if c_ == 0:
-                for j in used_y:
-                    for i in range(2 * st.in2_ls[j] + 1):
-                        A(f"      yb{j}I[{i}] = *reinterpret_cast<const T*>(cb + {lo[('y', 'I')] + 4 * (ypre[j] + i)});")
-                        A(f"      yb{j}X[{i}] = *reinterpret_cast<const T*>(cb + {lo[('y', 'X')] + 4 * (ypre[j] + i)});")
-            for b_ in used_blocks:
-                if xplace[b_] == c_:
-                    d1 = 2 * st.in1_ls[b_] + 1
-                    for i in range(d1):
-                        A(f"      xb{b_}J[{i}] = *reinterpret_cast<const T*>(cb + {lo[('x', b_)]} + l4 * {d1}u + {4 * i});")
-            for pth in chunk_paths[c_]:
+            L.extend(copies("        ", c_, "A", str(c_), lgkm=False))
+        A("      }")
+        A("      if (hasB) {")
+        L.extend(copies("        ", 0, "B", str(RC), lgkm=False))
+        A("      }")
+        A("      // (the owner's rows are in their registers before the loop starts: see bwd_pair_ring_kernel)")
+        L.extend(_nohoist(p, slots, "      "))
+        for b in blocks:
+            for i in range(2 * st.in1_ls[b] + 1):
+                A(f"      asm volatile(\"\" : \"+v\"(xb{b}O[{i}]));")
+        A("      int rot = 0;")
+        A("      bool first = true;")
+        A("      while (hasA) {")
+        A("        hasC = idx + 2 < end;")
+        A("        if (hasC) {")
+        A("          if (((kk + 2) & 63) == 0) {")
+        L.extend(blk_load("            ", "kk + 2"))
+        A("          }")
+        L.extend(_ring_index_get("C", "kk + 2", "          "))
+        A("        }")
+        A("        T* __restrict__ gwr_e = a.gw + (int64_t)prA * a.wn;")
+        A("        T* __restrict__ gxr = a.gxe + (int64_t)(ATOM ? jnA : idx) * a.din;")
+        A("#pragma unroll")
+        A("        for (int j = 0; j < kS; ++j) { qI[j] = T(0); qX[j] = T(0); }")
+        if n_owner_terms(st, paths) > SPLIT_NOHOIST:
+            L.extend(_nohoist(p, slots, "        "))
+        for c_ in range(RC):
+            lo = r.lds_off[c_]
+            A(f"        {{  // ---- chunk {c_}: paths {r.cpaths[c_]}")
+            A(f"          int s_ = rot + {c_}; s_ = s_ >= {RN} ? s_ - {RN} : s_;")
+            A(f"          const unsigned char* __restrict__ cb = nqa_smem + (wbase + (unsigned)s_ * {RSLOT}u);")
+            L.extend(ring_waits(r, c_, "          "))
+            L.extend(ring_operand_reads(p, r, c_, ys, "          "))
+            for pth in r.cpaths[c_]:
                 b_, j, s_ = st.instr[pth]
                 d1, d3 = 2 * st.in1_ls[b_] + 1, 2 * st.out_ls[s_] + 1
-                if first_path_of_block_r[b_] == pth:
+                if p.first_path[b_] == pth:
                     for i in range(d1):
-                        A(f"      gxa[{xpre[b_] + i}] = T(0);")
-                A(f"      {{  // path {pth}")
-                A(f"        const T wv_ = *reinterpret_cast<const T*>(cb + {lo[('w', pth)]} + l4);")
-                for k in range(d3):
-                    A(f"        gvJ[{opre[s_] + k}] = T({slot_coeff[s_]!r}) * *reinterpret_cast<const T*>(cb + {lo[('g', s_)]} + l4 * {d3}u + {4 * k});")
-                if ring_abl & 4:
-                    A("        T s_ = wv_;")
-                    for k in range(d3):
-                        A(f"        s_ += gvJ[{opre[s_] + k}] + gvO[{opre[s_] + k}];")
-                    for i in range(d1):
-                        A(f"        s_ += xb{b_}J[{i}] + xb{b_}O[{i}];")
-                    for jj in range(2 * st.in2_ls[j] + 1):
-                        A(f"        s_ += yb{j}I[{jj}] + yb{j}X[{jj}];")
-                    for i in range(d1):
-                        A(f"        gxa[{xpre[b_] + i}] += s_; gxO[{xpre[b_] + i}] += s_;")
-                    A(f"        qI[{ypre[j]}] += s_; qX[{ypre[j]}] += s_;")
-                    A(f"        {STG}{{ {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 's_')}; }}")
-                    A("      }")
-                    if last_path_of_block_r[b_] == pth:
-                        A(f"      if (GX{' && a.N < 0' if ring_abl & 1 else ''}) {{")
-                        for i in range(d1):
-                            A(f"        {emit_store(f'spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb)', f'gxa[{xpre[b_] + i}]')};")
-                        A("      }")
-                    continue
-                body = []
-                live_i, gx_i = pair_path(body, pth, "J", "gvO", "I", "i")
-                for comp, expr in gx_i:
-                    if expr:
-                        body.append(f"        if (GX) gxa[{comp}] += wv_ * ({expr});")
-                live_x, gx_x = pair_path(body, pth, "O", "gvJ", "X", "x")
-                for comp, expr in gx_x:
-                    if expr:
-                        body.append(f"        if (GX) gxO[{comp}] += wv_ * ({expr});")
-                L.extend(body)
-                terms = [f"yb{j}I[{jj}] * Bi{jj}" for jj in live_i] + [f"yb{j}X[{jj}] * Bx{jj}" for jj in live_x]
-                gw_expr = " + ".join(terms) if terms else "T(0)"
-                A(f"        {STG}{{ const T r_ = {gw_expr}; {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'r_')}; }}")
-                for jj in live_i:
-                    A(f"        qI[{ypre[j] + jj}] += wv_ * Bi{jj};")
-                for jj in live_x:
-                    A(f"        qX[{ypre[j] + jj}] += wv_ * Bx{jj};")
-                A("      }")
-                if last_path_of_block_r[b_] == pth:
-                    A(f"      if (GX{' && a.N < 0' if ring_abl & 1 else ''}) {{")
-                    for i in range(d1):
-                        st_ = emit_store(f'spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb)', f'gxa[{xpre[b_] + i}]')
-                        A(f"        if (ATOM) unsafeAtomicAdd(spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb), gxa[{xpre[b_] + i}]); else {st_};")
-                    A("      }")
-            if c_ == RC - 1:
-                if unused_r:
-                    A("      if (GX && !ATOM) {")
-                    for i in unused_r:
-                        A(f"        *spec_at(gxr + (unsigned)(mul * {i}), ucb) = T(0);")
-                    A("      }")
-                A("      // refill this slot with chunk 0 of the pair after next")
-                A("      if (hasC) {")
-                L.extend(ring_issue("        ", 0, "C", "s_"))
-                A("      }")
-                A("      // (a.gy_atomic: more than one channel chunk per edge -- the chunks add into grad_y itself instead of partial rows)")
-                A(f"      {STG}spec_wave_reduce_store<T, kS>(qI, a.gy + (int64_t)eiA * a.gy_stride + (a.gy_atomic ? 0 : chunk * kS), lane, a.gy_atomic != 0);")
-                A(f"      {STG}spec_wave_reduce_store<T, kS>(qX, a.gy + (int64_t)eoA * a.gy_stride + (a.gy_atomic ? 0 : chunk * kS), lane, a.gy_atomic != 0);")
-            else:
-                A(f"      // refill this slot with chunk {c_ + 1} of the next pair")
-                A("      if (hasB) {")
-                L.extend(ring_issue("        ", c_ + 1, "B", "s_"))
-                A("      }")
-            A("    }")
-        A("    jnA = jnB; prA = prB; eiA = eiB; eoA = eoB; jnB = jnC; prB = prC; eiB = eiC; eoB = eoC;")
-        A("    hasA = hasB; hasB = hasC; idx += WPN; ++kk; first = false;")
-        A(f"    rot += {RC}; rot = rot >= kRingSlots ? rot - kRingSlots : rot;")
-        A("  }")
-        A("  if (!GX) return;")
-        A("  // grad_x[owner]: the owner-side contributions of all its pairs (the other side arrives through the rows)")
-        A("  if (WPN > 1) {")
-        A("    T* red = reinterpret_cast<T*>(nqa_smem);  // (the rings are idle: every copy was waited for)")
-        A("    __syncthreads();")
-        A("    if (wsub > 0) {")
-        A("#pragma unroll")
-        A("      for (int k = 0; k < kXD; ++k) red[(((wid / WPN) * (WPN - 1) + wsub - 1) * kXD + k) * 64 + lane] = gxO[k];")
-        A("    }")
-        A("    __syncthreads();")
-        A("    if (wsub > 0) return;")
-        A("#pragma unroll")
-        A("    for (int k = 0; k < kXD; ++k) {")
-        A("#pragma unroll")
-        A("      for (int w2 = 0; w2 < WPN - 1; ++w2) gxO[k] += red[(((wid / WPN) * (WPN - 1) + w2) * kXD + k) * 64 + lane];")
-        A("    }")
-        A("  }")
-        A("  if (valid) {")
-        A("    T* __restrict__ ob = a.out + (int64_t)node * a.din;")
-        for b in range(NB):
-            d = 2 * st.in1_ls[b] + 1
-            for i in range(d):
-                A(f"    ob[(int64_t)mul * {xpre[b]} + (int64_t)u * {d} + {i}] = gxO[{xpre[b] + i}];")
-        A("  }")
-        A("}")
-
-    # ------------------------------------------------------------------ pair-centric backward, split by input block
-    # Structures whose two grad_out rows do not fit one wavefront's registers (l_max = 3: 99 values each): every input
-    # block l_1 owns its paths, its output slots, its weight columns and its grad_x components, so the pair kernel splits
-    # over PS wavefronts per (node, channel chunk) with no exchange -- wavefront `part` holds only its blocks' slice of
-    # grad_out[owner] / grad_out[other] / x / w.  Shared by the parts: the two y rows and the pair indices (scalar loads).
-    # grad_y: every part reduces its own partial sums into a [chunk, part] slot of the partial buffer (summed by
-    # spec_gy_reduce_kernel, as the chunk partials are).
-    pair_parts = 1 if pair_ok else 0
-    part_paths: List[List[int]] = []
-    if not pair_ok and os.environ.get("NQA_GEN_PAIR_SPLIT", "1") != "0":
-        by_block = {}
-        for pth, (b_, _, s_) in enumerate(st.instr):
-            by_block.setdefault(b_, []).append(pth)
-
-        def budget(paths):
-            od = sum(2 * st.out_ls[st.instr[p_][2]] + 1 for p_ in paths)
-            xd = sum(2 * st.in1_ls[b_] + 1 for b_ in {st.instr[p_][0] for p_ in paths})
-            return 2 * od + 3 * xd + len(paths)
-
-        # greedy merge of consecutive blocks while a (conservative) register budget holds: the l_max = 3 parts carry 32
-        # grad_y accumulators and up to 49 intermediates per path on top of what `budget` counts (merging l_1 = 0 and 1,
-        # budget 102, spilled 82 registers)
-        for b_ in sorted(by_block):
-            if part_paths and budget(part_paths[-1] + by_block[b_]) <= int(os.environ.get("NQA_GEN_SPLIT_MERGE", "70")):
-                part_paths[-1] = part_paths[-1] + by_block[b_]
-            else:
-                part_paths.append(list(by_block[b_]))
-        if all(budget(pp) <= 110 for pp in part_paths) and 1 < len(part_paths) <= 8:
-            pair_parts = len(part_paths)
-        else:
-            part_paths = []
-    if pair_parts > 1:
-        PS = pair_parts
-        A(f"constexpr int kPairParts = {PS};")
-        A("// ATOM (multiples of 64 channels): the other node's grad_x by atomics into the zeroed [N, dim_in1] accumulator a.gxe")
-        A("// (see bwd_pair_ring_kernel) instead of one row per pair")
-        A("template <typename T, bool FULL, bool GX, bool ATOM = false>")
-        A("__global__ __launch_bounds__(256, 2) void bwd_pair_split_kernel(const SpecArgs<T> a) {")
-        A("  const int lane = threadIdx.x & 63;")
-        A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
-        A("  const int mul = a.mul;")
-        A("  const int nchunk = (mul + 63) >> 6;")
-        A("  const int64_t item = (int64_t)spec_xcd_remap(blockIdx.x, gridDim.x) * 4 + wid;")
-        A("  if (item >= (int64_t)a.N * nchunk * kPairParts) return;")
-        A("  const int node = spec_uniform((int)(item / (nchunk * kPairParts)));")
-        A("  const int rem = (int)(item - (int64_t)node * (nchunk * kPairParts));")
-        A("  const int chunk = spec_uniform(rem / kPairParts);")
-        A("  const int part = spec_uniform(rem - chunk * kPairParts);")
-        A("  const int u = chunk * 64 + lane;")
-        A("  const bool act = FULL || (u < mul);")
-        A("  const int beg = a.rowptr[node], end = a.rowptr[node + 1];")
-        L.extend(lane_offsets("  ", want_x=True, want_g=True))
-        used_any = {b_ for b_, _, _ in st.instr}
-        unused_comps = [i for b in range(NB) if b not in used_any for i in range(xpre[b], xpre[b] + 2 * st.in1_ls[b] + 1)]
-
-        def sp_path(out, pth, xs, gname, ys, tag_):
-            b_, j, s_ = st.instr[pth]
-            l1, l2, l3 = st.in1_ls[b_], st.in2_ls[j], st.out_ls[s_]
-            d1, d2, d3 = 2 * l1 + 1, 2 * l2 + 1, 2 * l3 + 1
-            C = np.array(wigner_3j(l1, l2, l3), dtype=np.float64)
-            started = [False] * d2
-            gx_terms = []
-            for i in range(d1):
-                a_terms = []
-                for jj in range(d2):
-                    ks = [k for k in range(d3) if C[i, jj, k] != 0.0]
-                    if not ks:
-                        continue
-                    expr = " + ".join(f"T({float(C[i, jj, k])!r}) * {gname}[{opre[s_] + k}]" for k in ks)
-                    out.append(f"          const T t{tag_}{i}_{jj} = {expr};")
-                    if started[jj]:
-                        out.append(f"          B{tag_}{jj} += xb{b_}{xs}[{i}] * t{tag_}{i}_{jj};")
-                    else:
-                        out.append(f"          T B{tag_}{jj} = xb{b_}{xs}[{i}] * t{tag_}{i}_{jj};")
-                        started[jj] = True
-                    a_terms.append(f"yb{j}{ys}[{jj}] * t{tag_}{i}_{jj}")
-                gx_terms.append((xpre[b_] + i, " + ".join(a_terms) if a_terms else None))
-            return [jj for jj in range(d2) if started[jj]], gx_terms
-
-        def sp_load_g(ind, rowexpr, name, slots):
-            out = [f"{ind}{{ const T* __restrict__ gb = {rowexpr};"]
-            for s_ in slots:
-                for k in range(2 * st.out_ls[s_] + 1):
-                    out.append(f"{ind}  {name}[{opre[s_] + k}] = spec_at(gb, go{s_})[{k}];")
-            for s_ in slots:
-                for k in range(2 * st.out_ls[s_] + 1):
-                    out.append(f"{ind}  {name}[{opre[s_] + k}] = act ? T({slot_coeff[s_]!r}) * {name}[{opre[s_] + k}] : T(0);")
-            out.append(f"{ind}}}")
-            return out
-
-        def sp_load_x(ind, rowexpr, sfx, blocks):
-            out = []
-            for b in blocks:
-                for i in range(2 * st.in1_ls[b] + 1):
-                    out.append(f"{ind}xb{b}{sfx}[{i}] = spec_at({rowexpr}, xo{b})[{i}];")
-            return out
-
-        A("  switch (part) {")
-        for part_i, paths in enumerate(part_paths):
-            blocks = sorted({st.instr[p_][0] for p_ in paths})
-            slots = sorted({st.instr[p_][2] for p_ in paths})
-            ys = sorted({st.instr[p_][1] for p_ in paths})
-            A(f"    case {part_i}: {{  // input blocks {blocks}: paths {paths}")
-            A("      T gvO[kOD], gvJ[kOD], gxO[kXD], wv[kNP];")
-            for b in blocks:
-                A(f"      T xb{b}O[{2 * st.in1_ls[b] + 1}], xb{b}J[{2 * st.in1_ls[b] + 1}];")
-            for j in ys:
-                A(f"      T yb{j}I[{2 * st.in2_ls[j] + 1}], yb{j}X[{2 * st.in2_ls[j] + 1}];")
-            L.extend(sp_load_g("      ", "a.g + (int64_t)node * a.dout", "gvO", slots))
-            L.extend(sp_load_x("      ", "(a.x + (int64_t)node * a.din)", "O", blocks))
-            for b in blocks:
-                for i in range(2 * st.in1_ls[b] + 1):
-                    A(f"      gxO[{xpre[b] + i}] = T(0);")
-            A("      for (int idx = beg; idx < end; ++idx) {")
-            A("        const int j_ = spec_uniform(a.nbr[idx]), pr = spec_uniform(a.wid[idx]);")
-            A("        const int ei = spec_uniform(a.eid[idx]), eo = spec_uniform(a.eid2[idx]);")
-            A("        const T* __restrict__ xr = a.x + (int64_t)j_ * a.din;")
-            A("        const T* __restrict__ wr = a.w + (int64_t)pr * a.wn;")
-            A("        const T* __restrict__ yi = a.y + (int64_t)ei * kS;")
-            A("        const T* __restrict__ yo = a.y + (int64_t)eo * kS;")
-            for pth in paths:
-                A(f"        wv[{pth}] = *spec_at(wr + (unsigned)(mul * {pth}), ucb);")
-            L.extend(sp_load_x("        ", "xr", "J", blocks))
-            L.extend(sp_load_g("        ", "a.g + (int64_t)j_ * a.dout", "gvJ", slots))
-            for j in ys:
-                for i in range(2 * st.in2_ls[j] + 1):
-                    A(f"        yb{j}I[{i}] = yi[{ypre[j] + i}]; yb{j}X[{i}] = yo[{ypre[j] + i}];")
-            n_t = 0  # owner-side intermediates of this part (one per (path, i, j) with a non-zero 3j row)
-            for p_ in paths:
-                b2, j2, s2 = st.instr[p_]
-                C2 = np.array(wigner_3j(st.in1_ls[b2], st.in2_ls[j2], st.out_ls[s2]))
-                n_t += int((np.abs(C2).sum(axis=2) != 0).sum())
-            nohoist_limit = int(os.environ.get("NQA_GEN_SPLIT_NOHOIST", "64"))  # 0: always hoistable
-            if nohoist_limit and n_t > nohoist_limit:
-                # the owner-side intermediates T_ij = sum_k C_ijk grad_out[owner]_k are the same for all pairs; hoisted out
-                # of the pair loop they are ~150 live values for the l_1 = 3 block (79 spilled registers).  An empty asm
-                # that "modifies" the owner's slots makes them per-pair values.
-                for s_ in slots:
-                    for k in range(2 * st.out_ls[s_] + 1):
-                        A(f"        asm volatile(\"\" : \"+v\"(gvO[{opre[s_] + k}]));")
-            A("        T qI[kS], qX[kS], gxa[kXD];")
-            A("#pragma unroll")
-            A("        for (int j = 0; j < kS; ++j) { qI[j] = T(0); qX[j] = T(0); }")
-            A("        T* __restrict__ gwr_e = a.gw + (int64_t)pr * a.wn;")
-            A("        T* __restrict__ gxr = a.gxe + (int64_t)(ATOM ? j_ : idx) * a.din;")
-            last_of = {st.instr[p_][0]: p_ for p_ in paths}
-            first_of = {}
-            for p_ in paths:
-                first_of.setdefault(st.instr[p_][0], p_)
-            for pth in paths:
-                b_, j, s_ = st.instr[pth]
-                d1 = 2 * st.in1_ls[b_] + 1
-                if first_of[b_] == pth:
-                    for i in range(d1):
-                        A(f"        gxa[{xpre[b_] + i}] = T(0);")
+                        A(f"          gxa[{p.xpre[b_] + i}] = T(0);")
                 A(f"        {{  // path {pth}")
-                body = []
-                live_i, gx_i = sp_path(body, pth, "J", "gvO", "I", "i")
+                A(f"          const T wv_ = *reinterpret_cast<const T*>(cb + {lo[('w', pth)]} + l4);")
+                for k in range(d3):
+                    A(f"          gvJ[{p.opre[s_] + k}] = T({p.slot_coeff[s_]!r}) * *reinterpret_cast<const T*>(cb + {lo[('g', s_)]} + l4 * {d3}u + {4 * k});")
+                live_i, gx_i = path_terms(p, L, pth, "J", "gvO", "I", "i", "          ", dual=False)
                 for comp, expr in gx_i:
                     if expr:
-                        body.append(f"          if (GX) gxa[{comp}] += wv[{pth}] * ({expr});")
-                live_x, gx_x = sp_path(body, pth, "O", "gvJ", "X", "x")
+                        A(f"          if (GX) gxa[{comp}] += wv_ * ({expr});")
+                live_x, gx_x = path_terms(p, L, pth, "O", "gvJ", "X", "x", "          ", dual=False)
                 for comp, expr in gx_x:
                     if expr:
-                        body.append(f"          if (GX) gxO[{comp}] += wv[{pth}] * ({expr});")
+                        A(f"          if (GX) gxO[{comp}] += wv_ * ({expr});")
                 terms = [f"yb{j}I[{jj}] * Bi{jj}" for jj in live_i] + [f"yb{j}X[{jj}] * Bx{jj}" for jj in live_x]
                 gw_expr = " + ".join(terms) if terms else "T(0)"
-                body.append(f"          {{ const T r_ = {gw_expr}; if (act) {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'r_')}; }}")
+                A(f"          {{ const T r_ = {gw_expr}; {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'r_')}; }}")
                 for jj in live_i:
-                    body.append(f"          qI[{ypre[j] + jj}] += wv[{pth}] * Bi{jj};")
+                    A(f"          qI[{p.ypre[j] + jj}] += wv_ * Bi{jj};")
                 for jj in live_x:
-                    body.append(f"          qX[{ypre[j] + jj}] += wv[{pth}] * Bx{jj};")
-                L.extend(body)
+                    A(f"          qX[{p.ypre[j] + jj}] += wv_ * Bx{jj};")
                 A("        }")
-                if last_of[b_] == pth:
-                    A("        if (GX && act) {")
+                if p.last_path[b_] == pth:
+                    A("          if (GX) {")
                     for i in range(d1):
-                        st_ = emit_store(f'spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb)', f'gxa[{xpre[b_] + i}]')
-                        A(f"          if (ATOM) unsafeAtomicAdd(spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb), gxa[{xpre[b_] + i}]); else {st_};")
-                    A("        }")
-            if part_i == 0 and unused_comps:
-                A("        if (GX && act && !ATOM) {")
-                for i in unused_comps:
-                    A(f"          *spec_at(gxr + (unsigned)(mul * {i}), ucb) = T(0);")
-                A("        }")
-            A("        spec_mask_dup<T, kS>(qI, u < mul);")
-            A("        spec_mask_dup<T, kS>(qX, u < mul);")
-            A(f"        spec_wave_reduce_store<T, kS>(qI, a.gy + (int64_t)ei * a.gy_stride + (chunk * kPairParts + {part_i}) * kS, lane);")
-            A(f"        spec_wave_reduce_store<T, kS>(qX, a.gy + (int64_t)eo * a.gy_stride + (chunk * kPairParts + {part_i}) * kS, lane);")
-            A("      }")
-            A("      if (GX && act) {")
-            A("        const int uc = u < mul ? u : mul - 1;")
-            A("        T* __restrict__ ob = a.out + (int64_t)node * a.din;")
-            for b in blocks:
-                d = 2 * st.in1_ls[b] + 1
-                for i in range(d):
-                    A(f"        ob[(int64_t)mul * {xpre[b]} + (int64_t)uc * {d} + {i}] = gxO[{xpre[b] + i}];")
-            if part_i == 0:
-                for b in range(NB):
-                    if b not in used_any:
-                        d = 2 * st.in1_ls[b] + 1
-                        for i in range(d):
-                            A(f"        ob[(int64_t)mul * {xpre[b]} + (int64_t)uc * {d} + {i}] = T(0);")
-            A("      }")
-            A("    } break;")
-        A("    default: break;")
-        A("  }")
-        A("}")
-
-    # ------------------------------------------------------------------ split pair kernel on the LDS ring (round 6)
-    # The l_max = 3 structures' pair kernel (one wavefront per (node, chunk, input block)) walked its pairs with a plain loop:
-    # indices -> rows -> arithmetic -> stores, nothing of the next pair requested (the registers hold two grad_out slices).
-    # The same ring as bwd_pair_ring_kernel, per part: the part's slice of w / x[other] / grad_out[other] and the two y rows
-    # of the NEXT pair travel by LDS-DMA while this pair is evaluated out of the LDS.
-    split_ring_ok = pair_parts > 1 and os.environ.get("NQA_GEN_SPLIT_RING", "1") != "0"
-    if split_ring_ok:
-        import itertools as _it
-        SR_WAVE, SU = 20480, 16
-        sr_yrow_units = (S * 4 + SU - 1) // SU
-
-        def sr_plan(paths, blocks):
-            n_ = len(paths)
-            units = [16 + 16 * (2 * st.out_ls[st.instr[p_][2]] + 1) for p_ in paths]
-            xunits = {b_: 16 * (2 * st.in1_ls[b_] + 1) for b_ in blocks}
-            first_of = {}
-            for k_, p_ in enumerate(paths):
-                first_of.setdefault(st.instr[p_][0], k_)
-            for C in range(1, min(n_, 6) + 1):
-                best = None
-                for cuts in _it.combinations(range(1, n_), C - 1):
-                    bounds = [0] + list(cuts) + [n_]
-                    chunk_of = [0] * n_
-                    for c_ in range(C):
-                        for k_ in range(bounds[c_], bounds[c_ + 1]):
-                            chunk_of[k_] = c_
-                    base = [sum(units[bounds[c_]:bounds[c_ + 1]]) for c_ in range(C)]
-                    base[0] += 2 * sr_yrow_units
-                    for place in _it.product(*[range(chunk_of[first_of[b_]] + 1) for b_ in blocks]):
-                        tot = list(base)
-                        for b_, c_ in zip(blocks, place):
-                            tot[c_] += xunits[b_]
-                        key = (max(tot), sum(place))
-                        if best is None or key < best[0]:
-                            best = (key, bounds, dict(zip(blocks, place)))
-                slot_bytes = best[0][0] * SU
-                if SR_WAVE // slot_bytes >= C + 1:
-                    return C, slot_bytes, best[1], best[2]
-            return None
-
-        sr_plans = []
-        for paths in part_paths:
-            sr_plans.append(sr_plan(paths, sorted({st.instr[p_][0] for p_ in paths})))
-        if any(pl is None for pl in sr_plans):
-            split_ring_ok = False
-    if split_ring_ok:
-        sr_nt = set(os.environ.get("NQA_GEN_RING_NT", "w").replace("+", ",").split(","))
-
-        def sr_src_base(kind, ident):
-            if kind == "w":
-                return f"(unsigned)(mul * {ident} + chunk * 64) * 4u"
-            if kind == "x":
-                return f"(unsigned)(mul * {xpre[ident]} + chunk * {64 * (2 * st.in1_ls[ident] + 1)}) * 4u"
-            return f"(unsigned)(mul * {opre[ident]} + chunk * {64 * (2 * st.out_ls[ident] + 1)}) * 4u"
-
-        A("// (see bwd_pair_ring_kernel for the ring, the counted waits and ATOM; parts as in bwd_pair_split_kernel)")
-        A("template <bool GX, bool ATOM>")
-        A("__global__ __launch_bounds__(256, 2) void bwd_pair_split_ring_kernel(const SpecArgs<float> a) {")
-        A("  typedef float T;")
-        A("  extern __shared__ __align__(16) unsigned char nqa_smem[];")
-        A("  const int lane = threadIdx.x & 63;")
-        A("  const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));")
-        A("  const int mul = a.mul;  // a multiple of 64")
-        A("  const int nchunk = mul >> 6;")
-        A("  const int64_t item = (int64_t)spec_xcd_remap(blockIdx.x, gridDim.x) * 4 + wid;")
-        A("  if (item >= (int64_t)a.N * nchunk * kPairParts) return;")
-        A("  const int node = spec_uniform((int)(item / (nchunk * kPairParts)));")
-        A("  const int rem = (int)(item - (int64_t)node * (nchunk * kPairParts));")
-        A("  const int chunk = spec_uniform(rem / kPairParts);")
-        A("  const int part = spec_uniform(rem - chunk * kPairParts);")
-        A("  const int u = chunk * 64 + lane;")
-        A("  constexpr bool act = true;")
-        A("  const int beg = a.rowptr[node], end = a.rowptr[node + 1];")
-        L.extend(lane_offsets("  ", want_x=True, want_g=True))
-        A(f"  const unsigned wbase = (unsigned)wid * {SR_WAVE}u;  // this wavefront's ring (LDS byte address)")
-        A("  const unsigned l4 = (unsigned)lane * 4u, l16 = (unsigned)lane * 16u;")
-        A("  switch (part) {")
-        for part_i, paths in enumerate(part_paths):
-            blocks = sorted({st.instr[p_][0] for p_ in paths})
-            slots = sorted({st.instr[p_][2] for p_ in paths})
-            ys = sorted({st.instr[p_][1] for p_ in paths})
-            RC, RSLOT, rb, xplace = sr_plans[part_i]
-            RN = RC + 1
-            cpaths = [[paths[k_] for k_ in range(rb[c_], rb[c_ + 1])] for c_ in range(RC)]
-            first_pb, last_pb = {}, {}
-            for p_ in paths:
-                first_pb.setdefault(st.instr[p_][0], p_)
-                last_pb[st.instr[p_][0]] = p_
-            lds_off, dma = [], []
-            for c_ in range(RC):
-                streams = {"w": [(p_, 16) for p_ in cpaths[c_]],
-                           "x": [(b_, 16 * (2 * st.in1_ls[b_] + 1)) for b_ in blocks if xplace[b_] == c_],
-                           "g": [(st.instr[p_][2], 16 * (2 * st.out_ls[st.instr[p_][2]] + 1)) for p_ in cpaths[c_]]}
-                offs, ins, pos = {}, [], 0
-                for kind in ("w", "x", "g"):
-                    segs, start = [], 0
-                    for ident, units in streams[kind]:
-                        offs[(kind, ident)] = (pos + start) * SU
-                        segs.append((ident, start, units))
-                        start += units
-                    for i0 in range(0, start, 64):
-                        nl = min(64, start - i0)
-                        pieces = []
-                        for ident, sstart, units in segs:
-                            lo, hi = max(sstart, i0), min(sstart + units, i0 + nl)
-                            if lo < hi:
-                                pieces.append((lo - i0, hi - i0, ident, lo - sstart))
-                        ins.append((kind, (pos + i0) * SU, nl, pieces))
-                    pos += start
-                if c_ == 0:
-                    offs[("y", "I")] = pos * SU
-                    ins.append(("yI", pos * SU, S, None))
-                    pos += sr_yrow_units
-                    offs[("y", "X")] = pos * SU
-                    ins.append(("yX", pos * SU, S, None))
-                    pos += sr_yrow_units
-                assert pos * SU <= RSLOT
-                lds_off.append(offs)
-                dma.append(ins)
-            D_pair = sum(len(i_) for i_ in dma)
-            Sgw = [len(cpaths[c_]) for c_ in range(RC)]
-            Sgx = [sum(2 * st.in1_ls[b_] + 1 for b_ in blocks if last_pb[b_] in cpaths[c_]) for c_ in range(RC)]
-            Sgx_atom = list(Sgx)
-            if part_i == 0:
-                Sgx[RC - 1] += len(unused_comps)
-            assert sum(Sgw) + sum(Sgx) + D_pair < 64, "vmcnt range"
-            pfx = f"p{part_i}"
-
-            def issue(ind, c_, sfx, slotexpr, lgkm=True):
-                out = [f"{ind}{{ const unsigned sb_ = wbase + (unsigned)({slotexpr}) * {RSLOT}u;"]
-                if lgkm:
-                    out.append(f"{ind}  spec_wait_lgkm();")
-                kinds = {k_ for k_, _, _, _ in dma[c_]}
-                if "w" in kinds:
-                    out.append(f"{ind}  const T* __restrict__ wr_ = a.w + (int64_t)pr{sfx} * a.wn;")
-                if "x" in kinds:
-                    out.append(f"{ind}  const T* __restrict__ xr_ = a.x + (int64_t)jn{sfx} * a.din;")
-                if "g" in kinds:
-                    out.append(f"{ind}  const T* __restrict__ gr_ = a.g + (int64_t)jn{sfx} * a.dout;")
-                for i_, (kind, loff, nl, pieces) in enumerate(dma[c_]):
-                    if kind == "yI":
-                        out.append(f"{ind}  spec_glds4<{nl}>(sb_ + {loff}u, a.y + (int64_t)ei{sfx} * kS, l4);")
-                    elif kind == "yX":
-                        out.append(f"{ind}  spec_glds4<{nl}>(sb_ + {loff}u, a.y + (int64_t)eo{sfx} * kS, l4);")
-                    else:
-                        nt_ = ", true" if kind in sr_nt else ""
-                        if len(pieces) == 1:
-                            lo_, _, ident_, su_ = pieces[0]
-                            uoff = f"{sr_src_base(kind, ident_)} + (unsigned)({(su_ - lo_) * SU})"
-                            out.append(f"{ind}  spec_glds16<{nl}{nt_}>(sb_ + {loff}u, reinterpret_cast<const char*>({kind}r_) + ({uoff}), l16);")
-                        else:
-                            out.append(f"{ind}  spec_glds16<{nl}{nt_}>(sb_ + {loff}u, {kind}r_, {pfx}ro{c_}_{i_});")
-                out.append(f"{ind}}}")
-                return out
-
-            def blk_load(ind, first_pair):
-                return [f"{ind}{{ const int i_ = beg + ({first_pair}) + lane; const int ic_ = i_ < end ? i_ : end - 1;",
-                        f"{ind}  jnV = a.nbr[ic_]; prV = a.wid[ic_]; eiV = a.eid[ic_]; eoV = a.eid2[ic_]; }}"]
-
-            def idx_get(sfx, k, ind):
-                return [f"{ind}jn{sfx} = __builtin_amdgcn_readlane(jnV, ({k}) & 63); pr{sfx} = __builtin_amdgcn_readlane(prV, ({k}) & 63);",
-                        f"{ind}ei{sfx} = __builtin_amdgcn_readlane(eiV, ({k}) & 63); eo{sfx} = __builtin_amdgcn_readlane(eoV, ({k}) & 63);"]
-
-            A(f"    case {part_i}: {{  // input blocks {blocks}: paths {paths}; ring of {RN} slots of {RSLOT} bytes, {RC} chunk(s) per pair, {D_pair} copies")
-            for c_ in range(RC):
-                for i_, (kind, loff, nl, pieces) in enumerate(dma[c_]):
-                    if pieces is None or len(pieces) == 1:
-                        continue
-                    expr = None
-                    for lo, hi, ident, su_ in reversed(pieces):
-                        e_ = f"{sr_src_base(kind, ident)} + (unsigned)({(su_ - lo) * SU})"
-                        expr = e_ if expr is None else f"(lane < {hi} ? {e_} : {expr})"
-                    A(f"      const unsigned {pfx}ro{c_}_{i_} = ({expr}) + l16;")
-            A("      T gvO[kOD], gvJ[kOD], gxO[kXD], qI[kS], qX[kS], gxa[kXD];")
-            for b in blocks:
-                A(f"      T xb{b}O[{2 * st.in1_ls[b] + 1}], xb{b}J[{2 * st.in1_ls[b] + 1}];")
-            for j in ys:
-                A(f"      T yb{j}I[{2 * st.in2_ls[j] + 1}], yb{j}X[{2 * st.in2_ls[j] + 1}];")
-            L.extend(sp_load_g("      ", "a.g + (int64_t)node * a.dout", "gvO", slots))
-            L.extend(sp_load_x("      ", "(a.x + (int64_t)node * a.din)", "O", blocks))
-            for b in blocks:
-                for i in range(2 * st.in1_ls[b] + 1):
-                    A(f"      gxO[{xpre[b] + i}] = T(0);")
-            A("      int idx = beg, kk = 0;")
-            A("      int jnA = 0, prA = 0, eiA = 0, eoA = 0, jnB = 0, prB = 0, eiB = 0, eoB = 0, jnC = 0, prC = 0, eiC = 0, eoC = 0;")
-            A("      int jnV = 0, prV = 0, eiV = 0, eoV = 0;")
-            A("      bool hasA = idx < end, hasB = idx + 1 < end, hasC = false;")
-            A("      if (hasA) {")
-            L.extend(blk_load("        ", "0"))
-            L.extend(idx_get("A", "0", "        "))
-            L.extend(idx_get("B", "1", "        "))
-            for c_ in range(RC):
-                L.extend(issue("        ", c_, "A", str(c_), lgkm=False))
-            A("      }")
-            A("      if (hasB) {")
-            L.extend(issue("        ", 0, "B", str(RC), lgkm=False))
-            A("      }")
-            A("      // (the owner's rows are in their registers before the loop starts: see bwd_pair_ring_kernel)")
-            for s_ in slots:
-                for k in range(2 * st.out_ls[s_] + 1):
-                    A(f"      asm volatile(\"\" : \"+v\"(gvO[{opre[s_] + k}]));")
-            for b in blocks:
-                for i in range(2 * st.in1_ls[b] + 1):
-                    A(f"      asm volatile(\"\" : \"+v\"(xb{b}O[{i}]));")
-            n_t = 0
-            for p_ in paths:
-                b2, j2, s2 = st.instr[p_]
-                n_t += int((np.abs(np.array(wigner_3j(st.in1_ls[b2], st.in2_ls[j2], st.out_ls[s2]))).sum(axis=2) != 0).sum())
-            nohoist = n_t > int(os.environ.get("NQA_GEN_SPLIT_NOHOIST", "64"))
-            A("      int rot = 0;")
-            A("      bool first = true;")
-            A("      while (hasA) {")
-            A("        hasC = idx + 2 < end;")
-            A("        if (hasC) {")
-            A("          if (((kk + 2) & 63) == 0) {")
-            L.extend(blk_load("            ", "kk + 2"))
-            A("          }")
-            L.extend(idx_get("C", "kk + 2", "          "))
+                        st_ = emit_store(f'spec_at(gxr + (unsigned)(mul * {p.xpre[b_] + i}), ucb)', f'gxa[{p.xpre[b_] + i}]')
+                        A(f"            if (ATOM) unsafeAtomicAdd(spec_at(gxr + (unsigned)(mul * {p.xpre[b_] + i}), ucb), gxa[{p.xpre[b_] + i}]); else {st_};")
+                    A("          }")
+            if c_ == RC - 1:
+                if part_i == 0 and p.unused_comps:
+                    A("          if (GX && !ATOM) {")
+                    for i in p.unused_comps:
+                        A(f"            *spec_at(gxr + (unsigned)(mul * {i}), ucb) = T(0);")
+                    A("          }")
+                A("          if (hasC) {")
+                L.extend(copies("            ", 0, "C", "s_"))
+                A("          }")
+                A(f"          spec_wave_reduce_store<T, kS>(qI, a.gy + (int64_t)eiA * a.gy_stride + (a.gy_atomic ? 0 : (chunk * kPairParts + {part_i}) * kS), lane, a.gy_atomic != 0);")
+                A(f"          spec_wave_reduce_store<T, kS>(qX, a.gy + (int64_t)eoA * a.gy_stride + (a.gy_atomic ? 0 : (chunk * kPairParts + {part_i}) * kS), lane, a.gy_atomic != 0);")
+            else:
+                A("          if (hasB) {")
+                L.extend(copies("            ", c_ + 1, "B", "s_"))
+                A("          }")
             A("        }")
-            A("        T* __restrict__ gwr_e = a.gw + (int64_t)prA * a.wn;")
-            A("        T* __restrict__ gxr = a.gxe + (int64_t)(ATOM ? jnA : idx) * a.din;")
-            A("#pragma unroll")
-            A("        for (int j = 0; j < kS; ++j) { qI[j] = T(0); qX[j] = T(0); }")
-            if nohoist:
-                for s_ in slots:
-                    for k in range(2 * st.out_ls[s_] + 1):
-                        A(f"        asm volatile(\"\" : \"+v\"(gvO[{opre[s_] + k}]));")
-            for c_ in range(RC):
-                lo = lds_off[c_]
-                nfirst = D_pair + sum(Sgw[:c_])
-                nfirst_gx = f"(ATOM ? {nfirst + sum(Sgx_atom[:c_])} : {nfirst + sum(Sgx[:c_])})"
-                nsteady = D_pair + sum(Sgw)
-                nsteady_gx = f"(ATOM ? {nsteady + sum(Sgx_atom)} : {nsteady + sum(Sgx)})"
-                A(f"        {{  // ---- chunk {c_}: paths {cpaths[c_]}")
-                A(f"          int s_ = rot + {c_}; s_ = s_ >= {RN} ? s_ - {RN} : s_;")
-                A(f"          const unsigned char* __restrict__ cb = nqa_smem + (wbase + (unsigned)s_ * {RSLOT}u);")
-                A("          if (!hasB) spec_wait_vm<0>();")
-                A(f"          else if (first) spec_wait_vm<GX ? {nfirst_gx} : {nfirst}>();")
-                A(f"          else spec_wait_vm<GX ? {nsteady_gx} : {nsteady}>();")
-                if c_ == 0:
-                    for j in ys:
-                        for i in range(2 * st.in2_ls[j] + 1):
-                            A(f"          yb{j}I[{i}] = *reinterpret_cast<const T*>(cb + {lo[('y', 'I')] + 4 * (ypre[j] + i)});")
-                            A(f"          yb{j}X[{i}] = *reinterpret_cast<const T*>(cb + {lo[('y', 'X')] + 4 * (ypre[j] + i)});")
-                for b_ in blocks:
-                    if xplace[b_] == c_:
-                        d1 = 2 * st.in1_ls[b_] + 1
-                        for i in range(d1):
-                            A(f"          xb{b_}J[{i}] = *reinterpret_cast<const T*>(cb + {lo[('x', b_)]} + l4 * {d1}u + {4 * i});")
-                for pth in cpaths[c_]:
-                    b_, j, s_ = st.instr[pth]
-                    d1, d3 = 2 * st.in1_ls[b_] + 1, 2 * st.out_ls[s_] + 1
-                    if first_pb[b_] == pth:
-                        for i in range(d1):
-                            A(f"          gxa[{xpre[b_] + i}] = T(0);")
-                    A(f"        {{  // path {pth}")
-                    A(f"          const T wv_ = *reinterpret_cast<const T*>(cb + {lo[('w', pth)]} + l4);")
-                    for k in range(d3):
-                        A(f"          gvJ[{opre[s_] + k}] = T({slot_coeff[s_]!r}) * *reinterpret_cast<const T*>(cb + {lo[('g', s_)]} + l4 * {d3}u + {4 * k});")
-                    body = []
-                    live_i, gx_i = sp_path(body, pth, "J", "gvO", "I", "i")
-                    for comp, expr in gx_i:
-                        if expr:
-                            body.append(f"          if (GX) gxa[{comp}] += wv_ * ({expr});")
-                    live_x, gx_x = sp_path(body, pth, "O", "gvJ", "X", "x")
-                    for comp, expr in gx_x:
-                        if expr:
-                            body.append(f"          if (GX) gxO[{comp}] += wv_ * ({expr});")
-                    L.extend(body)
-                    terms = [f"yb{j}I[{jj}] * Bi{jj}" for jj in live_i] + [f"yb{j}X[{jj}] * Bx{jj}" for jj in live_x]
-                    gw_expr = " + ".join(terms) if terms else "T(0)"
-                    A(f"          {{ const T r_ = {gw_expr}; {emit_store(f'spec_at(gwr_e + (unsigned)(mul * {pth}), ucb)', 'r_')}; }}")
-                    for jj in live_i:
-                        A(f"          qI[{ypre[j] + jj}] += wv_ * Bi{jj};")
-                    for jj in live_x:
-                        A(f"          qX[{ypre[j] + jj}] += wv_ * Bx{jj};")
-                    A("        }")
-                    if last_pb[b_] == pth:
-                        A("          if (GX) {")
-                        for i in range(d1):
-                            st_ = emit_store(f'spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb)', f'gxa[{xpre[b_] + i}]')
-                            A(f"            if (ATOM) unsafeAtomicAdd(spec_at(gxr + (unsigned)(mul * {xpre[b_] + i}), ucb), gxa[{xpre[b_] + i}]); else {st_};")
-                        A("          }")
-                if c_ == RC - 1:
-                    if part_i == 0 and unused_comps:
-                        A("          if (GX && !ATOM) {")
-                        for i in unused_comps:
-                            A(f"            *spec_at(gxr + (unsigned)(mul * {i}), ucb) = T(0);")
-                        A("          }")
-                    A("          if (hasC) {")
-                    L.extend(issue("            ", 0, "C", "s_"))
-                    A("          }")
-                    A(f"          spec_wave_reduce_store<T, kS>(qI, a.gy + (int64_t)eiA * a.gy_stride + (a.gy_atomic ? 0 : (chunk * kPairParts + {part_i}) * kS), lane, a.gy_atomic != 0);")
-                    A(f"          spec_wave_reduce_store<T, kS>(qX, a.gy + (int64_t)eoA * a.gy_stride + (a.gy_atomic ? 0 : (chunk * kPairParts + {part_i}) * kS), lane, a.gy_atomic != 0);")
-                else:
-                    A("          if (hasB) {")
-                    L.extend(issue("            ", c_ + 1, "B", "s_"))
-                    A("          }")
-                A("        }")
-            A("        jnA = jnB; prA = prB; eiA = eiB; eoA = eoB; jnB = jnC; prB = prC; eiB = eiC; eoB = eoC;")
-            A("        hasA = hasB; hasB = hasC; ++idx; ++kk; first = false;")
-            A(f"        rot += {RC}; rot = rot >= {RN} ? rot - {RN} : rot;")
-            A("      }")
-            A("      if (GX) {")
-            A("        T* __restrict__ ob = a.out + (int64_t)node * a.din;")
-            for b in blocks:
-                d = 2 * st.in1_ls[b] + 1
-                for i in range(d):
-                    A(f"        ob[(int64_t)mul * {xpre[b]} + (int64_t)u * {d} + {i}] = gxO[{xpre[b] + i}];")
-            if part_i == 0:
-                for b in range(NB):
-                    if b not in used_any:
-                        d = 2 * st.in1_ls[b] + 1
-                        for i in range(d):
-                            A(f"        ob[(int64_t)mul * {xpre[b]} + (int64_t)u * {d} + {i}] = T(0);")
-            A("      }")
-            A("    } break;")
-        A("    default: break;")
-        A("  }")
-        A("}")
+        A("        jnA = jnB; prA = prB; eiA = eiB; eoA = eoB; jnB = jnC; prB = prC; eiB = eiC; eoB = eoC;")
+        A("        hasA = hasB; hasB = hasC; ++idx; ++kk; first = false;")
+        A(f"        rot += {RC}; rot = rot >= {RN} ? rot - {RN} : rot;")
+        A("      }")
+        A("      if (GX) {")
+        A("        T* __restrict__ ob = a.out + (int64_t)node * a.din;")
+        L.extend(_split_part_x_rows(p, part_i, blocks, "u"))
+        A("      }")
+        A("    } break;")
+    A("    default: break;")
+    A("  }")
+    A("}")
+    return L
 
-    # ------------------------------------------------------------------ accumulator form of grad_x (ATOM), last step
-    if pair_ok or pair_parts > 1:
+
+def emit_gx_kernels(p: Plan) -> List[str]:
+    """The last steps of grad_x: the accumulator form of the pair kernels (ATOM) and the per-source-node sum of the rows."""
+    st = p.st
+    L = []
+    A = L.append
+    if p.pair_parts:
         A("// a.out[n] += the accumulator row of n (ATOM forms of the pair kernels), re-ordered from component rows to the irreps layout")
         A("__global__ __launch_bounds__(256) void gx_acc_finish_kernel(const SpecArgs<float> a) {")
         A("  const int mul = a.mul;")
@@ -2219,13 +1663,11 @@ def _emit(st: Structure) -> str:
         A("  const int u = (int)(t - node * mul);")
         A("  const float* __restrict__ acc = a.gxe + node * a.din + u;")
         A("  float* __restrict__ ob = a.out + node * a.din;")
-        for b in used_blocks:
+        for b in p.used_blocks:
             d = 2 * st.in1_ls[b] + 1
             for i in range(d):
-                A(f"  ob[(int64_t)mul * {xpre[b]} + (int64_t)u * {d} + {i}] += acc[(int64_t)mul * {xpre[b] + i}];")
+                A(f"  ob[(int64_t)mul * {p.xpre[b]} + (int64_t)u * {d} + {i}] += acc[(int64_t)mul * {p.xpre[b] + i}];")
         A("}")
-
-    # ------------------------------------------------------------------ per-source-node sum of the fused rows
     A("// ACC: add the rows to what a.out already holds (pair-centric backward: the owner-side sums) instead of overwriting")
     A("template <typename T, bool ACC>")
     A("__global__ __launch_bounds__(256) void gx_rows_sum_kernel(const SpecArgs<T> a) {")
@@ -2265,21 +1707,27 @@ def _emit(st: Structure) -> str:
     A("  }")
     A("  if (act) {")
     A("    T* __restrict__ ob = a.out + (int64_t)node * a.din;")
-    for b in range(NB):
+    for b in range(p.NB):
         d = 2 * st.in1_ls[b] + 1
         for i in range(d):
-            A(f"    {{ T* o_ = ob + ((int64_t)mul * {xpre[b]} + (int64_t)u * {d} + {i}); *o_ = ACC ? *o_ + acc[{xpre[b] + i}] : acc[{xpre[b] + i}]; }}")
+            A(f"    {{ T* o_ = ob + ((int64_t)mul * {p.xpre[b]} + (int64_t)u * {d} + {i}); *o_ = ACC ? *o_ + acc[{p.xpre[b] + i}] : acc[{p.xpre[b] + i}]; }}")
     A("  }")
     A("}")
+    return L
 
-    # ------------------------------------------------------------------ launchers + registration
+
+def emit_launcher(p: Plan) -> List[str]:
+    """launch<WPN>(which, ...) for every entry point of tp_spec.h, and the structure's registration (closes the namespaces)."""
+    st = p.st
+    L = []
+    A = L.append
     # (NQA_LAB: scripts/micro/pair_lab.hip includes a generated file and launches single instantiations itself)
     A("#ifndef NQA_LAB")
     A("template <int WPN>")
     A("static int launch(int which, const SpecArgs<float>& a, hipStream_t stream) {")
     A("  const int nchunk = (a.mul + 63) / 64;")
     A("  const int64_t items = (int64_t)a.N * nchunk;")
-    # FULL for EVERY multiplicity (round 4): a lane beyond the last channel works on the clamped channel -- same loads, same
+    # FULL for EVERY multiplicity: a lane beyond the last channel works on the clamped channel -- same loads, same
     # arithmetic, and it rewrites its twin's stores with identical values; only the wave reductions (grad_y) mask it out
     # (spec_mask_dup) and the owner-side stores use the clamped channel.  The FULL = false instantiations (one exec-mask
     # branch region per store: 155 spilled registers in the l_max = 3 split pair kernel that the 32-channel segments of the
@@ -2292,13 +1740,12 @@ def _emit(st: Structure) -> str:
     A("    const dim3 grid((unsigned)blocks), blk(256);")
     A("    if (a.gxe != nullptr) {")
     A("      if (a.gw == nullptr || a.gy == nullptr) return 1;")
-    A("      if (full) hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, true, true, true, true>), grid, blk, 0, stream, a); else hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, true, true, true, false>), grid, blk, 0, stream, a);")
-    A("    } else if (a.gw != nullptr && a.gy != nullptr) {")
-    A("      if (full) hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, false, true, true, true>), grid, blk, 0, stream, a); else hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, false, true, true, false>), grid, blk, 0, stream, a);")
-    A("    } else if (a.gw != nullptr) {")
-    A("      if (full) hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, false, true, false, true>), grid, blk, 0, stream, a); else hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, false, true, false, false>), grid, blk, 0, stream, a);")
-    A("    } else if (a.gy != nullptr) {")
-    A("      if (full) hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, false, false, true, true>), grid, blk, 0, stream, a); else hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, false, false, true, false>), grid, blk, 0, stream, a);")
+    for cond, flags in ((None, "true, true, true"), ("a.gw != nullptr && a.gy != nullptr", "false, true, true"),
+                        ("a.gw != nullptr", "false, true, false"), ("a.gy != nullptr", "false, false, true")):
+        if cond is not None:
+            A(f"    }} else if ({cond}) {{")
+        A(f"      if (full) hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, {flags}, true>), grid, blk, 0, stream, a); "
+          f"else hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, {flags}, false>), grid, blk, 0, stream, a);")
     A("    }")
     A("    return 0;")
     A("  }")
@@ -2307,9 +1754,9 @@ def _emit(st: Structure) -> str:
     A("    return 0;")
     A("  }")
     A("  if (which == 4) {  // pair-centric backward (owner CSR in rowptr / nbr / wid / eid / eid2)")
-    if pair_ok:
+    if p.pair_ok:
         A("    if (a.gw == nullptr || a.gy == nullptr || a.eid2 == nullptr || (a.out != nullptr && a.gxe == nullptr)) return 1;")
-        if ring_ok:
+        if p.ring is not None:
             A("    // LDS-ring kernel (round 6): multiples of 64 channels; one wavefront per (node, chunk) when that fills the chip")
             A("    // (read at every launch: the tests switch kernels within one process)")
             A("    const bool ring_ = [] { const char* v = std::getenv(\"NQA_PAIR_RING\"); return v == nullptr || v[0] != '0'; }();")
@@ -2341,24 +1788,23 @@ def _emit(st: Structure) -> str:
         A("      else hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, false, false>), grid, blk, 0, stream, a);")
         A("    }")
         A("    return 0;")
-    elif pair_parts > 1:
+    elif p.pair_parts > 1:
         A("    if (a.gw == nullptr || a.gy == nullptr || a.eid2 == nullptr || (a.out != nullptr && a.gxe == nullptr)) return 1;")
         A("    const int64_t witems = items * kPairParts;  // one wavefront per (node, chunk, part)")
         A("    const dim3 grid((unsigned)((witems + 3) / 4)), blk(256);")
         A("    if (a.out != nullptr) {")
-        if split_ring_ok:
-            A("      // LDS-ring form (round 6): multiples of 64 channels; NQA_PAIR_RING=0 keeps the plain loop")
-            A("      const bool sring_ = [] { const char* v = std::getenv(\"NQA_PAIR_RING\"); return v == nullptr || v[0] != '0'; }();")
-            A("      if (sring_ && (a.mul & 63) == 0) {")
-            A(f"        const size_t rsmem = (size_t)4 * {SR_WAVE};")
-            A("#define NQA_SRING_LAUNCH(GX_, AT_) do { \\")
-            A("          static bool lds_ok_[64] = {}; \\")
-            A("          if (!spec_allow_lds((const void*)bwd_pair_split_ring_kernel<GX_, AT_>, 4 * " + str(20480) + ", lds_ok_)) return 1; \\")
-            A("          hipLaunchKernelGGL((bwd_pair_split_ring_kernel<GX_, AT_>), grid, blk, rsmem, stream, a); } while (0)")
-            A("        if (a.gx_atomic) NQA_SRING_LAUNCH(true, true); else NQA_SRING_LAUNCH(true, false);")
-            A("#undef NQA_SRING_LAUNCH")
-            A("        return 0;")
-            A("      }")
+        A("      // LDS-ring form (round 6): multiples of 64 channels; NQA_PAIR_RING=0 keeps the plain loop")
+        A("      const bool sring_ = [] { const char* v = std::getenv(\"NQA_PAIR_RING\"); return v == nullptr || v[0] != '0'; }();")
+        A("      if (sring_ && (a.mul & 63) == 0) {")
+        A(f"        const size_t rsmem = (size_t)4 * {RING_WAVE_BYTES};")
+        A("#define NQA_SRING_LAUNCH(GX_, AT_) do { \\")
+        A("          static bool lds_ok_[64] = {}; \\")
+        A(f"          if (!spec_allow_lds((const void*)bwd_pair_split_ring_kernel<GX_, AT_>, 4 * {RING_WAVE_BYTES}, lds_ok_)) return 1; \\")
+        A("          hipLaunchKernelGGL((bwd_pair_split_ring_kernel<GX_, AT_>), grid, blk, rsmem, stream, a); } while (0)")
+        A("        if (a.gx_atomic) NQA_SRING_LAUNCH(true, true); else NQA_SRING_LAUNCH(true, false);")
+        A("#undef NQA_SRING_LAUNCH")
+        A("        return 0;")
+        A("      }")
         A("      if (a.gx_atomic && (a.mul & 63) != 0) return 1;")
         A("      if (a.gx_atomic) hipLaunchKernelGGL((bwd_pair_split_kernel<float, true, true, true>), grid, blk, 0, stream, a);")
         A("      else if (full) hipLaunchKernelGGL((bwd_pair_split_kernel<float, true, true>), grid, blk, 0, stream, a);")
@@ -2385,7 +1831,7 @@ def _emit(st: Structure) -> str:
     A("    return 0;")
     A("  }")
     A("  if (which == 6) {  // dual pair-centric edge gradients (second-order backward), see bwd_pair_kernel<DUAL>")
-    if pair_ok:
+    if p.pair_ok:
         A("    if (a.gw == nullptr || a.gy == nullptr || a.eid2 == nullptr || a.x2 == nullptr || a.y2 == nullptr) return 1;")
         A("    const dim3 grid((unsigned)((items * WPN + 3) / 4)), blk(256);")
         A("    if (full) hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, true, false, true>), grid, blk, 0, stream, a);")
@@ -2395,7 +1841,7 @@ def _emit(st: Structure) -> str:
         A("    return 1;")
     A("  }")
     A("  if (which == 9) {  // grad_x += the accumulator rows of the atomic form of the pair kernels")
-    if pair_ok or pair_parts > 1:
+    if p.pair_parts:
         A("    const int64_t threads = (int64_t)a.N * a.mul;")
         A("    hipLaunchKernelGGL(gx_acc_finish_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);")
         A("    return 0;")
@@ -2421,11 +1867,25 @@ def _emit(st: Structure) -> str:
     A("  if (wpn >= 4 && kOD <= 64) return launch<4>(which, a, stream);")
     A("  return launch<1>(which, a, stream);")
     A("}")
-    A(f'static SpecRegistrar reg_{tag}("{st.key()}", &launch_any, kXD, kS, kOD, kNP, {pair_parts}, {2 if pair_parts > 1 else (1 if ring_ok else 0)});')
+    A(f'static SpecRegistrar reg_{st.tag()}("{st.key()}", &launch_any, kXD, kS, kOD, kNP, {p.pair_parts}, {p.ring_flag});')
     A("#endif  // NQA_LAB")
     A("}  // namespace")
     A("}  // namespace nqa")
-    return "\n".join(L) + "\n"
+    return L
+
+
+def emit_structure(st: Structure) -> str:
+    """The generated .hip source of one structure."""
+    p = plan_structure(st)
+    parts = [emit_header(p), emit_fwd(p), emit_bwd_edge(p), emit_bwd_x(p)]
+    if p.pair_ok:
+        parts.append(emit_pair(p))
+    if p.ring is not None:
+        parts.append(emit_pair_ring(p))
+    if p.pair_parts > 1:
+        parts += [emit_pair_split(p), emit_split_ring(p)]
+    parts += [emit_gx_kernels(p), emit_launcher(p)]
+    return "\n".join(line for part in parts for line in part) + "\n"
 
 
 def generate(out_dir: str) -> List[str]:
@@ -2433,7 +1893,7 @@ def generate(out_dir: str) -> List[str]:
     files = []
     for st in baseline_structures():
         path = os.path.join(out_dir, f"tp_spec_{st.name}_{st.tag()}.hip")
-        src = _emit(st)
+        src = emit_structure(st)
         if not os.path.exists(path) or open(path).read() != src:
             with open(path, "w") as f:
                 f.write(src)
@@ -2454,7 +1914,7 @@ def manifest() -> dict:
     tests/test_bench_contract.py pins them to the committed manifest)."""
     out = {}
     for st in baseline_structures():
-        src = _emit(st)
+        src = emit_structure(st)
         out[f"tp_spec_{st.name}_{st.tag()}.hip"] = {"sha256": hashlib.sha256(src.encode()).hexdigest(),
                                                      "lines": src.count("\n") + 1, "key": st.key()}
     return out

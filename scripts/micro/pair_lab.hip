@@ -1,11 +1,12 @@
 // Laboratory harness for the pair-centric backward (bwd_pair_kernel + gx_rows_sum_kernel) of ONE generated structure,
-// outside torch:  hipcc -DSPEC_FILE='"<generated .hip>"' [-DLAB_SPLIT] ... pair_lab.hip -o pair_lab_<variant>
+// outside torch:  hipcc -DSPEC_FILE='"<generated .hip>"' [-DLAB_RING | -DLAB_SPLIT [-DLAB_SRING]] ... pair_lab.hip -o pair_lab
+// (scripts/micro/lab_build.py does this)
 //
 //   pair_lab <topology dump (scripts/micro/dump_topo.py)> [reps] [mul] [relabel: 0 none | 1 morton | 2 random] [wpn] [mode] [morton cell] [extra LDS KiB]
 //
 // further positional arguments: [pair rows: 0 as built | 1 numbered in owner-slot order (w / grad_w walked sequentially)]
-//   [grad_x of the other node: 0 one row per pair + row sum | 1 atomic adds into a zeroed [N, dim_in1] accumulator (needs a
-//   generator variant with NQA_GEN_PAIR_GX_ATOMIC=1, or the ring kernel) + the row sum over ONE row per node]
+//   [grad_x of the other node: 0 one row per pair + row sum | 1 atomic adds into a zeroed [N, dim_in1] accumulator (the ATOM
+//   forms of the ring kernels) + the row sum over ONE row per node]
 // mode 0: pair kernel + row sum (what nqa_tp_scatter_bwd_pairs launches); 1: pair kernel only; 2: row sum only
 // Prints the average duration of each kernel (HIP events, one kernel per event pair) and checksums of the results, so that
 // variants built from differently generated files can be compared for speed AND for equality of what they compute.
@@ -91,6 +92,9 @@ int main(int argc, char** argv) {
 
   const int prid = argc > 9 ? atoi(argv[9]) : 0;
   const int gxat = argc > 10 ? atoi(argv[10]) : 0;
+#if !defined(LAB_RING) && !defined(LAB_SRING)
+  if (gxat) { fprintf(stderr, "the grad_x accumulator needs -DLAB_RING or -DLAB_SRING\n"); return 2; }
+#endif
   {
     double d = 0;
     for (int s = 0; s < P; ++s) d += std::abs((double)prow[s] - s);
@@ -177,7 +181,7 @@ int main(int argc, char** argv) {
   float *gw, *gy, *gxe, *out;
   CK(hipMalloc(&gw, (size_t)P * wn * 4));
   CK(hipMalloc(&gy, (size_t)E * kS * gyn * 4));
-  const size_t gxe_n = gxat == 2 ? (size_t)8 * N * din : (size_t)P * din;  // gxat 2: one accumulator per XCD
+  const size_t gxe_n = (size_t)std::max(P, N) * din;  // rows per pair, or (gxat) one accumulator row per node
   CK(hipMalloc(&gxe, gxe_n * 4));
   CK(hipMalloc(&out, (size_t)N * din * 4));
   CK(hipMemset(gw, 0, (size_t)P * wn * 4));
@@ -223,15 +227,10 @@ int main(int argc, char** argv) {
       return;
     }
 #endif
-#ifdef LAB_PK
-#define LAB_PAIR_KERNEL bwd_pair_pk_kernel
-#else
-#define LAB_PAIR_KERNEL bwd_pair_kernel
-#endif
     if (wpn >= 4) {
-      hipLaunchKernelGGL((LAB_PAIR_KERNEL<float, 4, true, true>), dim3((unsigned)items), dim3(256), (size_t)3 * kXD * 64 * 4 + extra_lds, 0, a);
+      hipLaunchKernelGGL((bwd_pair_kernel<float, 4, true, true>), dim3((unsigned)items), dim3(256), (size_t)3 * kXD * 64 * 4 + extra_lds, 0, a);
     } else {
-      hipLaunchKernelGGL((LAB_PAIR_KERNEL<float, 1, true, true>), dim3((unsigned)((items + 3) / 4)), dim3(256), extra_lds, 0, a);
+      hipLaunchKernelGGL((bwd_pair_kernel<float, 1, true, true>), dim3((unsigned)((items + 3) / 4)), dim3(256), extra_lds, 0, a);
     }
 #endif
   };
@@ -252,7 +251,7 @@ int main(int argc, char** argv) {
   double tp = 0, ts = 0;
   for (int r = -3; r < reps; ++r) {
     CK(hipEventRecord(e0, 0));
-    if (gxat) CK(hipMemsetAsync(gxe, 0, (gxat == 2 ? (size_t)8 : (size_t)1) * N * din * 4, 0));
+    if (gxat) CK(hipMemsetAsync(gxe, 0, (size_t)N * din * 4, 0));
     if (mode != 2) launch_pair();
     CK(hipEventRecord(e1, 0));
     if (mode != 1) launch_sum();
@@ -265,26 +264,8 @@ int main(int argc, char** argv) {
     if (r >= 0) { tp += m1; ts += m2; }
   }
   // checksums after ONE clean evaluation (the row sum accumulates into `out`, which the pair kernel overwrites first)
-  if (gxat) CK(hipMemsetAsync(gxe, 0, (gxat == 2 ? (size_t)8 : (size_t)1) * N * din * 4, 0));
+  if (gxat) CK(hipMemsetAsync(gxe, 0, (size_t)N * din * 4, 0));
   launch_pair();
-  if (gxat == 2) {  // fold the eight per-XCD accumulators into the first (host; checksum only) and count the rows each one holds
-    CK(hipDeviceSynchronize());
-    std::vector<float> h((size_t)8 * N * din);
-    CK(hipMemcpy(h.data(), gxe, h.size() * 4, hipMemcpyDeviceToHost));
-    size_t touched = 0;
-    for (int x = 0; x < 8; ++x)
-      for (int n = 0; n < N; ++n) {
-        bool t = false;
-        for (int i = 0; i < din; ++i) {
-          const float v = h[((size_t)x * N + n) * din + i];
-          if (v != 0.f) t = true;
-          if (x) h[(size_t)n * din + i] += v;
-        }
-        touched += t;
-      }
-    fprintf(stderr, "per-XCD accumulators: %zu (XCD, node) rows hold something = %.2f per node\n", touched, (double)touched / N);
-    CK(hipMemcpy(gxe, h.data(), (size_t)N * din * 4, hipMemcpyHostToDevice));
-  }
   launch_sum();
   CK(hipDeviceSynchronize());
   const double c_gw = checksum(gw, (size_t)P * wn), c_out = checksum(out, (size_t)N * din);
@@ -299,19 +280,6 @@ int main(int argc, char** argv) {
         c_gy += s * ((e * 9 + j) % 5 + 1);
       }
   }
-#ifdef LAB_TIMING
-  {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t[8];
-    CK(hipMemcpyToSymbol(HIP_SYMBOL(nqa_lab_tm), z, sizeof(z)));
-    launch_pair();
-    CK(hipDeviceSynchronize());
-    CK(hipMemcpyFromSymbol(t, HIP_SYMBOL(nqa_lab_tm), sizeof(t)));
-    const double n = (double)t[4];
-    printf("timing per pair and wavefront (shader cycles, %.0f pairs): indices+issue %.0f | rows arrive %.0f | compute+store issue %.0f | "
-           "stores drain %.0f | sum %.0f || per wavefront: loop start -> exit %.0f cycles, %.2f pairs\n", n, t[0] / n, t[1] / n, t[2] / n, t[3] / n,
-           (t[0] + t[1] + t[2] + t[3]) / n, (double)t[5] / (double)t[6], n / (double)t[6]);
-  }
-#endif
   const double bytes_alg = (double)E * (8.0 * wn + 8.0 * kS + 16.0) + 4.0 * N * (2.0 * din + dout);
   printf("N=%d E=%d P=%d mul=%d relabel=%d wpn=%d | pair %.1f us  sum %.1f us  total %.1f us | alg %.3f GB -> %.2f TB/s "
          "(%.3f of 8) | chk gw %.6e gy %.6e gx %.6e\n",
