@@ -705,6 +705,27 @@ int nqa_neighbor_list_fill(const void* workspace, const int32_t* rowptr, int64_t
 int nqa_neighbor_list_fill_padded(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t edge_capacity,
                                   int32_t* rowptr_padded, int64_t* edge_index, double* edge_cell_shift, int32_t* src_sorted,
                                   int32_t* status, nqa_stream stream);
+/* Batched variant: F frames (systems) in one set of launches, with one host read per batch instead of one per frame.
+ *   Frame f owns the atoms [frame_ptr[f], frame_ptr[f+1]) of pos [N,3] float64; frame_ptr int64 [F+1] (device) starts at 0
+ *   and ends at N.  cell [F,3,3] float64 (NULL = no frame has a cell), pbc int32 [F,3] (device; NULL = none): every frame has
+ *   its own cell and periodicity, and frames without a cell (all-zero) may sit next to periodic triclinic ones.  Zero lattice
+ *   vectors along non-periodic directions are completed on the device as the host path's _complete_cell does.
+ *   nqa_neighbor_list_batched_count plans every frame on the device (one header per frame: cell inverse, fractional origin,
+ *     bins per direction; frame f gets the n_f + 8 bins the single-frame plan gives it, so workspace bytes depend on (N, F)
+ *     alone) and writes rowptr [N+1] int32 (device, global atom numbering; rowptr[N] = E) and status int32[1] (device,
+ *     zeroed first): bit 0 more than 2^31 - 1 edges, bit 1 a zero lattice vector along a periodic direction, bit 2 linearly
+ *     dependent lattice vectors, bit 3 frame_ptr not a partition of [0, N), bit 4 periodicity without a cell.  The caller
+ *     reads rowptr[N] and status together (place them next to each other: one copy), rejects a non-zero status, and calls
+ *   nqa_neighbor_list_batched_fill with the same workspace.  edge_index / edge_cell_shift are bitwise the concatenation of
+ *     the single-frame lists of the frames with atom indices offset by frame_ptr[f]: grouped by centre atom in ascending
+ *     order (rowptr is the dst-CSR row pointer of the whole batch), the single-frame order within an atom, no edge between
+ *     two frames.  Needs N + 8F < 2^31. */
+int64_t nqa_neighbor_list_batched_workspace_bytes(int64_t num_atoms, int64_t num_frames);
+int nqa_neighbor_list_batched_count(const double* pos, const double* cell, const int32_t* pbc, const int64_t* frame_ptr,
+                                    double r_max, int64_t num_atoms, int64_t num_frames, void* workspace,
+                                    int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream);
+int nqa_neighbor_list_batched_fill(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t num_frames,
+                                   int64_t num_edges, int64_t* edge_index, double* edge_cell_shift, nqa_stream stream);
 
 #ifdef __cplusplus
 }

@@ -93,6 +93,76 @@ __device__ __forceinline__ void inv3(const double* c, double* inv) {
   inv[8] = (c[0] * c[4] - c[1] * c[3]) * r;
 }
 
+// Thread-0 part of a plan: header of one frame from its (completed) cell, its inverse and the bounding box [mn, mx] of its
+// fractional coordinates.  Shared by the single-frame and the batched plan, so a frame gets the same grid in both.
+__device__ void nl_size_grid(const double* c, const double* inv, const double* mn, const double* mx,
+                             const int32_t* __restrict__ pbc, double r_max, int64_t N, int64_t bin_capacity,
+                             NLHeader* __restrict__ h) {
+  for (int i = 0; i < 9; ++i) {
+    h->cell[i] = c[i];
+    h->inv[i] = inv[i];
+  }
+  // perpendicular height of the cell along direction d = 1 / | column d of cell^-1 |
+  int64_t nb[3];
+  double heights[3];
+  for (int d = 0; d < 3; ++d) {
+    const double height = 1.0 / sqrt(inv[d] * inv[d] + inv[3 + d] * inv[3 + d] + inv[6 + d] * inv[6 + d]);
+    const bool per = pbc != nullptr && pbc[d] != 0;
+    h->pbc[d] = per ? 1 : 0;
+    double lo, extent;  // fractional
+    if (per) {
+      lo = 0.0;
+      extent = 1.0;
+    } else {
+      lo = N > 0 ? mn[d] : 0.0;
+      extent = N > 0 ? (mx[d] - mn[d]) : 0.0;
+      extent = extent * (1.0 + 1e-9) + 1e-9;  // the topmost atom must fall inside the last bin
+    }
+    int64_t n = (int64_t)floor(extent * height / r_max);
+    if (n < 1) n = 1;
+    if (n > 1024) n = 1024;
+    nb[d] = n;
+    h->lo[d] = lo;
+    h->width[d] = extent;  // divided by nb below
+    h->reach[d] = 0;       // filled below (needs the final nb)
+    heights[d] = height;
+  }
+  while (nb[0] * nb[1] * nb[2] > bin_capacity) {  // coarser bins are always valid
+    int big = 0;
+    if (nb[1] > nb[big]) big = 1;
+    if (nb[2] > nb[big]) big = 2;
+    nb[big] = (nb[big] + 1) / 2;
+  }
+  for (int d = 0; d < 3; ++d) {
+    const double height = heights[d];
+    const double extent = h->width[d];
+    h->nb[d] = (int32_t)nb[d];
+    h->width[d] = extent / (double)nb[d];
+    const double thick = h->width[d] * height;  // real-space thickness of one bin
+    int reach = (int)ceil(r_max / thick);
+    if (!h->pbc[d] && reach > nb[d] - 1) reach = (int)(nb[d] - 1);  // nothing beyond the box
+    h->reach[d] = reach;
+  }
+  h->nbins = (int32_t)(nb[0] * nb[1] * nb[2]);
+  h->rmax2 = r_max * r_max;
+  // padding edges (nqa_neighbor_list_fill_padded): the shortest lattice vector among the periodic directions (any direction
+  // when there is none), repeated often enough to leave the cutoff sphere
+  int axis = -1;
+  double best = 0.0;
+  for (int pass = 0; pass < 2 && axis < 0; ++pass) {
+    for (int d = 0; d < 3; ++d) {
+      if (pass == 0 && !h->pbc[d]) continue;
+      const double len = sqrt(c[3 * d] * c[3 * d] + c[3 * d + 1] * c[3 * d + 1] + c[3 * d + 2] * c[3 * d + 2]);
+      if (axis < 0 || len < best) {
+        axis = d;
+        best = len;
+      }
+    }
+  }
+  h->pad_axis = axis;
+  h->pad_k0 = (int32_t)floor(r_max / best) + 1;
+}
+
 // One workgroup: bounding box of the fractional coordinates, then thread 0 sizes the grid.
 __global__ __launch_bounds__(1024) void nl_plan_kernel(const double* __restrict__ pos, const double* __restrict__ cell,
                                                        const int32_t* __restrict__ pbc, double r_max, int64_t N,
@@ -140,77 +210,16 @@ __global__ __launch_bounds__(1024) void nl_plan_kernel(const double* __restrict_
     __syncthreads();
   }
   if (tid != 0) return;
-  for (int i = 0; i < 9; ++i) {
-    h->cell[i] = c[i];
-    h->inv[i] = inv[i];
-  }
-  // perpendicular height of the cell along direction d = 1 / | column d of cell^-1 |
-  int64_t nb[3];
-  for (int d = 0; d < 3; ++d) {
-    const double height = 1.0 / sqrt(inv[d] * inv[d] + inv[3 + d] * inv[3 + d] + inv[6 + d] * inv[6 + d]);
-    const bool per = pbc != nullptr && pbc[d] != 0;
-    h->pbc[d] = per ? 1 : 0;
-    double lo, extent;  // fractional
-    if (per) {
-      lo = 0.0;
-      extent = 1.0;
-    } else {
-      lo = N > 0 ? smin[d][0] : 0.0;
-      extent = N > 0 ? (smax[d][0] - smin[d][0]) : 0.0;
-      extent = extent * (1.0 + 1e-9) + 1e-9;  // the topmost atom must fall inside the last bin
-    }
-    int64_t n = (int64_t)floor(extent * height / r_max);
-    if (n < 1) n = 1;
-    if (n > 1024) n = 1024;
-    nb[d] = n;
-    h->lo[d] = lo;
-    h->width[d] = extent;  // divided by nb below
-    h->reach[d] = 0;       // filled below (needs the final nb)
-    h->rmax2 = height;     // scratch; overwritten below
-    smin[d][1] = height;   // keep the height for the second pass
-  }
-  while (nb[0] * nb[1] * nb[2] > bin_capacity) {  // coarser bins are always valid
-    int big = 0;
-    if (nb[1] > nb[big]) big = 1;
-    if (nb[2] > nb[big]) big = 2;
-    nb[big] = (nb[big] + 1) / 2;
-  }
-  for (int d = 0; d < 3; ++d) {
-    const double height = smin[d][1];
-    const double extent = h->width[d];
-    h->nb[d] = (int32_t)nb[d];
-    h->width[d] = extent / (double)nb[d];
-    const double thick = h->width[d] * height;  // real-space thickness of one bin
-    int reach = (int)ceil(r_max / thick);
-    if (!h->pbc[d] && reach > nb[d] - 1) reach = (int)(nb[d] - 1);  // nothing beyond the box
-    h->reach[d] = reach;
-  }
-  h->nbins = (int32_t)(nb[0] * nb[1] * nb[2]);
-  h->rmax2 = r_max * r_max;
-  // padding edges (nqa_neighbor_list_fill_padded): the shortest lattice vector among the periodic directions (any direction
-  // when there is none), repeated often enough to leave the cutoff sphere
-  int axis = -1;
-  double best = 0.0;
-  for (int pass = 0; pass < 2 && axis < 0; ++pass) {
-    for (int d = 0; d < 3; ++d) {
-      if (pass == 0 && !h->pbc[d]) continue;
-      const double len = sqrt(c[3 * d] * c[3 * d] + c[3 * d + 1] * c[3 * d + 1] + c[3 * d + 2] * c[3 * d + 2]);
-      if (axis < 0 || len < best) {
-        axis = d;
-        best = len;
-      }
-    }
-  }
-  h->pad_axis = axis;
-  h->pad_k0 = (int32_t)floor(r_max / best) + 1;
+  const double mn0[3] = {smin[0][0], smin[1][0], smin[2][0]}, mx0[3] = {smax[0][0], smax[1][0], smax[2][0]};
+  nl_size_grid(c, inv, mn0, mx0, pbc, r_max, N, bin_capacity, h);
 }
 
-__global__ __launch_bounds__(256) void nl_bin_kernel(const double* __restrict__ pos, int64_t N,
-                                                     const NLHeader* __restrict__ h, double* __restrict__ sfrac,
-                                                     int32_t* __restrict__ ioff, int32_t* __restrict__ key,
-                                                     int32_t* __restrict__ val, int32_t* __restrict__ bin_count) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
+// Bin of atom i in the grid `h` (global bin id = bin_base + bin within the grid); fractional coordinates wrapped along periodic
+// directions, the integer parts kept in ioff.
+__device__ __forceinline__ void nl_bin_atom(int64_t i, const double* __restrict__ pos, const NLHeader* __restrict__ h,
+                                            int32_t bin_base, double* __restrict__ sfrac, int32_t* __restrict__ ioff,
+                                            int32_t* __restrict__ key, int32_t* __restrict__ val,
+                                            int32_t* __restrict__ bin_count) {
   const double x = pos[3 * i], y = pos[3 * i + 1], z = pos[3 * i + 2];
   int b[3];
   for (int d = 0; d < 3; ++d) {
@@ -232,9 +241,18 @@ __global__ __launch_bounds__(256) void nl_bin_kernel(const double* __restrict__ 
     sfrac[3 * i + d] = s;
     ioff[3 * i + d] = o;
   }
-  const int32_t bin = (b[0] * h->nb[1] + b[1]) * h->nb[2] + b[2];
+  const int32_t bin = bin_base + (b[0] * h->nb[1] + b[1]) * h->nb[2] + b[2];
   key[i] = bin;
   val[i] = atomicAdd(&bin_count[bin], 1);
+}
+
+__global__ __launch_bounds__(256) void nl_bin_kernel(const double* __restrict__ pos, int64_t N,
+                                                     const NLHeader* __restrict__ h, double* __restrict__ sfrac,
+                                                     int32_t* __restrict__ ioff, int32_t* __restrict__ key,
+                                                     int32_t* __restrict__ val, int32_t* __restrict__ bin_count) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  nl_bin_atom(i, pos, h, 0, sfrac, ioff, key, val, bin_count);
 }
 
 __global__ __launch_bounds__(256) void nl_place_kernel(int64_t N, const int32_t* __restrict__ key,
@@ -401,7 +419,7 @@ __global__ __launch_bounds__(1024) void nl_scan_kernel(int64_t N, const int32_t*
   if (tid == 1023) {
     const int64_t total = before + incl;
     rowptr[N] = (int32_t)total;
-    if (total > 2147483647LL && overflow != nullptr) *overflow = 1;
+    if (total > 2147483647LL && overflow != nullptr) *overflow |= 1;
   }
 }
 
@@ -484,6 +502,257 @@ __global__ __launch_bounds__(256) void nl_fill_padded_kernel(int64_t N, int64_t 
       for (int d = 0; d < 3; ++d) shift[3 * e + d] = d == axis ? (sgn ? -k : k) : 0.0;
     }
   }
+}
+
+// ---- batched list: F frames in one set of launches, one host read per batch ------------------------------------------------
+// Frame f owns the atoms [frame_ptr[f], frame_ptr[f+1]) and the bins [bin_off[f], bin_off[f] + n_f + 8), bin_off[f] =
+// frame_ptr[f] + 8 f: the bin budget the single-frame plan gives a frame of n_f atoms, so every frame is coarsened by the same
+// rule and gets the same grid, the same bin order of its atoms and therefore the same edge order as the single-frame list.  The
+// bins of all frames are contiguous, so ONE scan over the N + 8F bins sorts the whole batch by (frame, bin, atom index), and the
+// count / fill walks of the single-frame list run unchanged, one wavefront per atom over the whole batch, on the header and the
+// bin range of the atom's frame.  Atom indices stay global: edges never leave their frame (a frame's bins hold only its atoms).
+enum : int32_t {
+  NL_BAD_OVERFLOW = 1,        // more than 2^31 - 1 edges
+  NL_BAD_PERIODIC_ZERO = 2,   // zero lattice vector along a periodic direction
+  NL_BAD_DEPENDENT = 4,       // linearly dependent lattice vectors
+  NL_BAD_FRAME_PTR = 8,       // frame_ptr is not a partition of [0, N)
+  NL_BAD_PERIODIC_NO_CELL = 16,
+};
+
+static NLLayout nl_batched_layout(int64_t N, int64_t F, int64_t* bin_off, int64_t* atom_frame) {
+  const int64_t B = N + 8 * F;
+  NLLayout L{};
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) {
+    const int64_t o = off;
+    off = align256(off + bytes);
+    return o;
+  };
+  L.header = take(F * (int64_t)sizeof(NLHeader));
+  *bin_off = take(F * 4);
+  *atom_frame = take(N * 4);
+  L.sfrac = take(N * 3 * 8);
+  L.ioff = take(N * 3 * 4);
+  L.key = take(N * 4);
+  L.val = take(N * 4);
+  L.bin_count = take((B + 1) * 4);
+  L.rowptr_bin = take((B + 1) * 4);
+  L.atom_sorted = take(N * 4);
+  L.dummy_other = take(N * 4);
+  L.s_sorted = take(N * 3 * 8);
+  L.o_sorted = take(N * 3 * 4);
+  L.counts = take((N + 1) * 4);
+  L.total = off;
+  return L;
+}
+
+__device__ __forceinline__ int64_t nl_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// A device restatement of _complete_cell_host (nequip_amd/data/_nl.py), the ase.geometry.complete_cell analogue the single-frame
+// path runs on the host: missing (zero) lattice vectors along non-periodic directions become unit vectors orthogonal to the
+// present ones (Gram-Schmidt over the present vectors in index order; one missing: cross product of the two; two missing: the
+// coordinate axis with the largest orthogonal component, then the cross product).  An all-zero cell becomes the identity.  Same
+// steps in the same order, but not the same rounding: the host's dot products and norms go through numpy / BLAS, whose
+// summation order and FMA use are not fixed, so a completed vector may differ from the host's by an ulp (complete cells and
+// missing cells pass through unchanged, so only slabs and wires are affected).  Such a difference changes the list only for an
+// atom within rounding of a bin face along the completed direction.  Returns NL_BAD_* flags (then c is the identity).
+__device__ int32_t nl_complete_cell(double* c, const int32_t* __restrict__ pbc) {
+#pragma clang fp contract(off)
+  double norms[3];
+  bool missing[3];
+  int nmiss = 0;
+  for (int i = 0; i < 3; ++i) {
+    norms[i] = sqrt(c[3 * i] * c[3 * i] + c[3 * i + 1] * c[3 * i + 1] + c[3 * i + 2] * c[3 * i + 2]);
+    missing[i] = norms[i] < 1e-12;
+    nmiss += missing[i] ? 1 : 0;
+  }
+  auto det = [&]() {
+    return c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+  };
+  auto identity = [&]() {
+    for (int i = 0; i < 9; ++i) c[i] = (i % 4 == 0) ? 1.0 : 0.0;
+  };
+  int32_t bad = 0;
+  if (nmiss == 0) {
+    if (fabs(det()) < 1e-12 * fmax(1.0, norms[0] * norms[1] * norms[2])) bad = NL_BAD_DEPENDENT;
+  } else {
+    for (int i = 0; i < 3; ++i)
+      if (missing[i] && pbc != nullptr && pbc[i] != 0) bad = NL_BAD_PERIODIC_ZERO;
+    if (!bad && nmiss < 3) {
+      double basis[3][3];
+      int nb = 0;
+      for (int i = 0; i < 3 && !bad; ++i) {
+        if (missing[i]) continue;
+        double v[3] = {c[3 * i], c[3 * i + 1], c[3 * i + 2]};
+        for (int k = 0; k < nb; ++k) {
+          const double d = v[0] * basis[k][0] + v[1] * basis[k][1] + v[2] * basis[k][2];
+          for (int t = 0; t < 3; ++t) v[t] -= d * basis[k][t];
+        }
+        const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        if (n < 1e-12 * norms[i]) bad = NL_BAD_DEPENDENT;
+        for (int t = 0; t < 3; ++t) basis[nb][t] = v[t] / n;
+        ++nb;
+      }
+      for (int i = 0; i < 3 && !bad; ++i) {
+        if (!missing[i]) continue;
+        double v[3];
+        if (nb == 2) {
+          v[0] = basis[0][1] * basis[1][2] - basis[0][2] * basis[1][1];
+          v[1] = basis[0][2] * basis[1][0] - basis[0][0] * basis[1][2];
+          v[2] = basis[0][0] * basis[1][1] - basis[0][1] * basis[1][0];
+        } else {
+          double best = -1.0;
+          for (int a = 0; a < 3; ++a) {
+            double w[3] = {a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0};
+            for (int k = 0; k < nb; ++k) {
+              const double d = w[0] * basis[k][0] + w[1] * basis[k][1] + w[2] * basis[k][2];
+              for (int t = 0; t < 3; ++t) w[t] -= d * basis[k][t];
+            }
+            const double n = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+            if (best < 0.0 || n > best) {
+              best = n;
+              for (int t = 0; t < 3; ++t) v[t] = w[t];
+            }
+          }
+        }
+        const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        for (int t = 0; t < 3; ++t) {
+          c[3 * i + t] = v[t] / n;
+          basis[nb][t] = v[t] / n;
+        }
+        ++nb;
+      }
+      if (!bad && fabs(det()) < 1e-12) bad = NL_BAD_DEPENDENT;
+    } else if (!bad) {
+      identity();
+    }
+  }
+  if (bad) identity();  // a harmless grid for a frame the host rejects after the count
+  return bad;
+}
+
+// One workgroup per frame: completes the frame's cell, zeroes its bins, reduces the bounding box of its fractional coordinates,
+// then thread 0 sizes the frame's grid exactly as the single-frame plan does (nl_size_grid).
+__global__ __launch_bounds__(256) void nl_batched_plan_kernel(const double* __restrict__ pos, const double* __restrict__ cell,
+                                                              const int32_t* __restrict__ pbc,
+                                                              const int64_t* __restrict__ frame_ptr, double r_max, int64_t N,
+                                                              int64_t F, NLHeader* __restrict__ hdr,
+                                                              int32_t* __restrict__ bin_off, int32_t* __restrict__ bin_count,
+                                                              int32_t* __restrict__ status) {
+  __shared__ double smin[3][256], smax[3][256];
+  __shared__ double c[9], inv[9];
+  __shared__ int32_t pbc_f[3];
+  const int64_t f = blockIdx.x;
+  const int tid = threadIdx.x;
+  // Offsets clamped into [0, N], so every frame's bins lie inside [0, N + 8F) whatever frame_ptr holds (the host rejects a bad
+  // frame_ptr after the count, from the status word).  Every bin count of [0, N + 8F] is zeroed even then: the frames' ranges
+  // follow each other without gaps (a frame starts at or before the end of the previous one), block 0 zeroes the head in
+  // front of frame 0 (frame_ptr[0] > 0) and block F-1 the tail behind the last frame (frame_ptr[F] < N).  The counts then sum
+  // to N, so the bin scan, place and in-bin order stay inside their N-atom arrays.
+  const int64_t a0 = nl_clamp(frame_ptr[f], 0, N), a1 = nl_clamp(frame_ptr[f + 1], a0, N);
+  const int64_t boff = a0 + 8 * f, nbins = (a1 - a0) + 8;
+  for (int64_t b = tid; b < nbins; b += 256) bin_count[boff + b] = 0;
+  if (f == 0)
+    for (int64_t b = tid; b < boff; b += 256) bin_count[b] = 0;
+  if (f == F - 1)
+    for (int64_t b = boff + nbins + tid; b <= N + 8 * F; b += 256) bin_count[b] = 0;
+  if (tid == 0) {
+    int32_t bad = 0;
+    if (frame_ptr[f + 1] < frame_ptr[f] || (f == 0 && frame_ptr[0] != 0) || (f == F - 1 && frame_ptr[F] != N))
+      bad |= NL_BAD_FRAME_PTR;
+    for (int d = 0; d < 3; ++d) pbc_f[d] = pbc != nullptr ? pbc[3 * f + d] : 0;
+    for (int i = 0; i < 9; ++i) c[i] = cell != nullptr ? cell[9 * f + i] : 0.0;
+    if (cell == nullptr && (pbc_f[0] || pbc_f[1] || pbc_f[2])) bad |= NL_BAD_PERIODIC_NO_CELL;
+    const int32_t cbad = nl_complete_cell(c, pbc_f);
+    bad |= cbad;
+    if (bad) pbc_f[0] = pbc_f[1] = pbc_f[2] = 0;
+    inv3(c, inv);
+    bin_off[f] = (int32_t)boff;
+    if (bad) atomicOr(status, bad);
+  }
+  __syncthreads();
+  double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
+  for (int64_t i = a0 + tid; i < a1; i += 256) {
+    const double x = pos[3 * i], y = pos[3 * i + 1], z = pos[3 * i + 2];
+    for (int d = 0; d < 3; ++d) {
+      const double s = x * inv[d] + y * inv[3 + d] + z * inv[6 + d];
+      mn[d] = fmin(mn[d], s);
+      mx[d] = fmax(mx[d], s);
+    }
+  }
+  for (int d = 0; d < 3; ++d) {
+    smin[d][tid] = mn[d];
+    smax[d][tid] = mx[d];
+  }
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) {
+      for (int d = 0; d < 3; ++d) {
+        smin[d][tid] = fmin(smin[d][tid], smin[d][tid + off]);
+        smax[d][tid] = fmax(smax[d][tid], smax[d][tid + off]);
+      }
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const double mn0[3] = {smin[0][0], smin[1][0], smin[2][0]}, mx0[3] = {smax[0][0], smax[1][0], smax[2][0]};
+  nl_size_grid(c, inv, mn0, mx0, pbc_f, r_max, a1 - a0, nbins, hdr + f);
+}
+
+// Frame of every atom (last f with frame_ptr[f] <= i, binary search over the F + 1 offsets), then the single-frame binning in
+// that frame's grid and bin range.
+__global__ __launch_bounds__(256) void nl_batched_bin_kernel(const double* __restrict__ pos, const int64_t* __restrict__ frame_ptr,
+                                                             int64_t N, int64_t F, const NLHeader* __restrict__ hdr,
+                                                             const int32_t* __restrict__ bin_off,
+                                                             int32_t* __restrict__ atom_frame, double* __restrict__ sfrac,
+                                                             int32_t* __restrict__ ioff, int32_t* __restrict__ key,
+                                                             int32_t* __restrict__ val, int32_t* __restrict__ bin_count) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  int64_t lo = 0, hi = F - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (frame_ptr[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  atom_frame[i] = (int32_t)lo;
+  nl_bin_atom(i, pos, hdr + lo, bin_off[lo], sfrac, ioff, key, val, bin_count);
+}
+
+__global__ __launch_bounds__(256) void nl_batched_count_kernel(int64_t N, const NLHeader* __restrict__ hdr,
+                                                               const int32_t* __restrict__ bin_off,
+                                                               const int32_t* __restrict__ atom_frame,
+                                                               const double* __restrict__ sfrac,
+                                                               const int32_t* __restrict__ ioff,
+                                                               const int32_t* __restrict__ rowptr_bin,
+                                                               const int32_t* __restrict__ atom_sorted,
+                                                               const double* __restrict__ s_sorted,
+                                                               const int32_t* __restrict__ o_sorted,
+                                                               int32_t* __restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // one wavefront per atom
+  if (i >= N) return;
+  const int lane = threadIdx.x & 63;
+  const int f = __builtin_amdgcn_readfirstlane(atom_frame[i]);
+  const int cnt = nl_walk<false>(i, lane, hdr + f, sfrac, ioff, rowptr_bin + bin_off[f], atom_sorted, s_sorted, o_sorted, 0, 0,
+                                 nullptr, nullptr);
+  if (lane == 0) counts[i] = cnt;
+}
+
+__global__ __launch_bounds__(256) void nl_batched_fill_kernel(int64_t N, int64_t E, const NLHeader* __restrict__ hdr,
+                                                              const int32_t* __restrict__ bin_off,
+                                                              const int32_t* __restrict__ atom_frame,
+                                                              const double* __restrict__ sfrac, const int32_t* __restrict__ ioff,
+                                                              const int32_t* __restrict__ rowptr_bin,
+                                                              const int32_t* __restrict__ atom_sorted,
+                                                              const double* __restrict__ s_sorted,
+                                                              const int32_t* __restrict__ o_sorted,
+                                                              const int32_t* __restrict__ rowptr, int64_t* __restrict__ edge_index,
+                                                              double* __restrict__ shift) {
+  const int64_t i = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // one wavefront per atom
+  if (i >= N) return;
+  const int f = __builtin_amdgcn_readfirstlane(atom_frame[i]);
+  nl_walk<true>(i, (int)(threadIdx.x & 63), hdr + f, sfrac, ioff, rowptr_bin + bin_off[f], atom_sorted, s_sorted, o_sorted,
+                rowptr[i], E, edge_index, shift);
 }
 
 static int nl_status(const char* fn) {
@@ -585,6 +854,82 @@ int nqa_neighbor_list_fill_padded(const void* workspace, const int32_t* rowptr, 
                      reinterpret_cast<const int32_t*>(w + L.atom_sorted), reinterpret_cast<const double*>(w + L.s_sorted),
                      reinterpret_cast<const int32_t*>(w + L.o_sorted), rowptr, edge_index, edge_cell_shift, src_sorted);
   return nl_status("nqa_neighbor_list_fill_padded");
+}
+
+int64_t nqa_neighbor_list_batched_workspace_bytes(int64_t num_atoms, int64_t num_frames) {
+  if (num_atoms < 0 || num_frames < 1) return -1;
+  int64_t bo, af;
+  return nl_batched_layout(num_atoms, num_frames, &bo, &af).total;
+}
+
+int nqa_neighbor_list_batched_count(const double* pos, const double* cell, const int32_t* pbc, const int64_t* frame_ptr,
+                                    double r_max, int64_t num_atoms, int64_t num_frames, void* workspace,
+                                    int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream) {
+  if (num_atoms < 0 || num_frames < 1 || num_frames > 2147483647LL || num_atoms + 8 * num_frames > 2147483646LL ||
+      !(r_max > 0.0) || !rowptr || !status || !frame_ptr || (num_atoms > 0 && !pos)) {
+    set_error("nqa_neighbor_list_batched_count: invalid argument");
+    return NQA_ERR_INVALID;
+  }
+  int64_t o_bin_off, o_atom_frame;
+  const NLLayout L = nl_batched_layout(num_atoms, num_frames, &o_bin_off, &o_atom_frame);
+  if (!workspace || workspace_bytes < L.total) {
+    set_error("nqa_neighbor_list_batched_count: workspace missing or too small");
+    return NQA_ERR_WORKSPACE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* w = static_cast<char*>(workspace);
+  const int64_t N = num_atoms, F = num_frames, B = N + 8 * F;
+  NLHeader* hdr = reinterpret_cast<NLHeader*>(w + L.header);
+  int32_t* bin_off = reinterpret_cast<int32_t*>(w + o_bin_off);
+  int32_t* atom_frame = reinterpret_cast<int32_t*>(w + o_atom_frame);
+  double* sfrac = reinterpret_cast<double*>(w + L.sfrac);
+  int32_t* ioff = reinterpret_cast<int32_t*>(w + L.ioff);
+  int32_t* key = reinterpret_cast<int32_t*>(w + L.key);
+  int32_t* val = reinterpret_cast<int32_t*>(w + L.val);
+  int32_t* bin_count = reinterpret_cast<int32_t*>(w + L.bin_count);
+  int32_t* rowptr_bin = reinterpret_cast<int32_t*>(w + L.rowptr_bin);
+  int32_t* atom_sorted = reinterpret_cast<int32_t*>(w + L.atom_sorted);
+  int32_t* atom_arrival = reinterpret_cast<int32_t*>(w + L.dummy_other);
+  double* s_sorted = reinterpret_cast<double*>(w + L.s_sorted);
+  int32_t* o_sorted = reinterpret_cast<int32_t*>(w + L.o_sorted);
+  int32_t* counts = reinterpret_cast<int32_t*>(w + L.counts);
+  if (hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return nl_status("nqa_neighbor_list_batched_count");
+  hipLaunchKernelGGL(nl_batched_plan_kernel, dim3((unsigned)F), dim3(256), 0, s, pos, cell, pbc, frame_ptr, r_max, N, F, hdr,
+                     bin_off, bin_count, status);
+  if (N > 0) {
+    const unsigned g256 = (unsigned)((N + 255) / 256);
+    hipLaunchKernelGGL(nl_batched_bin_kernel, dim3(g256), dim3(256), 0, s, pos, frame_ptr, N, F, hdr, bin_off, atom_frame, sfrac,
+                       ioff, key, val, bin_count);
+    hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, B, bin_count, rowptr_bin, (int32_t*)nullptr);
+    hipLaunchKernelGGL(nl_place_kernel, dim3(g256), dim3(256), 0, s, N, key, val, rowptr_bin, atom_arrival);
+    hipLaunchKernelGGL(nl_order_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, B, rowptr_bin, atom_arrival, sfrac,
+                       ioff, atom_sorted, s_sorted, o_sorted);
+    hipLaunchKernelGGL(nl_batched_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, hdr, bin_off, atom_frame,
+                       sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, counts);
+  }
+  hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, N, counts, rowptr, status);  // status |= 1 on overflow
+  return nl_status("nqa_neighbor_list_batched_count");
+}
+
+int nqa_neighbor_list_batched_fill(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t num_frames,
+                                   int64_t num_edges, int64_t* edge_index, double* edge_cell_shift, nqa_stream stream) {
+  if (num_atoms < 0 || num_frames < 1 || num_edges < 0 || !workspace || !rowptr ||
+      (num_edges > 0 && (!edge_index || !edge_cell_shift))) {
+    set_error("nqa_neighbor_list_batched_fill: invalid argument");
+    return NQA_ERR_INVALID;
+  }
+  if (num_atoms == 0 || num_edges == 0) return NQA_OK;
+  int64_t o_bin_off, o_atom_frame;
+  const NLLayout L = nl_batched_layout(num_atoms, num_frames, &o_bin_off, &o_atom_frame);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const char* w = static_cast<const char*>(workspace);
+  hipLaunchKernelGGL(nl_batched_fill_kernel, dim3((unsigned)((num_atoms + 3) / 4)), dim3(256), 0, s, num_atoms, num_edges,
+                     reinterpret_cast<const NLHeader*>(w + L.header), reinterpret_cast<const int32_t*>(w + o_bin_off),
+                     reinterpret_cast<const int32_t*>(w + o_atom_frame), reinterpret_cast<const double*>(w + L.sfrac),
+                     reinterpret_cast<const int32_t*>(w + L.ioff), reinterpret_cast<const int32_t*>(w + L.rowptr_bin),
+                     reinterpret_cast<const int32_t*>(w + L.atom_sorted), reinterpret_cast<const double*>(w + L.s_sorted),
+                     reinterpret_cast<const int32_t*>(w + L.o_sorted), rowptr, edge_index, edge_cell_shift);
+  return nl_status("nqa_neighbor_list_batched_fill");
 }
 
 }  // extern "C"

@@ -8,14 +8,20 @@ calls matscipy / ASE / vesin, this backend runs a cell-list search on the GPU (`
 ``nequip_amd/csrc/neighbor_list.hip``) with the same pair semantics (``|r| < r_max``, no self pair with zero shift,
 mixed periodicity, cells thinner than the cutoff).  Edges come out grouped by centre atom, so the dst-CSR of the
 tensor-product kernels needs no sort for them.
+
+Batched data goes through ``nqa_neighbor_list_batched_count/fill``: one set of launches and one host read (the edge count)
+for the whole batch, bitwise the same list as the per-frame loop.  ``NQA_NL_PER_FRAME=1`` (read at every call) keeps the
+per-frame loop.
 """
 
 import ctypes
+import os
 from typing import Dict, Final, Optional, Tuple, Union
 
 import torch
 
 from .. import _lib
+from ..utils import ktimer
 from . import AtomicDataDict
 
 NEIGHBORLIST_BACKEND_NEQUIP_AMD: Final[str] = "nequip_amd"
@@ -245,14 +251,103 @@ def _frame_from_batched(data: AtomicDataDict.Type, idx: int, node_offsets) -> At
     return out
 
 
+_BATCHED_STATUS_ERRORS = (
+    (1, RuntimeError, "neighbour list has more than 2^31 - 1 edges"),
+    (2, ValueError, "a lattice vector is zero but the direction is periodic"),
+    (4, ValueError, "cell vectors are linearly dependent"),
+    (8, ValueError, "the frame sizes (num_nodes / batch) do not add up to the number of atoms"),
+    (16, ValueError, "Periodic boundary conditions requested but no cell was provided."),
+)
+
+
+def _batched_frame_count(data: AtomicDataDict.Type) -> int:
+    """Number of frames from shapes alone where the data has them (no host read); ``num_frames`` otherwise."""
+    K = AtomicDataDict
+    if K.NUM_NODES_KEY in data:
+        return data[K.NUM_NODES_KEY].size(0)
+    for key, width in ((K.CELL_KEY, 9), (K.PBC_KEY, 3)):
+        if data.get(key, None) is not None:
+            return data[key].numel() // width
+    return K.num_frames(data)
+
+
+def _frame_ptr(data: AtomicDataDict.Type, num_frames: int, device: torch.device) -> torch.Tensor:
+    """int64 [F + 1] atom offsets of the frames, built on the device: cumsum of ``num_nodes`` or, from ``batch`` (atoms grouped
+    by frame), the first atom of every frame (a search with a known frame count: no host read)."""
+    K = AtomicDataDict
+    ptr = torch.zeros(num_frames + 1, dtype=torch.int64, device=device)
+    if K.NUM_NODES_KEY in data:
+        torch.cumsum(data[K.NUM_NODES_KEY].view(-1).to(device=device, dtype=torch.int64), 0, out=ptr[1:])
+    else:
+        batch = data[K.BATCH_KEY].view(-1).to(device=device, dtype=torch.int64).contiguous()
+        ptr = torch.searchsorted(batch, torch.arange(num_frames + 1, dtype=torch.int64, device=device))
+    return ptr
+
+
+def _compute_neighborlist_batched(pos: torch.Tensor, r_max: float, frame_ptr: torch.Tensor,
+                                  cell: Optional[torch.Tensor] = None, pbc: Optional[torch.Tensor] = None):
+    """``(edge_index [2, E] int64, edge_cell_shift [E, 3], rowptr [N + 1] int32)`` of F frames in one pass: frame f holds the
+    atoms ``frame_ptr[f]:frame_ptr[f + 1]`` with cell ``cell[f]`` ([F, 3, 3] or None) and periodicity ``pbc[f]`` ([F, 3] or
+    None).  Equal to the concatenation of the frames' ``_compute_neighborlist_single_frame`` lists (atom indices offset);
+    reads the edge count and the status word back together: the one synchronisation of the batch."""
+    if not pos.is_cuda:
+        raise RuntimeError("the `nequip_amd` neighbour list runs on the GPU: positions must be a CUDA/HIP tensor")
+    lib = _lib.load()
+    device = pos.device
+    N = pos.shape[0]
+    F = frame_ptr.numel() - 1
+    if F < 1:
+        raise ValueError("a batched neighbour list needs at least one frame")
+    pos64 = pos.detach().to(torch.float64).contiguous()
+    cell64 = None
+    if cell is not None:
+        if cell.numel() != 9 * F:
+            raise ValueError(f"cell of shape {tuple(cell.shape)} for {F} frames: expected [{F}, 3, 3]")
+        cell64 = cell.detach().to(device=device, dtype=torch.float64).reshape(F, 3, 3).contiguous()
+    pbc32 = None
+    if pbc is not None:
+        if pbc.numel() != 3 * F:
+            raise ValueError(f"pbc of shape {tuple(pbc.shape)} for {F} frames: expected [{F}, 3]")
+        pbc32 = pbc.detach().to(device=device, dtype=torch.int32).reshape(F, 3).contiguous()
+    frame_ptr = frame_ptr.to(device=device, dtype=torch.int64).contiguous()
+    ws_bytes = lib.nqa_neighbor_list_batched_workspace_bytes(N, F)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+    aux = torch.empty(N + 2, dtype=torch.int32, device=device)  # rowptr [N + 1] and the status word, read back as one pair
+    rowptr, status = aux[:N + 1], aux[N + 1:]
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    nbytes = 8.0 * (2 * 3 * N + 9 * F) + 4.0 * (8 * N + 3 * F)  # count pass: positions in, grid and row pointer out
+    with torch.cuda.device(device), ktimer.region("nqa_neighbor_list_batched", nbytes):
+        rc = lib.nqa_neighbor_list_batched_count(_ptr(pos64), _ptr(cell64), _ptr(pbc32), _ptr(frame_ptr), float(r_max), N, F,
+                                                 _ptr(ws), ws_bytes, _ptr(rowptr), _ptr(status), stream)
+        _lib.check(rc, "nqa_neighbor_list_batched_count")
+        E, bad = aux[N:].tolist()  # the one synchronisation: the edge count is data dependent
+        for bit, exc, msg in _BATCHED_STATUS_ERRORS:
+            if bad & bit:
+                raise exc(msg)
+        if E < 0:
+            raise RuntimeError("neighbour list has more than 2^31 - 1 edges")
+        edge_index = torch.empty((2, E), dtype=torch.int64, device=device)
+        shifts = torch.empty((E, 3), dtype=torch.float64, device=device)
+        rc = lib.nqa_neighbor_list_batched_fill(_ptr(ws), _ptr(rowptr), N, F, E, _ptr(edge_index), _ptr(shifts), stream)
+        _lib.check(rc, "nqa_neighbor_list_batched_fill")
+    return edge_index, shifts.to(pos.dtype), rowptr
+
+
+def _per_frame_requested() -> bool:
+    return os.environ.get("NQA_NL_PER_FRAME", "") not in ("", "0")
+
+
 def compute_neighborlist_(data: AtomicDataDict.Type, r_max: float,
                           backend: str = DEFAULT_NEIGHBORLIST_BACKEND) -> AtomicDataDict.Type:
-    """Add a neighbour list to ``data`` in place (contract of ``nequip/data/_nl.py:364-381``)."""
+    """Add a neighbour list to ``data`` in place (contract of ``nequip/data/_nl.py:364-381``).  Batched data: one batched list
+    (``NQA_NL_PER_FRAME=1``: one list per frame, concatenated; the same result)."""
     if backend not in NEIGHBORLIST_BACKEND_OPTIONS:
         supported = ", ".join(f"`{b}`" for b in NEIGHBORLIST_BACKEND_OPTIONS)
         raise ValueError(f"Unknown neighborlist backend = `{backend}`. Supported backends: {supported}")
     K = AtomicDataDict
     batched = K.BATCH_KEY in data
+    if batched and not _per_frame_requested():
+        return _compute_neighborlist_batched_(data, r_max)
     nframes = K.num_frames(data)
     if batched:
         counts = data[K.NUM_NODES_KEY].view(-1).cpu().tolist() if K.NUM_NODES_KEY in data else torch.bincount(
@@ -291,6 +386,22 @@ def compute_neighborlist_(data: AtomicDataDict.Type, r_max: float,
     topology_cache.hint_sorted(data[K.EDGE_INDEX_KEY], rowptr)
     if has_cell:
         data[K.EDGE_CELL_SHIFT_KEY] = torch.cat(shifts, dim=0) if len(shifts) > 1 else shifts[0]
+    return data
+
+
+def _compute_neighborlist_batched_(data: AtomicDataDict.Type, r_max: float) -> AtomicDataDict.Type:
+    K = AtomicDataDict
+    pos = data[K.POSITIONS_KEY]
+    F = _batched_frame_count(data)
+    frame_ptr = _frame_ptr(data, F, pos.device)
+    cell = data.get(K.CELL_KEY, None)
+    edge_index, shifts, rowptr = _compute_neighborlist_batched(pos, r_max, frame_ptr, cell=cell, pbc=data.get(K.PBC_KEY, None))
+    data[K.EDGE_INDEX_KEY] = edge_index
+    from ..nn._topology import topology_cache
+
+    topology_cache.hint_sorted(edge_index, rowptr)
+    if cell is not None:
+        data[K.EDGE_CELL_SHIFT_KEY] = shifts
     return data
 
 
