@@ -726,6 +726,47 @@ int nqa_neighbor_list_batched_count(const double* pos, const double* cell, const
                                     int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream);
 int nqa_neighbor_list_batched_fill(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t num_frames,
                                    int64_t num_edges, int64_t* edge_index, double* edge_cell_shift, nqa_stream stream);
+/* Typed variants: per-edge-type cutoffs (nequip/data/transforms/neighborlist.py:9-117 prunes a finished list on the host; here
+ *   the pruning is part of the search).  atom_types int64 [N] (device), cutoff_table float64 [T,T] (device, row-major
+ *   (centre type, neighbour type): the table EdgeLengthNormalizer indexes with type[edge_index[0]] * T + type[edge_index[1]]),
+ *   1 <= T <= 32768.  The edge (i <- j, S) is kept iff  r2 < r_max^2  and  r2 <= cutoff_table[type_i][type_j]^2  (`<=` as the
+ *   reference's norm_length <= 1; the squares are formed once per call, on the device).  Everything else is the contract of the
+ *   untyped entry point of the same name: the grid is the r_max grid, so the result is bitwise the untyped list with the
+ *   dropped edges removed -- same grouping by centre atom, same order within an atom, rowptr = the dst-CSR row pointer of the
+ *   PRUNED list, batched = concatenation of the typed single-frame lists.  A symmetric table keeps the list symmetric (both
+ *   directions of a pair see the same r2); an asymmetric table legitimately does not.
+ *   The caller checks the table on the host (entries positive and <= r_max); the kernels do not.
+ *   Workspace: nqa_neighbor_list_typed_workspace_bytes(N, T) / nqa_neighbor_list_batched_typed_workspace_bytes(N, F, T) -- the
+ *   untyped workspace followed by the neighbour types in bin order (int32 [N], read coalesced by the walk) and the squared
+ *   table; the untyped queries return what they always did.
+ *   An atom type outside [0, T) never indexes outside the table (it is replaced by 0) and is reported as bit 5 (value 32) of
+ *   `status`: int32[1] (device, zeroed first) for the single-frame count, where bit 0 also reports more than 2^31 - 1 edges;
+ *   the sixth bit of the batched status word next to the five above.  Place it behind rowptr[N] and read both in one copy.
+ *   symmetrise != 0 (single-frame count): prune by max(rc[a][b], rc[b][a]) instead.  The capacity-padded form needs an even
+ *   number of free slots, i.e. a symmetric list, so nqa_neighbor_list_fill_padded_typed must follow a count with symmetrise
+ *   = 1; the few extra edges of an asymmetric table lie beyond their own type cutoff and are zeroed by the model like every
+ *   edge outside its cutoff.  Padding edges are longer than r_max, hence beyond every type cutoff: unchanged.
+ *   The fill calls take the same atom_types and num_types as the count. */
+int64_t nqa_neighbor_list_typed_workspace_bytes(int64_t num_atoms, int64_t num_types);
+int nqa_neighbor_list_count_typed(const double* pos, const double* cell, const int32_t* pbc, double r_max,
+                                  const int64_t* atom_types, const double* cutoff_table, int64_t num_types, int32_t symmetrise,
+                                  int64_t num_atoms, void* workspace, int64_t workspace_bytes, int32_t* rowptr, int32_t* status,
+                                  nqa_stream stream);
+int nqa_neighbor_list_fill_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types, int64_t num_atoms,
+                                 int64_t num_types, int64_t num_edges, int64_t* edge_index, double* edge_cell_shift,
+                                 nqa_stream stream);
+int nqa_neighbor_list_fill_padded_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types,
+                                        int64_t num_atoms, int64_t num_types, int64_t edge_capacity, int32_t* rowptr_padded,
+                                        int64_t* edge_index, double* edge_cell_shift, int32_t* src_sorted, int32_t* status,
+                                        nqa_stream stream);
+int64_t nqa_neighbor_list_batched_typed_workspace_bytes(int64_t num_atoms, int64_t num_frames, int64_t num_types);
+int nqa_neighbor_list_batched_count_typed(const double* pos, const double* cell, const int32_t* pbc, const int64_t* frame_ptr,
+                                          double r_max, const int64_t* atom_types, const double* cutoff_table,
+                                          int64_t num_types, int64_t num_atoms, int64_t num_frames, void* workspace,
+                                          int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream);
+int nqa_neighbor_list_batched_fill_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types,
+                                         int64_t num_atoms, int64_t num_frames, int64_t num_types, int64_t num_edges,
+                                         int64_t* edge_index, double* edge_cell_shift, nqa_stream stream);
 
 #ifdef __cplusplus
 }

@@ -278,6 +278,25 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     ),
     "nqa_neighbor_list_batched_fill": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nqa_neighbor_list_typed_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "nqa_neighbor_list_count_typed": (
+        c_int32,
+        [c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int64, c_void_p,
+         c_void_p, c_void_p],
+    ),
+    "nqa_neighbor_list_fill_typed": (
+        c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nqa_neighbor_list_fill_padded_typed": (
+        c_int32,
+        [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nqa_neighbor_list_batched_typed_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "nqa_neighbor_list_batched_count_typed": (
+        c_int32,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64,
+         c_void_p, c_void_p, c_void_p],
+    ),
+    "nqa_neighbor_list_batched_fill_typed": (
+        c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "nqa_gate": (
         c_int32,
         [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p],

@@ -293,13 +293,19 @@ __global__ __launch_bounds__(256) void nl_order_kernel(int64_t B, const int32_t*
 // bin are tested 64 at a time, one per lane; a hit's position in the atom's edge row is the number of hits before it (ballot +
 // population count), i.e. exactly the order in which a single thread walking the same bins would emit them.
 // FILL == false: returns the number of neighbours of atom i (the same value in every lane).
-template <bool FILL>
+// TYPED: a candidate must also lie within the cutoff of its (centre type, neighbour type) pair, r2 <= rc2_row[type_j]: the test
+// is part of the one `hit` expression, so count and fill agree and the typed list is the untyped one with edges removed.
+// rc2_row = the centre type's row of squared cutoffs (wavefront-uniform), type_sorted = neighbour types in bin order, both
+// already forced into range by nl_typed_prep_kernel.
+template <bool FILL, bool TYPED = false>
 __device__ __forceinline__ int nl_walk(int64_t i, int lane, const NLHeader* __restrict__ h, const double* __restrict__ sfrac,
                                        const int32_t* __restrict__ ioff, const int32_t* __restrict__ rowptr_bin,
                                        const int32_t* __restrict__ atom_sorted, const double* __restrict__ s_sorted,
                                        const int32_t* __restrict__ o_sorted, int64_t base, int64_t E,
                                        int64_t* __restrict__ edge_index, double* __restrict__ shift,
-                                       int32_t* __restrict__ src32 = nullptr) {
+                                       int32_t* __restrict__ src32 = nullptr,
+                                       const int32_t* __restrict__ type_sorted = nullptr,
+                                       const double* __restrict__ rc2_row = nullptr) {
   const double si[3] = {sfrac[3 * i], sfrac[3 * i + 1], sfrac[3 * i + 2]};
   const int oi[3] = {ioff[3 * i], ioff[3 * i + 1], ioff[3 * i + 2]};
   int bi[3];
@@ -357,6 +363,7 @@ __device__ __forceinline__ int nl_walk(int64_t i, int lane, const NLHeader* __re
             const double r2 = rx * rx + ry * ry + rz * rz;
             j = atom_sorted[k];
             hit = (r2 < h->rmax2) && !(j == i && nx == 0 && ny == 0 && nz == 0);
+            if (TYPED) hit = hit && r2 <= rc2_row[type_sorted[k]];
           }
           const uint64_t m = __builtin_amdgcn_ballot_w64(hit);
           if (FILL && hit) {
@@ -517,6 +524,7 @@ enum : int32_t {
   NL_BAD_DEPENDENT = 4,       // linearly dependent lattice vectors
   NL_BAD_FRAME_PTR = 8,       // frame_ptr is not a partition of [0, N)
   NL_BAD_PERIODIC_NO_CELL = 16,
+  NL_BAD_TYPE = 32,           // typed lists: an atom type outside [0, num_types)
 };
 
 static NLLayout nl_batched_layout(int64_t N, int64_t F, int64_t* bin_off, int64_t* atom_frame) {
@@ -755,6 +763,132 @@ __global__ __launch_bounds__(256) void nl_batched_fill_kernel(int64_t N, int64_t
                 rowptr[i], E, edge_index, shift);
 }
 
+// ---- typed lists: per-(centre type, neighbour type) cutoffs ------------------------------------------------------------------
+// The typed entry points run the untyped pipeline (plan, bin, order: the grid is the r_max grid, so the candidate order is that
+// of the untyped list) and then walk with the extra test r2 <= rc[type_i][type_j]^2.  Their workspace is the untyped one
+// followed by type_sorted int32 [N] (the type of atom_sorted[k]: read coalesced by the walk, next to s_sorted) and rc2
+// float64 [T, T] (squared cutoffs, formed once).
+struct NLTypedExt {
+  int64_t type_sorted, rc2, total;
+};
+static NLTypedExt nl_typed_ext(int64_t base_total, int64_t N, int64_t T) {
+  NLTypedExt X{};
+  X.type_sorted = align256(base_total);
+  X.rc2 = align256(X.type_sorted + N * 4);
+  X.total = align256(X.rc2 + T * T * 8);
+  return X;
+}
+
+// rc2 = cutoff_table^2 (symmetrise: of max(rc[a][b], rc[b][a])) and type_sorted[k] = type of atom_sorted[k].  A type outside
+// [0, T) is reported through `status` and replaced by 0, so that no walk ever indexes outside the table.
+__global__ __launch_bounds__(256) void nl_typed_prep_kernel(int64_t N, int64_t T, const int64_t* __restrict__ atom_types,
+                                                            const double* __restrict__ cutoff_table, int32_t symmetrise,
+                                                            const int32_t* __restrict__ atom_sorted,
+                                                            int32_t* __restrict__ type_sorted, double* __restrict__ rc2,
+                                                            int32_t* __restrict__ status) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k < T * T) {
+    double rc = cutoff_table[k];
+    if (symmetrise) rc = fmax(rc, cutoff_table[(k % T) * T + k / T]);
+    rc2[k] = rc * rc;
+  }
+  if (k < N) {
+    int64_t t = atom_types[atom_sorted[k]];
+    if (t < 0 || t >= T) {
+      atomicOr(status, NL_BAD_TYPE);
+      t = 0;
+    }
+    type_sorted[k] = (int32_t)t;
+  }
+}
+
+__device__ __forceinline__ const double* nl_rc2_row(const double* __restrict__ rc2, const int64_t* __restrict__ atom_types,
+                                                    int64_t i, int64_t T) {
+  int64_t t = atom_types[i];
+  t = (t < 0 || t >= T) ? 0 : t;  // (reported by nl_typed_prep_kernel)
+  const int ti = __builtin_amdgcn_readfirstlane((int)t);
+  return rc2 + (int64_t)ti * T;
+}
+
+// atom_frame == nullptr: one frame (hdr, rowptr_bin as they are); otherwise the batched walk on the atom's frame.
+__global__ __launch_bounds__(256) void nl_typed_count_kernel(int64_t N, const NLHeader* __restrict__ hdr,
+                                                             const int32_t* __restrict__ bin_off,
+                                                             const int32_t* __restrict__ atom_frame,
+                                                             const double* __restrict__ sfrac, const int32_t* __restrict__ ioff,
+                                                             const int32_t* __restrict__ rowptr_bin,
+                                                             const int32_t* __restrict__ atom_sorted,
+                                                             const double* __restrict__ s_sorted,
+                                                             const int32_t* __restrict__ o_sorted,
+                                                             const int64_t* __restrict__ atom_types, int64_t T,
+                                                             const int32_t* __restrict__ type_sorted,
+                                                             const double* __restrict__ rc2, int32_t* __restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // one wavefront per atom
+  if (i >= N) return;
+  const int lane = threadIdx.x & 63;
+  if (atom_frame != nullptr) {
+    const int f = __builtin_amdgcn_readfirstlane(atom_frame[i]);
+    hdr += f;
+    rowptr_bin += bin_off[f];
+  }
+  const int cnt = nl_walk<false, true>(i, lane, hdr, sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, 0, 0, nullptr,
+                                       nullptr, nullptr, type_sorted, nl_rc2_row(rc2, atom_types, i, T));
+  if (lane == 0) counts[i] = cnt;
+}
+
+__global__ __launch_bounds__(256) void nl_typed_fill_kernel(int64_t N, int64_t E, const NLHeader* __restrict__ hdr,
+                                                            const int32_t* __restrict__ bin_off,
+                                                            const int32_t* __restrict__ atom_frame,
+                                                            const double* __restrict__ sfrac, const int32_t* __restrict__ ioff,
+                                                            const int32_t* __restrict__ rowptr_bin,
+                                                            const int32_t* __restrict__ atom_sorted,
+                                                            const double* __restrict__ s_sorted,
+                                                            const int32_t* __restrict__ o_sorted,
+                                                            const int64_t* __restrict__ atom_types, int64_t T,
+                                                            const int32_t* __restrict__ type_sorted,
+                                                            const double* __restrict__ rc2, const int32_t* __restrict__ rowptr,
+                                                            int64_t* __restrict__ edge_index, double* __restrict__ shift) {
+  const int64_t i = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // one wavefront per atom
+  if (i >= N) return;
+  if (atom_frame != nullptr) {
+    const int f = __builtin_amdgcn_readfirstlane(atom_frame[i]);
+    hdr += f;
+    rowptr_bin += bin_off[f];
+  }
+  nl_walk<true, true>(i, (int)(threadIdx.x & 63), hdr, sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, rowptr[i], E,
+                      edge_index, shift, nullptr, type_sorted, nl_rc2_row(rc2, atom_types, i, T));
+}
+
+// nl_fill_padded_kernel with the typed walk (the padding edges are longer than r_max, hence beyond every type cutoff); its own
+// copy of the kernel, padding loop included, so that the untyped kernel's text stays what it was.
+__global__ __launch_bounds__(256) void nl_typed_fill_padded_kernel(
+    int64_t N, int64_t E_cap, const NLHeader* __restrict__ h, const double* __restrict__ sfrac, const int32_t* __restrict__ ioff,
+    const int32_t* __restrict__ rowptr_bin, const int32_t* __restrict__ atom_sorted, const double* __restrict__ s_sorted,
+    const int32_t* __restrict__ o_sorted, const int64_t* __restrict__ atom_types, int64_t T,
+    const int32_t* __restrict__ type_sorted, const double* __restrict__ rc2, const int32_t* __restrict__ rowptr,
+    int64_t* __restrict__ edge_index, double* __restrict__ shift, int32_t* __restrict__ src32) {
+  const int64_t i = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // one wavefront per atom
+  if (i >= N) return;
+  const int lane = threadIdx.x & 63;
+  const NLPadPlan p = nl_pad_plan(rowptr, N, E_cap);
+  const int64_t base = (p.bad ? 0 : (int64_t)rowptr[i]) + nl_pads_before(p, i);
+  int cnt = 0;
+  if (!p.bad)
+    cnt = nl_walk<true, true>(i, lane, h, sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, base, E_cap, edge_index,
+                              shift, src32, type_sorted, nl_rc2_row(rc2, atom_types, i, T));
+  const int64_t npad = p.q + (i < p.rem ? 1 : 0);
+  const int axis = h->pad_axis;
+  for (int64_t t = lane; t < npad; t += 64) {
+    const double k = (double)(h->pad_k0 + t);
+    for (int sgn = 0; sgn < 2; ++sgn) {
+      const int64_t e = base + cnt + 2 * t + sgn;
+      edge_index[e] = i;
+      edge_index[E_cap + e] = i;
+      if (src32 != nullptr) src32[e] = (int32_t)i;
+      for (int d = 0; d < 3; ++d) shift[3 * e + d] = d == axis ? (sgn ? -k : k) : 0.0;
+    }
+  }
+}
+
 static int nl_status(const char* fn) {
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) {
@@ -775,15 +909,31 @@ int64_t nqa_neighbor_list_workspace_bytes(int64_t num_atoms) {
   return nl_layout(num_atoms).total;
 }
 
-int nqa_neighbor_list_count(const double* pos, const double* cell, const int32_t* pbc, double r_max, int64_t num_atoms,
-                            void* workspace, int64_t workspace_bytes, int32_t* rowptr, nqa_stream stream) {
-  if (num_atoms < 0 || !(r_max > 0.0) || !rowptr || (num_atoms > 0 && !pos)) {
-    set_error("nqa_neighbor_list_count: invalid argument");
+// Typed operands of a count (nullptr: the untyped list).
+struct NLTyped {
+  const int64_t* atom_types;
+  const double* cutoff_table;
+  int64_t T;
+  int32_t symmetrise;
+  int32_t* status;
+};
+
+static bool nl_typed_args_ok(const int64_t* atom_types, const double* cutoff_table, int64_t num_types, int64_t num_atoms) {
+  return cutoff_table != nullptr && num_types >= 1 && num_types <= 32768 && (num_atoms == 0 || atom_types != nullptr);
+}
+
+static int nl_count_impl(const char* fn, const double* pos, const double* cell, const int32_t* pbc, double r_max,
+                         int64_t num_atoms, void* workspace, int64_t workspace_bytes, int32_t* rowptr, nqa_stream stream,
+                         const NLTyped* ty) {
+  if (num_atoms < 0 || !(r_max > 0.0) || !rowptr || (num_atoms > 0 && !pos) ||
+      (ty != nullptr && (!ty->status || !nl_typed_args_ok(ty->atom_types, ty->cutoff_table, ty->T, num_atoms)))) {
+    set_error(std::string(fn) + ": invalid argument");
     return NQA_ERR_INVALID;
   }
   const NLLayout L = nl_layout(num_atoms);
-  if (!workspace || workspace_bytes < L.total) {
-    set_error("nqa_neighbor_list_count: workspace missing or too small");
+  const NLTypedExt X = nl_typed_ext(L.total, num_atoms, ty ? ty->T : 0);
+  if (!workspace || workspace_bytes < (ty ? X.total : L.total)) {
+    set_error(std::string(fn) + ": workspace missing or too small");
     return NQA_ERR_WORKSPACE;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -809,11 +959,94 @@ int nqa_neighbor_list_count(const double* pos, const double* cell, const int32_t
     hipLaunchKernelGGL(nl_place_kernel, dim3(g256), dim3(256), 0, s, N, key, val, rowptr_bin, atom_arrival);
     hipLaunchKernelGGL(nl_order_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, B, rowptr_bin, atom_arrival, sfrac,
                        ioff, atom_sorted, s_sorted, o_sorted);
-    hipLaunchKernelGGL(nl_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, h, sfrac, ioff,
-                       rowptr_bin, atom_sorted, s_sorted, o_sorted, counts);
+    if (ty == nullptr) {
+      hipLaunchKernelGGL(nl_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, h, sfrac, ioff,
+                         rowptr_bin, atom_sorted, s_sorted, o_sorted, counts);
+    } else {
+      int32_t* type_sorted = reinterpret_cast<int32_t*>(w + X.type_sorted);
+      double* rc2 = reinterpret_cast<double*>(w + X.rc2);
+      const int64_t n = N > ty->T * ty->T ? N : ty->T * ty->T;
+      hipLaunchKernelGGL(nl_typed_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, N, ty->T, ty->atom_types,
+                         ty->cutoff_table, ty->symmetrise, atom_sorted, type_sorted, rc2, ty->status);
+      hipLaunchKernelGGL(nl_typed_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, h, (const int32_t*)nullptr,
+                         (const int32_t*)nullptr, sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, ty->atom_types,
+                         ty->T, type_sorted, rc2, counts);
+    }
   }
-  hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, N, counts, rowptr, (int32_t*)nullptr);
-  return nl_status("nqa_neighbor_list_count");
+  hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, N, counts, rowptr, ty ? ty->status : (int32_t*)nullptr);
+  return nl_status(fn);
+}
+
+int nqa_neighbor_list_count(const double* pos, const double* cell, const int32_t* pbc, double r_max, int64_t num_atoms,
+                            void* workspace, int64_t workspace_bytes, int32_t* rowptr, nqa_stream stream) {
+  return nl_count_impl("nqa_neighbor_list_count", pos, cell, pbc, r_max, num_atoms, workspace, workspace_bytes, rowptr, stream,
+                       nullptr);
+}
+
+int64_t nqa_neighbor_list_typed_workspace_bytes(int64_t num_atoms, int64_t num_types) {
+  if (num_atoms < 0 || num_types < 1 || num_types > 32768) return -1;
+  return nl_typed_ext(nl_layout(num_atoms).total, num_atoms, num_types).total;
+}
+
+int nqa_neighbor_list_count_typed(const double* pos, const double* cell, const int32_t* pbc, double r_max,
+                                  const int64_t* atom_types, const double* cutoff_table, int64_t num_types, int32_t symmetrise,
+                                  int64_t num_atoms, void* workspace, int64_t workspace_bytes, int32_t* rowptr, int32_t* status,
+                                  nqa_stream stream) {
+  const NLTyped ty{atom_types, cutoff_table, num_types, symmetrise, status};
+  if (status != nullptr &&
+      hipMemsetAsync(status, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)) != hipSuccess)
+    return nl_status("nqa_neighbor_list_count_typed");
+  return nl_count_impl("nqa_neighbor_list_count_typed", pos, cell, pbc, r_max, num_atoms, workspace, workspace_bytes, rowptr,
+                       stream, &ty);
+}
+
+int nqa_neighbor_list_fill_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types, int64_t num_atoms,
+                                 int64_t num_types, int64_t num_edges, int64_t* edge_index, double* edge_cell_shift,
+                                 nqa_stream stream) {
+  if (num_atoms < 0 || num_edges < 0 || !workspace || !rowptr || num_types < 1 || num_types > 32768 ||
+      (num_atoms > 0 && !atom_types) || (num_edges > 0 && (!edge_index || !edge_cell_shift))) {
+    set_error("nqa_neighbor_list_fill_typed: invalid argument");
+    return NQA_ERR_INVALID;
+  }
+  if (num_atoms == 0 || num_edges == 0) return NQA_OK;
+  const NLLayout L = nl_layout(num_atoms);
+  const NLTypedExt X = nl_typed_ext(L.total, num_atoms, num_types);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const char* w = static_cast<const char*>(workspace);
+  hipLaunchKernelGGL(nl_typed_fill_kernel, dim3((unsigned)((num_atoms + 3) / 4)), dim3(256), 0, s, num_atoms, num_edges,
+                     reinterpret_cast<const NLHeader*>(w + L.header), (const int32_t*)nullptr, (const int32_t*)nullptr,
+                     reinterpret_cast<const double*>(w + L.sfrac), reinterpret_cast<const int32_t*>(w + L.ioff),
+                     reinterpret_cast<const int32_t*>(w + L.rowptr_bin), reinterpret_cast<const int32_t*>(w + L.atom_sorted),
+                     reinterpret_cast<const double*>(w + L.s_sorted), reinterpret_cast<const int32_t*>(w + L.o_sorted),
+                     atom_types, num_types, reinterpret_cast<const int32_t*>(w + X.type_sorted),
+                     reinterpret_cast<const double*>(w + X.rc2), rowptr, edge_index, edge_cell_shift);
+  return nl_status("nqa_neighbor_list_fill_typed");
+}
+
+int nqa_neighbor_list_fill_padded_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types,
+                                        int64_t num_atoms, int64_t num_types, int64_t edge_capacity, int32_t* rowptr_padded,
+                                        int64_t* edge_index, double* edge_cell_shift, int32_t* src_sorted, int32_t* status,
+                                        nqa_stream stream) {
+  if (num_atoms <= 0 || edge_capacity < 0 || (edge_capacity & 1) != 0 || edge_capacity > 2147483646LL || !workspace ||
+      !rowptr || !rowptr_padded || !atom_types || num_types < 1 || num_types > 32768 ||
+      (edge_capacity > 0 && (!edge_index || !edge_cell_shift))) {
+    set_error("nqa_neighbor_list_fill_padded_typed: invalid argument (needs atoms, types and an even capacity below 2^31)");
+    return NQA_ERR_INVALID;
+  }
+  const NLLayout L = nl_layout(num_atoms);
+  const NLTypedExt X = nl_typed_ext(L.total, num_atoms, num_types);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const char* w = static_cast<const char*>(workspace);
+  hipLaunchKernelGGL(nl_pad_rowptr_kernel, dim3((unsigned)((num_atoms + 1 + 255) / 256)), dim3(256), 0, s, num_atoms,
+                     edge_capacity, rowptr, rowptr_padded, status);
+  hipLaunchKernelGGL(nl_typed_fill_padded_kernel, dim3((unsigned)((num_atoms + 3) / 4)), dim3(256), 0, s, num_atoms,
+                     edge_capacity, reinterpret_cast<const NLHeader*>(w + L.header),
+                     reinterpret_cast<const double*>(w + L.sfrac), reinterpret_cast<const int32_t*>(w + L.ioff),
+                     reinterpret_cast<const int32_t*>(w + L.rowptr_bin), reinterpret_cast<const int32_t*>(w + L.atom_sorted),
+                     reinterpret_cast<const double*>(w + L.s_sorted), reinterpret_cast<const int32_t*>(w + L.o_sorted),
+                     atom_types, num_types, reinterpret_cast<const int32_t*>(w + X.type_sorted),
+                     reinterpret_cast<const double*>(w + X.rc2), rowptr, edge_index, edge_cell_shift, src_sorted);
+  return nl_status("nqa_neighbor_list_fill_padded_typed");
 }
 
 int nqa_neighbor_list_fill(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t num_edges,
@@ -862,18 +1095,21 @@ int64_t nqa_neighbor_list_batched_workspace_bytes(int64_t num_atoms, int64_t num
   return nl_batched_layout(num_atoms, num_frames, &bo, &af).total;
 }
 
-int nqa_neighbor_list_batched_count(const double* pos, const double* cell, const int32_t* pbc, const int64_t* frame_ptr,
-                                    double r_max, int64_t num_atoms, int64_t num_frames, void* workspace,
-                                    int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream) {
+static int nl_batched_count_impl(const char* fn, const double* pos, const double* cell, const int32_t* pbc,
+                                 const int64_t* frame_ptr, double r_max, int64_t num_atoms, int64_t num_frames,
+                                 void* workspace, int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream,
+                                 const NLTyped* ty) {
   if (num_atoms < 0 || num_frames < 1 || num_frames > 2147483647LL || num_atoms + 8 * num_frames > 2147483646LL ||
-      !(r_max > 0.0) || !rowptr || !status || !frame_ptr || (num_atoms > 0 && !pos)) {
-    set_error("nqa_neighbor_list_batched_count: invalid argument");
+      !(r_max > 0.0) || !rowptr || !status || !frame_ptr || (num_atoms > 0 && !pos) ||
+      (ty != nullptr && !nl_typed_args_ok(ty->atom_types, ty->cutoff_table, ty->T, num_atoms))) {
+    set_error(std::string(fn) + ": invalid argument");
     return NQA_ERR_INVALID;
   }
   int64_t o_bin_off, o_atom_frame;
   const NLLayout L = nl_batched_layout(num_atoms, num_frames, &o_bin_off, &o_atom_frame);
-  if (!workspace || workspace_bytes < L.total) {
-    set_error("nqa_neighbor_list_batched_count: workspace missing or too small");
+  const NLTypedExt X = nl_typed_ext(L.total, num_atoms, ty ? ty->T : 0);
+  if (!workspace || workspace_bytes < (ty ? X.total : L.total)) {
+    set_error(std::string(fn) + ": workspace missing or too small");
     return NQA_ERR_WORKSPACE;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -893,7 +1129,7 @@ int nqa_neighbor_list_batched_count(const double* pos, const double* cell, const
   double* s_sorted = reinterpret_cast<double*>(w + L.s_sorted);
   int32_t* o_sorted = reinterpret_cast<int32_t*>(w + L.o_sorted);
   int32_t* counts = reinterpret_cast<int32_t*>(w + L.counts);
-  if (hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return nl_status("nqa_neighbor_list_batched_count");
+  if (hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return nl_status(fn);
   hipLaunchKernelGGL(nl_batched_plan_kernel, dim3((unsigned)F), dim3(256), 0, s, pos, cell, pbc, frame_ptr, r_max, N, F, hdr,
                      bin_off, bin_count, status);
   if (N > 0) {
@@ -904,11 +1140,69 @@ int nqa_neighbor_list_batched_count(const double* pos, const double* cell, const
     hipLaunchKernelGGL(nl_place_kernel, dim3(g256), dim3(256), 0, s, N, key, val, rowptr_bin, atom_arrival);
     hipLaunchKernelGGL(nl_order_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, B, rowptr_bin, atom_arrival, sfrac,
                        ioff, atom_sorted, s_sorted, o_sorted);
-    hipLaunchKernelGGL(nl_batched_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, hdr, bin_off, atom_frame,
-                       sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, counts);
+    if (ty == nullptr) {
+      hipLaunchKernelGGL(nl_batched_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, hdr, bin_off, atom_frame,
+                         sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, counts);
+    } else {
+      int32_t* type_sorted = reinterpret_cast<int32_t*>(w + X.type_sorted);
+      double* rc2 = reinterpret_cast<double*>(w + X.rc2);
+      const int64_t n = N > ty->T * ty->T ? N : ty->T * ty->T;
+      hipLaunchKernelGGL(nl_typed_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, N, ty->T, ty->atom_types,
+                         ty->cutoff_table, ty->symmetrise, atom_sorted, type_sorted, rc2, status);
+      hipLaunchKernelGGL(nl_typed_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, hdr, bin_off, atom_frame,
+                         sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, ty->atom_types, ty->T, type_sorted, rc2,
+                         counts);
+    }
   }
   hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, N, counts, rowptr, status);  // status |= 1 on overflow
-  return nl_status("nqa_neighbor_list_batched_count");
+  return nl_status(fn);
+}
+
+int nqa_neighbor_list_batched_count(const double* pos, const double* cell, const int32_t* pbc, const int64_t* frame_ptr,
+                                    double r_max, int64_t num_atoms, int64_t num_frames, void* workspace,
+                                    int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream) {
+  return nl_batched_count_impl("nqa_neighbor_list_batched_count", pos, cell, pbc, frame_ptr, r_max, num_atoms, num_frames,
+                               workspace, workspace_bytes, rowptr, status, stream, nullptr);
+}
+
+int64_t nqa_neighbor_list_batched_typed_workspace_bytes(int64_t num_atoms, int64_t num_frames, int64_t num_types) {
+  if (num_atoms < 0 || num_frames < 1 || num_types < 1 || num_types > 32768) return -1;
+  int64_t bo, af;
+  return nl_typed_ext(nl_batched_layout(num_atoms, num_frames, &bo, &af).total, num_atoms, num_types).total;
+}
+
+int nqa_neighbor_list_batched_count_typed(const double* pos, const double* cell, const int32_t* pbc, const int64_t* frame_ptr,
+                                          double r_max, const int64_t* atom_types, const double* cutoff_table,
+                                          int64_t num_types, int64_t num_atoms, int64_t num_frames, void* workspace,
+                                          int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream) {
+  const NLTyped ty{atom_types, cutoff_table, num_types, 0, status};
+  return nl_batched_count_impl("nqa_neighbor_list_batched_count_typed", pos, cell, pbc, frame_ptr, r_max, num_atoms, num_frames,
+                               workspace, workspace_bytes, rowptr, status, stream, &ty);
+}
+
+int nqa_neighbor_list_batched_fill_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types,
+                                         int64_t num_atoms, int64_t num_frames, int64_t num_types, int64_t num_edges,
+                                         int64_t* edge_index, double* edge_cell_shift, nqa_stream stream) {
+  if (num_atoms < 0 || num_frames < 1 || num_edges < 0 || !workspace || !rowptr || num_types < 1 || num_types > 32768 ||
+      (num_atoms > 0 && !atom_types) || (num_edges > 0 && (!edge_index || !edge_cell_shift))) {
+    set_error("nqa_neighbor_list_batched_fill_typed: invalid argument");
+    return NQA_ERR_INVALID;
+  }
+  if (num_atoms == 0 || num_edges == 0) return NQA_OK;
+  int64_t o_bin_off, o_atom_frame;
+  const NLLayout L = nl_batched_layout(num_atoms, num_frames, &o_bin_off, &o_atom_frame);
+  const NLTypedExt X = nl_typed_ext(L.total, num_atoms, num_types);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const char* w = static_cast<const char*>(workspace);
+  hipLaunchKernelGGL(nl_typed_fill_kernel, dim3((unsigned)((num_atoms + 3) / 4)), dim3(256), 0, s, num_atoms, num_edges,
+                     reinterpret_cast<const NLHeader*>(w + L.header), reinterpret_cast<const int32_t*>(w + o_bin_off),
+                     reinterpret_cast<const int32_t*>(w + o_atom_frame), reinterpret_cast<const double*>(w + L.sfrac),
+                     reinterpret_cast<const int32_t*>(w + L.ioff), reinterpret_cast<const int32_t*>(w + L.rowptr_bin),
+                     reinterpret_cast<const int32_t*>(w + L.atom_sorted), reinterpret_cast<const double*>(w + L.s_sorted),
+                     reinterpret_cast<const int32_t*>(w + L.o_sorted), atom_types, num_types,
+                     reinterpret_cast<const int32_t*>(w + X.type_sorted), reinterpret_cast<const double*>(w + X.rc2), rowptr,
+                     edge_index, edge_cell_shift);
+  return nl_status("nqa_neighbor_list_batched_fill_typed");
 }
 
 int nqa_neighbor_list_batched_fill(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t num_frames,

@@ -1,8 +1,9 @@
 """Which fields hold one value per frame (mirror of the graph-field part of ``nequip/data/_key_registry.py:24-36,75-145``).
 
 ``NodeTypeEmbed`` accepts only these as categorical graph fields, and ``AtomicDataDict.batched_from_list`` concatenates
-them one row per frame.  ``register_fields(graph_fields=...)`` adds custom ones (the per-node / per-edge / long /
-Cartesian-tensor registries of the reference have no counterpart here).
+them one row per frame.  ``register_fields(graph_fields=...)`` adds custom ones (the per-node / long / Cartesian-tensor
+registries of the reference have no counterpart here).  The per-edge registry (``edge_fields``) names the fields that hold one
+row per edge: what ``NeighborListPruneTransform`` masks together with ``edge_index``.
 """
 
 from typing import Optional, Sequence, Set
@@ -26,10 +27,31 @@ _DEFAULT_GRAPH_FIELDS: Set[str] = {
 }
 _GRAPH_FIELDS: Set[str] = set(_DEFAULT_GRAPH_FIELDS)
 
+# one row per edge (``edge_index`` itself is [2, E] and handled on its own)
+_DEFAULT_EDGE_FIELDS: Set[str] = {
+    _keys.EDGE_CELL_SHIFT_KEY,
+    _keys.EDGE_VECTORS_KEY,
+    _keys.EDGE_LENGTH_KEY,
+    _keys.NORM_LENGTH_KEY,
+    _keys.EDGE_ATTRS_KEY,
+    _keys.EDGE_EMBEDDING_KEY,
+    "edge_features",
+    _keys.EDGE_CUTOFF_KEY,
+    "edge_energy",
+    _keys.EDGE_FORCE_KEY,
+}
+_EDGE_FIELDS: Set[str] = set(_DEFAULT_EDGE_FIELDS)
 
-def register_fields(graph_fields: Optional[Sequence[str]] = None) -> None:
-    """Register custom fields as per-frame (``graph_fields``)."""
+
+def register_fields(graph_fields: Optional[Sequence[str]] = None, edge_fields: Optional[Sequence[str]] = None) -> None:
+    """Register custom fields as per-frame (``graph_fields``) or per-edge (``edge_fields``)."""
     graph_fields = [] if graph_fields is None else graph_fields
+    edge_fields = [] if edge_fields is None else edge_fields
     assert not isinstance(graph_fields, str), (
         "graph_fields must be a sequence of strings, each representing a field name, rather than a single string")
+    assert not isinstance(edge_fields, str), (
+        "edge_fields must be a sequence of strings, each representing a field name, rather than a single string")
+    assert not set(graph_fields) & (set(edge_fields) | _EDGE_FIELDS) and not set(edge_fields) & _GRAPH_FIELDS, (
+        "a field cannot be both per-frame and per-edge")
     _GRAPH_FIELDS.update(graph_fields)
+    _EDGE_FIELDS.update(edge_fields)

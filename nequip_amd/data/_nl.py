@@ -12,11 +12,17 @@ tensor-product kernels needs no sort for them.
 Batched data goes through ``nqa_neighbor_list_batched_count/fill``: one set of launches and one host read (the edge count)
 for the whole batch, bitwise the same list as the per-frame loop.  ``NQA_NL_PER_FRAME=1`` (read at every call) keeps the
 per-frame loop.
+
+``per_edge_type_cutoff`` (a dict as the model builders take it, with ``type_names``; a ``[T, T]`` tensor, rows = centre type; or
+a ``CutoffTable``) makes every form of the list typed: the edge ``i <- j`` is kept iff ``r < r_max`` and
+``r <= cutoff[type_i][type_j]`` (``nqa_neighbor_list_*_typed``), which is the reference's ``NeighborListTransform(
+per_edge_type_cutoff=...)`` (``nequip/data/transforms/neighborlist.py:9-117``) without building the full list first.  The result
+is bitwise the untyped list with the other edges removed.  ``None`` is the untyped code path, unchanged.
 """
 
 import ctypes
 import os
-from typing import Dict, Final, Optional, Tuple, Union
+from typing import Dict, Final, List, Optional, Tuple, Union
 
 import torch
 
@@ -91,14 +97,84 @@ def _complete_cell_host(cell64: torch.Tensor, pbc: Tuple[bool, bool, bool]) -> t
     return torch.as_tensor(c, dtype=torch.float64, device=cell64.device).contiguous()
 
 
+_NL_BAD_TYPE = 32  # status bit of the typed entry points: an atom type outside [0, num_types)
+_BAD_TYPE_MSG = "atom_types holds a type index outside [0, {T}): the per-edge-type cutoff table has {T} types"
+_MISSING_TYPES_MSG = (
+    f"Per-edge-type cutoffs require '{AtomicDataDict.ATOM_TYPE_KEY}' to be present in the data. "
+    "This is likely because the chemical species have not been mapped to atom types before the neighborlist is built. "
+    "Please check your data transform order.")
+
+
+class CutoffTable:
+    """A checked per-edge-type cutoff table: float64 ``[T, T]`` on the host, row-major (centre type, neighbour type), every
+    entry positive and ``<= r_max`` (the reference asserts both, ``nequip/nn/embedding/utils.py``); device copies are made once
+    per device."""
+
+    def __init__(self, table: torch.Tensor, r_max: float):
+        table = torch.as_tensor(table).detach().to(device="cpu", dtype=torch.float64)
+        if table.dim() != 2 or table.shape[0] != table.shape[1] or table.shape[0] < 1:
+            raise ValueError(f"per-edge-type cutoffs must be a [T, T] table, got shape {tuple(table.shape)}")
+        if not bool(torch.all(table > 0)):  # (also refuses NaN)
+            raise ValueError("per-edge-type cutoffs must be positive")
+        if not bool(torch.all(table <= float(r_max))):
+            raise ValueError(f"per-edge-type cutoffs cannot exceed r_max = {r_max} (largest entry: {float(table.max())})")
+        self.table = table.contiguous()
+        self.r_max = float(r_max)
+        self.num_types = int(table.shape[0])
+        self.symmetric = bool(torch.equal(table, table.t()))
+        self._on: Dict[torch.device, torch.Tensor] = {}
+
+    def on(self, device: torch.device) -> torch.Tensor:
+        key = torch.device(device)
+        if key not in self._on:
+            self._on[key] = self.table.to(device)
+        return self._on[key]
+
+
+def as_cutoff_table(per_edge_type_cutoff, type_names: Optional[List[str]], r_max: float) -> Optional[CutoffTable]:
+    """``None`` -> ``None``; a dict (``{"H": 3.0, "O": {"H": 3.5}}``, needs ``type_names``), a ``[T, T]`` tensor or a
+    ``CutoffTable`` -> a ``CutoffTable`` checked against ``r_max`` (on the host, before anything is launched)."""
+    if per_edge_type_cutoff is None:
+        return None
+    if isinstance(per_edge_type_cutoff, CutoffTable):
+        if per_edge_type_cutoff.r_max > float(r_max):
+            return CutoffTable(per_edge_type_cutoff.table, r_max)
+        return per_edge_type_cutoff
+    if isinstance(per_edge_type_cutoff, dict):
+        if type_names is None:
+            raise ValueError("`type_names` required for `per_edge_type_cutoff`")
+        from ..nn.embedding import cutoff_partialdict_to_tensor
+
+        per_edge_type_cutoff = cutoff_partialdict_to_tensor(per_edge_type_cutoff, list(type_names), float(r_max))
+    return CutoffTable(per_edge_type_cutoff, r_max)
+
+
+def _types_for(table: Optional[CutoffTable], atom_types: Optional[torch.Tensor], N: int, device) -> Optional[torch.Tensor]:
+    if table is None:
+        return None
+    if atom_types is None:
+        raise KeyError(_MISSING_TYPES_MSG)
+    types = atom_types.detach().reshape(-1).to(device=device, dtype=torch.int64).contiguous()
+    if types.numel() != N:
+        raise ValueError(f"{types.numel()} atom types for {N} atoms")
+    return types
+
+
 def _compute_neighborlist_single_frame(
     pos: torch.Tensor,
     r_max: float,
     cell: Optional[torch.Tensor] = None,
     pbc: Union[bool, Tuple[bool, bool, bool], torch.Tensor] = False,
     return_rowptr: bool = False,
+    atom_types: Optional[torch.Tensor] = None,
+    per_edge_type_cutoff=None,
+    type_names: Optional[List[str]] = None,
+    symmetrise: bool = False,
 ):
-    """``(edge_index [2, E] int64, edge_cell_shift [E, 3])`` of one frame (``nequip/data/_nl.py:63-165``)."""
+    """``(edge_index [2, E] int64, edge_cell_shift [E, 3])`` of one frame (``nequip/data/_nl.py:63-165``); with
+    ``per_edge_type_cutoff`` (and ``atom_types``) the typed list; ``symmetrise``: typed by ``max(rc[a][b], rc[b][a])`` (the
+    kernel's flag), the list the capacity-padded form holds."""
+    table = as_cutoff_table(per_edge_type_cutoff, type_names, r_max)
     if not pos.is_cuda:
         raise RuntimeError("the `nequip_amd` neighbour list runs on the GPU: positions must be a CUDA/HIP tensor")
     if isinstance(pbc, bool):
@@ -116,10 +192,35 @@ def _compute_neighborlist_single_frame(
     if cell64 is not None:
         cell64 = _complete_cell(cell64, pbc)
     pbc_dev = torch.tensor([int(b) for b in pbc], dtype=torch.int32, device=device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    if table is not None:
+        types = _types_for(table, atom_types, N, device)
+        T = table.num_types
+        ws_bytes = lib.nqa_neighbor_list_typed_workspace_bytes(N, T)
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+        aux = torch.empty(N + 2, dtype=torch.int32, device=device)  # rowptr [N + 1] and the status word, read back as one pair
+        rowptr, status = aux[:N + 1], aux[N + 1:]
+        with torch.cuda.device(device):
+            rc = lib.nqa_neighbor_list_count_typed(_ptr(pos64), _ptr(cell64), _ptr(pbc_dev), float(r_max), _ptr(types),
+                                                   _ptr(table.on(device)), T, int(bool(symmetrise)), N, _ptr(ws), ws_bytes, _ptr(rowptr),
+                                                   _ptr(status), stream)
+            _lib.check(rc, "nqa_neighbor_list_count_typed")
+            E, bad = aux[N:].tolist()  # the one synchronisation: the edge count is data dependent
+            if bad & _NL_BAD_TYPE:
+                raise ValueError(_BAD_TYPE_MSG.format(T=T))
+            if E < 0 or bad & 1:
+                raise RuntimeError("neighbour list has more than 2^31 - 1 edges")
+            edge_index = torch.empty((2, E), dtype=torch.int64, device=device)
+            shifts = torch.empty((E, 3), dtype=torch.float64, device=device)
+            rc = lib.nqa_neighbor_list_fill_typed(_ptr(ws), _ptr(rowptr), _ptr(types), N, T, E, _ptr(edge_index), _ptr(shifts),
+                                                  stream)
+            _lib.check(rc, "nqa_neighbor_list_fill_typed")
+        if return_rowptr:
+            return edge_index, shifts.to(out_dtype), rowptr
+        return edge_index, shifts.to(out_dtype)
     ws_bytes = lib.nqa_neighbor_list_workspace_bytes(N)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
     rowptr = torch.empty(N + 1, dtype=torch.int32, device=device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     with torch.cuda.device(device):
         rc = lib.nqa_neighbor_list_count(_ptr(pos64), _ptr(cell64), _ptr(pbc_dev), float(r_max), N, _ptr(ws), ws_bytes,
                                          _ptr(rowptr), stream)
@@ -148,11 +249,17 @@ class PaddedNeighborList:
     weights and all derivatives vanish: energies, forces and virials are those of the unpadded list.  Needs a cell.
 
     ``status()`` (a synchronising read, for AFTER the step) reports ``(fits, E)``: when the list did not fit, the output of that
-    ``build`` holds padding only and the caller repeats the step with a larger capacity."""
+    ``build`` holds padding only and the caller repeats the step with a larger capacity.
+
+    With ``per_edge_type_cutoff`` and ``atom_types`` (fixed for the life of the object, checked against the table once, here)
+    the real edges are the typed list of the SYMMETRISED table ``max(rc[a][b], rc[b][a])``: the padding comes in pairs, so the
+    number of real edges has to be even, which a symmetric list guarantees.  The extra edges of an asymmetric table lie beyond
+    their own type cutoff and are zeroed by the model, as every edge outside its cutoff is."""
 
     def __init__(self, num_atoms: int, r_max: float, cell: torch.Tensor,
                  pbc: Union[bool, Tuple[bool, bool, bool], torch.Tensor], edge_capacity: int,
-                 shift_dtype: torch.dtype = torch.float32):
+                 shift_dtype: torch.dtype = torch.float32, atom_types: Optional[torch.Tensor] = None,
+                 per_edge_type_cutoff=None, type_names: Optional[List[str]] = None):
         if cell is None:
             raise ValueError("a capacity-padded neighbour list needs a cell (its padding edges are lattice images)")
         if not cell.is_cuda:
@@ -175,7 +282,17 @@ class PaddedNeighborList:
         self.cell64 = torch.empty(3, 3, dtype=torch.float64, device=self.device)
         self.set_cell(cell)
         self._pbc_dev = torch.tensor([int(b) for b in pbc], dtype=torch.int32, device=self.device)
-        self._ws_bytes = lib.nqa_neighbor_list_workspace_bytes(self.num_atoms)
+        self.cutoff_table = as_cutoff_table(per_edge_type_cutoff, type_names, self.r_max)
+        self._types = _types_for(self.cutoff_table, atom_types, self.num_atoms, self.device)
+        if self.cutoff_table is not None:
+            T = self.cutoff_table.num_types
+            if bool(((self._types < 0) | (self._types >= T)).any()):
+                raise ValueError(_BAD_TYPE_MSG.format(T=T))
+            self._table_dev = self.cutoff_table.on(self.device)  # (symmetrised by the count kernel: symmetrise = 1)
+            self._type_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._ws_bytes = lib.nqa_neighbor_list_typed_workspace_bytes(self.num_atoms, T)
+        else:
+            self._ws_bytes = lib.nqa_neighbor_list_workspace_bytes(self.num_atoms)
         self._ws = torch.empty(max(self._ws_bytes, 1), dtype=torch.uint8, device=self.device)
         self._rowptr = torch.empty(self.num_atoms + 1, dtype=torch.int32, device=self.device)
         self._status = torch.zeros(2, dtype=torch.int32, device=self.device)
@@ -203,12 +320,25 @@ class PaddedNeighborList:
         src32 = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         with torch.cuda.device(dev):
-            rc = lib.nqa_neighbor_list_count(_ptr(pos64), _ptr(self.cell64), _ptr(self._pbc_dev), self.r_max,
-                                             self.num_atoms, _ptr(self._ws), self._ws_bytes, _ptr(self._rowptr), stream)
-            _lib.check(rc, "nqa_neighbor_list_count")
-            rc = lib.nqa_neighbor_list_fill_padded(_ptr(self._ws), _ptr(self._rowptr), self.num_atoms, cap, _ptr(rowptr),
-                                                   _ptr(edge_index), _ptr(shifts), _ptr(src32), _ptr(self._status), stream)
-            _lib.check(rc, "nqa_neighbor_list_fill_padded")
+            if self.cutoff_table is not None:
+                T = self.cutoff_table.num_types
+                rc = lib.nqa_neighbor_list_count_typed(_ptr(pos64), _ptr(self.cell64), _ptr(self._pbc_dev), self.r_max,
+                                                       _ptr(self._types), _ptr(self._table_dev), T, 1, self.num_atoms,
+                                                       _ptr(self._ws), self._ws_bytes, _ptr(self._rowptr),
+                                                       _ptr(self._type_status), stream)
+                _lib.check(rc, "nqa_neighbor_list_count_typed")
+                rc = lib.nqa_neighbor_list_fill_padded_typed(_ptr(self._ws), _ptr(self._rowptr), _ptr(self._types),
+                                                             self.num_atoms, T, cap, _ptr(rowptr), _ptr(edge_index),
+                                                             _ptr(shifts), _ptr(src32), _ptr(self._status), stream)
+                _lib.check(rc, "nqa_neighbor_list_fill_padded_typed")
+            else:
+                rc = lib.nqa_neighbor_list_count(_ptr(pos64), _ptr(self.cell64), _ptr(self._pbc_dev), self.r_max,
+                                                 self.num_atoms, _ptr(self._ws), self._ws_bytes, _ptr(self._rowptr), stream)
+                _lib.check(rc, "nqa_neighbor_list_count")
+                rc = lib.nqa_neighbor_list_fill_padded(_ptr(self._ws), _ptr(self._rowptr), self.num_atoms, cap, _ptr(rowptr),
+                                                       _ptr(edge_index), _ptr(shifts), _ptr(src32), _ptr(self._status),
+                                                       stream)
+                _lib.check(rc, "nqa_neighbor_list_fill_padded")
         self.last_csr = (rowptr, self._edge_ids, src32)  # the dst-CSR of the list just built (edge ids = 0 .. capacity - 1)
         return edge_index, shifts.to(self.shift_dtype), rowptr
 
@@ -285,11 +415,15 @@ def _frame_ptr(data: AtomicDataDict.Type, num_frames: int, device: torch.device)
 
 
 def _compute_neighborlist_batched(pos: torch.Tensor, r_max: float, frame_ptr: torch.Tensor,
-                                  cell: Optional[torch.Tensor] = None, pbc: Optional[torch.Tensor] = None):
+                                  cell: Optional[torch.Tensor] = None, pbc: Optional[torch.Tensor] = None,
+                                  atom_types: Optional[torch.Tensor] = None, per_edge_type_cutoff=None,
+                                  type_names: Optional[List[str]] = None):
     """``(edge_index [2, E] int64, edge_cell_shift [E, 3], rowptr [N + 1] int32)`` of F frames in one pass: frame f holds the
     atoms ``frame_ptr[f]:frame_ptr[f + 1]`` with cell ``cell[f]`` ([F, 3, 3] or None) and periodicity ``pbc[f]`` ([F, 3] or
     None).  Equal to the concatenation of the frames' ``_compute_neighborlist_single_frame`` lists (atom indices offset);
-    reads the edge count and the status word back together: the one synchronisation of the batch."""
+    reads the edge count and the status word back together: the one synchronisation of the batch.  With
+    ``per_edge_type_cutoff``: the typed list (``atom_types`` [N] over the whole batch, one table for all frames)."""
+    table = as_cutoff_table(per_edge_type_cutoff, type_names, r_max)
     if not pos.is_cuda:
         raise RuntimeError("the `nequip_amd` neighbour list runs on the GPU: positions must be a CUDA/HIP tensor")
     lib = _lib.load()
@@ -310,17 +444,28 @@ def _compute_neighborlist_batched(pos: torch.Tensor, r_max: float, frame_ptr: to
             raise ValueError(f"pbc of shape {tuple(pbc.shape)} for {F} frames: expected [{F}, 3]")
         pbc32 = pbc.detach().to(device=device, dtype=torch.int32).reshape(F, 3).contiguous()
     frame_ptr = frame_ptr.to(device=device, dtype=torch.int64).contiguous()
-    ws_bytes = lib.nqa_neighbor_list_batched_workspace_bytes(N, F)
+    types = _types_for(table, atom_types, N, device)
+    T = table.num_types if table is not None else 0
+    ws_bytes = (lib.nqa_neighbor_list_batched_workspace_bytes(N, F) if table is None
+                else lib.nqa_neighbor_list_batched_typed_workspace_bytes(N, F, T))
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
     aux = torch.empty(N + 2, dtype=torch.int32, device=device)  # rowptr [N + 1] and the status word, read back as one pair
     rowptr, status = aux[:N + 1], aux[N + 1:]
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     nbytes = 8.0 * (2 * 3 * N + 9 * F) + 4.0 * (8 * N + 3 * F)  # count pass: positions in, grid and row pointer out
     with torch.cuda.device(device), ktimer.region("nqa_neighbor_list_batched", nbytes):
-        rc = lib.nqa_neighbor_list_batched_count(_ptr(pos64), _ptr(cell64), _ptr(pbc32), _ptr(frame_ptr), float(r_max), N, F,
-                                                 _ptr(ws), ws_bytes, _ptr(rowptr), _ptr(status), stream)
-        _lib.check(rc, "nqa_neighbor_list_batched_count")
+        if table is None:
+            rc = lib.nqa_neighbor_list_batched_count(_ptr(pos64), _ptr(cell64), _ptr(pbc32), _ptr(frame_ptr), float(r_max), N, F,
+                                                     _ptr(ws), ws_bytes, _ptr(rowptr), _ptr(status), stream)
+            _lib.check(rc, "nqa_neighbor_list_batched_count")
+        else:
+            rc = lib.nqa_neighbor_list_batched_count_typed(_ptr(pos64), _ptr(cell64), _ptr(pbc32), _ptr(frame_ptr), float(r_max),
+                                                           _ptr(types), _ptr(table.on(device)), T, N, F, _ptr(ws), ws_bytes,
+                                                           _ptr(rowptr), _ptr(status), stream)
+            _lib.check(rc, "nqa_neighbor_list_batched_count_typed")
         E, bad = aux[N:].tolist()  # the one synchronisation: the edge count is data dependent
+        if bad & _NL_BAD_TYPE:
+            raise ValueError(_BAD_TYPE_MSG.format(T=T))
         for bit, exc, msg in _BATCHED_STATUS_ERRORS:
             if bad & bit:
                 raise exc(msg)
@@ -328,8 +473,13 @@ def _compute_neighborlist_batched(pos: torch.Tensor, r_max: float, frame_ptr: to
             raise RuntimeError("neighbour list has more than 2^31 - 1 edges")
         edge_index = torch.empty((2, E), dtype=torch.int64, device=device)
         shifts = torch.empty((E, 3), dtype=torch.float64, device=device)
-        rc = lib.nqa_neighbor_list_batched_fill(_ptr(ws), _ptr(rowptr), N, F, E, _ptr(edge_index), _ptr(shifts), stream)
-        _lib.check(rc, "nqa_neighbor_list_batched_fill")
+        if table is None:
+            rc = lib.nqa_neighbor_list_batched_fill(_ptr(ws), _ptr(rowptr), N, F, E, _ptr(edge_index), _ptr(shifts), stream)
+            _lib.check(rc, "nqa_neighbor_list_batched_fill")
+        else:
+            rc = lib.nqa_neighbor_list_batched_fill_typed(_ptr(ws), _ptr(rowptr), _ptr(types), N, F, T, E, _ptr(edge_index),
+                                                          _ptr(shifts), stream)
+            _lib.check(rc, "nqa_neighbor_list_batched_fill_typed")
     return edge_index, shifts.to(pos.dtype), rowptr
 
 
@@ -337,17 +487,21 @@ def _per_frame_requested() -> bool:
     return os.environ.get("NQA_NL_PER_FRAME", "") not in ("", "0")
 
 
-def compute_neighborlist_(data: AtomicDataDict.Type, r_max: float,
-                          backend: str = DEFAULT_NEIGHBORLIST_BACKEND) -> AtomicDataDict.Type:
+def compute_neighborlist_(data: AtomicDataDict.Type, r_max: float, backend: str = DEFAULT_NEIGHBORLIST_BACKEND,
+                          per_edge_type_cutoff=None, type_names: Optional[List[str]] = None) -> AtomicDataDict.Type:
     """Add a neighbour list to ``data`` in place (contract of ``nequip/data/_nl.py:364-381``).  Batched data: one batched list
-    (``NQA_NL_PER_FRAME=1``: one list per frame, concatenated; the same result)."""
+    (``NQA_NL_PER_FRAME=1``: one list per frame, concatenated; the same result).  ``per_edge_type_cutoff``: the typed list
+    (needs ``atom_types`` in ``data``); the topology hint is the row pointer of the pruned list."""
     if backend not in NEIGHBORLIST_BACKEND_OPTIONS:
         supported = ", ".join(f"`{b}`" for b in NEIGHBORLIST_BACKEND_OPTIONS)
         raise ValueError(f"Unknown neighborlist backend = `{backend}`. Supported backends: {supported}")
     K = AtomicDataDict
+    table = as_cutoff_table(per_edge_type_cutoff, type_names, r_max)
+    if table is not None and K.ATOM_TYPE_KEY not in data:
+        raise KeyError(_MISSING_TYPES_MSG)
     batched = K.BATCH_KEY in data
     if batched and not _per_frame_requested():
-        return _compute_neighborlist_batched_(data, r_max)
+        return _compute_neighborlist_batched_(data, r_max, table)
     nframes = K.num_frames(data)
     if batched:
         counts = data[K.NUM_NODES_KEY].view(-1).cpu().tolist() if K.NUM_NODES_KEY in data else torch.bincount(
@@ -366,7 +520,8 @@ def compute_neighborlist_(data: AtomicDataDict.Type, r_max: float,
         if pbc is None:
             pbc = False
         ei, sh, rp = _compute_neighborlist_single_frame(frame[K.POSITIONS_KEY], r_max, cell=cell, pbc=pbc,
-                                                        return_rowptr=True)
+                                                        return_rowptr=True, atom_types=frame.get(K.ATOM_TYPE_KEY, None),
+                                                        per_edge_type_cutoff=table)
         eidx.append(ei + offsets[f])
         rowptrs.append(rp)
         shifts.append(sh)
@@ -389,13 +544,16 @@ def compute_neighborlist_(data: AtomicDataDict.Type, r_max: float,
     return data
 
 
-def _compute_neighborlist_batched_(data: AtomicDataDict.Type, r_max: float) -> AtomicDataDict.Type:
+def _compute_neighborlist_batched_(data: AtomicDataDict.Type, r_max: float,
+                                   table: Optional[CutoffTable] = None) -> AtomicDataDict.Type:
     K = AtomicDataDict
     pos = data[K.POSITIONS_KEY]
     F = _batched_frame_count(data)
     frame_ptr = _frame_ptr(data, F, pos.device)
     cell = data.get(K.CELL_KEY, None)
-    edge_index, shifts, rowptr = _compute_neighborlist_batched(pos, r_max, frame_ptr, cell=cell, pbc=data.get(K.PBC_KEY, None))
+    edge_index, shifts, rowptr = _compute_neighborlist_batched(pos, r_max, frame_ptr, cell=cell, pbc=data.get(K.PBC_KEY, None),
+                                                               atom_types=data.get(K.ATOM_TYPE_KEY, None),
+                                                               per_edge_type_cutoff=table)
     data[K.EDGE_INDEX_KEY] = edge_index
     from ..nn._topology import topology_cache
 

@@ -85,9 +85,15 @@ class NequIPCalculator(Calculator):
         transforms: Sequence[Callable] = (),
         graphed_md: bool = False,
         graphed_md_headroom: float = 1.02,
+        prune_neighborlist: bool = True,
         **kwargs,
     ):
-        """``graphed_md=True``: successive calls on the same atoms (same species, same periodicity -- a molecular-dynamics
+        """``prune_neighborlist``: a model with per-edge-type cutoffs (``model.metadata["per_edge_type_cutoff"]``) gets the typed
+        neighbour list, i.e. only the edges within their type's cutoff (as the reference's calculators prune through
+        ``basic_transforms``, nequip/integrations/utils.py:28-70); ``False`` builds the full ``r_max`` list, which gives the
+        same numbers (the extra edges carry no interaction) at the cost of their kernels' time.  No effect on other models.
+
+        ``graphed_md=True``: successive calls on the same atoms (same species, same periodicity -- a molecular-dynamics
         run) replay positions -> neighbour list -> model as one hipGraph (``integrations/graphed_step.py``) instead of
         launching ~110 kernels per step from Python; any change of the atoms' identity captures anew, a changed cell is
         written in place.  Needs a cell, an eager ``nequip_amd`` model (not a compiled package) and no ``transforms``."""
@@ -102,6 +108,10 @@ class NequIPCalculator(Calculator):
         self.energy_units_to_eV = energy_units_to_eV
         self.length_units_to_A = length_units_to_A
         self.transforms = list(transforms)
+        self.prune_neighborlist = bool(prune_neighborlist)
+        from ..data.transforms import cutoff_table_from_model
+
+        self._cutoff_table = cutoff_table_from_model(model, self.r_max) if self.prune_neighborlist else None
         self.graphed_md = bool(graphed_md)
         self.graphed_md_headroom = float(graphed_md_headroom)
         self._graphed = None  # (identity of the atoms, GraphedStep, cell as last written)
@@ -160,7 +170,7 @@ class NequIPCalculator(Calculator):
         for t in self.transforms:
             data = t(data)
         if K.EDGE_INDEX_KEY not in data:
-            compute_neighborlist_(data, self.r_max)
+            compute_neighborlist_(data, self.r_max, per_edge_type_cutoff=self._cutoff_table)
         return data
 
     def call_model(self, data: AtomicDataDict.Type) -> AtomicDataDict.Type:
@@ -185,7 +195,8 @@ class NequIPCalculator(Calculator):
                                  f"{sorted(self._type_of_symbol)}") from None
             step = GraphedStep(
                 self.model, torch.as_tensor(types).to(self.device), torch.as_tensor(cell).to(self.device), pbc, self.r_max,
-                headroom=self.graphed_md_headroom,
+                headroom=self.graphed_md_headroom, per_edge_type_cutoff=self._cutoff_table,
+                prune_neighborlist=self.prune_neighborlist,
                 outputs=(K.TOTAL_ENERGY_KEY, K.PER_ATOM_ENERGY_KEY, K.FORCE_KEY, K.STRESS_KEY, K.VIRIAL_KEY))
             self._graphed = (ident, step, cell.copy())
         _, step, last_cell = self._graphed

@@ -21,7 +21,8 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 import torch
 
 from ..data import AtomicDataDict
-from ..data._nl import PaddedNeighborList, compute_neighborlist_, compute_neighborlist_padded_
+from ..data._nl import (PaddedNeighborList, _compute_neighborlist_single_frame, compute_neighborlist_,
+                        compute_neighborlist_padded_)
 from ..nn._topology import topology_cache
 
 
@@ -32,12 +33,16 @@ class GraphedStep:
     lattice vectors); ``pbc`` three flags; ``r_max`` the model's cutoff.  ``headroom``: slots per edge of the first list
     (the capacity grows by the same factor whenever a list does not fit).  ``outputs``: the fields of the model's output to
     keep (static tensors, overwritten by the next step: copy what must survive).  Positions are float64 by default, as the
-    reference's data is (``nequip/data/_key_registry`` / ASE): the model casts where it computes."""
+    reference's data is (``nequip/data/_key_registry`` / ASE): the model casts where it computes.
+    ``per_edge_type_cutoff``: the model's cutoff table (dict with the model's type names, ``[T, T]`` tensor or ``CutoffTable``;
+    default: read from the model) -- the padded list is then typed, by the symmetrised table (``PaddedNeighborList``), and the
+    first capacity comes from that pruned list; ``prune_neighborlist=False`` keeps the full ``r_max`` list."""
 
     def __init__(self, model: torch.nn.Module, atom_types: torch.Tensor, cell: torch.Tensor,
                  pbc: Union[bool, Sequence[bool], torch.Tensor], r_max: float, headroom: float = 1.02,
                  outputs: Sequence[str] = (AtomicDataDict.TOTAL_ENERGY_KEY, AtomicDataDict.FORCE_KEY),
-                 pos_dtype: torch.dtype = torch.float64, edge_capacity: Optional[int] = None):
+                 pos_dtype: torch.dtype = torch.float64, edge_capacity: Optional[int] = None,
+                 per_edge_type_cutoff=None, prune_neighborlist: bool = True):
         if not atom_types.is_cuda:
             raise RuntimeError("GraphedStep runs on the GPU only (HIP kernels; there is no CPU path)")
         assert not model.training, "call .eval() on the model before building a GraphedStep"
@@ -62,6 +67,15 @@ class GraphedStep:
         self._pbc_t = torch.tensor([list(self._pbc)], device=self.device)
         self._pos = torch.zeros(self.num_atoms, 3, dtype=pos_dtype, device=self.device)
         self._capacity = edge_capacity
+        from ..data._nl import as_cutoff_table
+        from ..data.transforms import cutoff_table_from_model
+
+        if not prune_neighborlist:
+            self._table = None
+        elif per_edge_type_cutoff is not None:
+            self._table = as_cutoff_table(per_edge_type_cutoff, list(getattr(model, "type_names", []) or []) or None, self.r_max)
+        else:
+            self._table = cutoff_table_from_model(model, self.r_max)
         self._side = torch.cuda.Stream(self.device)
         # (the evaluations that pair at all: float32 models, see GraphModel._start_pairing)
         self._pairs = getattr(model, "model_dtype", torch.float32) == torch.float32
@@ -101,14 +115,20 @@ class GraphedStep:
         return {k: out[k].detach() for k in self.outputs if k in out and out[k] is not None}, flags
 
     def _evaluate_eager(self) -> Dict[str, torch.Tensor]:
-        data = compute_neighborlist_(self._data(), self.r_max)
+        data = compute_neighborlist_(self._data(), self.r_max, per_edge_type_cutoff=self._table)
         out = self.model(data)
         return {k: out[k].detach() for k in self.outputs if k in out and out[k] is not None}
 
     def _first_capacity(self) -> int:
         K = AtomicDataDict
-        data = compute_neighborlist_(self._data(), self.r_max)
-        return int(data[K.EDGE_INDEX_KEY].shape[1])
+        if self._table is None:
+            data = compute_neighborlist_(self._data(), self.r_max)
+            return int(data[K.EDGE_INDEX_KEY].shape[1])
+        # the list the padded form will hold: typed by the symmetrised table
+        edge_index, _ = _compute_neighborlist_single_frame(self._pos, self.r_max, cell=self._cell[0], pbc=self._pbc,
+                                                           atom_types=self._types, per_edge_type_cutoff=self._table,
+                                                           symmetrise=True)
+        return int(edge_index.shape[1])
 
     def _capture(self) -> None:
         """(Re)build the neighbour-list buffers for the current capacity and capture the step."""
@@ -117,7 +137,8 @@ class GraphedStep:
         self._graph = None
         self._out, self._flags, self._topo = {}, None, None
         self._nl = PaddedNeighborList(self.num_atoms, self.r_max, self._cell[0], self._pbc, self._capacity,
-                                      shift_dtype=self._pos.dtype)
+                                      shift_dtype=self._pos.dtype, atom_types=self._types,
+                                      per_edge_type_cutoff=self._table)
         self._capacity = self._nl.edge_capacity
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))

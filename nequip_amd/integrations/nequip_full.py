@@ -415,7 +415,26 @@ def convert(model: torch.nn.Module) -> torch.nn.Module:
     for name, factory in _factories(model).items():
         model = _replace(model, name, factory)
     _plan(model)
+    _carry_cutoff_table(model)
     return model
+
+
+def _carry_cutoff_table(model: torch.nn.Module) -> None:
+    """A converted model keeps publishing its per-edge-type cutoffs: where the root's metadata (the reference's ``GraphModel``
+    keeps a ``_metadata`` dict) does not carry the ``per_edge_type_cutoff`` key, it is filled in from the converted
+    ``EdgeLengthNormalizer``, so that this project's calculators prune the neighbour list of such a model too."""
+    from ..nn import embedding as aemb
+    from ..nn.embedding import cutoff_tensor_to_str
+
+    meta = getattr(model, "_metadata", None)
+    if not isinstance(meta, dict) or meta.get("per_edge_type_cutoff"):
+        return
+    for m in model.modules():
+        if isinstance(m, aemb.EdgeLengthNormalizer) and m._per_edge_type:
+            # (1 / (1 / rc) may land an ulp above r_max, which the calculators' table check would refuse)
+            table = m._rmax_recip.detach().to("cpu", torch.float64).reciprocal().clamp(max=float(m.r_max))
+            meta["per_edge_type_cutoff"] = cutoff_tensor_to_str(table)
+            return
 
 
 def make_full_modifier(base_cls):

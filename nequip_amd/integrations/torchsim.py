@@ -64,6 +64,8 @@ class NequIPTorchSimCalc(ModelInterface):
         chemical_species_to_atom_type_map: chemical symbol -> model type name (dict), or the chemical symbols of the
             model's types in type order (list); default: the model's type names are chemical symbols
         r_max: neighbour-list cutoff; default: the model's ``r_max``
+        prune_neighborlist: a model with per-edge-type cutoffs gets the typed (pruned) batched list; ``False``: the full
+            ``r_max`` list (the same numbers, more edges)
     """
 
     def __init__(
@@ -75,6 +77,7 @@ class NequIPTorchSimCalc(ModelInterface):
         system_idx: Optional[torch.Tensor] = None,
         chemical_species_to_atom_type_map: Optional[Union[Dict[str, str], Sequence[str]]] = None,
         r_max: Optional[float] = None,
+        prune_neighborlist: bool = True,
     ) -> None:
         super().__init__()
         if isinstance(device, str):
@@ -98,6 +101,10 @@ class NequIPTorchSimCalc(ModelInterface):
         if r_max is None:
             raise ValueError("no cutoff: pass r_max or a model with an r_max attribute")
         self.r_max = float(r_max)
+        self.prune_neighborlist = bool(prune_neighborlist)
+        from ..data.transforms import cutoff_table_from_model
+
+        self._cutoff_table = cutoff_table_from_model(model, self.r_max) if self.prune_neighborlist else None
 
         # atomic number -> type index on the device (-1: not a species of the model)
         type_names = list(getattr(model, "type_names", []) or [])
@@ -218,7 +225,7 @@ class NequIPTorchSimCalc(ModelInterface):
         for t in self.transforms:
             data = t(data)
         if K.EDGE_INDEX_KEY not in data:
-            compute_neighborlist_(data, self.r_max)
+            compute_neighborlist_(data, self.r_max, per_edge_type_cutoff=self._cutoff_table)
         data = {k: (v.contiguous() if torch.is_tensor(v) else v) for k, v in data.items()}
 
         out = self.model(data)

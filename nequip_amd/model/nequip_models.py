@@ -75,7 +75,13 @@ def _build(builder, seed: int, model_dtype, **kwargs) -> GraphModel:
             model = builder(**kwargs)
     finally:
         torch.set_rng_state(cpu_state)
-    return GraphModel(model, type_names=kwargs.get("type_names", ()), model_dtype=dtype, r_max=kwargs.get("r_max"))
+    table = None
+    if kwargs.get("per_edge_type_cutoff") is not None:
+        from ..nn.embedding import cutoff_partialdict_to_tensor
+
+        table = cutoff_partialdict_to_tensor(kwargs["per_edge_type_cutoff"], list(kwargs["type_names"]), kwargs["r_max"])
+    return GraphModel(model, type_names=kwargs.get("type_names", ()), model_dtype=dtype, r_max=kwargs.get("r_max"),
+                      per_edge_type_cutoff=table)
 
 
 def PresetNequIPGNNModel(preset: str, **kwargs) -> GraphModel:

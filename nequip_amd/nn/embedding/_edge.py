@@ -147,6 +147,22 @@ def cutoff_partialdict_to_tensor(partial_dict: Dict, type_names: List[str], r_ma
     return table
 
 
+def cutoff_tensor_to_str(cutoff_tensor: torch.Tensor) -> str:
+    """``[T, T]`` cutoffs -> the metadata string: ``T * T`` space-separated values, row-major (centre type first)."""
+    return " ".join(str(float(v)) for v in cutoff_tensor.detach().to(_GLOBAL_DTYPE).reshape(-1).tolist())
+
+
+def cutoff_str_to_fulldict(cutoff_str: Optional[str], type_names: List[str]) -> Optional[Dict[str, Dict[str, float]]]:
+    """The metadata string back to ``{centre: {neighbour: cutoff}}`` with every pair present (``None`` for no string)."""
+    if cutoff_str is None or cutoff_str == "":
+        return None
+    values = [float(x) for x in cutoff_str.split()]
+    T = len(type_names)
+    if len(values) != T * T:
+        raise ValueError(f"expected {T * T} cutoff values for {T} types, got {len(values)}")
+    return {a: {b: values[i * T + j] for j, b in enumerate(type_names)} for i, a in enumerate(type_names)}
+
+
 class _EdgeEmbedPairedFn(torch.autograd.Function):
     """``edge_vec [E, 3] -> (sh [E, S], emb [E, nb], emb_pairs [P, nb])`` in one launch for a list with a reverse-edge pairing
     (``nqa_edge_embed_fwd_paired``): the per-pair rows are what ``pair_rows(emb, pairing)`` would gather, and the backward

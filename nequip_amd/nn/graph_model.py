@@ -2,7 +2,7 @@
 keeps only the model's input fields and exposes the custom-ops metadata of accelerated submodules."""
 
 import os
-from typing import List
+from typing import List, Optional
 
 import torch
 
@@ -14,12 +14,17 @@ class GraphModel(GraphModuleMixin, torch.nn.Module):
     is_compile_graph_model: bool = False
 
     def __init__(self, model: GraphModuleMixin, type_names: List[str] = (), model_dtype=torch.float32,
-                 r_max: float = None) -> None:
+                 r_max: float = None, per_edge_type_cutoff: Optional[torch.Tensor] = None) -> None:
+        """``per_edge_type_cutoff``: the model's ``[T, T]`` cutoff table (rows = centre type) when it has one; published in
+        ``metadata`` so that calculators build the pruned neighbour list."""
         super().__init__()
         self.model = model
         self.type_names = list(type_names)
         self.model_dtype = model_dtype
         self.r_max = r_max
+        self.per_edge_type_cutoff = None
+        if per_edge_type_cutoff is not None:
+            self.per_edge_type_cutoff = torch.as_tensor(per_edge_type_cutoff).detach().to("cpu", torch.float64).clone()
         self.model_input_fields = [
             AtomicDataDict.POSITIONS_KEY, AtomicDataDict.EDGE_INDEX_KEY, AtomicDataDict.ATOM_TYPE_KEY,
             AtomicDataDict.CELL_KEY, AtomicDataDict.EDGE_CELL_SHIFT_KEY, AtomicDataDict.BATCH_KEY,
@@ -47,7 +52,8 @@ class GraphModel(GraphModuleMixin, torch.nn.Module):
     @property
     def metadata(self):
         """String-valued model metadata for compiled artefacts (nequip/nn/graph_model.py:20-36,100-146): model dtype,
-        type names, cutoff, and the libraries whose import registers the custom ops the model calls."""
+        type names, cutoff, per-edge-type cutoffs (only for a model that has them: ``T * T`` space-separated values, row-major,
+        centre type first) and the libraries whose import registers the custom ops the model calls."""
         out = {
             "model_dtype": {torch.float32: "float32", torch.float64: "float64"}.get(self.model_dtype, str(self.model_dtype)),
             "type_names": " ".join(self.type_names),
@@ -55,6 +61,10 @@ class GraphModel(GraphModuleMixin, torch.nn.Module):
         }
         if self.r_max is not None:
             out["r_max"] = str(self.r_max)
+        if self.per_edge_type_cutoff is not None:
+            from .embedding import cutoff_tensor_to_str
+
+            out["per_edge_type_cutoff"] = cutoff_tensor_to_str(self.per_edge_type_cutoff)
         libs = self.nequip_custom_ops_libs
         if libs:
             out["nequip_custom_ops_libs"] = " ".join(sorted(libs))
