@@ -22,6 +22,11 @@
 //               dependent) and allocates the outputs.
 //   4. fill   : same walk, writes (i, j, S) at rowptr[i] + k.  Edges come out grouped by centre atom in ascending order
 //               (= the dst-sorted order the tensor-product kernels want) and deterministically ordered within an atom.
+//
+// Forms of the list: F frames in one pass (the batched list: one header per frame, B = N + 8 F bins), T atom types with a cutoff
+// per (centre type, neighbour type) (the typed list: two more workspace fields), a fixed number of edge slots (the
+// capacity-padded fill).  They share the workspace layout (nl_layout(N, F, T), below) and the host code: one count driver and one
+// fill driver at the end of this file, where the table of the entry points is.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -46,15 +51,21 @@ struct NLHeader {
   int32_t pad_k0;    // this lattice vector, pad_k0 * |a| > r_max: longer than the cutoff, so they carry no interaction
 };
 
-// workspace layout (all offsets 256-byte aligned), N atoms, B = N + 8 bins capacity
+// Workspace layout of every form of the list (all offsets 256-byte aligned): N atoms; F frames (0: the single-frame list, one
+// header, B = N + 8 bins; F >= 1: the batched list, one header per frame, B = N + 8 F bins, plus bin_off and atom_frame);
+// T atom types (0: untyped; T >= 1: plus type_sorted and rc2 behind everything else, so a typed workspace begins with the
+// untyped one).  NL_ABSENT marks a field the form does not have.
+constexpr int64_t NL_ABSENT = -1;
+
 struct NLLayout {
-  int64_t header, sfrac, ioff, key, val, bin_count, rowptr_bin, atom_sorted, dummy_other, s_sorted, o_sorted, counts, total;
+  int64_t header, bin_off, atom_frame, sfrac, ioff, key, val, bin_count, rowptr_bin, atom_sorted, atom_arrival, s_sorted,
+      o_sorted, counts, type_sorted, rc2, total;
 };
 
 static int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
-static NLLayout nl_layout(int64_t N) {
-  const int64_t B = N + 8;
+static NLLayout nl_layout(int64_t N, int64_t F, int64_t T) {
+  const int64_t frames = F > 0 ? F : 1, B = N + 8 * frames;
   NLLayout L{};
   int64_t off = 0;
   auto take = [&](int64_t bytes) {
@@ -62,20 +73,63 @@ static NLLayout nl_layout(int64_t N) {
     off = align256(off + bytes);
     return o;
   };
-  L.header = take(sizeof(NLHeader));
-  L.sfrac = take(N * 3 * 8);        // wrapped fractional coordinates
-  L.ioff = take(N * 3 * 4);         // integer parts removed by the wrapping
-  L.key = take(N * 4);              // bin id per atom
-  L.val = take(N * 4);              // arrival slot of the atom in its bin
-  L.bin_count = take((B + 1) * 4);  // atoms per bin (zeroed by the plan kernel)
+  L.header = take(frames * (int64_t)sizeof(NLHeader));
+  L.bin_off = F > 0 ? take(F * 4) : NL_ABSENT;     // first bin of every frame
+  L.atom_frame = F > 0 ? take(N * 4) : NL_ABSENT;  // frame of every atom
+  L.sfrac = take(N * 3 * 8);                       // wrapped fractional coordinates
+  L.ioff = take(N * 3 * 4);                        // integer parts removed by the wrapping
+  L.key = take(N * 4);                             // bin id per atom
+  L.val = take(N * 4);                             // arrival slot of the atom in its bin
+  L.bin_count = take((B + 1) * 4);                 // atoms per bin (zeroed by the plan kernel)
   L.rowptr_bin = take((B + 1) * 4);
-  L.atom_sorted = take(N * 4);      // atom indices in bin order, ascending within a bin
-  L.dummy_other = take(N * 4);      // atom indices in bin order, arrival order within a bin
+  L.atom_sorted = take(N * 4);                     // atom indices in bin order, ascending within a bin
+  L.atom_arrival = take(N * 4);                    // atom indices in bin order, arrival order within a bin
   L.s_sorted = take(N * 3 * 8);
   L.o_sorted = take(N * 3 * 4);
   L.counts = take((N + 1) * 4);
+  L.type_sorted = T > 0 ? take(N * 4) : NL_ABSENT;  // type of atom_sorted[k]: read coalesced by the walk, next to s_sorted
+  L.rc2 = T > 0 ? take(T * T * 8) : NL_ABSENT;      // squared cutoffs [T, T], formed once per count
   L.total = off;
   return L;
+}
+
+// The workspace as typed pointers (nullptr for an absent field): the one place where a layout offset becomes a pointer.  The
+// fills only read through it.
+struct NLWork {
+  NLHeader* hdr;
+  int32_t *bin_off, *atom_frame;
+  double* sfrac;
+  int32_t *ioff, *key, *val, *bin_count, *rowptr_bin, *atom_sorted, *atom_arrival;
+  double* s_sorted;
+  int32_t *o_sorted, *counts, *type_sorted;
+  double* rc2;
+};
+
+template <typename T>
+static T* nl_at(char* w, int64_t offset) {
+  return offset == NL_ABSENT ? nullptr : reinterpret_cast<T*>(w + offset);
+}
+
+static NLWork nl_work(const void* workspace, const NLLayout& L) {
+  char* w = static_cast<char*>(const_cast<void*>(workspace));
+  NLWork W{};
+  W.hdr = nl_at<NLHeader>(w, L.header);
+  W.bin_off = nl_at<int32_t>(w, L.bin_off);
+  W.atom_frame = nl_at<int32_t>(w, L.atom_frame);
+  W.sfrac = nl_at<double>(w, L.sfrac);
+  W.ioff = nl_at<int32_t>(w, L.ioff);
+  W.key = nl_at<int32_t>(w, L.key);
+  W.val = nl_at<int32_t>(w, L.val);
+  W.bin_count = nl_at<int32_t>(w, L.bin_count);
+  W.rowptr_bin = nl_at<int32_t>(w, L.rowptr_bin);
+  W.atom_sorted = nl_at<int32_t>(w, L.atom_sorted);
+  W.atom_arrival = nl_at<int32_t>(w, L.atom_arrival);
+  W.s_sorted = nl_at<double>(w, L.s_sorted);
+  W.o_sorted = nl_at<int32_t>(w, L.o_sorted);
+  W.counts = nl_at<int32_t>(w, L.counts);
+  W.type_sorted = nl_at<int32_t>(w, L.type_sorted);
+  W.rc2 = nl_at<double>(w, L.rc2);
+  return W;
 }
 
 __device__ __forceinline__ void inv3(const double* c, double* inv) {
@@ -527,33 +581,6 @@ enum : int32_t {
   NL_BAD_TYPE = 32,           // typed lists: an atom type outside [0, num_types)
 };
 
-static NLLayout nl_batched_layout(int64_t N, int64_t F, int64_t* bin_off, int64_t* atom_frame) {
-  const int64_t B = N + 8 * F;
-  NLLayout L{};
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    const int64_t o = off;
-    off = align256(off + bytes);
-    return o;
-  };
-  L.header = take(F * (int64_t)sizeof(NLHeader));
-  *bin_off = take(F * 4);
-  *atom_frame = take(N * 4);
-  L.sfrac = take(N * 3 * 8);
-  L.ioff = take(N * 3 * 4);
-  L.key = take(N * 4);
-  L.val = take(N * 4);
-  L.bin_count = take((B + 1) * 4);
-  L.rowptr_bin = take((B + 1) * 4);
-  L.atom_sorted = take(N * 4);
-  L.dummy_other = take(N * 4);
-  L.s_sorted = take(N * 3 * 8);
-  L.o_sorted = take(N * 3 * 4);
-  L.counts = take((N + 1) * 4);
-  L.total = off;
-  return L;
-}
-
 __device__ __forceinline__ int64_t nl_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // A device restatement of _complete_cell_host (nequip_amd/data/_nl.py), the ase.geometry.complete_cell analogue the single-frame
@@ -766,18 +793,7 @@ __global__ __launch_bounds__(256) void nl_batched_fill_kernel(int64_t N, int64_t
 // ---- typed lists: per-(centre type, neighbour type) cutoffs ------------------------------------------------------------------
 // The typed entry points run the untyped pipeline (plan, bin, order: the grid is the r_max grid, so the candidate order is that
 // of the untyped list) and then walk with the extra test r2 <= rc[type_i][type_j]^2.  Their workspace is the untyped one
-// followed by type_sorted int32 [N] (the type of atom_sorted[k]: read coalesced by the walk, next to s_sorted) and rc2
-// float64 [T, T] (squared cutoffs, formed once).
-struct NLTypedExt {
-  int64_t type_sorted, rc2, total;
-};
-static NLTypedExt nl_typed_ext(int64_t base_total, int64_t N, int64_t T) {
-  NLTypedExt X{};
-  X.type_sorted = align256(base_total);
-  X.rc2 = align256(X.type_sorted + N * 4);
-  X.total = align256(X.rc2 + T * T * 8);
-  return X;
-}
+// followed by type_sorted int32 [N] and rc2 float64 [T, T] (nl_layout with T >= 1).
 
 // rc2 = cutoff_table^2 (symmetrise: of max(rc[a][b], rc[b][a])) and type_sorted[k] = type of atom_sorted[k].  A type outside
 // [0, T) is reported through `status` and replaced by 0, so that no walk ever indexes outside the table.
@@ -889,6 +905,32 @@ __global__ __launch_bounds__(256) void nl_typed_fill_padded_kernel(
   }
 }
 
+// ---- host side: one count driver and one fill driver behind the 14 entry points ---------------------------------------------
+// Every entry point is a form of the same list; the optional operand groups (nullptr: absent) say which:
+//
+//   entry point                                   | batched (NLFrames) | typed (NLTyped) | padded (NLPadded)
+//   nqa_neighbor_list_count                       |         -          |        -        |
+//   nqa_neighbor_list_count_typed                 |         -          |        x        |
+//   nqa_neighbor_list_batched_count               |         x          |        -        |
+//   nqa_neighbor_list_batched_count_typed         |         x          |        x        |
+//   nqa_neighbor_list_fill                        |         -          |        -        |        -
+//   nqa_neighbor_list_fill_typed                  |         -          |        x        |        -
+//   nqa_neighbor_list_fill_padded                 |         -          |        -        |        x
+//   nqa_neighbor_list_fill_padded_typed           |         -          |        x        |        x
+//   nqa_neighbor_list_batched_fill                |         x          |        -        |        -
+//   nqa_neighbor_list_batched_fill_typed          |         x          |        x        |        -
+//
+// and the four *_workspace_bytes are nl_layout(N, F or 0, T or 0).total.  A padded list is filled after a single-frame count.
+//
+// Launches of a count, in order (N == 0: plan and the final scan only):
+//   plan   nl_plan_kernel (1 x 1024)                  | batched: status word zeroed, nl_batched_plan_kernel (F x 256)
+//   bin    nl_bin_kernel                              | batched: nl_batched_bin_kernel
+//   scan of the B bins, place, order                  : the same kernels in every form
+//   typed: nl_typed_prep_kernel, then nl_typed_count_kernel (bin_off = atom_frame = nullptr for one frame)
+//   untyped: nl_count_kernel                          | batched: nl_batched_count_kernel
+//   scan of the N counts into rowptr (sets the overflow bit where there is a status word)
+// A fill is one launch of nl_fill_kernel, nl_batched_fill_kernel or nl_typed_fill_kernel (single and batched); a padded fill is
+// nl_pad_rowptr_kernel and then nl_fill_padded_kernel or nl_typed_fill_padded_kernel.
 static int nl_status(const char* fn) {
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) {
@@ -896,6 +938,130 @@ static int nl_status(const char* fn) {
     return NQA_ERR_LAUNCH;
   }
   return NQA_OK;
+}
+
+// Frames of a batched list.  The fills read F only.
+struct NLFrames {
+  const int64_t* frame_ptr;
+  int64_t F;
+};
+
+// Typed operands.  The fills read atom_types and T only.
+struct NLTyped {
+  const int64_t* atom_types;
+  const double* cutoff_table;
+  int64_t T;
+  int32_t symmetrise;
+};
+
+// Outputs of a capacity-padded fill beside the edges.
+struct NLPadded {
+  int32_t* rowptr_padded;
+  int32_t* src_sorted;
+  int32_t* status;
+};
+
+static bool nl_num_types_ok(int64_t T) { return T >= 1 && T <= 32768; }
+
+// `status`: required by the batched and the typed forms, nullptr for the plain single-frame count.  The batched forms zero it
+// here, once the arguments are accepted; the single-frame typed entry point zeroes it before it comes here.
+static int nl_count(const char* fn, const double* pos, const double* cell, const int32_t* pbc, double r_max, int64_t N,
+                    void* workspace, int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream,
+                    const NLFrames* fr, const NLTyped* ty) {
+  bool ok = N >= 0 && r_max > 0.0 && rowptr && (N == 0 || pos) && (status || (!fr && !ty));
+  if (fr) ok = ok && fr->F >= 1 && fr->F <= 2147483647LL && N + 8 * fr->F <= 2147483646LL && fr->frame_ptr;
+  if (ty) ok = ok && ty->cutoff_table && nl_num_types_ok(ty->T) && (N == 0 || ty->atom_types);
+  if (!ok) {
+    set_error(std::string(fn) + ": invalid argument");
+    return NQA_ERR_INVALID;
+  }
+  const int64_t F = fr ? fr->F : 0, B = N + 8 * (fr ? F : 1);
+  const NLLayout L = nl_layout(N, F, ty ? ty->T : 0);
+  if (!workspace || workspace_bytes < L.total) {
+    set_error(std::string(fn) + ": workspace missing or too small");
+    return NQA_ERR_WORKSPACE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const NLWork W = nl_work(workspace, L);
+  if (fr) {
+    if (hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return nl_status(fn);
+    hipLaunchKernelGGL(nl_batched_plan_kernel, dim3((unsigned)F), dim3(256), 0, s, pos, cell, pbc, fr->frame_ptr, r_max, N, F,
+                       W.hdr, W.bin_off, W.bin_count, status);
+  } else {
+    hipLaunchKernelGGL(nl_plan_kernel, dim3(1), dim3(1024), 0, s, pos, cell, pbc, r_max, N, B, W.hdr, W.bin_count);
+  }
+  if (N > 0) {
+    const unsigned g256 = (unsigned)((N + 255) / 256), g4 = (unsigned)((N + 3) / 4);
+    if (fr)
+      hipLaunchKernelGGL(nl_batched_bin_kernel, dim3(g256), dim3(256), 0, s, pos, fr->frame_ptr, N, F, W.hdr, W.bin_off,
+                         W.atom_frame, W.sfrac, W.ioff, W.key, W.val, W.bin_count);
+    else
+      hipLaunchKernelGGL(nl_bin_kernel, dim3(g256), dim3(256), 0, s, pos, N, W.hdr, W.sfrac, W.ioff, W.key, W.val, W.bin_count);
+    hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, B, W.bin_count, W.rowptr_bin, (int32_t*)nullptr);
+    hipLaunchKernelGGL(nl_place_kernel, dim3(g256), dim3(256), 0, s, N, W.key, W.val, W.rowptr_bin, W.atom_arrival);
+    hipLaunchKernelGGL(nl_order_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, B, W.rowptr_bin, W.atom_arrival, W.sfrac,
+                       W.ioff, W.atom_sorted, W.s_sorted, W.o_sorted);
+    if (ty) {
+      const int64_t n = N > ty->T * ty->T ? N : ty->T * ty->T;
+      hipLaunchKernelGGL(nl_typed_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, N, ty->T, ty->atom_types,
+                         ty->cutoff_table, ty->symmetrise, W.atom_sorted, W.type_sorted, W.rc2, status);
+      hipLaunchKernelGGL(nl_typed_count_kernel, dim3(g4), dim3(256), 0, s, N, W.hdr, W.bin_off, W.atom_frame, W.sfrac, W.ioff,
+                         W.rowptr_bin, W.atom_sorted, W.s_sorted, W.o_sorted, ty->atom_types, ty->T, W.type_sorted, W.rc2,
+                         W.counts);
+    } else if (fr) {
+      hipLaunchKernelGGL(nl_batched_count_kernel, dim3(g4), dim3(256), 0, s, N, W.hdr, W.bin_off, W.atom_frame, W.sfrac, W.ioff,
+                         W.rowptr_bin, W.atom_sorted, W.s_sorted, W.o_sorted, W.counts);
+    } else {
+      hipLaunchKernelGGL(nl_count_kernel, dim3(g4), dim3(256), 0, s, N, W.hdr, W.sfrac, W.ioff, W.rowptr_bin, W.atom_sorted,
+                         W.s_sorted, W.o_sorted, W.counts);
+    }
+  }
+  hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, N, W.counts, rowptr, status);  // status |= 1 on overflow
+  return nl_status(fn);
+}
+
+// `E`: the number of edges, or the (even) capacity of a padded list.
+static int nl_fill(const char* fn, const void* workspace, const int32_t* rowptr, int64_t N, int64_t E, int64_t* edge_index,
+                   double* shift, nqa_stream stream, const NLFrames* fr, const NLTyped* ty, const NLPadded* pad) {
+  bool ok = workspace && rowptr && E >= 0 && (E == 0 || (edge_index && shift));
+  if (fr) ok = ok && fr->F >= 1;
+  if (ty) ok = ok && nl_num_types_ok(ty->T) && (N <= 0 || ty->atom_types);
+  if (pad)
+    ok = ok && N > 0 && (E & 1) == 0 && E <= 2147483646LL && pad->rowptr_padded;
+  else
+    ok = ok && N >= 0;
+  if (!ok) {
+    const char* needs = !pad ? "" : ty ? " (needs atoms, types and an even capacity below 2^31)"
+                                       : " (needs atoms and an even capacity below 2^31)";
+    set_error(std::string(fn) + ": invalid argument" + needs);
+    return NQA_ERR_INVALID;
+  }
+  if (!pad && (N == 0 || E == 0)) return NQA_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const NLWork W = nl_work(workspace, nl_layout(N, fr ? fr->F : 0, ty ? ty->T : 0));
+  const dim3 g4((unsigned)((N + 3) / 4));
+  if (pad) {
+    hipLaunchKernelGGL(nl_pad_rowptr_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, N, E, rowptr,
+                       pad->rowptr_padded, pad->status);
+    if (ty)
+      hipLaunchKernelGGL(nl_typed_fill_padded_kernel, g4, dim3(256), 0, s, N, E, W.hdr, W.sfrac, W.ioff, W.rowptr_bin,
+                         W.atom_sorted, W.s_sorted, W.o_sorted, ty->atom_types, ty->T, W.type_sorted, W.rc2, rowptr, edge_index,
+                         shift, pad->src_sorted);
+    else
+      hipLaunchKernelGGL(nl_fill_padded_kernel, g4, dim3(256), 0, s, N, E, W.hdr, W.sfrac, W.ioff, W.rowptr_bin, W.atom_sorted,
+                         W.s_sorted, W.o_sorted, rowptr, edge_index, shift, pad->src_sorted);
+  } else if (ty) {
+    hipLaunchKernelGGL(nl_typed_fill_kernel, g4, dim3(256), 0, s, N, E, W.hdr, W.bin_off, W.atom_frame, W.sfrac, W.ioff,
+                       W.rowptr_bin, W.atom_sorted, W.s_sorted, W.o_sorted, ty->atom_types, ty->T, W.type_sorted, W.rc2, rowptr,
+                       edge_index, shift);
+  } else if (fr) {
+    hipLaunchKernelGGL(nl_batched_fill_kernel, g4, dim3(256), 0, s, N, E, W.hdr, W.bin_off, W.atom_frame, W.sfrac, W.ioff,
+                       W.rowptr_bin, W.atom_sorted, W.s_sorted, W.o_sorted, rowptr, edge_index, shift);
+  } else {
+    hipLaunchKernelGGL(nl_fill_kernel, g4, dim3(256), 0, s, N, E, W.hdr, W.sfrac, W.ioff, W.rowptr_bin, W.atom_sorted,
+                       W.s_sorted, W.o_sorted, rowptr, edge_index, shift);
+  }
+  return nl_status(fn);
 }
 
 }  // namespace nqa
@@ -906,324 +1072,106 @@ extern "C" {
 
 int64_t nqa_neighbor_list_workspace_bytes(int64_t num_atoms) {
   if (num_atoms < 0) return -1;
-  return nl_layout(num_atoms).total;
+  return nl_layout(num_atoms, 0, 0).total;
 }
 
-// Typed operands of a count (nullptr: the untyped list).
-struct NLTyped {
-  const int64_t* atom_types;
-  const double* cutoff_table;
-  int64_t T;
-  int32_t symmetrise;
-  int32_t* status;
-};
-
-static bool nl_typed_args_ok(const int64_t* atom_types, const double* cutoff_table, int64_t num_types, int64_t num_atoms) {
-  return cutoff_table != nullptr && num_types >= 1 && num_types <= 32768 && (num_atoms == 0 || atom_types != nullptr);
+int64_t nqa_neighbor_list_typed_workspace_bytes(int64_t num_atoms, int64_t num_types) {
+  if (num_atoms < 0 || !nl_num_types_ok(num_types)) return -1;
+  return nl_layout(num_atoms, 0, num_types).total;
 }
 
-static int nl_count_impl(const char* fn, const double* pos, const double* cell, const int32_t* pbc, double r_max,
-                         int64_t num_atoms, void* workspace, int64_t workspace_bytes, int32_t* rowptr, nqa_stream stream,
-                         const NLTyped* ty) {
-  if (num_atoms < 0 || !(r_max > 0.0) || !rowptr || (num_atoms > 0 && !pos) ||
-      (ty != nullptr && (!ty->status || !nl_typed_args_ok(ty->atom_types, ty->cutoff_table, ty->T, num_atoms)))) {
-    set_error(std::string(fn) + ": invalid argument");
-    return NQA_ERR_INVALID;
-  }
-  const NLLayout L = nl_layout(num_atoms);
-  const NLTypedExt X = nl_typed_ext(L.total, num_atoms, ty ? ty->T : 0);
-  if (!workspace || workspace_bytes < (ty ? X.total : L.total)) {
-    set_error(std::string(fn) + ": workspace missing or too small");
-    return NQA_ERR_WORKSPACE;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(workspace);
-  const int64_t N = num_atoms, B = N + 8;
-  NLHeader* h = reinterpret_cast<NLHeader*>(w + L.header);
-  double* sfrac = reinterpret_cast<double*>(w + L.sfrac);
-  int32_t* ioff = reinterpret_cast<int32_t*>(w + L.ioff);
-  int32_t* key = reinterpret_cast<int32_t*>(w + L.key);
-  int32_t* val = reinterpret_cast<int32_t*>(w + L.val);
-  int32_t* bin_count = reinterpret_cast<int32_t*>(w + L.bin_count);
-  int32_t* rowptr_bin = reinterpret_cast<int32_t*>(w + L.rowptr_bin);
-  int32_t* atom_sorted = reinterpret_cast<int32_t*>(w + L.atom_sorted);
-  int32_t* atom_arrival = reinterpret_cast<int32_t*>(w + L.dummy_other);
-  double* s_sorted = reinterpret_cast<double*>(w + L.s_sorted);
-  int32_t* o_sorted = reinterpret_cast<int32_t*>(w + L.o_sorted);
-  int32_t* counts = reinterpret_cast<int32_t*>(w + L.counts);
-  hipLaunchKernelGGL(nl_plan_kernel, dim3(1), dim3(1024), 0, s, pos, cell, pbc, r_max, N, B, h, bin_count);
-  if (N > 0) {
-    const unsigned g256 = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(nl_bin_kernel, dim3(g256), dim3(256), 0, s, pos, N, h, sfrac, ioff, key, val, bin_count);
-    hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, B, bin_count, rowptr_bin, (int32_t*)nullptr);
-    hipLaunchKernelGGL(nl_place_kernel, dim3(g256), dim3(256), 0, s, N, key, val, rowptr_bin, atom_arrival);
-    hipLaunchKernelGGL(nl_order_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, B, rowptr_bin, atom_arrival, sfrac,
-                       ioff, atom_sorted, s_sorted, o_sorted);
-    if (ty == nullptr) {
-      hipLaunchKernelGGL(nl_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, h, sfrac, ioff,
-                         rowptr_bin, atom_sorted, s_sorted, o_sorted, counts);
-    } else {
-      int32_t* type_sorted = reinterpret_cast<int32_t*>(w + X.type_sorted);
-      double* rc2 = reinterpret_cast<double*>(w + X.rc2);
-      const int64_t n = N > ty->T * ty->T ? N : ty->T * ty->T;
-      hipLaunchKernelGGL(nl_typed_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, N, ty->T, ty->atom_types,
-                         ty->cutoff_table, ty->symmetrise, atom_sorted, type_sorted, rc2, ty->status);
-      hipLaunchKernelGGL(nl_typed_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, h, (const int32_t*)nullptr,
-                         (const int32_t*)nullptr, sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, ty->atom_types,
-                         ty->T, type_sorted, rc2, counts);
-    }
-  }
-  hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, N, counts, rowptr, ty ? ty->status : (int32_t*)nullptr);
-  return nl_status(fn);
+int64_t nqa_neighbor_list_batched_workspace_bytes(int64_t num_atoms, int64_t num_frames) {
+  if (num_atoms < 0 || num_frames < 1) return -1;
+  return nl_layout(num_atoms, num_frames, 0).total;
+}
+
+int64_t nqa_neighbor_list_batched_typed_workspace_bytes(int64_t num_atoms, int64_t num_frames, int64_t num_types) {
+  if (num_atoms < 0 || num_frames < 1 || !nl_num_types_ok(num_types)) return -1;
+  return nl_layout(num_atoms, num_frames, num_types).total;
 }
 
 int nqa_neighbor_list_count(const double* pos, const double* cell, const int32_t* pbc, double r_max, int64_t num_atoms,
                             void* workspace, int64_t workspace_bytes, int32_t* rowptr, nqa_stream stream) {
-  return nl_count_impl("nqa_neighbor_list_count", pos, cell, pbc, r_max, num_atoms, workspace, workspace_bytes, rowptr, stream,
-                       nullptr);
-}
-
-int64_t nqa_neighbor_list_typed_workspace_bytes(int64_t num_atoms, int64_t num_types) {
-  if (num_atoms < 0 || num_types < 1 || num_types > 32768) return -1;
-  return nl_typed_ext(nl_layout(num_atoms).total, num_atoms, num_types).total;
+  return nl_count("nqa_neighbor_list_count", pos, cell, pbc, r_max, num_atoms, workspace, workspace_bytes, rowptr, nullptr,
+                  stream, nullptr, nullptr);
 }
 
 int nqa_neighbor_list_count_typed(const double* pos, const double* cell, const int32_t* pbc, double r_max,
                                   const int64_t* atom_types, const double* cutoff_table, int64_t num_types, int32_t symmetrise,
                                   int64_t num_atoms, void* workspace, int64_t workspace_bytes, int32_t* rowptr, int32_t* status,
                                   nqa_stream stream) {
-  const NLTyped ty{atom_types, cutoff_table, num_types, symmetrise, status};
+  const NLTyped ty{atom_types, cutoff_table, num_types, symmetrise};
   if (status != nullptr &&
       hipMemsetAsync(status, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)) != hipSuccess)
     return nl_status("nqa_neighbor_list_count_typed");
-  return nl_count_impl("nqa_neighbor_list_count_typed", pos, cell, pbc, r_max, num_atoms, workspace, workspace_bytes, rowptr,
-                       stream, &ty);
-}
-
-int nqa_neighbor_list_fill_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types, int64_t num_atoms,
-                                 int64_t num_types, int64_t num_edges, int64_t* edge_index, double* edge_cell_shift,
-                                 nqa_stream stream) {
-  if (num_atoms < 0 || num_edges < 0 || !workspace || !rowptr || num_types < 1 || num_types > 32768 ||
-      (num_atoms > 0 && !atom_types) || (num_edges > 0 && (!edge_index || !edge_cell_shift))) {
-    set_error("nqa_neighbor_list_fill_typed: invalid argument");
-    return NQA_ERR_INVALID;
-  }
-  if (num_atoms == 0 || num_edges == 0) return NQA_OK;
-  const NLLayout L = nl_layout(num_atoms);
-  const NLTypedExt X = nl_typed_ext(L.total, num_atoms, num_types);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const char* w = static_cast<const char*>(workspace);
-  hipLaunchKernelGGL(nl_typed_fill_kernel, dim3((unsigned)((num_atoms + 3) / 4)), dim3(256), 0, s, num_atoms, num_edges,
-                     reinterpret_cast<const NLHeader*>(w + L.header), (const int32_t*)nullptr, (const int32_t*)nullptr,
-                     reinterpret_cast<const double*>(w + L.sfrac), reinterpret_cast<const int32_t*>(w + L.ioff),
-                     reinterpret_cast<const int32_t*>(w + L.rowptr_bin), reinterpret_cast<const int32_t*>(w + L.atom_sorted),
-                     reinterpret_cast<const double*>(w + L.s_sorted), reinterpret_cast<const int32_t*>(w + L.o_sorted),
-                     atom_types, num_types, reinterpret_cast<const int32_t*>(w + X.type_sorted),
-                     reinterpret_cast<const double*>(w + X.rc2), rowptr, edge_index, edge_cell_shift);
-  return nl_status("nqa_neighbor_list_fill_typed");
-}
-
-int nqa_neighbor_list_fill_padded_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types,
-                                        int64_t num_atoms, int64_t num_types, int64_t edge_capacity, int32_t* rowptr_padded,
-                                        int64_t* edge_index, double* edge_cell_shift, int32_t* src_sorted, int32_t* status,
-                                        nqa_stream stream) {
-  if (num_atoms <= 0 || edge_capacity < 0 || (edge_capacity & 1) != 0 || edge_capacity > 2147483646LL || !workspace ||
-      !rowptr || !rowptr_padded || !atom_types || num_types < 1 || num_types > 32768 ||
-      (edge_capacity > 0 && (!edge_index || !edge_cell_shift))) {
-    set_error("nqa_neighbor_list_fill_padded_typed: invalid argument (needs atoms, types and an even capacity below 2^31)");
-    return NQA_ERR_INVALID;
-  }
-  const NLLayout L = nl_layout(num_atoms);
-  const NLTypedExt X = nl_typed_ext(L.total, num_atoms, num_types);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const char* w = static_cast<const char*>(workspace);
-  hipLaunchKernelGGL(nl_pad_rowptr_kernel, dim3((unsigned)((num_atoms + 1 + 255) / 256)), dim3(256), 0, s, num_atoms,
-                     edge_capacity, rowptr, rowptr_padded, status);
-  hipLaunchKernelGGL(nl_typed_fill_padded_kernel, dim3((unsigned)((num_atoms + 3) / 4)), dim3(256), 0, s, num_atoms,
-                     edge_capacity, reinterpret_cast<const NLHeader*>(w + L.header),
-                     reinterpret_cast<const double*>(w + L.sfrac), reinterpret_cast<const int32_t*>(w + L.ioff),
-                     reinterpret_cast<const int32_t*>(w + L.rowptr_bin), reinterpret_cast<const int32_t*>(w + L.atom_sorted),
-                     reinterpret_cast<const double*>(w + L.s_sorted), reinterpret_cast<const int32_t*>(w + L.o_sorted),
-                     atom_types, num_types, reinterpret_cast<const int32_t*>(w + X.type_sorted),
-                     reinterpret_cast<const double*>(w + X.rc2), rowptr, edge_index, edge_cell_shift, src_sorted);
-  return nl_status("nqa_neighbor_list_fill_padded_typed");
-}
-
-int nqa_neighbor_list_fill(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t num_edges,
-                           int64_t* edge_index, double* edge_cell_shift, nqa_stream stream) {
-  if (num_atoms < 0 || num_edges < 0 || !workspace || !rowptr ||
-      (num_edges > 0 && (!edge_index || !edge_cell_shift))) {
-    set_error("nqa_neighbor_list_fill: invalid argument");
-    return NQA_ERR_INVALID;
-  }
-  if (num_atoms == 0 || num_edges == 0) return NQA_OK;
-  const NLLayout L = nl_layout(num_atoms);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const char* w = static_cast<const char*>(workspace);
-  hipLaunchKernelGGL(nl_fill_kernel, dim3((unsigned)((num_atoms + 3) / 4)), dim3(256), 0, s, num_atoms, num_edges,
-                     reinterpret_cast<const NLHeader*>(w + L.header), reinterpret_cast<const double*>(w + L.sfrac),
-                     reinterpret_cast<const int32_t*>(w + L.ioff), reinterpret_cast<const int32_t*>(w + L.rowptr_bin),
-                     reinterpret_cast<const int32_t*>(w + L.atom_sorted), reinterpret_cast<const double*>(w + L.s_sorted),
-                     reinterpret_cast<const int32_t*>(w + L.o_sorted), rowptr, edge_index, edge_cell_shift);
-  return nl_status("nqa_neighbor_list_fill");
-}
-
-int nqa_neighbor_list_fill_padded(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t edge_capacity,
-                                  int32_t* rowptr_padded, int64_t* edge_index, double* edge_cell_shift, int32_t* src_sorted,
-                                  int32_t* status, nqa_stream stream) {
-  if (num_atoms <= 0 || edge_capacity < 0 || (edge_capacity & 1) != 0 || edge_capacity > 2147483646LL || !workspace ||
-      !rowptr || !rowptr_padded || (edge_capacity > 0 && (!edge_index || !edge_cell_shift))) {
-    set_error("nqa_neighbor_list_fill_padded: invalid argument (needs atoms and an even capacity below 2^31)");
-    return NQA_ERR_INVALID;
-  }
-  const NLLayout L = nl_layout(num_atoms);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const char* w = static_cast<const char*>(workspace);
-  hipLaunchKernelGGL(nl_pad_rowptr_kernel, dim3((unsigned)((num_atoms + 1 + 255) / 256)), dim3(256), 0, s, num_atoms,
-                     edge_capacity, rowptr, rowptr_padded, status);
-  hipLaunchKernelGGL(nl_fill_padded_kernel, dim3((unsigned)((num_atoms + 3) / 4)), dim3(256), 0, s, num_atoms, edge_capacity,
-                     reinterpret_cast<const NLHeader*>(w + L.header), reinterpret_cast<const double*>(w + L.sfrac),
-                     reinterpret_cast<const int32_t*>(w + L.ioff), reinterpret_cast<const int32_t*>(w + L.rowptr_bin),
-                     reinterpret_cast<const int32_t*>(w + L.atom_sorted), reinterpret_cast<const double*>(w + L.s_sorted),
-                     reinterpret_cast<const int32_t*>(w + L.o_sorted), rowptr, edge_index, edge_cell_shift, src_sorted);
-  return nl_status("nqa_neighbor_list_fill_padded");
-}
-
-int64_t nqa_neighbor_list_batched_workspace_bytes(int64_t num_atoms, int64_t num_frames) {
-  if (num_atoms < 0 || num_frames < 1) return -1;
-  int64_t bo, af;
-  return nl_batched_layout(num_atoms, num_frames, &bo, &af).total;
-}
-
-static int nl_batched_count_impl(const char* fn, const double* pos, const double* cell, const int32_t* pbc,
-                                 const int64_t* frame_ptr, double r_max, int64_t num_atoms, int64_t num_frames,
-                                 void* workspace, int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream,
-                                 const NLTyped* ty) {
-  if (num_atoms < 0 || num_frames < 1 || num_frames > 2147483647LL || num_atoms + 8 * num_frames > 2147483646LL ||
-      !(r_max > 0.0) || !rowptr || !status || !frame_ptr || (num_atoms > 0 && !pos) ||
-      (ty != nullptr && !nl_typed_args_ok(ty->atom_types, ty->cutoff_table, ty->T, num_atoms))) {
-    set_error(std::string(fn) + ": invalid argument");
-    return NQA_ERR_INVALID;
-  }
-  int64_t o_bin_off, o_atom_frame;
-  const NLLayout L = nl_batched_layout(num_atoms, num_frames, &o_bin_off, &o_atom_frame);
-  const NLTypedExt X = nl_typed_ext(L.total, num_atoms, ty ? ty->T : 0);
-  if (!workspace || workspace_bytes < (ty ? X.total : L.total)) {
-    set_error(std::string(fn) + ": workspace missing or too small");
-    return NQA_ERR_WORKSPACE;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(workspace);
-  const int64_t N = num_atoms, F = num_frames, B = N + 8 * F;
-  NLHeader* hdr = reinterpret_cast<NLHeader*>(w + L.header);
-  int32_t* bin_off = reinterpret_cast<int32_t*>(w + o_bin_off);
-  int32_t* atom_frame = reinterpret_cast<int32_t*>(w + o_atom_frame);
-  double* sfrac = reinterpret_cast<double*>(w + L.sfrac);
-  int32_t* ioff = reinterpret_cast<int32_t*>(w + L.ioff);
-  int32_t* key = reinterpret_cast<int32_t*>(w + L.key);
-  int32_t* val = reinterpret_cast<int32_t*>(w + L.val);
-  int32_t* bin_count = reinterpret_cast<int32_t*>(w + L.bin_count);
-  int32_t* rowptr_bin = reinterpret_cast<int32_t*>(w + L.rowptr_bin);
-  int32_t* atom_sorted = reinterpret_cast<int32_t*>(w + L.atom_sorted);
-  int32_t* atom_arrival = reinterpret_cast<int32_t*>(w + L.dummy_other);
-  double* s_sorted = reinterpret_cast<double*>(w + L.s_sorted);
-  int32_t* o_sorted = reinterpret_cast<int32_t*>(w + L.o_sorted);
-  int32_t* counts = reinterpret_cast<int32_t*>(w + L.counts);
-  if (hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess) return nl_status(fn);
-  hipLaunchKernelGGL(nl_batched_plan_kernel, dim3((unsigned)F), dim3(256), 0, s, pos, cell, pbc, frame_ptr, r_max, N, F, hdr,
-                     bin_off, bin_count, status);
-  if (N > 0) {
-    const unsigned g256 = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(nl_batched_bin_kernel, dim3(g256), dim3(256), 0, s, pos, frame_ptr, N, F, hdr, bin_off, atom_frame, sfrac,
-                       ioff, key, val, bin_count);
-    hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, B, bin_count, rowptr_bin, (int32_t*)nullptr);
-    hipLaunchKernelGGL(nl_place_kernel, dim3(g256), dim3(256), 0, s, N, key, val, rowptr_bin, atom_arrival);
-    hipLaunchKernelGGL(nl_order_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, B, rowptr_bin, atom_arrival, sfrac,
-                       ioff, atom_sorted, s_sorted, o_sorted);
-    if (ty == nullptr) {
-      hipLaunchKernelGGL(nl_batched_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, hdr, bin_off, atom_frame,
-                         sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, counts);
-    } else {
-      int32_t* type_sorted = reinterpret_cast<int32_t*>(w + X.type_sorted);
-      double* rc2 = reinterpret_cast<double*>(w + X.rc2);
-      const int64_t n = N > ty->T * ty->T ? N : ty->T * ty->T;
-      hipLaunchKernelGGL(nl_typed_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, N, ty->T, ty->atom_types,
-                         ty->cutoff_table, ty->symmetrise, atom_sorted, type_sorted, rc2, status);
-      hipLaunchKernelGGL(nl_typed_count_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, N, hdr, bin_off, atom_frame,
-                         sfrac, ioff, rowptr_bin, atom_sorted, s_sorted, o_sorted, ty->atom_types, ty->T, type_sorted, rc2,
-                         counts);
-    }
-  }
-  hipLaunchKernelGGL(nl_scan_kernel, dim3(1), dim3(1024), 0, s, N, counts, rowptr, status);  // status |= 1 on overflow
-  return nl_status(fn);
+  return nl_count("nqa_neighbor_list_count_typed", pos, cell, pbc, r_max, num_atoms, workspace, workspace_bytes, rowptr, status,
+                  stream, nullptr, &ty);
 }
 
 int nqa_neighbor_list_batched_count(const double* pos, const double* cell, const int32_t* pbc, const int64_t* frame_ptr,
                                     double r_max, int64_t num_atoms, int64_t num_frames, void* workspace,
                                     int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream) {
-  return nl_batched_count_impl("nqa_neighbor_list_batched_count", pos, cell, pbc, frame_ptr, r_max, num_atoms, num_frames,
-                               workspace, workspace_bytes, rowptr, status, stream, nullptr);
-}
-
-int64_t nqa_neighbor_list_batched_typed_workspace_bytes(int64_t num_atoms, int64_t num_frames, int64_t num_types) {
-  if (num_atoms < 0 || num_frames < 1 || num_types < 1 || num_types > 32768) return -1;
-  int64_t bo, af;
-  return nl_typed_ext(nl_batched_layout(num_atoms, num_frames, &bo, &af).total, num_atoms, num_types).total;
+  const NLFrames fr{frame_ptr, num_frames};
+  return nl_count("nqa_neighbor_list_batched_count", pos, cell, pbc, r_max, num_atoms, workspace, workspace_bytes, rowptr, status,
+                  stream, &fr, nullptr);
 }
 
 int nqa_neighbor_list_batched_count_typed(const double* pos, const double* cell, const int32_t* pbc, const int64_t* frame_ptr,
                                           double r_max, const int64_t* atom_types, const double* cutoff_table,
                                           int64_t num_types, int64_t num_atoms, int64_t num_frames, void* workspace,
                                           int64_t workspace_bytes, int32_t* rowptr, int32_t* status, nqa_stream stream) {
-  const NLTyped ty{atom_types, cutoff_table, num_types, 0, status};
-  return nl_batched_count_impl("nqa_neighbor_list_batched_count_typed", pos, cell, pbc, frame_ptr, r_max, num_atoms, num_frames,
-                               workspace, workspace_bytes, rowptr, status, stream, &ty);
+  const NLFrames fr{frame_ptr, num_frames};
+  const NLTyped ty{atom_types, cutoff_table, num_types, 0};
+  return nl_count("nqa_neighbor_list_batched_count_typed", pos, cell, pbc, r_max, num_atoms, workspace, workspace_bytes, rowptr,
+                  status, stream, &fr, &ty);
+}
+
+int nqa_neighbor_list_fill(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t num_edges,
+                           int64_t* edge_index, double* edge_cell_shift, nqa_stream stream) {
+  return nl_fill("nqa_neighbor_list_fill", workspace, rowptr, num_atoms, num_edges, edge_index, edge_cell_shift, stream, nullptr,
+                 nullptr, nullptr);
+}
+
+int nqa_neighbor_list_fill_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types, int64_t num_atoms,
+                                 int64_t num_types, int64_t num_edges, int64_t* edge_index, double* edge_cell_shift,
+                                 nqa_stream stream) {
+  const NLTyped ty{atom_types, nullptr, num_types, 0};
+  return nl_fill("nqa_neighbor_list_fill_typed", workspace, rowptr, num_atoms, num_edges, edge_index, edge_cell_shift, stream,
+                 nullptr, &ty, nullptr);
+}
+
+int nqa_neighbor_list_fill_padded(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t edge_capacity,
+                                  int32_t* rowptr_padded, int64_t* edge_index, double* edge_cell_shift, int32_t* src_sorted,
+                                  int32_t* status, nqa_stream stream) {
+  const NLPadded pad{rowptr_padded, src_sorted, status};
+  return nl_fill("nqa_neighbor_list_fill_padded", workspace, rowptr, num_atoms, edge_capacity, edge_index, edge_cell_shift,
+                 stream, nullptr, nullptr, &pad);
+}
+
+int nqa_neighbor_list_fill_padded_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types,
+                                        int64_t num_atoms, int64_t num_types, int64_t edge_capacity, int32_t* rowptr_padded,
+                                        int64_t* edge_index, double* edge_cell_shift, int32_t* src_sorted, int32_t* status,
+                                        nqa_stream stream) {
+  const NLTyped ty{atom_types, nullptr, num_types, 0};
+  const NLPadded pad{rowptr_padded, src_sorted, status};
+  return nl_fill("nqa_neighbor_list_fill_padded_typed", workspace, rowptr, num_atoms, edge_capacity, edge_index, edge_cell_shift,
+                 stream, nullptr, &ty, &pad);
+}
+
+int nqa_neighbor_list_batched_fill(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t num_frames,
+                                   int64_t num_edges, int64_t* edge_index, double* edge_cell_shift, nqa_stream stream) {
+  const NLFrames fr{nullptr, num_frames};
+  return nl_fill("nqa_neighbor_list_batched_fill", workspace, rowptr, num_atoms, num_edges, edge_index, edge_cell_shift, stream,
+                 &fr, nullptr, nullptr);
 }
 
 int nqa_neighbor_list_batched_fill_typed(const void* workspace, const int32_t* rowptr, const int64_t* atom_types,
                                          int64_t num_atoms, int64_t num_frames, int64_t num_types, int64_t num_edges,
                                          int64_t* edge_index, double* edge_cell_shift, nqa_stream stream) {
-  if (num_atoms < 0 || num_frames < 1 || num_edges < 0 || !workspace || !rowptr || num_types < 1 || num_types > 32768 ||
-      (num_atoms > 0 && !atom_types) || (num_edges > 0 && (!edge_index || !edge_cell_shift))) {
-    set_error("nqa_neighbor_list_batched_fill_typed: invalid argument");
-    return NQA_ERR_INVALID;
-  }
-  if (num_atoms == 0 || num_edges == 0) return NQA_OK;
-  int64_t o_bin_off, o_atom_frame;
-  const NLLayout L = nl_batched_layout(num_atoms, num_frames, &o_bin_off, &o_atom_frame);
-  const NLTypedExt X = nl_typed_ext(L.total, num_atoms, num_types);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const char* w = static_cast<const char*>(workspace);
-  hipLaunchKernelGGL(nl_typed_fill_kernel, dim3((unsigned)((num_atoms + 3) / 4)), dim3(256), 0, s, num_atoms, num_edges,
-                     reinterpret_cast<const NLHeader*>(w + L.header), reinterpret_cast<const int32_t*>(w + o_bin_off),
-                     reinterpret_cast<const int32_t*>(w + o_atom_frame), reinterpret_cast<const double*>(w + L.sfrac),
-                     reinterpret_cast<const int32_t*>(w + L.ioff), reinterpret_cast<const int32_t*>(w + L.rowptr_bin),
-                     reinterpret_cast<const int32_t*>(w + L.atom_sorted), reinterpret_cast<const double*>(w + L.s_sorted),
-                     reinterpret_cast<const int32_t*>(w + L.o_sorted), atom_types, num_types,
-                     reinterpret_cast<const int32_t*>(w + X.type_sorted), reinterpret_cast<const double*>(w + X.rc2), rowptr,
-                     edge_index, edge_cell_shift);
-  return nl_status("nqa_neighbor_list_batched_fill_typed");
-}
-
-int nqa_neighbor_list_batched_fill(const void* workspace, const int32_t* rowptr, int64_t num_atoms, int64_t num_frames,
-                                   int64_t num_edges, int64_t* edge_index, double* edge_cell_shift, nqa_stream stream) {
-  if (num_atoms < 0 || num_frames < 1 || num_edges < 0 || !workspace || !rowptr ||
-      (num_edges > 0 && (!edge_index || !edge_cell_shift))) {
-    set_error("nqa_neighbor_list_batched_fill: invalid argument");
-    return NQA_ERR_INVALID;
-  }
-  if (num_atoms == 0 || num_edges == 0) return NQA_OK;
-  int64_t o_bin_off, o_atom_frame;
-  const NLLayout L = nl_batched_layout(num_atoms, num_frames, &o_bin_off, &o_atom_frame);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const char* w = static_cast<const char*>(workspace);
-  hipLaunchKernelGGL(nl_batched_fill_kernel, dim3((unsigned)((num_atoms + 3) / 4)), dim3(256), 0, s, num_atoms, num_edges,
-                     reinterpret_cast<const NLHeader*>(w + L.header), reinterpret_cast<const int32_t*>(w + o_bin_off),
-                     reinterpret_cast<const int32_t*>(w + o_atom_frame), reinterpret_cast<const double*>(w + L.sfrac),
-                     reinterpret_cast<const int32_t*>(w + L.ioff), reinterpret_cast<const int32_t*>(w + L.rowptr_bin),
-                     reinterpret_cast<const int32_t*>(w + L.atom_sorted), reinterpret_cast<const double*>(w + L.s_sorted),
-                     reinterpret_cast<const int32_t*>(w + L.o_sorted), rowptr, edge_index, edge_cell_shift);
-  return nl_status("nqa_neighbor_list_batched_fill");
+  const NLFrames fr{nullptr, num_frames};
+  const NLTyped ty{atom_types, nullptr, num_types, 0};
+  return nl_fill("nqa_neighbor_list_batched_fill_typed", workspace, rowptr, num_atoms, num_edges, edge_index, edge_cell_shift,
+                 stream, &fr, &ty, nullptr);
 }
 
 }  // extern "C"

@@ -38,7 +38,7 @@ def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p()
 
 
-def _complete_cell(cell64: torch.Tensor, pbc: Tuple[bool, bool, bool]) -> torch.Tensor:
+def _complete_cell_host(cell64: torch.Tensor, pbc: Tuple[bool, bool, bool]) -> torch.Tensor:
     """Cells with zero lattice vectors along non-periodic directions (ASE slabs / wires / molecules with pbc = (T, T, F)
     and c = 0): complete them with unit vectors orthogonal to the span of the others, as ``ase.geometry.complete_cell``
     does and the reference's backends accept -- the kernel inverts the cell.  A zero (or linearly dependent) vector
@@ -47,10 +47,6 @@ def _complete_cell(cell64: torch.Tensor, pbc: Tuple[bool, bool, bool]) -> torch.
     The check reads the nine numbers on the host: one small copy per call, next to the one synchronisation the
     neighbour list needs anyway (the data-dependent edge count).  Deliberately not memoised on the tensor's storage:
     a recycled allocation would look like the same cell."""
-    return _complete_cell_host(cell64, pbc)
-
-
-def _complete_cell_host(cell64: torch.Tensor, pbc: Tuple[bool, bool, bool]) -> torch.Tensor:
     import numpy as np
 
     c = cell64.detach().cpu().numpy().copy()
@@ -95,6 +91,9 @@ def _complete_cell_host(cell64: torch.Tensor, pbc: Tuple[bool, bool, bool]) -> t
     if abs(np.linalg.det(c)) < 1e-12:
         raise ValueError("cell vectors are linearly dependent")
     return torch.as_tensor(c, dtype=torch.float64, device=cell64.device).contiguous()
+
+
+_complete_cell = _complete_cell_host  # (the name the single-frame callers use; the batched list completes cells on the device)
 
 
 _NL_BAD_TYPE = 32  # status bit of the typed entry points: an atom type outside [0, num_types)
@@ -160,6 +159,86 @@ def _types_for(table: Optional[CutoffTable], atom_types: Optional[torch.Tensor],
     return types
 
 
+def _norm_pbc(pbc: Union[bool, Tuple[bool, bool, bool], torch.Tensor]) -> Tuple[bool, bool, bool]:
+    if isinstance(pbc, bool):
+        return (pbc,) * 3
+    if isinstance(pbc, torch.Tensor):
+        pbc = pbc.detach().cpu().view(-1).tolist()
+    return tuple(bool(b) for b in pbc)
+
+
+# ---- the library calls: every form of the list goes through these three -------------------------------------------------
+# The operands that are there pick the entry point: ``frame_ptr`` / ``F`` (a batched list), ``types`` and ``table`` / ``T`` (a
+# typed list), ``padded`` (the extra outputs of a capacity-padded fill).
+
+
+def _nl_workspace_bytes(lib, N: int, F: Optional[int] = None, T: int = 0) -> int:
+    if F is None:
+        return lib.nqa_neighbor_list_typed_workspace_bytes(N, T) if T else lib.nqa_neighbor_list_workspace_bytes(N)
+    if T:
+        return lib.nqa_neighbor_list_batched_typed_workspace_bytes(N, F, T)
+    return lib.nqa_neighbor_list_batched_workspace_bytes(N, F)
+
+
+def _nl_count(lib, pos64, cell64, pbc32, r_max: float, N: int, ws, ws_bytes: int, rowptr, stream, frame_ptr=None, types=None,
+              table=None, symmetrise: bool = False, status=None) -> None:
+    """The count pass into ``rowptr`` [N + 1].  ``table``: the cutoffs [T, T] on the device (with ``types`` [N]); ``status``: the
+    int32 word of the batched and the typed forms; ``symmetrise``: single-frame typed lists only."""
+    batched, typed = frame_ptr is not None, table is not None
+    if batched:
+        fn = lib.nqa_neighbor_list_batched_count_typed if typed else lib.nqa_neighbor_list_batched_count
+    else:
+        fn = lib.nqa_neighbor_list_count_typed if typed else lib.nqa_neighbor_list_count
+    args = [_ptr(pos64), _ptr(cell64), _ptr(pbc32)] + ([_ptr(frame_ptr)] if batched else []) + [float(r_max)]
+    if typed:
+        args += [_ptr(types), _ptr(table), table.shape[0]] + ([] if batched else [int(bool(symmetrise))])
+    args += [N] + ([frame_ptr.numel() - 1] if batched else []) + [_ptr(ws), ws_bytes, _ptr(rowptr)]
+    if batched or typed:
+        args.append(_ptr(status))
+    _lib.check(fn(*args, stream), fn.__name__)
+
+
+def _nl_fill(lib, ws, rowptr, N: int, E: int, edge_index, shifts, stream, F: Optional[int] = None, types=None, T: int = 0,
+             padded=None) -> None:
+    """The fill pass after a count with the same ``F`` / ``T``.  ``padded = (rowptr_padded, src32, status)``: the capacity-padded
+    fill, ``E`` is then the capacity."""
+    batched, typed = F is not None, types is not None
+    if padded is not None:
+        fn = lib.nqa_neighbor_list_fill_padded_typed if typed else lib.nqa_neighbor_list_fill_padded
+    elif batched:
+        fn = lib.nqa_neighbor_list_batched_fill_typed if typed else lib.nqa_neighbor_list_batched_fill
+    else:
+        fn = lib.nqa_neighbor_list_fill_typed if typed else lib.nqa_neighbor_list_fill
+    args = [_ptr(ws), _ptr(rowptr)] + ([_ptr(types)] if typed else []) + [N] + ([F] if batched else [])
+    args += ([T] if typed else []) + [E]
+    if padded is None:
+        args += [_ptr(edge_index), _ptr(shifts)]
+    else:
+        args += [_ptr(padded[0]), _ptr(edge_index), _ptr(shifts), _ptr(padded[1]), _ptr(padded[2])]
+    _lib.check(fn(*args, stream), fn.__name__)
+
+
+_BATCHED_STATUS_ERRORS = (
+    (1, RuntimeError, "neighbour list has more than 2^31 - 1 edges"),
+    (2, ValueError, "a lattice vector is zero but the direction is periodic"),
+    (4, ValueError, "cell vectors are linearly dependent"),
+    (8, ValueError, "the frame sizes (num_nodes / batch) do not add up to the number of atoms"),
+    (16, ValueError, "Periodic boundary conditions requested but no cell was provided."),
+)
+
+
+def _raise_for_status(E: int, bad: int, T: int) -> None:
+    """The errors a count reports on the device: ``bad`` is its status word (0 where the form has none), ``E`` the edge count
+    (negative after an int32 overflow of the scan)."""
+    if bad & _NL_BAD_TYPE:
+        raise ValueError(_BAD_TYPE_MSG.format(T=T))
+    for bit, exc, msg in _BATCHED_STATUS_ERRORS:
+        if bad & bit:
+            raise exc(msg)
+    if E < 0:
+        raise RuntimeError(_BATCHED_STATUS_ERRORS[0][2])
+
+
 def _compute_neighborlist_single_frame(
     pos: torch.Tensor,
     r_max: float,
@@ -177,10 +256,7 @@ def _compute_neighborlist_single_frame(
     table = as_cutoff_table(per_edge_type_cutoff, type_names, r_max)
     if not pos.is_cuda:
         raise RuntimeError("the `nequip_amd` neighbour list runs on the GPU: positions must be a CUDA/HIP tensor")
-    if isinstance(pbc, bool):
-        pbc = (pbc,) * 3
-    elif isinstance(pbc, torch.Tensor):
-        pbc = tuple(bool(b) for b in pbc.detach().cpu().view(-1).tolist())
+    pbc = _norm_pbc(pbc)
     if cell is None and any(pbc):
         raise ValueError("Periodic boundary conditions requested but no cell was provided.")
     lib = _lib.load()
@@ -193,45 +269,24 @@ def _compute_neighborlist_single_frame(
         cell64 = _complete_cell(cell64, pbc)
     pbc_dev = torch.tensor([int(b) for b in pbc], dtype=torch.int32, device=device)
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    if table is not None:
-        types = _types_for(table, atom_types, N, device)
-        T = table.num_types
-        ws_bytes = lib.nqa_neighbor_list_typed_workspace_bytes(N, T)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+    types = _types_for(table, atom_types, N, device)
+    T = table.num_types if table is not None else 0
+    ws_bytes = _nl_workspace_bytes(lib, N, T=T)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+    if table is None:
+        rowptr, status = torch.empty(N + 1, dtype=torch.int32, device=device), None
+    else:
         aux = torch.empty(N + 2, dtype=torch.int32, device=device)  # rowptr [N + 1] and the status word, read back as one pair
         rowptr, status = aux[:N + 1], aux[N + 1:]
-        with torch.cuda.device(device):
-            rc = lib.nqa_neighbor_list_count_typed(_ptr(pos64), _ptr(cell64), _ptr(pbc_dev), float(r_max), _ptr(types),
-                                                   _ptr(table.on(device)), T, int(bool(symmetrise)), N, _ptr(ws), ws_bytes, _ptr(rowptr),
-                                                   _ptr(status), stream)
-            _lib.check(rc, "nqa_neighbor_list_count_typed")
-            E, bad = aux[N:].tolist()  # the one synchronisation: the edge count is data dependent
-            if bad & _NL_BAD_TYPE:
-                raise ValueError(_BAD_TYPE_MSG.format(T=T))
-            if E < 0 or bad & 1:
-                raise RuntimeError("neighbour list has more than 2^31 - 1 edges")
-            edge_index = torch.empty((2, E), dtype=torch.int64, device=device)
-            shifts = torch.empty((E, 3), dtype=torch.float64, device=device)
-            rc = lib.nqa_neighbor_list_fill_typed(_ptr(ws), _ptr(rowptr), _ptr(types), N, T, E, _ptr(edge_index), _ptr(shifts),
-                                                  stream)
-            _lib.check(rc, "nqa_neighbor_list_fill_typed")
-        if return_rowptr:
-            return edge_index, shifts.to(out_dtype), rowptr
-        return edge_index, shifts.to(out_dtype)
-    ws_bytes = lib.nqa_neighbor_list_workspace_bytes(N)
-    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
-    rowptr = torch.empty(N + 1, dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        rc = lib.nqa_neighbor_list_count(_ptr(pos64), _ptr(cell64), _ptr(pbc_dev), float(r_max), N, _ptr(ws), ws_bytes,
-                                         _ptr(rowptr), stream)
-        _lib.check(rc, "nqa_neighbor_list_count")
-        E = int(rowptr[N].item())  # the one synchronisation: the edge count is data dependent
-        if E < 0:
-            raise RuntimeError("neighbour list has more than 2^31 - 1 edges")
+        _nl_count(lib, pos64, cell64, pbc_dev, r_max, N, ws, ws_bytes, rowptr, stream, types=types,
+                  table=table.on(device) if table is not None else None, symmetrise=symmetrise, status=status)
+        # the one synchronisation: the edge count is data dependent
+        E, bad = (int(rowptr[N].item()), 0) if table is None else aux[N:].tolist()
+        _raise_for_status(E, bad, T)
         edge_index = torch.empty((2, E), dtype=torch.int64, device=device)
         shifts = torch.empty((E, 3), dtype=torch.float64, device=device)
-        rc = lib.nqa_neighbor_list_fill(_ptr(ws), _ptr(rowptr), N, E, _ptr(edge_index), _ptr(shifts), stream)
-        _lib.check(rc, "nqa_neighbor_list_fill")
+        _nl_fill(lib, ws, rowptr, N, E, edge_index, shifts, stream, types=types, T=T)
     if return_rowptr:
         return edge_index, shifts.to(out_dtype), rowptr
     return edge_index, shifts.to(out_dtype)
@@ -264,10 +319,7 @@ class PaddedNeighborList:
             raise ValueError("a capacity-padded neighbour list needs a cell (its padding edges are lattice images)")
         if not cell.is_cuda:
             raise RuntimeError("the `nequip_amd` neighbour list runs on the GPU: the cell must be a CUDA/HIP tensor")
-        if isinstance(pbc, bool):
-            pbc = (pbc,) * 3
-        elif isinstance(pbc, torch.Tensor):
-            pbc = tuple(bool(b) for b in pbc.detach().cpu().view(-1).tolist())
+        pbc = _norm_pbc(pbc)
         self.num_atoms = int(num_atoms)
         if self.num_atoms < 1:
             raise ValueError("a capacity-padded neighbour list needs at least one atom")
@@ -277,22 +329,21 @@ class PaddedNeighborList:
             raise ValueError("edge capacity outside the int32 index range of the kernels")
         self.shift_dtype = shift_dtype
         self.device = cell.device
-        self.pbc = tuple(pbc)
+        self.pbc = pbc
         lib = _lib.load()
         self.cell64 = torch.empty(3, 3, dtype=torch.float64, device=self.device)
         self.set_cell(cell)
         self._pbc_dev = torch.tensor([int(b) for b in pbc], dtype=torch.int32, device=self.device)
         self.cutoff_table = as_cutoff_table(per_edge_type_cutoff, type_names, self.r_max)
         self._types = _types_for(self.cutoff_table, atom_types, self.num_atoms, self.device)
+        self._table_dev = self._type_status = None
+        self._num_types = T = self.cutoff_table.num_types if self.cutoff_table is not None else 0
         if self.cutoff_table is not None:
-            T = self.cutoff_table.num_types
             if bool(((self._types < 0) | (self._types >= T)).any()):
                 raise ValueError(_BAD_TYPE_MSG.format(T=T))
             self._table_dev = self.cutoff_table.on(self.device)  # (symmetrised by the count kernel: symmetrise = 1)
             self._type_status = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self._ws_bytes = lib.nqa_neighbor_list_typed_workspace_bytes(self.num_atoms, T)
-        else:
-            self._ws_bytes = lib.nqa_neighbor_list_workspace_bytes(self.num_atoms)
+        self._ws_bytes = _nl_workspace_bytes(lib, self.num_atoms, T=T)
         self._ws = torch.empty(max(self._ws_bytes, 1), dtype=torch.uint8, device=self.device)
         self._rowptr = torch.empty(self.num_atoms + 1, dtype=torch.int32, device=self.device)
         self._status = torch.zeros(2, dtype=torch.int32, device=self.device)
@@ -320,25 +371,10 @@ class PaddedNeighborList:
         src32 = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         with torch.cuda.device(dev):
-            if self.cutoff_table is not None:
-                T = self.cutoff_table.num_types
-                rc = lib.nqa_neighbor_list_count_typed(_ptr(pos64), _ptr(self.cell64), _ptr(self._pbc_dev), self.r_max,
-                                                       _ptr(self._types), _ptr(self._table_dev), T, 1, self.num_atoms,
-                                                       _ptr(self._ws), self._ws_bytes, _ptr(self._rowptr),
-                                                       _ptr(self._type_status), stream)
-                _lib.check(rc, "nqa_neighbor_list_count_typed")
-                rc = lib.nqa_neighbor_list_fill_padded_typed(_ptr(self._ws), _ptr(self._rowptr), _ptr(self._types),
-                                                             self.num_atoms, T, cap, _ptr(rowptr), _ptr(edge_index),
-                                                             _ptr(shifts), _ptr(src32), _ptr(self._status), stream)
-                _lib.check(rc, "nqa_neighbor_list_fill_padded_typed")
-            else:
-                rc = lib.nqa_neighbor_list_count(_ptr(pos64), _ptr(self.cell64), _ptr(self._pbc_dev), self.r_max,
-                                                 self.num_atoms, _ptr(self._ws), self._ws_bytes, _ptr(self._rowptr), stream)
-                _lib.check(rc, "nqa_neighbor_list_count")
-                rc = lib.nqa_neighbor_list_fill_padded(_ptr(self._ws), _ptr(self._rowptr), self.num_atoms, cap, _ptr(rowptr),
-                                                       _ptr(edge_index), _ptr(shifts), _ptr(src32), _ptr(self._status),
-                                                       stream)
-                _lib.check(rc, "nqa_neighbor_list_fill_padded")
+            _nl_count(lib, pos64, self.cell64, self._pbc_dev, self.r_max, self.num_atoms, self._ws, self._ws_bytes, self._rowptr,
+                      stream, types=self._types, table=self._table_dev, symmetrise=True, status=self._type_status)
+            _nl_fill(lib, self._ws, self._rowptr, self.num_atoms, cap, edge_index, shifts, stream, types=self._types,
+                     T=self._num_types, padded=(rowptr, src32, self._status))
         self.last_csr = (rowptr, self._edge_ids, src32)  # the dst-CSR of the list just built (edge ids = 0 .. capacity - 1)
         return edge_index, shifts.to(self.shift_dtype), rowptr
 
@@ -379,15 +415,6 @@ def _frame_from_batched(data: AtomicDataDict.Type, idx: int, node_offsets) -> At
     if K.PBC_KEY in data:
         out[K.PBC_KEY] = data[K.PBC_KEY].view(-1, 3)[idx]
     return out
-
-
-_BATCHED_STATUS_ERRORS = (
-    (1, RuntimeError, "neighbour list has more than 2^31 - 1 edges"),
-    (2, ValueError, "a lattice vector is zero but the direction is periodic"),
-    (4, ValueError, "cell vectors are linearly dependent"),
-    (8, ValueError, "the frame sizes (num_nodes / batch) do not add up to the number of atoms"),
-    (16, ValueError, "Periodic boundary conditions requested but no cell was provided."),
-)
 
 
 def _batched_frame_count(data: AtomicDataDict.Type) -> int:
@@ -446,41 +473,33 @@ def _compute_neighborlist_batched(pos: torch.Tensor, r_max: float, frame_ptr: to
     frame_ptr = frame_ptr.to(device=device, dtype=torch.int64).contiguous()
     types = _types_for(table, atom_types, N, device)
     T = table.num_types if table is not None else 0
-    ws_bytes = (lib.nqa_neighbor_list_batched_workspace_bytes(N, F) if table is None
-                else lib.nqa_neighbor_list_batched_typed_workspace_bytes(N, F, T))
+    ws_bytes = _nl_workspace_bytes(lib, N, F, T)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
     aux = torch.empty(N + 2, dtype=torch.int32, device=device)  # rowptr [N + 1] and the status word, read back as one pair
     rowptr, status = aux[:N + 1], aux[N + 1:]
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     nbytes = 8.0 * (2 * 3 * N + 9 * F) + 4.0 * (8 * N + 3 * F)  # count pass: positions in, grid and row pointer out
     with torch.cuda.device(device), ktimer.region("nqa_neighbor_list_batched", nbytes):
-        if table is None:
-            rc = lib.nqa_neighbor_list_batched_count(_ptr(pos64), _ptr(cell64), _ptr(pbc32), _ptr(frame_ptr), float(r_max), N, F,
-                                                     _ptr(ws), ws_bytes, _ptr(rowptr), _ptr(status), stream)
-            _lib.check(rc, "nqa_neighbor_list_batched_count")
-        else:
-            rc = lib.nqa_neighbor_list_batched_count_typed(_ptr(pos64), _ptr(cell64), _ptr(pbc32), _ptr(frame_ptr), float(r_max),
-                                                           _ptr(types), _ptr(table.on(device)), T, N, F, _ptr(ws), ws_bytes,
-                                                           _ptr(rowptr), _ptr(status), stream)
-            _lib.check(rc, "nqa_neighbor_list_batched_count_typed")
+        _nl_count(lib, pos64, cell64, pbc32, r_max, N, ws, ws_bytes, rowptr, stream, frame_ptr=frame_ptr, types=types,
+                  table=table.on(device) if table is not None else None, status=status)
         E, bad = aux[N:].tolist()  # the one synchronisation: the edge count is data dependent
-        if bad & _NL_BAD_TYPE:
-            raise ValueError(_BAD_TYPE_MSG.format(T=T))
-        for bit, exc, msg in _BATCHED_STATUS_ERRORS:
-            if bad & bit:
-                raise exc(msg)
-        if E < 0:
-            raise RuntimeError("neighbour list has more than 2^31 - 1 edges")
+        _raise_for_status(E, bad, T)
         edge_index = torch.empty((2, E), dtype=torch.int64, device=device)
         shifts = torch.empty((E, 3), dtype=torch.float64, device=device)
-        if table is None:
-            rc = lib.nqa_neighbor_list_batched_fill(_ptr(ws), _ptr(rowptr), N, F, E, _ptr(edge_index), _ptr(shifts), stream)
-            _lib.check(rc, "nqa_neighbor_list_batched_fill")
-        else:
-            rc = lib.nqa_neighbor_list_batched_fill_typed(_ptr(ws), _ptr(rowptr), _ptr(types), N, F, T, E, _ptr(edge_index),
-                                                          _ptr(shifts), stream)
-            _lib.check(rc, "nqa_neighbor_list_batched_fill_typed")
+        _nl_fill(lib, ws, rowptr, N, E, edge_index, shifts, stream, F=F, types=types, T=T)
     return edge_index, shifts.to(pos.dtype), rowptr
+
+
+def _concat_rowptrs(rowptrs: List[torch.Tensor], edge_counts: List[int]) -> torch.Tensor:
+    """Row pointer [N + 1] of the concatenation of per-frame lists from their row pointers and edge counts."""
+    if len(rowptrs) == 1:
+        return rowptrs[0]
+    parts, eoff = [], 0
+    for rp, e in zip(rowptrs, edge_counts):
+        parts.append(rp[:-1] + eoff)
+        eoff += e
+    parts.append(torch.tensor([eoff], dtype=torch.int32, device=rowptrs[0].device))
+    return torch.cat(parts).to(torch.int32)
 
 
 def _per_frame_requested() -> bool:
@@ -529,16 +548,7 @@ def compute_neighborlist_(data: AtomicDataDict.Type, r_max: float, backend: str 
     # the list is grouped by centre atom: give the tensor-product kernels its row pointer (saves the dst sort)
     from ..nn._topology import topology_cache
 
-    if len(rowptrs) == 1:
-        rowptr = rowptrs[0]
-    else:
-        parts, eoff = [], 0
-        for f, rp in enumerate(rowptrs):
-            parts.append(rp[:-1] + eoff)
-            eoff += int(eidx[f].shape[1])
-        parts.append(torch.tensor([eoff], dtype=torch.int32, device=rowptrs[0].device))
-        rowptr = torch.cat(parts).to(torch.int32)
-    topology_cache.hint_sorted(data[K.EDGE_INDEX_KEY], rowptr)
+    topology_cache.hint_sorted(data[K.EDGE_INDEX_KEY], _concat_rowptrs(rowptrs, [int(ei.shape[1]) for ei in eidx]))
     if has_cell:
         data[K.EDGE_CELL_SHIFT_KEY] = torch.cat(shifts, dim=0) if len(shifts) > 1 else shifts[0]
     return data
