@@ -366,6 +366,18 @@ def check(rc: int, what: str = "") -> None:
         raise RuntimeError(f"libnequip_amd {what} failed (code {rc}): {msg.decode() if msg else ''}")
 
 
+def ptr(t):
+    """Device address of a tensor as a ``void*`` argument; null for ``None``."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p()
+
+
+def stream_ptr(device):
+    """The current stream of ``device`` as an ``nqa_stream`` argument."""
+    import torch
+
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def int32_array(values):
     arr = (c_int32 * max(len(values), 1))()
     for i, v in enumerate(values):

@@ -17,6 +17,8 @@
 // The GEMM core is the per-wavefront pipeline of node_linear_wave_bf16_unit<D, F16 = true> (two-plane fp16 split with a
 // running per-column exponent, weights packed by nqa_node_weights_pack, fp32-accurate); what is new is around it:
 // operand sets per instruction, destinations per chunk, the load-time transform and the epilogues.
+#include "mfma_split.h"
+
 namespace nqa {
 
 constexpr int kNFMaxChunks = 24;
@@ -26,7 +28,7 @@ constexpr int kNFGS = 10 * kNFGateStride + 24; // floats of gate table per wavef
 
 struct NFSet {  // operand set: rows + packed weights
   const float* __restrict__ x;
-  const nl_u32x4* __restrict__ wf;
+  const u32x4* __restrict__ wf;
   const int32_t* __restrict__ wexp;
   int64_t frag_stride;
   int32_t din, n_types, exp_stride, pad;
@@ -307,17 +309,17 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
     }
   };
 
-  nl_u32x4 Af[2][2];  // [tile][plane]
+  u32x4 Af[2][2];  // [tile][plane]
   int we_blk = 0;
   auto load_a = [&](const NFStage& st, int k16) __attribute__((always_inline)) {
     const NFSet& s = a.sets[__builtin_amdgcn_readfirstlane(st.set)];
-    const nl_u32x4* __restrict__ p = s.wf + (int64_t)st.t * s.frag_stride + st.frag_off + lane +
+    const u32x4* __restrict__ p = s.wf + (int64_t)st.t * s.frag_stride + st.frag_off + lane +
                                      ((int64_t)(k16 * nct + ct0) * 2) * 64;
     Af[0][0] = p[0]; Af[0][1] = p[64];
     if (two_tiles) { Af[1][0] = p[128]; Af[1][1] = p[192]; }
     we_blk = s.wexp[st.t * s.exp_stride + st.exp_off + k16];
   };
-  f32x16n acc0 = {0}, acc1 = {0};
+  f32x16 acc0 = {0}, acc1 = {0};
   constexpr int kUnset = 1 << 20;
   int Scol = kUnset;
   auto block = [&](int s, bool on, bool gated, bool masked) __attribute__((always_inline)) {
@@ -367,25 +369,25 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
     int q = Scol == kUnset ? 0 : Scol - we;
     q = q > 120 ? 120 : (q < -120 ? -120 : q);
     const float qs = ldexpf(1.f, q);
-    nl_u32x4 Bh, Bl;
+    u32x4 Bh, Bl;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float v0 = bq[2 * e] * qs, v1 = bq[2 * e + 1] * qs;
       uint32_t x, y;
-      nl_split_pair_f16(v0, v1, x, y);
+      split_pair_f16(v0, v1, x, y);
       Bh[e] = x; Bl[e] = y;
     }
     if (two_tiles) {
-      acc0 = nl_mfma_f16(Af[0][1], Bh, acc0);
-      acc1 = nl_mfma_f16(Af[1][1], Bh, acc1);
-      acc0 = nl_mfma_f16(Af[0][0], Bl, acc0);
-      acc1 = nl_mfma_f16(Af[1][0], Bl, acc1);
-      acc0 = nl_mfma_f16(Af[0][0], Bh, acc0);
-      acc1 = nl_mfma_f16(Af[1][0], Bh, acc1);
+      acc0 = mfma_f16(Af[0][1], Bh, acc0);
+      acc1 = mfma_f16(Af[1][1], Bh, acc1);
+      acc0 = mfma_f16(Af[0][0], Bl, acc0);
+      acc1 = mfma_f16(Af[1][0], Bl, acc1);
+      acc0 = mfma_f16(Af[0][0], Bh, acc0);
+      acc1 = mfma_f16(Af[1][0], Bh, acc1);
     } else {
-      acc0 = nl_mfma_f16(Af[0][1], Bh, acc0);
-      acc0 = nl_mfma_f16(Af[0][0], Bl, acc0);
-      acc0 = nl_mfma_f16(Af[0][0], Bh, acc0);
+      acc0 = mfma_f16(Af[0][1], Bh, acc0);
+      acc0 = mfma_f16(Af[0][0], Bl, acc0);
+      acc0 = mfma_f16(Af[0][0], Bh, acc0);
     }
   };
 
@@ -394,7 +396,7 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
   NFStage cur = first_stage();
   NFStage ld = cur;
   if constexpr (PIPE) {
-    nl_u32x4 Ap[2][2][2][2];  // [buffer][K block][tile][plane]
+    u32x4 Ap[2][2][2][2];  // [buffer][K block][tile][plane]
     int wep[2][2];
     auto load_a2 = [&](int b, const NFStage& st) __attribute__((always_inline)) {
       const NFSet& s = a.sets[__builtin_amdgcn_readfirstlane(st.set)];
@@ -403,7 +405,7 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         const int k16 = (kb == 1 && second) ? k16a + 1 : k16a;
-        const nl_u32x4* __restrict__ p = s.wf + (int64_t)st.t * s.frag_stride + st.frag_off + lane +
+        const u32x4* __restrict__ p = s.wf + (int64_t)st.t * s.frag_stride + st.frag_off + lane +
                                          ((int64_t)(k16 * nct + ct0) * 2) * 64;
         Ap[b][kb][0][0] = p[0]; Ap[b][kb][0][1] = p[64];
         if (two_tiles) { Ap[b][kb][1][0] = p[128]; Ap[b][kb][1][1] = p[192]; }
@@ -832,7 +834,7 @@ int nqa_node_fused(const nqa_node_part* parts, int32_t n_parts, const int64_t* a
                                               static_cast<const NodeInstr*>(pt.instr_table), pt.n_instr, fo, mo, 2);
     NFSet& s = a.sets[p];
     s.x = static_cast<const float*>(pt.x);
-    s.wf = static_cast<const nl_u32x4*>(pt.packed);
+    s.wf = static_cast<const u32x4*>(pt.packed);
     s.frag_stride = per_type;
     s.exp_stride = node_exp_layout(static_cast<const NodeInstr*>(pt.instr_table), pt.n_instr, eo);
     s.wexp = reinterpret_cast<const int32_t*>(static_cast<const char*>(pt.packed) + per_type * 16 * pt.n_types);

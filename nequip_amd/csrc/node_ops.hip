@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "mfma_split.h"
 #include "plan.h"
 
 namespace nqa {
@@ -196,7 +197,6 @@ __global__ __launch_bounds__(256) void node_linear_kernel(const NodeLinearArgs<T
 // (Round 1-2 ran this as 4-wavefront workgroups with the weight slab staged in LDS and barriers around every stage --
 // `node_linear_mfma_kernel`, 225 VGPRs, 2 wavefronts per SIMD; the per-wavefront kernels below replaced it in round 3:
 // same time in exact fp32, 0-18 % faster with split-bf16 operands depending on the box)
-using f32x16n = __attribute__((ext_vector_type(16))) float;
 
 constexpr int kNLW = 64;                       // output channels per chunk (two 32-row MFMA tiles)
 constexpr int kNLXS = 32 * (kNLW + 1);         // floats per wavefront slab: NZT atoms x (64+1)*d, NZT*d <= 32
@@ -342,7 +342,7 @@ __device__ __forceinline__ void node_linear_wave_unit(const NodeLinearArgs<float
     }
   };
 
-  f32x16n acc0 = {0}, acc1 = {0};
+  f32x16 acc0 = {0}, acc1 = {0};
   bool have = q < ch.instr_end;
   if (have) load_x(ins, k0);
   while (have) {
@@ -474,26 +474,7 @@ __global__ __launch_bounds__(64, 4) void node_linear_wave_kernel(const NodeLinea
 //   * x: staged through the wavefront's LDS slab as before; the 8 k-values of a lane are read from the slab and split
 //     in registers (11 VALU per pair of values);
 //   * the rest (units, enumeration, epilogue) is the per-wavefront kernel above.
-__device__ __forceinline__ uint32_t nl_cvt_pk_bf16(float lo, float hi) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));  // round-to-nearest-even, lo -> bits [15:0]
-  return r;
-}
-__device__ __forceinline__ void nl_split_pair(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) {
-  h = nl_cvt_pk_bf16(x0, x1);
-  float r0 = x0 - __uint_as_float(h << 16);
-  float r1 = x1 - __uint_as_float(h & 0xffff0000u);
-  m = nl_cvt_pk_bf16(r0, r1);
-  r0 -= __uint_as_float(m << 16);
-  r1 -= __uint_as_float(m & 0xffff0000u);
-  l = nl_cvt_pk_bf16(r0, r1);
-}
-using nl_bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using nl_u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-__device__ __forceinline__ f32x16n nl_mfma_bf16(const nl_u32x4& a, const nl_u32x4& b, const f32x16n& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(nl_bf16x8, a), __builtin_bit_cast(nl_bf16x8, b), c,
-                                                 0, 0, 0);
-}
+// The split helpers are in mfma_split.h.
 
 // ---- two-plane fp16 split with a running per-column scale (default; NQA_NODE_F16=0 keeps the bf16 split) ----------------
 // As in the radial MLP's backward (radial_mlp.hip): x = h + l with h = fp16(x), l = fp16(x - h) carries 22 significand
@@ -504,22 +485,10 @@ __device__ __forceinline__ f32x16n nl_mfma_bf16(const nl_u32x4& a, const nl_u32x
 // sums, the 16 x-values of a K block are multiplied by 2^(S - e) before they are split, and when a block's largest
 // magnitude would leave the range S drops (three bits below the limit) and the lane's accumulators are multiplied by the
 // bridging power of two.  The epilogue multiplies by 2^-S.
-using nl_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using nl_f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-__device__ __forceinline__ f32x16n nl_mfma_f16(const nl_u32x4& a, const nl_u32x4& b, const f32x16n& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(nl_f16x8, a), __builtin_bit_cast(nl_f16x8, b), c, 0,
-                                                0, 0);
-}
-__device__ __forceinline__ void nl_split_pair_f16(float x0, float x1, uint32_t& h, uint32_t& l) {
-  const nl_f16x2 hh = {(_Float16)x0, (_Float16)x1};
-  const nl_f16x2 ll = {(_Float16)(x0 - (float)hh[0]), (_Float16)(x1 - (float)hh[1])};
-  h = __builtin_bit_cast(uint32_t, hh);
-  l = __builtin_bit_cast(uint32_t, ll);
-}
 
 struct NodePackArgs {
   const float* __restrict__ w;  // [n_types][wstride]
-  nl_u32x4* __restrict__ out;   // [n_types][frag_stride]
+  u32x4* __restrict__ out;      // [n_types][frag_stride]
   int32_t* __restrict__ wexp;   // F16: [n_types][exp_stride] exponent of every (instruction, 16-row K block)
   int64_t wstride, frag_stride;
   int32_t n_instr, n_types, exp_stride;
@@ -571,17 +540,17 @@ __global__ __launch_bounds__(256) void node_weights_pack_f16_kernel(const NodePa
   const int u0 = 16 * k16 + 8 * (lane >> 5);
   const float* __restrict__ wq = a.w + (int64_t)t * a.wstride + a.w_off[q];
   const float su = ldexpf(1.f, a.wexp[t * a.exp_stride + a.exp_off[q] + k16]);
-  nl_u32x4 h, l;
+  u32x4 h, l;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int u = u0 + 2 * e;
     const float v0 = (c < a.mul_out[q] && u < a.mul_in[q]) ? wq[(int64_t)u * a.mul_out[q] + c] * su : 0.f;
     const float v1 = (c < a.mul_out[q] && u + 1 < a.mul_in[q]) ? wq[(int64_t)(u + 1) * a.mul_out[q] + c] * su : 0.f;
     uint32_t x, y;
-    nl_split_pair_f16(v0, v1, x, y);
+    split_pair_f16(v0, v1, x, y);
     h[e] = x; l[e] = y;
   }
-  nl_u32x4* __restrict__ o = a.out + (int64_t)t * a.frag_stride + a.frag_off[q] + ((f >> 6) * 2) * 64 + lane;
+  u32x4* __restrict__ o = a.out + (int64_t)t * a.frag_stride + a.frag_off[q] + ((f >> 6) * 2) * 64 + lane;
   o[0] = h; o[64] = l;
 }
 
@@ -600,23 +569,23 @@ __global__ __launch_bounds__(256) void node_weights_pack_kernel(const NodePackAr
   const int c = 32 * tile + (lane & 31);
   const int u0 = 16 * k16 + 8 * (lane >> 5);
   const float* __restrict__ wq = a.w + (int64_t)t * a.wstride + a.w_off[q];
-  nl_u32x4 h, m, l;
+  u32x4 h, m, l;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int u = u0 + 2 * e;
     const float v0 = (c < a.mul_out[q] && u < a.mul_in[q]) ? wq[(int64_t)u * a.mul_out[q] + c] : 0.f;
     const float v1 = (c < a.mul_out[q] && u + 1 < a.mul_in[q]) ? wq[(int64_t)(u + 1) * a.mul_out[q] + c] : 0.f;
     uint32_t x, y, z;
-    nl_split_pair(v0, v1, x, y, z);
+    split_pair(v0, v1, x, y, z);
     h[e] = x; m[e] = y; l[e] = z;
   }
-  nl_u32x4* __restrict__ o = a.out + (int64_t)t * a.frag_stride + a.frag_off[q] + ((f >> 6) * 3) * 64 + lane;
+  u32x4* __restrict__ o = a.out + (int64_t)t * a.frag_stride + a.frag_off[q] + ((f >> 6) * 3) * 64 + lane;
   o[0] = h; o[64] = m; o[128] = l;
 }
 
 struct NodeLinearPackedArgs {
   NodeLinearArgs<float> base;            // base.w is unused
-  const nl_u32x4* __restrict__ wf;       // packed weights
+  const u32x4* __restrict__ wf;       // packed weights
   const int32_t* __restrict__ wexp;      // F16: [n_types][exp_stride], index base.instr[q].pad + K block
   int32_t exp_stride;
   int64_t frag_stride;                   // uint4 per atom type
@@ -790,10 +759,10 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
   // (a stage whose slab holds 16 channels or fewer -- multiplicities that are not multiples of 32 -- repeats its block
   // with B = 0: branch-free, wasted work only for such shapes).  They come out of the L2 (all wavefronts of a chunk read
   // the same 12 KiB per stage) and land behind the LDS write / B split; double-buffering them (measured) buys nothing.
-  nl_u32x4 Af[1][2][NPL];
+  u32x4 Af[1][2][NPL];
   int we_blk = 0;  // F16: exponent of the K block whose fragments are in Af
   auto load_a = [&](int buf, const NodeStage& st, int k16) {
-    const nl_u32x4* __restrict__ p = pa.wf + (int64_t)st.t * pa.frag_stride + pa.frag_off[st.q] + lane +
+    const u32x4* __restrict__ p = pa.wf + (int64_t)st.t * pa.frag_stride + pa.frag_off[st.q] + lane +
                                      ((int64_t)(k16 * nct + ct0) * NPL) * 64;
     if constexpr (F16) {
       Af[buf][0][0] = p[0]; Af[buf][0][1] = p[64];
@@ -804,7 +773,7 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
       if (two_tiles) { Af[buf][1][0] = p[192]; Af[buf][1][1] = p[256]; Af[buf][1][2] = p[320]; }
     }
   };
-  f32x16n acc0 = {0}, acc1 = {0};
+  f32x16 acc0 = {0}, acc1 = {0};
   constexpr int kUnset = 1 << 20;
   int Scol = kUnset;  // F16: running exponent of this lane's column
   auto block = [&](int buf, int s, bool on) {
@@ -848,59 +817,59 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
       int q = Scol == kUnset ? 0 : Scol - we;
       q = q > 120 ? 120 : (q < -120 ? -120 : q);
       const float qs = ldexpf(1.f, q);
-      nl_u32x4 Bh, Bl;
+      u32x4 Bh, Bl;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float v0 = bq[2 * e] * qs, v1 = bq[2 * e + 1] * qs;
         uint32_t x, y;
-        nl_split_pair_f16(v0, v1, x, y);
+        split_pair_f16(v0, v1, x, y);
         Bh[e] = x; Bl[e] = y;
       }
       // three partial products per tile, small ones first; the two tiles alternate
       if (two_tiles) {
-        acc0 = nl_mfma_f16(Af[buf][0][1], Bh, acc0);
-        acc1 = nl_mfma_f16(Af[buf][1][1], Bh, acc1);
-        acc0 = nl_mfma_f16(Af[buf][0][0], Bl, acc0);
-        acc1 = nl_mfma_f16(Af[buf][1][0], Bl, acc1);
-        acc0 = nl_mfma_f16(Af[buf][0][0], Bh, acc0);
-        acc1 = nl_mfma_f16(Af[buf][1][0], Bh, acc1);
+        acc0 = mfma_f16(Af[buf][0][1], Bh, acc0);
+        acc1 = mfma_f16(Af[buf][1][1], Bh, acc1);
+        acc0 = mfma_f16(Af[buf][0][0], Bl, acc0);
+        acc1 = mfma_f16(Af[buf][1][0], Bl, acc1);
+        acc0 = mfma_f16(Af[buf][0][0], Bh, acc0);
+        acc1 = mfma_f16(Af[buf][1][0], Bh, acc1);
       } else {
-        acc0 = nl_mfma_f16(Af[buf][0][1], Bh, acc0);
-        acc0 = nl_mfma_f16(Af[buf][0][0], Bl, acc0);
-        acc0 = nl_mfma_f16(Af[buf][0][0], Bh, acc0);
+        acc0 = mfma_f16(Af[buf][0][1], Bh, acc0);
+        acc0 = mfma_f16(Af[buf][0][0], Bl, acc0);
+        acc0 = mfma_f16(Af[buf][0][0], Bh, acc0);
       }
       return;
     }
-    nl_u32x4 Bh, Bm, Bl;
+    u32x4 Bh, Bm, Bl;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float v0 = bq[2 * e], v1 = bq[2 * e + 1];
       uint32_t x, y, zz;
-      nl_split_pair(v0, v1, x, y, zz);
+      split_pair(v0, v1, x, y, zz);
       Bh[e] = x; Bm[e] = y; Bl[e] = zz;
     }
     // six partial products per tile, smallest first (hi.lo, lo.hi, mid.mid, mid.hi, hi.mid, hi.hi); the two tiles
     // alternate so that consecutive MFMAs never wait for each other's accumulator
     if (two_tiles) {
-      acc0 = nl_mfma_bf16(Af[buf][0][0], Bl, acc0);
-      acc1 = nl_mfma_bf16(Af[buf][1][0], Bl, acc1);
-      acc0 = nl_mfma_bf16(Af[buf][0][2], Bh, acc0);
-      acc1 = nl_mfma_bf16(Af[buf][1][2], Bh, acc1);
-      acc0 = nl_mfma_bf16(Af[buf][0][1], Bm, acc0);
-      acc1 = nl_mfma_bf16(Af[buf][1][1], Bm, acc1);
-      acc0 = nl_mfma_bf16(Af[buf][0][1], Bh, acc0);
-      acc1 = nl_mfma_bf16(Af[buf][1][1], Bh, acc1);
-      acc0 = nl_mfma_bf16(Af[buf][0][0], Bm, acc0);
-      acc1 = nl_mfma_bf16(Af[buf][1][0], Bm, acc1);
-      acc0 = nl_mfma_bf16(Af[buf][0][0], Bh, acc0);
-      acc1 = nl_mfma_bf16(Af[buf][1][0], Bh, acc1);
+      acc0 = mfma_bf16(Af[buf][0][0], Bl, acc0);
+      acc1 = mfma_bf16(Af[buf][1][0], Bl, acc1);
+      acc0 = mfma_bf16(Af[buf][0][2], Bh, acc0);
+      acc1 = mfma_bf16(Af[buf][1][2], Bh, acc1);
+      acc0 = mfma_bf16(Af[buf][0][1], Bm, acc0);
+      acc1 = mfma_bf16(Af[buf][1][1], Bm, acc1);
+      acc0 = mfma_bf16(Af[buf][0][1], Bh, acc0);
+      acc1 = mfma_bf16(Af[buf][1][1], Bh, acc1);
+      acc0 = mfma_bf16(Af[buf][0][0], Bm, acc0);
+      acc1 = mfma_bf16(Af[buf][1][0], Bm, acc1);
+      acc0 = mfma_bf16(Af[buf][0][0], Bh, acc0);
+      acc1 = mfma_bf16(Af[buf][1][0], Bh, acc1);
     } else {
-      acc0 = nl_mfma_bf16(Af[buf][0][0], Bl, acc0);
-      acc0 = nl_mfma_bf16(Af[buf][0][2], Bh, acc0);
-      acc0 = nl_mfma_bf16(Af[buf][0][1], Bm, acc0);
-      acc0 = nl_mfma_bf16(Af[buf][0][1], Bh, acc0);
-      acc0 = nl_mfma_bf16(Af[buf][0][0], Bm, acc0);
-      acc0 = nl_mfma_bf16(Af[buf][0][0], Bh, acc0);
+      acc0 = mfma_bf16(Af[buf][0][0], Bl, acc0);
+      acc0 = mfma_bf16(Af[buf][0][2], Bh, acc0);
+      acc0 = mfma_bf16(Af[buf][0][1], Bm, acc0);
+      acc0 = mfma_bf16(Af[buf][0][1], Bh, acc0);
+      acc0 = mfma_bf16(Af[buf][0][0], Bm, acc0);
+      acc0 = mfma_bf16(Af[buf][0][0], Bh, acc0);
     }
   };
 
@@ -923,7 +892,7 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
   NodeStage cur = first_stage();
   NodeStage ld = cur;  // the stage whose slab is requested next
   if constexpr (PIPE && F16) {
-    nl_u32x4 Ap[2][2][2][2];  // [buffer][K block][tile][plane]
+    u32x4 Ap[2][2][2][2];  // [buffer][K block][tile][plane]
     int wep[2][2];
     auto load_a2 = [&](int b, const NodeStage& st) {
       const int k16a = st.k0 >> 4;
@@ -931,7 +900,7 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         const int k16 = (kb == 1 && second) ? k16a + 1 : k16a;
-        const nl_u32x4* __restrict__ p = pa.wf + (int64_t)st.t * pa.frag_stride + pa.frag_off[st.q] + lane +
+        const u32x4* __restrict__ p = pa.wf + (int64_t)st.t * pa.frag_stride + pa.frag_off[st.q] + lane +
                                          ((int64_t)(k16 * nct + ct0) * 2) * 64;
         Ap[b][kb][0][0] = p[0]; Ap[b][kb][0][1] = p[64];
         if (two_tiles) { Ap[b][kb][1][0] = p[128]; Ap[b][kb][1][1] = p[192]; }
@@ -1531,7 +1500,7 @@ int nqa_node_weights_pack(const void* weights, const void* chunk_table, int32_t 
     a.w_off[q] = instr[q].w_off;
   }
   a.w = static_cast<const float*>(weights);
-  a.out = static_cast<nl_u32x4*>(packed);
+  a.out = static_cast<u32x4*>(packed);
   a.wstride = weight_stride;
   a.frag_stride = per_type;
   a.n_instr = n_instr;
@@ -1588,7 +1557,7 @@ int nqa_node_linear_packed_ordered(const void* x, const void* packed, const void
   }
   for (int q = 0; q < n_instr; ++q) pa.frag_off[q] = frag_off[q];
   pa.frag_stride = per_type;
-  pa.wf = static_cast<const nl_u32x4*>(packed);
+  pa.wf = static_cast<const u32x4*>(packed);
   int32_t exp_off[kMaxNodeInstr + 1];
   pa.exp_stride = node_exp_layout(instr, n_instr, exp_off);
   pa.wexp = reinterpret_cast<const int32_t*>(static_cast<const char*>(packed) + per_type * 16 * n_types);

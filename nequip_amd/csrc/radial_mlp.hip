@@ -26,12 +26,12 @@
 #include <cstdint>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
+#include "mfma_split.h"
 #include "plan.h"
 
 namespace nqa {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int kMlpRows = 128;  // edges per workgroup (4 wavefronts x 32 rows)
 constexpr int kMaxNb = 8;    // radial basis size limit of the fused kernels (nequip default num_bessels = 8)
@@ -76,6 +76,9 @@ __device__ __forceinline__ float silu_grad_f(float x) {
 // columns per register quad -> float4 stores.
 __device__ __forceinline__ constexpr int mlp_kmap(int s) { return 32 * (s >> 4) + (s & 3) + 8 * ((s & 15) >> 2); }
 
+// `dbg` is always 0: the host passes the constant.  Its bits selected timing ablations (removed from every other kernel
+// and from the host); the never-taken tests stay in this kernel's text because without them the compiler allocates 2-8
+// more VGPRs for six instantiations, the default backward among them (profiles/mlp_refactor_kernel_resources_*.txt).
 template <int H>
 __global__ __launch_bounds__(256) void radial_mlp_fwd_kernel(const float* __restrict__ emb,
                                                              const float* __restrict__ W0,
@@ -382,80 +385,15 @@ __global__ __launch_bounds__(256) void radial_mlp_bwd_kernel(const float* __rest
 }
 
 // ============================================================================================================
-// Split-bf16 ("bf16x6") variants: fp32-accurate GEMMs on the bf16 matrix cores.
+// Split-operand variants: fp32-accurate GEMMs on the bf16 ("bf16x6") and fp16 ("f16x3") matrix cores; the splits and
+// their error analysis are in mfma_split.h.
 // ============================================================================================================
-// Every fp32 operand is written as the exact sum of three bf16 numbers, x = hi + mid + lo (8 + 8 + 8 significand
-// bits; the residuals are formed exactly in fp32), and a product is accumulated in fp32 from the six partial
-// products whose weight is >= 2^-16:  hi.hi + hi.mid + mid.hi + (mid.mid + hi.lo + lo.hi).  The dropped terms
-// (mid.lo, lo.mid, lo.lo) are below 2^-24 relative -- the rounding level of an fp32 fma chain -- so the result
-// carries fp32 accuracy (tests/test_radial_mlp.py measures both variants against float64), while
-// v_mfma_f32_32x32x16_bf16 retires 16x the MACs per cycle of v_mfma_f32_32x32x2_f32: 6 instructions of 16384 MACs
-// replace 8 of 2048 for the same tile, i.e. 2.7x the fp32-MFMA ceiling, which moves both kernels from MFMA-bound to
-// HBM-bound (the forward writes, the backward reads, 4*W bytes per edge).
-//
-// v_mfma_f32_32x32x16_bf16 register maps: A: lane l holds A[i = l&31][k = 8*(l>>5) + t], t = 0..7 (4 VGPRs);
-// B: B[k = 8*(l>>5) + t][j = l&31]; D as the 32x32 fp32 form.  Weights are split once per call by a small prepass
-// kernel that also lays them out in fragment order (one contiguous 1 KiB wave read per fragment, conflict-free
-// ds_read_b128), so staging a tile into LDS is a plain copy.
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
-
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));  // round-to-nearest-even, lo -> bits [15:0]
-  return r;
-}
-
-// two floats -> three packed bf16 pairs with x == hi + mid + lo (+ O(2^-25))
-__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) {
-  h = cvt_pk_bf16(x0, x1);
-  float r0 = x0 - __uint_as_float(h << 16);
-  float r1 = x1 - __uint_as_float(h & 0xffff0000u);
-  m = cvt_pk_bf16(r0, r1);
-  r0 -= __uint_as_float(m << 16);
-  r1 -= __uint_as_float(m & 0xffff0000u);
-  l = cvt_pk_bf16(r0, r1);
-}
-
-__device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0,
-                                                 0);
-}
-
-// ---- two-plane fp16 split ("f16x3"): x = h + l with h = fp16(x), l = fp16(x - h) represents x to 2^-22 |x| (two
-// 11-bit significands), so a product needs three matrix instructions (h h, h l, l h; the dropped l l term is 2^-24 of
-// the product) accumulated into ONE fp32 accumulator, instead of the six of the three-plane bf16 split.  fp16 has no
-// exponent range to spare, so every operand is first multiplied by a power of two that puts the largest magnitude of its
-// group into [2^14, 2^15): weights per 32-column tile (prepass), hidden activations per row (in registers, the row's
-// values sit in one lane pair) -- exact, undone on the accumulators.  With the group's maximum up there, whatever falls
-// below fp16's smallest normal number 2^-14 -- an element under 2^-28 of the maximum, or the low part of an element
-// under 2^-17 of it -- is lost to at most 2^-14 absolute = 2^-28 of the maximum, whether or not the matrix pipe flushes
-// subnormal inputs.  Applies where the scale of a row is known before its first k-step, i.e. to the forward GEMM; the
-// backward streams the gradient rows and keeps the bf16 split (fp32 exponent range).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f32x16 mfma_f16(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void split_pair_f16(float x0, float x1, uint32_t& h, uint32_t& l) {
-  const f16x2 hh = {(_Float16)x0, (_Float16)x1};
-  const f16x2 ll = {(_Float16)(x0 - (float)hh[0]), (_Float16)(x1 - (float)hh[1])};
-  h = __builtin_bit_cast(uint32_t, hh);
-  l = __builtin_bit_cast(uint32_t, ll);
-}
-
-// power of two that brings a maximum magnitude m into [2^14, 2^15); 1 for m = 0 or a non-finite m (the row / tile then
-// carries its inf / NaN through the fp16 conversion as the fp32 arithmetic would)
-__device__ __forceinline__ float f16_scale_up(float m) {
-  if (!(m > 0.f) || !(m < 3.0e38f)) return 1.f;
-  int e;
-  (void)frexpf(m, &e);  // m = f 2^e, f in [0.5, 1)
-  int k = 15 - e;
-  k = k > 100 ? 100 : (k < -100 ? -100 : k);
-  return ldexpf(1.f, k);
-}
+// The split moves both kernels from MFMA-bound to HBM-bound (the forward writes, the backward reads, 4*W bytes per
+// edge).  Weights are split once per call by a small prepass kernel that also lays them out in fragment order (one
+// contiguous 1 KiB wave read per fragment, conflict-free ds_read_b128), so staging a tile into LDS is a plain copy.
+// The power-of-two scales of the fp16 split: weights per 32-column tile (prepass), hidden activations per row (in
+// registers, the row's values sit in one lane pair).  That applies where the scale of a row is known before its first
+// k-step, i.e. to the forward GEMM; the backward streams the gradient rows and scales them per chunk.
 
 // hidden index held by lane-half `half`, element t of bf16 k-step s, when the hidden layer is produced by the
 // transposed fp32 MFMA of step 1 (accumulator register r = 8*(s&1) + t of 32-row block s>>1)
@@ -597,16 +535,17 @@ __global__ __launch_bounds__(256) void radial_mlp_split_w1_bwd_f16_kernel(const 
   }
 }
 
-// NW wavefronts (32 edges each) share every staged weight tile: 8 instead of 4 halves the L2 -> LDS weight traffic
-// (1.7 GB per middle-layer launch at NW = 4, i.e. the whole L2 bandwidth for ~100 us).
+// The four wavefronts (32 edges each) share every staged weight tile (1.7 GB of L2 -> LDS weight traffic per
+// middle-layer launch, i.e. the whole L2 bandwidth for ~100 us).
 // TAN (nqa_radial_mlp_fwd_tangent): the hidden layer fed to the second GEMM is (cemb W0) silu'(emb W0) instead of
 // silu(emb W0) -- the directional derivative of the MLP along cemb; only step 1 differs.
-template <int H, int NW, bool TAN = false>
-__global__ __launch_bounds__(NW * 64, 2) void radial_mlp_fwd_bf16x6_kernel(const float* __restrict__ emb,
+template <int H, bool TAN = false>
+__global__ __launch_bounds__(256, 2) void radial_mlp_fwd_bf16x6_kernel(const float* __restrict__ emb,
                                                                     const float* __restrict__ W0,
                                                                     const u32x4* __restrict__ Wf, float a0, int nb,
                                                                     int W, int64_t E, float* __restrict__ out,
-                                                                    int dbg, const float* __restrict__ cemb = nullptr) {
+                                                                    const float* __restrict__ cemb = nullptr) {
+  constexpr int NW = 4;                 // wavefronts per workgroup
   constexpr int KS = H / 16;            // bf16 k-steps
   constexpr int TILE = KS * 3 * 64;     // uint4 per 32-column weight tile (24 KiB for H = 128)
   constexpr int NTH = NW * 64;          // threads per workgroup
@@ -680,13 +619,11 @@ __global__ __launch_bounds__(NW * 64, 2) void radial_mlp_fwd_bf16x6_kernel(const
 #pragma unroll
     for (int kb = 0; kb < H / 32; ++kb) {
       f32x16 hacc = {0};
-      if (!(dbg & 16)) {  // (ablation bit 16: skip the hidden-layer MFMAs)
 #pragma unroll
-        for (int s2 = 0; s2 < kMaxNb / 2; ++s2) {
-          const float av = w0s[(kb * 32 + l31) * kMaxNb + 2 * s2 + half];
-          const float bv = half ? ev[2 * s2 + 1] : ev[2 * s2];
-          hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, hacc, 0, 0, 0);
-        }
+      for (int s2 = 0; s2 < kMaxNb / 2; ++s2) {
+        const float av = w0s[(kb * 32 + l31) * kMaxNb + 2 * s2 + half];
+        const float bv = half ? ev[2 * s2 + 1] : ev[2 * s2];
+        hacc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, hacc, 0, 0, 0);
       }
       f32x16 qacc = {0};
       if (TAN) {
@@ -699,11 +636,6 @@ __global__ __launch_bounds__(NW * 64, 2) void radial_mlp_fwd_bf16x6_kernel(const
       }
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
-        if (dbg & 16) {
-          const int s = 2 * kb + (r >> 3), tp = (r & 7) >> 1;
-          bh[s][tp] = 0x3f803f80u + lane; bm[s][tp] = 0x3c003c00u; bl[s][tp] = 0x38003800u;
-          continue;
-        }
         const float h0 = row_ok ? (TAN ? qacc[r] * silu_grad_f(hacc[r]) : silu_f(hacc[r])) : 0.f;
         const float h1 = row_ok ? (TAN ? qacc[r + 1] * silu_grad_f(hacc[r + 1]) : silu_f(hacc[r + 1])) : 0.f;
         uint32_t a, b, c;
@@ -722,12 +654,8 @@ __global__ __launch_bounds__(NW * 64, 2) void radial_mlp_fwd_bf16x6_kernel(const
   // instruction would touch 32 lines with 32 B each.  A wave-private LDS transpose (4 KiB) turns the tile into
   // row-major order so that each store instruction writes 8 complete 128 B row segments.
   float* __restrict__ tb = tbuf + wv * (32 * kTS);
-  const int64_t wrow0 = (int64_t)((dbg & 8) ? (blockIdx.x & 15) : blockIdx.x) * (NW * 32) + wv * 32;
+  const int64_t wrow0 = (int64_t)blockIdx.x * (NW * 32) + wv * 32;
   auto emit = [&](const f32x16& pa, const f32x16& pb, int tile) {
-    if (dbg & 1) {
-      if (pa[0] == 12345.f && pb[3] == 777.f) out[0] = 1.f;  // ablation: keep the MFMAs live, skip the stores
-      return;
-    }
     // lane (edge, half) holds columns 8*g + 4*half + (0..3) of its row in registers 4g..4g+3
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -752,8 +680,8 @@ __global__ __launch_bounds__(NW * 64, 2) void radial_mlp_fwd_bf16x6_kernel(const
   };
   auto tile_body = [&](int tile, f32x16& accA, f32x16& accB, const f32x16& prevA, const f32x16& prevB) {
     const int buf = tile & 1;
-    if (tile + 1 < ntiles && !(dbg & 2)) stage_store(buf ^ 1);
-    if (tile + 2 < ntiles && !(dbg & 2)) stage_load(tile + 2);
+    if (tile + 1 < ntiles) stage_store(buf ^ 1);
+    if (tile + 2 < ntiles) stage_load(tile + 2);
     const u32x4* __restrict__ a = as[buf] + lane;
     accA = (f32x16){0};  // large partial products
     accB = (f32x16){0};  // small partial products, summed with accA at the end
@@ -762,12 +690,12 @@ __global__ __launch_bounds__(NW * 64, 2) void radial_mlp_fwd_bf16x6_kernel(const
     for (int q = 0; q < 3; ++q) fa[0][q] = a[q * 64];
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      if (s + 1 < KS && !(dbg & 32)) {  // (ablation bit 32: no LDS fragment reads after the first k-step)
+      if (s + 1 < KS) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) fa[(s + 1) & 1][q] = a[((s + 1) * 3 + q) * 64];
       }
       __builtin_amdgcn_sched_barrier(0);
-      const int sb = (dbg & 32) ? 0 : (s & 1);
+      const int sb = s & 1;
       const u32x4 &ah = fa[sb][0], &am = fa[sb][1], &al = fa[sb][2];
       accA = mfma_bf16(ah, bh[s], accA);
       accB = mfma_bf16(am, bm[s], accB);
@@ -781,7 +709,7 @@ __global__ __launch_bounds__(NW * 64, 2) void radial_mlp_fwd_bf16x6_kernel(const
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if (!(dbg & 4)) lds_barrier();
+    lds_barrier();
   };
   f32x16 a0A, a0B, a1A, a1B;
   for (int tile = 0; tile < ntiles; tile += 2) {
@@ -1079,6 +1007,7 @@ namespace nqa {
 // is 2^-22 of the row's (running) maximum x the chunk's weight maximum, the rounding level of the fp32 sum itself.
 // XIN (nqa_radial_mlp_last_bwd, TM = 0): the last layer of a deeper MLP -- `emb` holds the pre-activations P [E, H] of the
 // layer's input, the result is grad_P = (g W^T) silu'(P) written to `g_emb` as [E, H]; no first-layer GEMV.
+// (`dbg`: always 0, as for radial_mlp_fwd_kernel)
 template <int H, int TM, bool PAIR = false, bool F16 = false, bool XIN = false>
 __global__ __launch_bounds__(256, 2) void radial_mlp_bwd_split_kernel(const float* __restrict__ emb,
                                                                     const float* __restrict__ W0,
@@ -1476,22 +1405,363 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_bwd_split_kernel(const floa
   }
 }
 
-static int check_args(const void* emb, const void* W0, const void* W1, int nb, int H, int W, int64_t E,
-                      const char* fn) {
-  if (E < 0 || nb <= 0 || nb > kMaxNb || W <= 0 || (E > 0 && (!emb || !W0 || !W1))) {
-    set_error(std::string(fn) + ": invalid argument");
-    return NQA_ERR_INVALID;
-  }
-  if (H != 64 && H != 128) {
-    set_error(std::string(fn) + ": hidden width must be 64 or 128 for the fused MFMA kernel");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  return NQA_OK;
-}
-
 }  // namespace nqa
 
 using namespace nqa;
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+namespace {
+
+// Switches.  Every one is read at every call, because the tests select kernel forms within one process; only the CU
+// count is looked up once.  A flag that defaults to on is switched off by a leading '0', one that defaults to off is
+// switched on by a leading '1'.
+bool env_flag(const char* name, bool dflt) {
+  const char* v = std::getenv(name);
+  return v == nullptr ? dflt : (dflt ? v[0] != '0' : v[0] == '1');
+}
+int env_int(const char* name, int dflt) {
+  const char* v = std::getenv(name);
+  return v ? std::atoi(v) : dflt;
+}
+int mlp_num_cus() {
+  static const int num_cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    return n;
+  }();
+  return num_cus;
+}
+
+// Workspace of one (mode, direction, H, W): the weight fragments (fp32 backward: the transposed weights) and, for the
+// fp16 split, a second field behind them -- forward: one float per 32-column tile (the inverse of the tile's
+// power-of-two scale), backward: one int per 32-column chunk (the exponent the chunk was scaled by).
+//   F16X3 forward : ceil(W/32) tiles x (H/16) k-steps x 2 planes x 1 KiB     F16X3 backward: ceil(W/32) chunks x 2 k-steps
+//   BF16X6        : ceil(W/32) tiles x (H/16) k-steps x 3 planes x 1 KiB                     x 2 planes x (H/32) x 1 KiB
+//   FP32 backward : [W (+ 4 x 64 padding rows read by the last chunk)][H] floats; the FP32 forward needs none.
+struct MlpLayout {
+  int64_t total;   // bytes; -1: no such form
+  int64_t second;  // byte offset of the second field; -1: none
+};
+MlpLayout mlp_layout(int32_t mode, int32_t backward, int32_t H, int32_t W) {
+  if (H <= 0 || W <= 0) return {-1, -1};
+  const int64_t n32 = (W + 31) / 32;
+  if (mode == NQA_MLP_F16X3) {
+    const int64_t frag = backward ? n32 * 2 * 2 * (H / 32) * 1024 : n32 * (H / 16) * 2 * 1024;
+    return {frag + ((n32 * 4 + 255) & ~(int64_t)255), frag};
+  }
+  if (mode == NQA_MLP_BF16X6) return {n32 * (H / 16) * 3 * 1024, -1};
+  if (mode != NQA_MLP_FP32) return {-1, -1};
+  if (!backward) return {0, -1};
+  return {(int64_t)H * W * (int64_t)sizeof(float) + 4 * 64 * H * (int64_t)sizeof(float), -1};
+}
+struct MlpWorkspace {
+  u32x4* fragments;
+  void* second;
+  template <class T>
+  T* second_as() const { return static_cast<T*>(second); }
+};
+MlpWorkspace mlp_view(void* workspace, const MlpLayout& lay) {
+  return {static_cast<u32x4*>(workspace),
+          lay.second < 0 ? nullptr : reinterpret_cast<void*>(static_cast<char*>(workspace) + lay.second)};
+}
+
+int fail(int rc, const std::string& text) {
+  set_error(text);
+  return rc;
+}
+int launch_status(const char* fn) {
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? NQA_OK : fail(NQA_ERR_LAUNCH, std::string(fn) + ": " + hipGetErrorString(err));
+}
+
+// Operands of the two drivers.  `fn` names the entry point in the error texts.  `xin`: `in` holds the pre-activations
+// [E, H] of the last layer of a deeper MLP (no first layer: w0 null, alpha0 = 1, nb = 0; fp16 split only).
+struct MlpCall {
+  const char* fn;
+  int32_t dtype, mode;
+  bool xin;
+  const void *in, *w0;
+  double alpha0;
+  const void* w1;
+  double alpha1;
+  int32_t nb, H, W;
+  int64_t E;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t workspace_ready;
+  nqa_stream stream;
+};
+
+// Checks shared by both directions; `io_ok`: the direction's own pointers are there.  NQA_OK with E == 0 is the
+// caller's early return.
+int mlp_check(const MlpCall& c, bool io_ok) {
+  const std::string fn(c.fn);
+  const bool h_ok = c.H == 64 || c.H == 128;
+  if (c.xin) {
+    if (c.dtype != NQA_F32 || c.mode != NQA_MLP_F16X3)
+      return fail(NQA_ERR_UNSUPPORTED, fn + ": float32 on the two-plane fp16 split (NQA_MLP_F16X3) only");
+    if (c.E < 0 || !h_ok || c.W <= 0 || c.W % 4 != 0 || (c.E > 0 && (!c.in || !c.w1 || !io_ok)))
+      return fail(h_ok ? NQA_ERR_INVALID : NQA_ERR_UNSUPPORTED,
+                  fn + ": invalid argument (hidden 64 / 128, out_features % 4 == 0)");
+    return NQA_OK;
+  }
+  if (c.dtype != NQA_F32) return fail(NQA_ERR_UNSUPPORTED, fn + ": only float32 is implemented on MFMA");
+  if (c.mode != NQA_MLP_FP32 && c.mode != NQA_MLP_BF16X6 && c.mode != NQA_MLP_F16X3)
+    return fail(NQA_ERR_INVALID, fn + ": unknown mode");
+  if (c.E < 0 || c.nb <= 0 || c.nb > kMaxNb || c.W <= 0 || (c.E > 0 && (!c.in || !c.w0 || !c.w1)))
+    return fail(NQA_ERR_INVALID, fn + ": invalid argument");
+  if (!h_ok) return fail(NQA_ERR_UNSUPPORTED, fn + ": hidden width must be 64 or 128 for the fused MFMA kernel");
+  return NQA_OK;
+}
+
+// The template dispatch, once per kernel family: f(H) and f(H, TM, PAIR) with the values as integral constants.
+template <int V>
+using ic = std::integral_constant<int, V>;
+template <class F>
+void by_h(int H, F&& f) {
+  if (H == 128) f(ic<128>{});
+  else f(ic<64>{});
+}
+template <class F>
+void by_h_tm_pair(int H, int tm, bool pair, F&& f) {  // (a second gradient stream goes with tm == 0 only)
+  by_h(H, [&](auto h) {
+    if (pair) f(h, ic<0>{}, std::true_type{});
+    else if (tm == 0) f(h, ic<0>{}, std::false_type{});
+    else if (tm == 1) f(h, ic<1>{}, std::false_type{});
+    else f(h, ic<2>{}, std::false_type{});
+  });
+}
+
+// forward; `cotangent`: the tangent of the output along it instead (NQA_MLP_BF16X6)
+int mlp_fwd(const MlpCall& c, const void* cotangent, void* out) {
+  const std::string fn(c.fn);
+  int rc = mlp_check(c, out != nullptr);
+  if (rc != NQA_OK || c.E == 0) return rc;
+  if (out == nullptr || c.W % 4 != 0) return fail(NQA_ERR_INVALID, fn + ": invalid output (needs out_features % 4 == 0)");
+  const MlpLayout lay = mlp_layout(c.mode, 0, c.H, c.W);
+  if (lay.total > 0 && (c.workspace == nullptr || c.workspace_bytes < lay.total))
+    return fail(NQA_ERR_WORKSPACE, fn + ": workspace missing or too small");
+  if (cotangent != nullptr && c.mode != NQA_MLP_BF16X6)
+    return fail(NQA_ERR_UNSUPPORTED,
+                c.mode == NQA_MLP_F16X3
+                    ? "nqa_radial_mlp_fwd_tangent: NQA_MLP_F16X3 is a mode of the plain forward (use NQA_MLP_BF16X6)"
+                    : "nqa_radial_mlp_fwd_tangent: only NQA_MLP_BF16X6 is implemented");
+  const MlpWorkspace ws = mlp_view(c.workspace, lay);
+  hipStream_t s = static_cast<hipStream_t>(c.stream);
+  const int nb = c.nb, H = c.H, W = c.W;
+  const int64_t E = c.E;
+  const float a0 = (float)c.alpha0, a1 = (float)c.alpha1;
+  const float* e = static_cast<const float*>(c.in);
+  const float* a = static_cast<const float*>(c.w0);
+  const float* b = static_cast<const float*>(c.w1);
+  float* o = static_cast<float*>(out);
+  u32x4* wf = ws.fragments;
+  const int ntiles = (W + 31) / 32;
+  const unsigned grid = (unsigned)((E + kMlpRows - 1) / kMlpRows);
+  // balanced work-unit ranges (128-row block x 32-column tile) over a fixed grid of two workgroups per CU
+  const auto balanced_grid = [&] {
+    const int64_t units = (int64_t)grid * ntiles, slots = 2 * (int64_t)mlp_num_cus();
+    return (unsigned)(units < slots ? units : slots);
+  };
+  if (c.mode == NQA_MLP_F16X3) {
+    float* ts = ws.second_as<float>();
+    if (!c.workspace_ready)
+      hipLaunchKernelGGL(radial_mlp_split_w1_fwd_f16_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, b, a1, H, W, wf, ts);
+    const unsigned gb = balanced_grid();
+    // round 5: outputs of complete 32-column tiles run on the issue-scheduled kernel (radial_mlp_pipe.h; NQA_MLP_PIPE=0:
+    // the general kernel)
+    // (H = 64 stays on the general kernel: its 166 registers keep three wavefronts per SIMD, the scheduled form needs 170)
+    if (!c.xin && env_flag("NQA_MLP_PIPE", true) && H == 128 && W % 32 == 0 && ntiles <= 128) {
+      // tile epilogue: through the wave-private LDS transpose (default: 128-133 us for the cfg-3 middle layer, 48 us for the
+      // first / last one) or straight from the accumulators with the MFMA operands swapped (NQA_MLP_PIPE_DIRECT=1: 134-161
+      // / 50 us at 244 registers) -- profiles/r5_mlp_fwd_kernel_trace.txt; the round-4 kernel: 149-161 / 60 us
+      if (env_flag("NQA_MLP_PIPE_DIRECT", false))
+        hipLaunchKernelGGL((radial_mlp_fwd_pipe_kernel<128, true>), dim3(gb), dim3(256), 0, s, e, a, wf, a0, nb, W, E, o, ts);
+      else
+        hipLaunchKernelGGL((radial_mlp_fwd_pipe_kernel<128, false>), dim3(gb), dim3(256), 0, s, e, a, wf, a0, nb, W, E, o, ts);
+      return launch_status(c.fn);
+    }
+    by_h(H, [&](auto h) {
+      constexpr int HH = decltype(h)::value;
+      if (c.xin)
+        hipLaunchKernelGGL((radial_mlp_fwd_split_bal_kernel<HH, true, true>), dim3(gb), dim3(256), 0, s, e, a, wf, a0, nb,
+                           W, E, o, ts);
+      else
+        hipLaunchKernelGGL((radial_mlp_fwd_split_bal_kernel<HH, true>), dim3(gb), dim3(256), 0, s, e, a, wf, a0, nb, W, E,
+                           o, ts);
+    });
+    return launch_status(c.fn);
+  }
+  if (c.mode == NQA_MLP_BF16X6) {
+    const int nfrag = ntiles * (H / 16) * 64;
+    if (!c.workspace_ready)
+      hipLaunchKernelGGL(radial_mlp_split_w1_fwd_kernel, dim3((unsigned)((nfrag + 255) / 256)), dim3(256), 0, s, b, a1, H,
+                         W, wf);
+    if (cotangent != nullptr) {
+      const float* ct = static_cast<const float*>(cotangent);
+      by_h(H, [&](auto h) {
+        hipLaunchKernelGGL((radial_mlp_fwd_bf16x6_kernel<decltype(h)::value, true>), dim3(grid), dim3(256), 0, s, e, a, wf,
+                           a0, nb, W, E, o, ct);
+      });
+      return launch_status("nqa_radial_mlp_fwd_tangent");
+    }
+    // default: the balanced form (NQA_MLP_FWD_BALANCED=0: one workgroup per 128-row block)
+    if (env_flag("NQA_MLP_FWD_BALANCED", true)) {
+      const unsigned gb = balanced_grid();
+      by_h(H, [&](auto h) {
+        hipLaunchKernelGGL((radial_mlp_fwd_split_bal_kernel<decltype(h)::value, false>), dim3(gb), dim3(256), 0, s, e, a,
+                           wf, a0, nb, W, E, o, nullptr);
+      });
+      return launch_status(c.fn);
+    }
+    by_h(H, [&](auto h) {
+      hipLaunchKernelGGL((radial_mlp_fwd_bf16x6_kernel<decltype(h)::value>), dim3(grid), dim3(256), 0, s, e, a, wf, a0, nb,
+                         W, E, o, nullptr);
+    });
+    return launch_status(c.fn);
+  }
+  by_h(H, [&](auto h) {
+    hipLaunchKernelGGL(radial_mlp_fwd_kernel<decltype(h)::value>, dim3(grid), dim3(256), 0, s, e, a, b, a0, a1, nb, W, E,
+                       o, 0);
+  });
+  return launch_status(c.fn);
+}
+
+// backward to the input.  tm = 1 / 2: the training forms (hidden_out, w0_partials; 2: second order along `cotangent`);
+// `gw2`: a second gradient stream for the paired rows; the idle hint rides in c.mode.
+int mlp_bwd(MlpCall c, int tm, const void* cotangent, void* hidden_out, void* w0_partials, const void* gw, const void* gw2,
+            void* grad_in) {
+  const std::string fn(c.fn);
+  const bool device_idle = !c.xin && (c.mode & NQA_MLP_HINT_DEVICE_IS_IDLE) != 0;
+  if (!c.xin) c.mode &= ~NQA_MLP_HINT_DEVICE_IS_IDLE;
+  int rc = mlp_check(c, gw != nullptr && grad_in != nullptr);
+  if (rc != NQA_OK || c.E == 0) return rc;
+  if (gw == nullptr || grad_in == nullptr || c.W % 4 != 0)
+    return fail(NQA_ERR_INVALID, fn + ": invalid argument (needs out_features % 4 == 0)");
+  const MlpLayout lay = mlp_layout(c.mode, 1, c.H, c.W);
+  if (c.workspace == nullptr || c.workspace_bytes < lay.total)
+    return fail(NQA_ERR_WORKSPACE, fn + ": workspace missing or too small");
+  if (c.mode == NQA_MLP_FP32 && (tm != 0 || gw2 != nullptr))
+    return fail(NQA_ERR_UNSUPPORTED, "nqa_radial_mlp_bwd_train / _paired: only NQA_MLP_BF16X6 is implemented");
+  if (gw2 != nullptr && tm != 0) return fail(NQA_ERR_UNSUPPORTED, "nqa_radial_mlp_bwd_paired: inference backward only");
+  const MlpWorkspace ws = mlp_view(c.workspace, lay);
+  hipStream_t s = static_cast<hipStream_t>(c.stream);
+  const int nb = c.nb, H = c.H, W = c.W;
+  const int64_t E = c.E;
+  const float a0 = (float)c.alpha0, a1 = (float)c.alpha1;
+  const float* e = static_cast<const float*>(c.in);
+  const float* a = static_cast<const float*>(c.w0);
+  const float* b = static_cast<const float*>(c.w1);
+  const float* g = static_cast<const float*>(gw);
+  const float* g2 = static_cast<const float*>(gw2);
+  const float* ct = static_cast<const float*>(cotangent);
+  float* ho = static_cast<float*>(hidden_out);
+  float* wp = static_cast<float*>(w0_partials);
+  float* o = static_cast<float*>(grad_in);
+  u32x4* wb = ws.fragments;
+  const int nchunks = (W + 31) / 32;
+  const unsigned grid = (unsigned)((E + kMlpRows - 1) / kMlpRows);
+  const char* launch_fn = g2 != nullptr && !c.xin ? "nqa_radial_mlp_bwd_paired" : c.fn;
+  if (c.mode == NQA_MLP_F16X3) {
+    int* ce = ws.second_as<int>();
+    if (!c.workspace_ready)
+      hipLaunchKernelGGL(radial_mlp_split_w1_bwd_f16_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, b, a1, H, W, wb, ce);
+    // round 5 (radial_mlp_pipe.h): three more forms of the inference backward, all OPT-IN:
+    //   NQA_MLP_BWD_COAL=1     radial_mlp_bwd_coal_kernel (widths that are multiples of 64): g_w in coalesced 256-byte row pieces
+    //                          through an LDS transpose -- alone 226-230 us for the cfg-3 middle layer against 240-244 us of the
+    //                          general kernel (94 / 96 us first / last layer; profiles/r5_mlp_bwd_kernel_trace.txt);
+    //   NQA_MLP_BWD_BALANCED=1 radial_mlp_bwd_pipe_kernel: lane-=-row loads like the general kernel, 235-243 us.
+    // Neither is the default: in the step the radial backward runs on a side stream NEXT TO the node / tensor-product kernels,
+    // and a persistent launch that holds two workgroups on every CU for its whole duration costs those more than it saves
+    // (same-box A/B of the whole step, profiles/r5_step_ab_mlp.txt: 2.37-2.39 ms with the general backward kernel, 2.48-2.49 ms
+    // with the coalesced persistent one, both with the new forward).
+    //   NQA_MLP_BWD_SMALL      0 never (default), 1 with NQA_MLP_HINT_DEVICE_IS_IDLE, 2 whenever the shape fits: narrow
+    //                          outputs (W <= 256: the first / last layer of the BASELINE models), all fragments resident in
+    //                          LDS, independent wavefronts, epilogue in registers (radial_mlp_bwd_small_kernel: alone 96 -> 76 us
+    //                          at cfg-3's W = 192, inside the step 87 -> 72 us for the first layer's launch -- and yet the step
+    //                          as a whole comes out 2 % SLOWER in four of four same-box repetitions, with the hint and without;
+    //                          profiles/r5_mlp_bwd_small.txt).
+    if (!c.xin && tm == 0 && g2 == nullptr && env_flag("NQA_MLP_PIPE", true)) {
+      const int small_mode = env_int("NQA_MLP_BWD_SMALL", 0);
+      if ((small_mode == 2 || (small_mode == 1 && device_idle)) && H == 128 && W % 32 == 0 && W <= 256) {
+        const size_t lds = (size_t)nchunks * (2 * 2 * (H / 32) * 64) * 16 + (size_t)(H / 32) * 16 * 2 * kMaxNb * 4 +
+                           (size_t)kMaxNb * H * 4 + (((size_t)nchunks * 4 + 15) & ~(size_t)15);
+        static bool attr_set = false;
+        if (!attr_set) {
+          if (hipFuncSetAttribute(reinterpret_cast<const void*>(&radial_mlp_bwd_small_kernel<128>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) {
+            (void)hipGetLastError();
+          }
+          attr_set = true;
+        }
+        const int64_t want = ((E + 31) / 32 + 7) / 8;  // one 32-row block per wavefront at least
+        const unsigned gb = (unsigned)(want < (int64_t)mlp_num_cus() ? want : (int64_t)mlp_num_cus());
+        hipLaunchKernelGGL((radial_mlp_bwd_small_kernel<128>), dim3(gb), dim3(512), lds, s, e, a, wb, g, a0, nb, W, E, o, ce);
+        return launch_status(c.fn);
+      }
+      const bool balanced = env_flag("NQA_MLP_BWD_BALANCED", false);
+      const bool use_coal = env_flag("NQA_MLP_BWD_COAL", false) && H == 128 && W % 64 == 0;
+      if (use_coal || (balanced && W % 32 == 0)) {
+        // NQA_MLP_BWD_WGS_PER_CU=1: half the chip for the (side-stream) persistent launch
+        const int per_cu = env_int("NQA_MLP_BWD_WGS_PER_CU", 2);
+        const int64_t slots = (int64_t)(per_cu >= 1 && per_cu <= 2 ? per_cu : 2) * mlp_num_cus();
+        const unsigned gb = (unsigned)((int64_t)grid < slots ? (int64_t)grid : slots);
+        if (hipMemsetAsync(o, 0, (size_t)E * nb * sizeof(float), s) != hipSuccess)
+          return fail(NQA_ERR_LAUNCH, fn + ": hipMemsetAsync failed");
+        const auto launch = [&](auto h, auto pf) {
+          hipLaunchKernelGGL((radial_mlp_bwd_pipe_kernel<decltype(h)::value, decltype(pf)::value>), dim3(gb), dim3(256), 0,
+                             s, e, a, wb, g, a0, nb, W, E, o, ce);
+        };
+        if (use_coal && !balanced)
+          hipLaunchKernelGGL((radial_mlp_bwd_coal_kernel<128>), dim3(gb), dim3(256), 0, s, e, a, wb, g, a0, nb, W, E, o, ce);
+        else if (H == 64) launch(ic<64>{}, ic<2>{});
+        else if (env_int("NQA_MLP_BWD_PF", 2) == 4) launch(ic<128>{}, ic<4>{});
+        else launch(ic<128>{}, ic<2>{});
+        return launch_status(c.fn);
+      }
+    }
+    by_h_tm_pair(H, tm, g2 != nullptr, [&](auto h, auto t, auto p) {
+      constexpr int HH = decltype(h)::value, TT = decltype(t)::value;
+      constexpr bool PP = decltype(p)::value;
+      if constexpr (TT == 0) {
+        if (c.xin) {
+          hipLaunchKernelGGL((radial_mlp_bwd_split_kernel<HH, 0, PP, true, true>), dim3(grid), dim3(256), 0, s, e, a, wb, g,
+                             a0, nb, W, E, o, 0, ct, ho, wp, g2, ce);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((radial_mlp_bwd_split_kernel<HH, TT, PP, true>), dim3(grid), dim3(256), 0, s, e, a, wb, g, a0, nb,
+                         W, E, o, 0, ct, ho, wp, g2, ce);
+    });
+    return launch_status(launch_fn);
+  }
+  if (c.mode == NQA_MLP_BF16X6) {
+    const int nfrag = nchunks * 2 * (H / 32) * 64;
+    if (!c.workspace_ready)
+      hipLaunchKernelGGL(radial_mlp_split_w1_bwd_kernel, dim3((unsigned)((nfrag + 255) / 256)), dim3(256), 0, s, b, a1, H,
+                         W, wb);
+    by_h_tm_pair(H, tm, g2 != nullptr, [&](auto h, auto t, auto p) {
+      constexpr int HH = decltype(h)::value, TT = decltype(t)::value;
+      constexpr bool PP = decltype(p)::value;
+      hipLaunchKernelGGL((radial_mlp_bwd_split_kernel<HH, TT, PP>), dim3(grid), dim3(256), 0, s, e, a, wb, g, a0, nb, W, E,
+                         o, 0, ct, ho, wp, g2, nullptr);
+    });
+    return launch_status(launch_fn);
+  }
+  float* w1t = static_cast<float*>(c.workspace);  // [W (+ padding rows read by the last chunk)][H]
+  if (!c.workspace_ready)
+    hipLaunchKernelGGL(radial_mlp_transpose_w1_kernel, dim3((unsigned)((H * W + 255) / 256)), dim3(256), 0, s, b, a1, H, W,
+                       w1t);
+  by_h(H, [&](auto h) {
+    hipLaunchKernelGGL(radial_mlp_bwd_kernel<decltype(h)::value>, dim3(grid), dim3(256), 0, s, e, a, w1t, g, a0, nb, W, E,
+                       o);
+  });
+  return launch_status(c.fn);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1503,424 +1773,40 @@ int nqa_radial_mlp_supported(int32_t dtype, int32_t num_basis, int32_t hidden, i
 }
 
 int64_t nqa_radial_mlp_workspace_bytes(int32_t mode, int32_t backward, int32_t hidden, int32_t out_features) {
-  if (hidden <= 0 || out_features <= 0) return -1;
-  if (mode == NQA_MLP_F16X3 && backward) {
-    // backward fragments on the two-plane fp16 split: ceil(W/32) chunks x 2 k-steps x 2 planes x (H/32) x 1 KiB, then
-    // one int per chunk (the exponent the chunk was scaled by)
-    const int64_t nchunks = (out_features + 31) / 32;
-    return nchunks * 2 * 2 * (hidden / 32) * 1024 + ((nchunks * 4 + 255) & ~(int64_t)255);
-  }
-  if (mode == NQA_MLP_F16X3 && !backward) {
-    // forward fragments on the two-plane fp16 split: ceil(W/32) tiles x (H/16) k-steps x 2 planes x 1 KiB, then one
-    // float per tile (the inverse of the tile's power-of-two scale)
-    const int64_t ntiles = (out_features + 31) / 32;
-    return ntiles * (hidden / 16) * 2 * 1024 + ((ntiles * 4 + 255) & ~(int64_t)255);
-  }
-  if (mode == NQA_MLP_BF16X6 || mode == NQA_MLP_F16X3) {
-    // weight fragments: ceil(W/32) tiles x (H/16) k-steps x 3 splits x 1 KiB (same size for both directions)
-    return (int64_t)((out_features + 31) / 32) * (hidden / 16) * 3 * 1024;
-  }
-  if (mode != NQA_MLP_FP32) return -1;
-  if (!backward) return 0;
-  return (int64_t)hidden * out_features * (int64_t)sizeof(float) + 4 * 64 * hidden * (int64_t)sizeof(float);
+  return mlp_layout(mode, backward, hidden, out_features).total;
 }
 
-static int check_mode(int32_t dtype, int32_t mode, const char* fn) {
-  if (dtype != NQA_F32) {
-    set_error(std::string(fn) + ": only float32 is implemented on MFMA");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  if (mode != NQA_MLP_FP32 && mode != NQA_MLP_BF16X6 && mode != NQA_MLP_F16X3) {
-    set_error(std::string(fn) + ": unknown mode");
-    return NQA_ERR_INVALID;
-  }
-  return NQA_OK;
-}
-
-static int launch_status(const char* fn) {
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_error(std::string(fn) + ": " + hipGetErrorString(err));
-    return NQA_ERR_LAUNCH;
-  }
-  return NQA_OK;
-}
-
-static int mlp_fwd_impl(int32_t dtype, int32_t mode, const void* edge_embedding, const void* cotangent,
-                        const void* w0, double alpha0, const void* w1, double alpha1, int32_t num_basis,
-                        int32_t hidden, int32_t out_features, int64_t num_edges, void* edge_weight, void* workspace,
-                        int64_t workspace_bytes, int32_t workspace_ready, nqa_stream stream) {
-  int rc = check_mode(dtype, mode, "nqa_radial_mlp_fwd");
-  if (rc != NQA_OK) return rc;
-  rc = check_args(edge_embedding, w0, w1, num_basis, hidden, out_features, num_edges, "nqa_radial_mlp_fwd");
-  if (rc != NQA_OK) return rc;
-  if (num_edges == 0) return NQA_OK;
-  if (edge_weight == nullptr || out_features % 4 != 0) {
-    set_error("nqa_radial_mlp_fwd: invalid output (needs out_features % 4 == 0)");
-    return NQA_ERR_INVALID;
-  }
-  const int64_t need = nqa_radial_mlp_workspace_bytes(mode, 0, hidden, out_features);
-  if (need > 0 && (workspace == nullptr || workspace_bytes < need)) {
-    set_error("nqa_radial_mlp_fwd: workspace missing or too small");
-    return NQA_ERR_WORKSPACE;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned grid = (unsigned)((num_edges + kMlpRows - 1) / kMlpRows);
-  const float* e = static_cast<const float*>(edge_embedding);
-  const float* a = static_cast<const float*>(w0);
-  const float* b = static_cast<const float*>(w1);
-  float* o = static_cast<float*>(edge_weight);
-  static const int dbg = [] {
-    const char* v = std::getenv("NQA_MLP_DBG");
-    return v ? std::atoi(v) : 0;
-  }();
-  static const int num_cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  if (mode == NQA_MLP_F16X3) {
-    if (cotangent != nullptr) {
-      set_error("nqa_radial_mlp_fwd_tangent: NQA_MLP_F16X3 is a mode of the plain forward (use NQA_MLP_BF16X6)");
-      return NQA_ERR_UNSUPPORTED;
-    }
-    const int ntiles = (out_features + 31) / 32;
-    u32x4* wf = static_cast<u32x4*>(workspace);
-    float* ts = reinterpret_cast<float*>(static_cast<char*>(workspace) + (int64_t)ntiles * (hidden / 16) * 2 * 1024);
-    if (!workspace_ready)
-      hipLaunchKernelGGL(radial_mlp_split_w1_fwd_f16_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, b, (float)alpha1,
-                         hidden, out_features, wf, ts);
-    // round 5: outputs of complete 32-column tiles run on the issue-scheduled kernel (radial_mlp_pipe.h; NQA_MLP_PIPE=0:
-    // the general kernel)
-    const bool pipe = [] {  // (read at every call: the tests switch kernels within one process)
-      const char* v = std::getenv("NQA_MLP_PIPE");
-      return v == nullptr || v[0] != '0';
-    }();
-    // (H = 64 stays on the general kernel: its 166 registers keep three wavefronts per SIMD, the scheduled form needs 170)
-    if (pipe && hidden == 128 && out_features % 32 == 0 && ntiles <= 128) {
-      const int64_t e_done = num_edges;
-      const int64_t units = (int64_t)grid * ntiles;
-      const unsigned gb = (unsigned)(units < 2 * (int64_t)num_cus ? units : 2 * (int64_t)num_cus);
-      // tile epilogue: through the wave-private LDS transpose (default: 128-133 us for the cfg-3 middle layer, 48 us for the
-      // first / last one) or straight from the accumulators with the MFMA operands swapped (NQA_MLP_PIPE_DIRECT=1: 134-161
-      // / 50 us at 244 registers) -- profiles/r5_mlp_fwd_kernel_trace.txt; the round-4 kernel: 149-161 / 60 us
-      const bool via_lds = [] {
-        const char* v = std::getenv("NQA_MLP_PIPE_DIRECT");
-        return !(v != nullptr && v[0] == '1');
-      }();
-#define NQA_PIPE_LAUNCH(HH, ABL, DIRECT)                                                                          \
-  hipLaunchKernelGGL((radial_mlp_fwd_pipe_kernel<HH, ABL, DIRECT>), dim3(gb), dim3(256), 0, s, e, a, wf, (float)alpha0, \
-                     num_basis, out_features, e_done, o, ts, dbg)
-      if (dbg != 0 && via_lds) NQA_PIPE_LAUNCH(128, true, false);   // (timing ablations, radial_mlp_pipe.h)
-      else if (dbg != 0) NQA_PIPE_LAUNCH(128, true, true);
-      else if (via_lds) NQA_PIPE_LAUNCH(128, false, false);
-      else NQA_PIPE_LAUNCH(128, false, true);
-#undef NQA_PIPE_LAUNCH
-      return launch_status("nqa_radial_mlp_fwd");
-    }
-    {
-      const int64_t units = (int64_t)grid * ntiles;
-      const unsigned gb = (unsigned)(units < 2 * (int64_t)num_cus ? units : 2 * (int64_t)num_cus);
-      if (hidden == 128)
-        hipLaunchKernelGGL((radial_mlp_fwd_split_bal_kernel<128, true>), dim3(gb), dim3(256), 0, s, e, a, wf,
-                           (float)alpha0, num_basis, out_features, num_edges, o, ts);
-      else
-        hipLaunchKernelGGL((radial_mlp_fwd_split_bal_kernel<64, true>), dim3(gb), dim3(256), 0, s, e, a, wf,
-                           (float)alpha0, num_basis, out_features, num_edges, o, ts);
-    }
-    return launch_status("nqa_radial_mlp_fwd");
-  }
-  if (mode == NQA_MLP_BF16X6) {
-    u32x4* wf = static_cast<u32x4*>(workspace);
-    const int nfrag = ((out_features + 31) / 32) * (hidden / 16) * 64;
-    if (!workspace_ready)
-      hipLaunchKernelGGL(radial_mlp_split_w1_fwd_kernel, dim3((unsigned)((nfrag + 255) / 256)), dim3(256), 0, s, b,
-                         (float)alpha1, hidden, out_features, wf);
-    const bool wide = (dbg & 64) != 0;  // NQA_MLP_DBG bit 6: 8 wavefronts (256 edges) per workgroup (measured: no gain)
-    const unsigned g8 = (unsigned)((num_edges + 255) / 256);
-    if (cotangent != nullptr) {
-      const float* c = static_cast<const float*>(cotangent);
-      if (hidden == 128)
-        hipLaunchKernelGGL((radial_mlp_fwd_bf16x6_kernel<128, 4, true>), dim3(grid), dim3(256), 0, s, e, a, wf,
-                           (float)alpha0, num_basis, out_features, num_edges, o, 0, c);
-      else
-        hipLaunchKernelGGL((radial_mlp_fwd_bf16x6_kernel<64, 4, true>), dim3(grid), dim3(256), 0, s, e, a, wf,
-                           (float)alpha0, num_basis, out_features, num_edges, o, 0, c);
-      return launch_status("nqa_radial_mlp_fwd_tangent");
-    }
-    // default: balanced work-unit ranges over a fixed grid of two workgroups per CU (NQA_MLP_FWD_BALANCED=0 or any
-    // ablation bit: one workgroup per 128-row block)
-    const bool balanced = [] {
-      const char* v = std::getenv("NQA_MLP_FWD_BALANCED");
-      return v == nullptr || v[0] != '0';
-    }();
-    if (balanced && dbg == 0) {
-      const int64_t units = (int64_t)grid * ((out_features + 31) / 32);
-      const unsigned gb = (unsigned)(units < 2 * (int64_t)num_cus ? units : 2 * (int64_t)num_cus);
-      if (hidden == 128)
-        hipLaunchKernelGGL((radial_mlp_fwd_split_bal_kernel<128, false>), dim3(gb), dim3(256), 0, s, e, a, wf,
-                           (float)alpha0, num_basis, out_features, num_edges, o, nullptr);
-      else
-        hipLaunchKernelGGL((radial_mlp_fwd_split_bal_kernel<64, false>), dim3(gb), dim3(256), 0, s, e, a, wf,
-                           (float)alpha0, num_basis, out_features, num_edges, o, nullptr);
-      return launch_status("nqa_radial_mlp_fwd");
-    }
-    if (hidden == 128 && wide)
-      hipLaunchKernelGGL((radial_mlp_fwd_bf16x6_kernel<128, 8>), dim3(g8), dim3(512), 0, s, e, a, wf, (float)alpha0,
-                         num_basis, out_features, num_edges, o, dbg);
-    else if (hidden == 128)
-      hipLaunchKernelGGL((radial_mlp_fwd_bf16x6_kernel<128, 4>), dim3(grid), dim3(256), 0, s, e, a, wf, (float)alpha0,
-                         num_basis, out_features, num_edges, o, dbg);
-    else
-      hipLaunchKernelGGL((radial_mlp_fwd_bf16x6_kernel<64, 4>), dim3(grid), dim3(256), 0, s, e, a, wf, (float)alpha0,
-                         num_basis, out_features, num_edges, o, dbg);
-    return launch_status("nqa_radial_mlp_fwd");
-  }
-  if (cotangent != nullptr) {
-    set_error("nqa_radial_mlp_fwd_tangent: only NQA_MLP_BF16X6 is implemented");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  if (hidden == 128)
-    hipLaunchKernelGGL(radial_mlp_fwd_kernel<128>, dim3(grid), dim3(256), 0, s, e, a, b, (float)alpha0,
-                       (float)alpha1, num_basis, out_features, num_edges, o, dbg);
-  else
-    hipLaunchKernelGGL(radial_mlp_fwd_kernel<64>, dim3(grid), dim3(256), 0, s, e, a, b, (float)alpha0,
-                       (float)alpha1, num_basis, out_features, num_edges, o, dbg);
-  return launch_status("nqa_radial_mlp_fwd");
+int64_t nqa_radial_mlp_train_tiles(int64_t num_edges) {
+  return num_edges <= 0 ? 0 : (num_edges + kMlpRows - 1) / kMlpRows;
 }
 
 int nqa_radial_mlp_fwd(int32_t dtype, int32_t mode, const void* edge_embedding, const void* w0, double alpha0,
                        const void* w1, double alpha1, int32_t num_basis, int32_t hidden, int32_t out_features,
                        int64_t num_edges, void* edge_weight, void* workspace, int64_t workspace_bytes,
                        int32_t workspace_ready, nqa_stream stream) {
-  return mlp_fwd_impl(dtype, mode, edge_embedding, nullptr, w0, alpha0, w1, alpha1, num_basis, hidden, out_features,
-                      num_edges, edge_weight, workspace, workspace_bytes, workspace_ready, stream);
+  return mlp_fwd({"nqa_radial_mlp_fwd", dtype, mode, false, edge_embedding, w0, alpha0, w1, alpha1, num_basis, hidden,
+                  out_features, num_edges, workspace, workspace_bytes, workspace_ready, stream},
+                 nullptr, edge_weight);
 }
 
 int nqa_radial_mlp_fwd_tangent(int32_t dtype, int32_t mode, const void* edge_embedding, const void* cotangent,
                                const void* w0, double alpha0, const void* w1, double alpha1, int32_t num_basis,
                                int32_t hidden, int32_t out_features, int64_t num_edges, void* out, void* workspace,
                                int64_t workspace_bytes, int32_t workspace_ready, nqa_stream stream) {
-  if (num_edges > 0 && cotangent == nullptr) {
-    set_error("nqa_radial_mlp_fwd_tangent: cotangent is required");
-    return NQA_ERR_INVALID;
-  }
-  return mlp_fwd_impl(dtype, mode, edge_embedding, cotangent, w0, alpha0, w1, alpha1, num_basis, hidden,
-                      out_features, num_edges, out, workspace, workspace_bytes, workspace_ready, stream);
-}
-
-static int mlp_bwd_impl(int32_t dtype, int32_t mode, int tm, const void* edge_embedding, const void* cotangent,
-                        void* hidden_out, void* w0_partials, const void* w0, double alpha0, const void* w1,
-                        double alpha1, const void* grad_edge_weight, const void* grad_edge_weight2,
-                        int32_t num_basis, int32_t hidden,
-                        int32_t out_features, int64_t num_edges, void* grad_edge_embedding, void* workspace,
-                        int64_t workspace_bytes, int32_t workspace_ready, nqa_stream stream) {
-  const bool device_idle = (mode & NQA_MLP_HINT_DEVICE_IS_IDLE) != 0;
-  mode &= ~NQA_MLP_HINT_DEVICE_IS_IDLE;
-  int rc = check_mode(dtype, mode, "nqa_radial_mlp_bwd");
-  if (rc != NQA_OK) return rc;
-  rc = check_args(edge_embedding, w0, w1, num_basis, hidden, out_features, num_edges, "nqa_radial_mlp_bwd");
-  if (rc != NQA_OK) return rc;
-  if (num_edges == 0) return NQA_OK;
-  if (grad_edge_weight == nullptr || grad_edge_embedding == nullptr || out_features % 4 != 0) {
-    set_error("nqa_radial_mlp_bwd: invalid argument (needs out_features % 4 == 0)");
-    return NQA_ERR_INVALID;
-  }
-  if (workspace == nullptr || workspace_bytes < nqa_radial_mlp_workspace_bytes(mode, 1, hidden, out_features)) {
-    set_error("nqa_radial_mlp_bwd: workspace missing or too small");
-    return NQA_ERR_WORKSPACE;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned grid = (unsigned)((num_edges + kMlpRows - 1) / kMlpRows);
-  const float* e = static_cast<const float*>(edge_embedding);
-  const float* a = static_cast<const float*>(w0);
-  const float* b = static_cast<const float*>(w1);
-  const float* g = static_cast<const float*>(grad_edge_weight);
-  float* o = static_cast<float*>(grad_edge_embedding);
-  static const int dbg = [] {
-    const char* v = std::getenv("NQA_MLP_DBG_BWD");
-    return v ? std::atoi(v) : 0;
-  }();
-  if (mode == NQA_MLP_F16X3) {
-    const int nchunks = (out_features + 31) / 32;
-    u32x4* wb = static_cast<u32x4*>(workspace);
-    int* ce = reinterpret_cast<int*>(static_cast<char*>(workspace) + (int64_t)nchunks * 2 * 2 * (hidden / 32) * 1024);
-    if (!workspace_ready)
-      hipLaunchKernelGGL(radial_mlp_split_w1_bwd_f16_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, b, (float)alpha1,
-                         hidden, out_features, wb, ce);
-    const float* g2 = static_cast<const float*>(grad_edge_weight2);
-    if (g2 != nullptr && tm != 0) {
-      set_error("nqa_radial_mlp_bwd_paired: inference backward only");
-      return NQA_ERR_UNSUPPORTED;
-    }
-#define NQA_MLP_BWD_F16_LAUNCH(HH, TT, PP)                                                                           \
-  hipLaunchKernelGGL((radial_mlp_bwd_split_kernel<HH, TT, PP, true>), dim3(grid), dim3(256), 0, s, e, a, wb, g,      \
-                     (float)alpha0, num_basis, out_features, num_edges, o, 0, static_cast<const float*>(cotangent),  \
-                     static_cast<float*>(hidden_out), static_cast<float*>(w0_partials), g2, ce)
-    // round 5 (radial_mlp_pipe.h): two more forms of the inference backward over balanced work-unit ranges, both OPT-IN:
-    //   NQA_MLP_BWD_COAL=1     radial_mlp_bwd_coal_kernel (widths that are multiples of 64): g_w in coalesced 256-byte row pieces
-    //                          through an LDS transpose -- alone 226-230 us for the cfg-3 middle layer against 240-244 us of the
-    //                          general kernel (94 / 96 us first / last layer; profiles/r5_mlp_bwd_kernel_trace.txt);
-    //   NQA_MLP_BWD_BALANCED=1 radial_mlp_bwd_pipe_kernel: lane-=-row loads like the general kernel, 235-243 us.
-    // Neither is the default: in the step the radial backward runs on a side stream NEXT TO the node / tensor-product kernels,
-    // and a persistent launch that holds two workgroups on every CU for its whole duration costs those more than it saves
-    // (same-box A/B of the whole step, profiles/r5_step_ab_mlp.txt: 2.37-2.39 ms with the general backward kernel, 2.48-2.49 ms
-    // with the coalesced persistent one, both with the new forward).
-    const bool pipe = [] {
-      const char* v = std::getenv("NQA_MLP_PIPE");
-      return v == nullptr || v[0] != '0';
-    }();
-    const bool coal = [] {
-      const char* v = std::getenv("NQA_MLP_BWD_COAL");
-      return v != nullptr && v[0] == '1';
-    }();
-    const bool balanced = [] {
-      const char* v = std::getenv("NQA_MLP_BWD_BALANCED");
-      return v != nullptr && v[0] == '1';
-    }();
-    const int pf = [] {
-      const char* v = std::getenv("NQA_MLP_BWD_PF");
-      return v ? std::atoi(v) : 2;
-    }();
-    static const int num_cus = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-      return n;
-    }();
-    // narrow outputs (W <= 256: the first / last layer of the BASELINE models) when the caller says that the launch has the
-    // device to itself (NQA_MLP_HINT_DEVICE_IS_IDLE): all fragments resident in LDS, independent wavefronts, epilogue in
-    // registers (radial_mlp_bwd_small_kernel: alone 96 -> 76 us at cfg-3's W = 192, inside the step 87 -> 72 us for the
-    // first layer's launch -- and yet the step as a whole comes out 2 % SLOWER in four of four same-box repetitions, with
-    // the hint and without (profiles/r5_mlp_bwd_small.txt); opt-in: NQA_MLP_BWD_SMALL=1 with the hint, 2 always)
-    const int small_mode = [] {  // NQA_MLP_BWD_SMALL: 0 never (default), 1 with the hint, 2 whenever the shape fits
-      const char* v = std::getenv("NQA_MLP_BWD_SMALL");
-      return v ? std::atoi(v) : 0;
-    }();
-    const bool small_ok = small_mode == 2 || (small_mode == 1 && device_idle);
-    if (pipe && small_ok && tm == 0 && g2 == nullptr && hidden == 128 && out_features % 32 == 0 && out_features <= 256 &&
-        dbg == 0) {
-      const size_t lds = (size_t)nchunks * (2 * 2 * (hidden / 32) * 64) * 16 + (size_t)(hidden / 32) * 16 * 2 * kMaxNb * 4 +
-                         (size_t)kMaxNb * hidden * 4 + (((size_t)nchunks * 4 + 15) & ~(size_t)15);
-      static bool attr_set = false;
-      if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&radial_mlp_bwd_small_kernel<128>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) {
-          (void)hipGetLastError();
-        }
-        attr_set = true;
-      }
-      const int64_t nb32 = (num_edges + 31) / 32;
-      const int64_t want = (nb32 + 7) / 8;  // one 32-row block per wavefront at least
-      const unsigned gb = (unsigned)(want < (int64_t)num_cus ? want : (int64_t)num_cus);
-      hipLaunchKernelGGL((radial_mlp_bwd_small_kernel<128>), dim3(gb), dim3(512), lds, s, e, a, wb, g, (float)alpha0,
-                         num_basis, out_features, num_edges, o, ce);
-      return launch_status("nqa_radial_mlp_bwd");
-    }
-    const bool use_coal = coal && hidden == 128 && out_features % 64 == 0 && dbg == 0;
-    const bool use_bal = (balanced || dbg != 0) && out_features % 32 == 0;
-    if (pipe && tm == 0 && g2 == nullptr && (use_coal || use_bal)) {
-      const int wgs_per_cu = [] {  // NQA_MLP_BWD_WGS_PER_CU=1: half the chip for the (side-stream) persistent launch
-        const char* v = std::getenv("NQA_MLP_BWD_WGS_PER_CU");
-        const int n = v ? std::atoi(v) : 2;
-        return n >= 1 && n <= 2 ? n : 2;
-      }();
-      const int64_t slots = (int64_t)wgs_per_cu * num_cus;
-      const unsigned gb = (unsigned)((int64_t)grid < slots ? (int64_t)grid : slots);
-      if (hipMemsetAsync(o, 0, (size_t)num_edges * num_basis * sizeof(float), s) != hipSuccess) {
-        set_error("nqa_radial_mlp_bwd: hipMemsetAsync failed");
-        return NQA_ERR_LAUNCH;
-      }
-      if (use_coal && !(balanced || dbg != 0)) {
-        hipLaunchKernelGGL((radial_mlp_bwd_coal_kernel<128>), dim3(gb), dim3(256), 0, s, e, a, wb, g, (float)alpha0,
-                           num_basis, out_features, num_edges, o, ce);
-        return launch_status("nqa_radial_mlp_bwd");
-      }
-#define NQA_BPIPE_LAUNCH(HH, PP, RR, AA)                                                                              \
-  hipLaunchKernelGGL((radial_mlp_bwd_pipe_kernel<HH, PP, RR, AA>), dim3(gb), dim3(256), 0, s, e, a, wb, g, (float)alpha0, \
-                     num_basis, out_features, num_edges, o, ce, dbg)
-      if (hidden == 64) NQA_BPIPE_LAUNCH(64, 2, true, false);
-      else if (dbg != 0) NQA_BPIPE_LAUNCH(128, 2, true, true);  // (timing ablations, radial_mlp_pipe.h)
-      else if (pf == 4) NQA_BPIPE_LAUNCH(128, 4, true, false);
-      else NQA_BPIPE_LAUNCH(128, 2, true, false);
-#undef NQA_BPIPE_LAUNCH
-      return launch_status("nqa_radial_mlp_bwd");
-    }
-    if (hidden == 128) {
-      if (g2 != nullptr) NQA_MLP_BWD_F16_LAUNCH(128, 0, true);
-      else if (tm == 0) NQA_MLP_BWD_F16_LAUNCH(128, 0, false);
-      else if (tm == 1) NQA_MLP_BWD_F16_LAUNCH(128, 1, false);
-      else NQA_MLP_BWD_F16_LAUNCH(128, 2, false);
-    } else {
-      if (g2 != nullptr) NQA_MLP_BWD_F16_LAUNCH(64, 0, true);
-      else if (tm == 0) NQA_MLP_BWD_F16_LAUNCH(64, 0, false);
-      else if (tm == 1) NQA_MLP_BWD_F16_LAUNCH(64, 1, false);
-      else NQA_MLP_BWD_F16_LAUNCH(64, 2, false);
-    }
-#undef NQA_MLP_BWD_F16_LAUNCH
-    return launch_status(g2 != nullptr ? "nqa_radial_mlp_bwd_paired" : "nqa_radial_mlp_bwd");
-  }
-  if (mode == NQA_MLP_BF16X6) {
-    u32x4* wb = static_cast<u32x4*>(workspace);
-    const int nfrag = ((out_features + 31) / 32) * 2 * (hidden / 32) * 64;
-    if (!workspace_ready)
-      hipLaunchKernelGGL(radial_mlp_split_w1_bwd_kernel, dim3((unsigned)((nfrag + 255) / 256)), dim3(256), 0, s, b,
-                         (float)alpha1, hidden, out_features, wb);
-    const float* c = static_cast<const float*>(cotangent);
-    float* ho = static_cast<float*>(hidden_out);
-    float* wp = static_cast<float*>(w0_partials);
-#define NQA_MLP_BWD_LAUNCH(HH, TT)                                                                              \
-  hipLaunchKernelGGL((radial_mlp_bwd_split_kernel<HH, TT>), dim3(grid), dim3(256), 0, s, e, a, wb, g,          \
-                     (float)alpha0, num_basis, out_features, num_edges, o, (TT) == 0 ? dbg : 0, c, ho, wp)
-    if (grad_edge_weight2 != nullptr) {
-      const float* g2 = static_cast<const float*>(grad_edge_weight2);
-      if (tm != 0) {
-        set_error("nqa_radial_mlp_bwd_paired: inference backward only");
-        return NQA_ERR_UNSUPPORTED;
-      }
-      if (hidden == 128)
-        hipLaunchKernelGGL((radial_mlp_bwd_split_kernel<128, 0, true>), dim3(grid), dim3(256), 0, s, e, a, wb, g,
-                           (float)alpha0, num_basis, out_features, num_edges, o, 0, c, ho, wp, g2);
-      else
-        hipLaunchKernelGGL((radial_mlp_bwd_split_kernel<64, 0, true>), dim3(grid), dim3(256), 0, s, e, a, wb, g,
-                           (float)alpha0, num_basis, out_features, num_edges, o, 0, c, ho, wp, g2);
-      return launch_status("nqa_radial_mlp_bwd_paired");
-    }
-    if (hidden == 128) {
-      if (tm == 0) NQA_MLP_BWD_LAUNCH(128, 0);
-      else if (tm == 1) NQA_MLP_BWD_LAUNCH(128, 1);
-      else NQA_MLP_BWD_LAUNCH(128, 2);
-    } else {
-      if (tm == 0) NQA_MLP_BWD_LAUNCH(64, 0);
-      else if (tm == 1) NQA_MLP_BWD_LAUNCH(64, 1);
-      else NQA_MLP_BWD_LAUNCH(64, 2);
-    }
-#undef NQA_MLP_BWD_LAUNCH
-    return launch_status("nqa_radial_mlp_bwd");
-  }
-  if (tm != 0 || grad_edge_weight2 != nullptr) {
-    set_error("nqa_radial_mlp_bwd_train / _paired: only NQA_MLP_BF16X6 is implemented");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  float* w1t = static_cast<float*>(workspace);  // [W (+ padding rows read by the last chunk)][H]
-  if (!workspace_ready)
-    hipLaunchKernelGGL(radial_mlp_transpose_w1_kernel, dim3((unsigned)((hidden * out_features + 255) / 256)),
-                       dim3(256), 0, s, b, (float)alpha1, hidden, out_features, w1t);
-  if (hidden == 128)
-    hipLaunchKernelGGL(radial_mlp_bwd_kernel<128>, dim3(grid), dim3(256), 0, s, e, a, w1t, g, (float)alpha0,
-                       num_basis, out_features, num_edges, o);
-  else
-    hipLaunchKernelGGL(radial_mlp_bwd_kernel<64>, dim3(grid), dim3(256), 0, s, e, a, w1t, g, (float)alpha0,
-                       num_basis, out_features, num_edges, o);
-  return launch_status("nqa_radial_mlp_bwd");
+  if (num_edges > 0 && cotangent == nullptr)
+    return fail(NQA_ERR_INVALID, "nqa_radial_mlp_fwd_tangent: cotangent is required");
+  return mlp_fwd({"nqa_radial_mlp_fwd", dtype, mode, false, edge_embedding, w0, alpha0, w1, alpha1, num_basis, hidden,
+                  out_features, num_edges, workspace, workspace_bytes, workspace_ready, stream},
+                 cotangent, out);
 }
 
 int nqa_radial_mlp_bwd(int32_t dtype, int32_t mode, const void* edge_embedding, const void* w0, double alpha0,
                        const void* w1, double alpha1, const void* grad_edge_weight, int32_t num_basis,
                        int32_t hidden, int32_t out_features, int64_t num_edges, void* grad_edge_embedding,
                        void* workspace, int64_t workspace_bytes, int32_t workspace_ready, nqa_stream stream) {
-  return mlp_bwd_impl(dtype, mode, 0, edge_embedding, nullptr, nullptr, nullptr, w0, alpha0, w1, alpha1,
-                      grad_edge_weight, nullptr, num_basis, hidden, out_features, num_edges, grad_edge_embedding, workspace,
-                      workspace_bytes, workspace_ready, stream);
+  return mlp_bwd({"nqa_radial_mlp_bwd", dtype, mode, false, edge_embedding, w0, alpha0, w1, alpha1, num_basis, hidden,
+                  out_features, num_edges, workspace, workspace_bytes, workspace_ready, stream},
+                 0, nullptr, nullptr, nullptr, grad_edge_weight, nullptr, grad_edge_embedding);
 }
 
 int nqa_radial_mlp_bwd_paired(int32_t dtype, int32_t mode, const void* edge_embedding, const void* w0, double alpha0,
@@ -1928,107 +1814,11 @@ int nqa_radial_mlp_bwd_paired(int32_t dtype, int32_t mode, const void* edge_embe
                               const void* grad_edge_weight2, int32_t num_basis, int32_t hidden, int32_t out_features,
                               int64_t num_edges, void* grad_edge_embedding, void* workspace, int64_t workspace_bytes,
                               int32_t workspace_ready, nqa_stream stream) {
-  if (num_edges > 0 && grad_edge_weight2 == nullptr) {
-    set_error("nqa_radial_mlp_bwd_paired: second gradient stream is required");
-    return NQA_ERR_INVALID;
-  }
-  return mlp_bwd_impl(dtype, mode, 0, edge_embedding, nullptr, nullptr, nullptr, w0, alpha0, w1, alpha1,
-                      grad_edge_weight, grad_edge_weight2, num_basis, hidden, out_features, num_edges,
-                      grad_edge_embedding, workspace, workspace_bytes, workspace_ready, stream);
-}
-
-// ---- the last layer of a deeper MLP on the same GEMM cores (depth >= 2: nequip/nn/mlp.py:81-196 with
-// hidden_layers_depth >= 2, e.g. configs/tutorial.yaml:222-223) -------------------------------------------------------
-int nqa_radial_mlp_last_fwd(int32_t dtype, int32_t mode, const void* pre, const void* w, double alpha, int32_t hidden,
-                            int32_t out_features, int64_t num_edges, void* out, void* workspace, int64_t workspace_bytes,
-                            int32_t workspace_ready, nqa_stream stream) {
-  if (dtype != NQA_F32 || mode != NQA_MLP_F16X3) {
-    set_error("nqa_radial_mlp_last_fwd: float32 on the two-plane fp16 split (NQA_MLP_F16X3) only");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  if (num_edges < 0 || (hidden != 64 && hidden != 128) || out_features <= 0 || out_features % 4 != 0 ||
-      (num_edges > 0 && (!pre || !w || !out))) {
-    set_error("nqa_radial_mlp_last_fwd: invalid argument (hidden 64 / 128, out_features % 4 == 0)");
-    return hidden != 64 && hidden != 128 ? NQA_ERR_UNSUPPORTED : NQA_ERR_INVALID;
-  }
-  if (num_edges == 0) return NQA_OK;
-  const int64_t need = nqa_radial_mlp_workspace_bytes(mode, 0, hidden, out_features);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("nqa_radial_mlp_last_fwd: workspace missing or too small");
-    return NQA_ERR_WORKSPACE;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  static const int num_cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  const unsigned grid = (unsigned)((num_edges + kMlpRows - 1) / kMlpRows);
-  const int ntiles = (out_features + 31) / 32;
-  u32x4* wf = static_cast<u32x4*>(workspace);
-  float* ts = reinterpret_cast<float*>(static_cast<char*>(workspace) + (int64_t)ntiles * (hidden / 16) * 2 * 1024);
-  if (!workspace_ready)
-    hipLaunchKernelGGL(radial_mlp_split_w1_fwd_f16_kernel, dim3((unsigned)ntiles), dim3(256), 0, s,
-                       static_cast<const float*>(w), (float)alpha, hidden, out_features, wf, ts);
-  const int64_t units = (int64_t)grid * ntiles;
-  const unsigned gb = (unsigned)(units < 2 * (int64_t)num_cus ? units : 2 * (int64_t)num_cus);
-  const float* p = static_cast<const float*>(pre);
-  float* o = static_cast<float*>(out);
-  if (hidden == 128)
-    hipLaunchKernelGGL((radial_mlp_fwd_split_bal_kernel<128, true, true>), dim3(gb), dim3(256), 0, s, p, nullptr, wf, 1.f,
-                       0, out_features, num_edges, o, ts);
-  else
-    hipLaunchKernelGGL((radial_mlp_fwd_split_bal_kernel<64, true, true>), dim3(gb), dim3(256), 0, s, p, nullptr, wf, 1.f, 0,
-                       out_features, num_edges, o, ts);
-  return launch_status("nqa_radial_mlp_last_fwd");
-}
-
-int nqa_radial_mlp_last_bwd(int32_t dtype, int32_t mode, const void* pre, const void* w, double alpha,
-                            const void* grad_out, const void* grad_out2, int32_t hidden, int32_t out_features,
-                            int64_t num_edges, void* grad_pre, void* workspace, int64_t workspace_bytes,
-                            int32_t workspace_ready, nqa_stream stream) {
-  if (dtype != NQA_F32 || mode != NQA_MLP_F16X3) {
-    set_error("nqa_radial_mlp_last_bwd: float32 on the two-plane fp16 split (NQA_MLP_F16X3) only");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  if (num_edges < 0 || (hidden != 64 && hidden != 128) || out_features <= 0 || out_features % 4 != 0 ||
-      (num_edges > 0 && (!pre || !w || !grad_out || !grad_pre))) {
-    set_error("nqa_radial_mlp_last_bwd: invalid argument (hidden 64 / 128, out_features % 4 == 0)");
-    return hidden != 64 && hidden != 128 ? NQA_ERR_UNSUPPORTED : NQA_ERR_INVALID;
-  }
-  if (num_edges == 0) return NQA_OK;
-  if (workspace == nullptr || workspace_bytes < nqa_radial_mlp_workspace_bytes(mode, 1, hidden, out_features)) {
-    set_error("nqa_radial_mlp_last_bwd: workspace missing or too small");
-    return NQA_ERR_WORKSPACE;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned grid = (unsigned)((num_edges + kMlpRows - 1) / kMlpRows);
-  const int nchunks = (out_features + 31) / 32;
-  u32x4* wb = static_cast<u32x4*>(workspace);
-  int* ce = reinterpret_cast<int*>(static_cast<char*>(workspace) + (int64_t)nchunks * 2 * 2 * (hidden / 32) * 1024);
-  if (!workspace_ready)
-    hipLaunchKernelGGL(radial_mlp_split_w1_bwd_f16_kernel, dim3((unsigned)nchunks), dim3(256), 0, s,
-                       static_cast<const float*>(w), (float)alpha, hidden, out_features, wb, ce);
-  const float* p = static_cast<const float*>(pre);
-  const float* g = static_cast<const float*>(grad_out);
-  const float* g2 = static_cast<const float*>(grad_out2);
-  float* o = static_cast<float*>(grad_pre);
-#define NQA_MLP_LAST_BWD(HH, PP)                                                                                        \
-  hipLaunchKernelGGL((radial_mlp_bwd_split_kernel<HH, 0, PP, true, true>), dim3(grid), dim3(256), 0, s, p, nullptr, wb, \
-                     g, 1.f, 0, out_features, num_edges, o, 0, nullptr, nullptr, nullptr, g2, ce)
-  if (hidden == 128) {
-    if (g2 != nullptr) NQA_MLP_LAST_BWD(128, true);
-    else NQA_MLP_LAST_BWD(128, false);
-  } else {
-    if (g2 != nullptr) NQA_MLP_LAST_BWD(64, true);
-    else NQA_MLP_LAST_BWD(64, false);
-  }
-#undef NQA_MLP_LAST_BWD
-  return launch_status("nqa_radial_mlp_last_bwd");
-}
-
-int64_t nqa_radial_mlp_train_tiles(int64_t num_edges) {
-  return num_edges <= 0 ? 0 : (num_edges + kMlpRows - 1) / kMlpRows;
+  if (num_edges > 0 && grad_edge_weight2 == nullptr)
+    return fail(NQA_ERR_INVALID, "nqa_radial_mlp_bwd_paired: second gradient stream is required");
+  return mlp_bwd({"nqa_radial_mlp_bwd", dtype, mode, false, edge_embedding, w0, alpha0, w1, alpha1, num_basis, hidden,
+                  out_features, num_edges, workspace, workspace_bytes, workspace_ready, stream},
+                 0, nullptr, nullptr, nullptr, grad_edge_weight, grad_edge_weight2, grad_edge_embedding);
 }
 
 int nqa_radial_mlp_bwd_train(int32_t dtype, int32_t mode, const void* edge_embedding, const void* cotangent,
@@ -2036,13 +1826,30 @@ int nqa_radial_mlp_bwd_train(int32_t dtype, int32_t mode, const void* edge_embed
                              const void* grad_edge_weight, int32_t num_basis, int32_t hidden, int32_t out_features,
                              int64_t num_edges, void* grad_edge_embedding, void* hidden_out, void* w0_partials,
                              void* workspace, int64_t workspace_bytes, int32_t workspace_ready, nqa_stream stream) {
-  if (num_edges > 0 && (hidden_out == nullptr || w0_partials == nullptr)) {
-    set_error("nqa_radial_mlp_bwd_train: hidden_out and w0_partials are required");
-    return NQA_ERR_INVALID;
-  }
-  return mlp_bwd_impl(dtype, mode, cotangent ? 2 : 1, edge_embedding, cotangent, hidden_out, w0_partials, w0, alpha0,
-                      w1, alpha1, grad_edge_weight, nullptr, num_basis, hidden, out_features, num_edges, grad_edge_embedding,
-                      workspace, workspace_bytes, workspace_ready, stream);
+  if (num_edges > 0 && (hidden_out == nullptr || w0_partials == nullptr))
+    return fail(NQA_ERR_INVALID, "nqa_radial_mlp_bwd_train: hidden_out and w0_partials are required");
+  return mlp_bwd({"nqa_radial_mlp_bwd", dtype, mode, false, edge_embedding, w0, alpha0, w1, alpha1, num_basis, hidden,
+                  out_features, num_edges, workspace, workspace_bytes, workspace_ready, stream},
+                 cotangent ? 2 : 1, cotangent, hidden_out, w0_partials, grad_edge_weight, nullptr, grad_edge_embedding);
+}
+
+// ---- the last layer of a deeper MLP on the same GEMM cores (depth >= 2: nequip/nn/mlp.py:81-196 with
+// hidden_layers_depth >= 2, e.g. configs/tutorial.yaml:222-223) -------------------------------------------------------
+int nqa_radial_mlp_last_fwd(int32_t dtype, int32_t mode, const void* pre, const void* w, double alpha, int32_t hidden,
+                            int32_t out_features, int64_t num_edges, void* out, void* workspace, int64_t workspace_bytes,
+                            int32_t workspace_ready, nqa_stream stream) {
+  return mlp_fwd({"nqa_radial_mlp_last_fwd", dtype, mode, true, pre, nullptr, 1.0, w, alpha, 0, hidden, out_features,
+                  num_edges, workspace, workspace_bytes, workspace_ready, stream},
+                 nullptr, out);
+}
+
+int nqa_radial_mlp_last_bwd(int32_t dtype, int32_t mode, const void* pre, const void* w, double alpha,
+                            const void* grad_out, const void* grad_out2, int32_t hidden, int32_t out_features,
+                            int64_t num_edges, void* grad_pre, void* workspace, int64_t workspace_bytes,
+                            int32_t workspace_ready, nqa_stream stream) {
+  return mlp_bwd({"nqa_radial_mlp_last_bwd", dtype, mode, true, pre, nullptr, 1.0, w, alpha, 0, hidden, out_features,
+                  num_edges, workspace, workspace_bytes, workspace_ready, stream},
+                 0, nullptr, nullptr, nullptr, grad_out, grad_out2, grad_pre);
 }
 
 }  // extern "C"

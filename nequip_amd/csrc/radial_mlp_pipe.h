@@ -17,6 +17,8 @@
 
 #include <type_traits>
 
+#include "mfma_split.h"
+
 namespace nqa {
 
 // silu(x) = x / (1 + e^-x) on v_exp_f32 / v_rcp_f32 (1 ulp each; as the fused node stage, csrc/node_fused.h)
@@ -24,27 +26,18 @@ __device__ __forceinline__ float silu_fast_f(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
 
-// false for every valid launch, opaque to the compiler (ablation branches)
-__device__ __forceinline__ bool ntiles_never(int W) { return W < 0; }
-
 __device__ __forceinline__ float mlp_readlane_f(float v, int l) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
 }
 
 // Preconditions (checked by the host): E > 0, W % 32 == 0, W / 32 <= 128, nb <= kMaxNb.  The last block may be ragged:
 // its missing rows compute on row E - 1 and are not stored (one wave-uniform test per unit).
-template <int H, bool ABL = false, bool DIRECT = true>
+template <int H, bool DIRECT = true>
 __global__ __launch_bounds__(256, 2) void radial_mlp_fwd_pipe_kernel(const float* __restrict__ emb,
                                                                      const float* __restrict__ W0,
                                                                      const u32x4* __restrict__ Wf, float a0, int nb,
                                                                      int W, int64_t E, float* __restrict__ out,
-                                                                     const float* __restrict__ tile_scale, int dbg_arg) {
-  // ABL (NQA_MLP_DBG != 0; timing ablations, wrong results): the pieces named by the bits sit behind wave-uniform branches
-  // that are never taken at run time, so that everything feeding them stays alive: 1 = no global stores, 2 = no matrix
-  // instructions, 4 = no weight-tile staging after the first tile, 8 = no workgroup barrier, 16 = the hidden layer of the
-  // first block for every block, 32 = the first k-step's LDS fragments for every k-step
-  const int dbg = ABL ? dbg_arg : 0;
-  const bool never = ABL && ntiles_never(W);
+                                                                     const float* __restrict__ tile_scale) {
   constexpr int KS = H / 16;
   constexpr int TILE = KS * 2 * 64;  // uint4 per weight tile (two planes)
   constexpr int NV = TILE / 256;
@@ -206,7 +199,7 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_fwd_pipe_kernel(const float
         if (r < r0 || r >= r1) continue;
         const float v = (pa[r] + pb[r]) * fr[r];
         float* __restrict__ dst = reinterpret_cast<float*>(reinterpret_cast<char*>(ob + (int64_t)(r & 3) * W) + soff[r >> 2]);
-        if (!(dbg & 1) || never) __builtin_nontemporal_store(v, dst);
+        __builtin_nontemporal_store(v, dst);
       }
     } else {
 #pragma unroll
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_fwd_pipe_kernel(const float
     if (rows_left >= 32) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        if (q >= q0 && q < q1 && (!(dbg & 1) || never))
+        if (q >= q0 && q < q1)
           mlp_store4(reinterpret_cast<float*>(reinterpret_cast<char*>(ob) + soff[q]), rd[q]);
     } else {
 #pragma unroll
@@ -238,7 +231,7 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_fwd_pipe_kernel(const float
       ++blk;
 #pragma unroll
       for (int c = 0; c < kMaxNb; ++c) ev[c] = evn[c];
-      if (!(dbg & 16) || never) hidden(ev);
+      hidden(ev);
       load_ev(blk + 1, evn);
     }
     const int buf = i & 1;
@@ -246,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_fwd_pipe_kernel(const float
     // the epilogue's stores in program order: inside one region the compiler counts the memory queue exactly (the
     // younger stores stay in flight).  Consumed at the top of the next unit instead, the wait sat behind a loop head
     // where the counts of all predecessors merge, and every unit waited for its own stores.
-    if (!(dbg & 4) || never) stage_load(tile_after(t, 1));  // unconditional: past the range a valid tile is fetched and never used
+    stage_load(tile_after(t, 1));  // unconditional: past the range a valid tile is fetched and never used
     const u32x4* __restrict__ a = as[buf] + lane;
     accA = (f32x16){0};
     accB = (f32x16){0};
@@ -268,13 +261,12 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_fwd_pipe_kernel(const float
     }
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      if (s + 2 < KS && (!(dbg & 32) || never)) {
+      if (s + 2 < KS) {
         fa[(s + 2) % 3][0] = a[((s + 2) * 2) * 64];
         fa[(s + 2) % 3][1] = a[((s + 2) * 2 + 1) * 64];
       }
       const u32x4 &ah = fa[s % 3][0], &al = fa[s % 3][1];
-      if (ABL && (dbg & 2) && !never) {
-      } else if constexpr (DIRECT) {
+      if constexpr (DIRECT) {
         if (s & 1) {
           accB = mfma_f16(bl[s], ah, accB);
           accA = mfma_f16(bh[s], al, accA);
@@ -310,7 +302,7 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_fwd_pipe_kernel(const float
         }
         if (s >= sS && s < sS + nS) store_rows(ob, rd, (s - sS) * 4 / nS, (s - sS + 1) * 4 / nS, rows_left);
       }
-      if (s == sG && (!(dbg & 4) || never)) stage_store(buf ^ 1);
+      if (s == sG) stage_store(buf ^ 1);
       if constexpr (DIRECT) {
         if (s == KS - 1) {
           const float tsc = tscale(t);
@@ -320,7 +312,7 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_fwd_pipe_kernel(const float
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (!(dbg & 8)) lds_barrier();
+    lds_barrier();
     prev_tile = t;
     prev_row0 = blk * kMlpRows + wv * 32;
     prev_rs = row_scale;
@@ -384,17 +376,13 @@ __device__ __forceinline__ float silu_grad_fast_f(float x) {
 //    never used) -- the chunk body has no exec-masked region besides the rare rescale.
 //    The last block may be ragged: its missing rows read row E - 1 again and are never written.
 // Preconditions (host): E > 0, W % 32 == 0, gridDim.x <= ceil(E / kMlpRows), g_emb zero-filled.
-template <int H, int PF = 2, bool RAGGED = true, bool ABL = false>
+template <int H, int PF = 2, bool RAGGED = true>
 __global__ __launch_bounds__(256, 2) void radial_mlp_bwd_pipe_kernel(const float* __restrict__ emb,
                                                                      const float* __restrict__ W0,
                                                                      const u32x4* __restrict__ Wb,
                                                                      const float* __restrict__ gw, float a0, int nb,
                                                                      int W, int64_t E, float* __restrict__ g_emb,
-                                                                     const int* __restrict__ chunk_exp, int dbg_arg) {
-  // ABL (NQA_MLP_DBG_BWD != 0; timing ablations, wrong results; never-taken wave-uniform branches keep the operands alive):
-  // 2 = no matrix instructions, 4 = no weight-fragment staging, 32 = no LDS fragment reads
-  const int dbg = ABL ? dbg_arg : 0;
-  const bool never = ABL && ntiles_never(W);
+                                                                     const int* __restrict__ chunk_exp) {
   constexpr int NT = H / 32;
   constexpr int CH = 2 * 2 * NT * 64;  // uint4 per chunk of B fragments (two k-steps x two planes)
   constexpr int NV = CH / 256;
@@ -550,7 +538,7 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_bwd_pipe_kernel(const float
       }
       // weight fragments (L2) of the next chunk BEFORE the g_w request (HBM) of a later chunk: vmcnt retires in order,
       // so the wait for the fragments at the end of this body leaves the four younger HBM loads in flight
-      if (!(dbg & 4) || never) load_b(ch + 1);
+      load_b(ch + 1);
       if constexpr (kPF == 4) {
         // PF == 4: the rows are requested in bursts of TWO adjacent chunks (256 contiguous bytes per row instead of 128) by
         // the odd bodies, once both register sets involved are free: chunks ch + 3 and ch + 4
@@ -565,32 +553,20 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_bwd_pipe_kernel(const float
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         u32x4 fb[2][NT];
-        if (!(dbg & 32) || never || (s == 0 && j == 0)) {
 #pragma unroll
-          for (int p = 0; p < 2; ++p)
+        for (int p = 0; p < 2; ++p)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) fb[p][t] = bs[((s * 2 + p) * NT + t) * 64];
-        } else {
-#pragma unroll
-          for (int p = 0; p < 2; ++p)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) fb[p][t] = (u32x4){ah[s][0] + (unsigned)t, al[s][1], ah[s][2] + (unsigned)p, al[s][3]};
-        }
+          for (int t = 0; t < NT; ++t) fb[p][t] = bs[((s * 2 + p) * NT + t) * 64];
         __builtin_amdgcn_sched_barrier(0);
-        if (ABL && (dbg & 2) && !never) {
 #pragma unroll
-          for (int t = 0; t < NT; ++t) acc[t][0] += __builtin_bit_cast(float, fb[0][t][0] ^ fb[1][t][1] ^ al[s][t & 3] ^ ah[s][(t + 1) & 3]);
-        } else {
+        for (int t = 0; t < NT; ++t) acc[t] = mfma_f16(al[s], fb[0][t], acc[t]);
 #pragma unroll
-          for (int t = 0; t < NT; ++t) acc[t] = mfma_f16(al[s], fb[0][t], acc[t]);
+        for (int t = 0; t < NT; ++t) acc[t] = mfma_f16(ah[s], fb[1][t], acc[t]);
 #pragma unroll
-          for (int t = 0; t < NT; ++t) acc[t] = mfma_f16(ah[s], fb[1][t], acc[t]);
-#pragma unroll
-          for (int t = 0; t < NT; ++t) acc[t] = mfma_f16(ah[s], fb[0][t], acc[t]);
-        }
+        for (int t = 0; t < NT; ++t) acc[t] = mfma_f16(ah[s], fb[0][t], acc[t]);
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (!(dbg & 4) || never) store_b(buf ^ 1);
+      store_b(buf ^ 1);
       lds_barrier();
     };
     for (int j = 0; j < n; j += kPF) {

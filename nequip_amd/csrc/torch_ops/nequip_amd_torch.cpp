@@ -714,7 +714,13 @@ Tensor edge_embed_bwd(const Tensor& edge_vec, const Tensor& bessel_weights, cons
 }
 
 // ---- radial MLP --------------------------------------------------------------------------------------------------------
-int32_t mlp_mode() { return env_on("NQA_MLP_EXACT_FP32") ? NQA_MLP_FP32 : NQA_MLP_BF16X6; }
+// GEMM mode of a forward / backward launch, as nequip_amd/nn/mlp.py (radial_mlp_mode, forward_mode, backward_mode): the
+// split-bf16 default runs on the two-plane fp16 split unless NQA_MLP_FWD_F16=0 / NQA_MLP_BWD_F16=0
+int32_t mlp_mode(bool backward) {
+  if (env_on("NQA_MLP_EXACT_FP32")) return NQA_MLP_FP32;
+  const char* v = std::getenv(backward ? "NQA_MLP_BWD_F16" : "NQA_MLP_FWD_F16");
+  return v && v[0] == '0' ? NQA_MLP_BF16X6 : NQA_MLP_F16X3;
+}
 
 // (image, ready): the workspace of nqa_radial_mlp_fwd / _bwd for one constant `w1` -- ready once a launch has filled it
 // (the prepass folds alpha1 into the image; a launch over zero rows returns before it: no entry is made for one)
@@ -742,9 +748,7 @@ Tensor radial_mlp_fwd(const Tensor& emb_, const Tensor& w0_, const Tensor& w1_, 
   const Tensor emb = emb_.contiguous(), w0 = w0_.contiguous(), w1 = w1_.contiguous();
   const int64_t E = emb.size(0);
   const int32_t nb = (int32_t)emb.size(1), H = (int32_t)w1.size(0), W = (int32_t)w1.size(1);
-  int32_t mode = mlp_mode();
-  if (mode == NQA_MLP_BF16X6 && !(std::getenv("NQA_MLP_FWD_F16") && std::getenv("NQA_MLP_FWD_F16")[0] == '0'))
-    mode = NQA_MLP_F16X3;  // (nequip_amd/nn/mlp.py::forward_mode)
+  const int32_t mode = mlp_mode(false);
   Tensor out = at::empty({E, W}, emb.options());
   const int64_t ws_bytes = nqa_radial_mlp_workspace_bytes(mode, 0, H, W);
   TORCH_CHECK(ws_bytes >= 0, "nequip_amd::radial_mlp_fwd: workspace query failed");
@@ -756,45 +760,39 @@ Tensor radial_mlp_fwd(const Tensor& emb_, const Tensor& w0_, const Tensor& w1_, 
   return out;
 }
 
+// The tail shared by the backward ops (mode, weight image, call): the gradient w.r.t. the embedding rows from the weight
+// gradient `g1` (nqa_radial_mlp_bwd), or -- `g2` defined -- from its two halves `g1 + g2` for the rows of pairs
+// (nqa_radial_mlp_bwd_paired).  The callers have checked the arguments and made them contiguous.
+Tensor radial_mlp_bwd_impl(const Tensor& emb, const Tensor& w0, const Tensor& w1, const Tensor& g1, const Tensor& g2,
+                             double alpha0, double alpha1) {
+  const int64_t P = emb.size(0);
+  const int32_t nb = (int32_t)emb.size(1), H = (int32_t)w1.size(0), W = (int32_t)w1.size(1);
+  const int32_t mode = mlp_mode(true);
+  Tensor g_emb = at::empty_like(emb);
+  const int64_t ws_bytes = nqa_radial_mlp_workspace_bytes(mode, 1, H, W);
+  TORCH_CHECK(ws_bytes >= 0, "nequip_amd::", g2.defined() ? "radial_tp_bwd" : "radial_mlp_bwd", ": workspace query failed");
+  const auto ws = mlp_image(w1, alpha1, mode, 1, ws_bytes, P);
+  if (g2.defined())
+    NQA_CALL(nqa_radial_mlp_bwd_paired(NQA_F32, mode, emb.data_ptr(), w0.data_ptr(), alpha0, w1.data_ptr(), alpha1,
+                                       g1.data_ptr(), g2.data_ptr(), nb, H, W, P, g_emb.data_ptr(), ws.first.data_ptr(),
+                                       ws_bytes, ws.second ? 1 : 0, stream_of(emb)),
+             "nqa_radial_mlp_bwd_paired");
+  else
+    NQA_CALL(nqa_radial_mlp_bwd(NQA_F32, mode, emb.data_ptr(), w0.data_ptr(), alpha0, w1.data_ptr(), alpha1, g1.data_ptr(),
+                                nb, H, W, P, g_emb.data_ptr(), ws.first.data_ptr(), ws_bytes, ws.second ? 1 : 0,
+                                stream_of(emb)),
+             "nqa_radial_mlp_bwd");
+  return g_emb;
+}
+
 Tensor radial_mlp_bwd(const Tensor& emb_, const Tensor& w0_, const Tensor& w1_, const Tensor& g_, double alpha0,
                       double alpha1) {
   check_mlp(emb_, w0_, w1_, "radial_mlp_bwd");
   c10::DeviceGuard guard(emb_.device());
   const Tensor emb = emb_.contiguous(), w0 = w0_.contiguous(), w1 = w1_.contiguous(), g = g_.contiguous();
-  const int64_t E = emb.size(0);
-  const int32_t nb = (int32_t)emb.size(1), H = (int32_t)w1.size(0), W = (int32_t)w1.size(1);
-  TORCH_CHECK(g.scalar_type() == at::kFloat && g.dim() == 2 && g.size(0) == E && g.size(1) == W,
+  TORCH_CHECK(g.scalar_type() == at::kFloat && g.dim() == 2 && g.size(0) == emb.size(0) && g.size(1) == w1.size(1),
               "nequip_amd::radial_mlp_bwd: g must be float32 [E, W]");
-  int32_t mode = mlp_mode();
-  if (mode == NQA_MLP_BF16X6 && !(std::getenv("NQA_MLP_BWD_F16") && std::getenv("NQA_MLP_BWD_F16")[0] == '0'))
-    mode = NQA_MLP_F16X3;  // (nequip_amd/nn/mlp.py::backward_mode)
-  Tensor g_emb = at::empty_like(emb);
-  const int64_t ws_bytes = nqa_radial_mlp_workspace_bytes(mode, 1, H, W);
-  TORCH_CHECK(ws_bytes >= 0, "nequip_amd::radial_mlp_bwd: workspace query failed");
-  const auto ws = mlp_image(w1, alpha1, mode, 1, ws_bytes, E);
-  NQA_CALL(nqa_radial_mlp_bwd(NQA_F32, mode, emb.data_ptr(), w0.data_ptr(), alpha0, w1.data_ptr(), alpha1, g.data_ptr(), nb,
-                              H, W, E, g_emb.data_ptr(), ws.first.data_ptr(), ws_bytes, ws.second ? 1 : 0, stream_of(emb)),
-           "nqa_radial_mlp_bwd");
-  return g_emb;
-}
-
-// gradient w.r.t. the embedding rows of the pairs from the two halves of the weight gradient (nqa_radial_mlp_bwd_paired)
-Tensor radial_mlp_bwd_halves(const Tensor& emb, const Tensor& w0, const Tensor& w1, const Tensor& g1, const Tensor& g2,
-                             double alpha0, double alpha1) {
-  const int64_t P = emb.size(0);
-  const int32_t nb = (int32_t)emb.size(1), H = (int32_t)w1.size(0), W = (int32_t)w1.size(1);
-  int32_t mode = mlp_mode();
-  if (mode == NQA_MLP_BF16X6 && !(std::getenv("NQA_MLP_BWD_F16") && std::getenv("NQA_MLP_BWD_F16")[0] == '0'))
-    mode = NQA_MLP_F16X3;
-  Tensor g_emb = at::empty_like(emb);
-  const int64_t ws_bytes = nqa_radial_mlp_workspace_bytes(mode, 1, H, W);
-  TORCH_CHECK(ws_bytes >= 0, "nequip_amd::radial_tp_bwd: workspace query failed");
-  const auto ws = mlp_image(w1, alpha1, mode, 1, ws_bytes, P);
-  NQA_CALL(nqa_radial_mlp_bwd_paired(NQA_F32, mode, emb.data_ptr(), w0.data_ptr(), alpha0, w1.data_ptr(), alpha1,
-                                     g1.data_ptr(), g2.data_ptr(), nb, H, W, P, g_emb.data_ptr(), ws.first.data_ptr(),
-                                     ws_bytes, ws.second ? 1 : 0, stream_of(emb)),
-           "nqa_radial_mlp_bwd_paired");
-  return g_emb;
+  return radial_mlp_bwd_impl(emb, w0, w1, g, Tensor(), alpha0, alpha1);
 }
 
 // ---- radial_tp: radial MLP + tensor-product scatter of one convolution, pairing decided here (nn/_radial_tp_ops.py) -----
@@ -966,7 +964,7 @@ std::tuple<Tensor, Tensor, Tensor> radial_tp_bwd(const Tensor& g_, const Tensor&
   if (need_emb) {
     const Tensor emb_half = pair_rows(emb, pr);
     const Tensor g_half = folded ? radial_mlp_bwd(emb_half, w0, w1, G, alpha0, alpha1)
-                                 : radial_mlp_bwd_halves(emb_half, w0, w1, G.slice(0, 0, Pn), G.slice(0, Pn, 2 * Pn), alpha0,
+                                 : radial_mlp_bwd_impl(emb_half, w0, w1, G.slice(0, 0, Pn), G.slice(0, Pn, 2 * Pn), alpha0,
                                                          alpha1);
     g_emb = at::empty_like(emb);
     NQA_CALL(nqa_pair_expand(g_half.data_ptr(), i32(pr.rows), E, Pn, (int32_t)emb.size(1), g_emb.data_ptr(), stream_of(emb)),

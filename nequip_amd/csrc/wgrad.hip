@@ -19,6 +19,7 @@
 #include <cstring>
 #include <string>
 
+#include "mfma_split.h"
 #include "plan.h"
 
 namespace nqa {
@@ -41,8 +42,6 @@ struct WgradArgs {
   int32_t total_units, pad;
   WgradInstr instr[kMaxWgradInstr];
 };
-
-typedef float wg_f16 __attribute__((ext_vector_type(16)));
 
 // RB: 32-row blocks of the output tile owned by a wavefront (M <= 32*RB per tile), two 32-column blocks.
 // WGRED: the four wavefronts of a workgroup share one (tile, partial) unit (reduced on chip); otherwise one unit each
@@ -83,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
   }
   const uint32_t lda4 = 4u * (uint32_t)a.lda, ldb4 = 4u * (uint32_t)a.ldb;
 
-  wg_f16 acc[RB][2];
+  f32x16 acc[RB][2];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -220,32 +219,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
 // in flight during the MFMAs of the current one).  Measured: the 128-row calls of the training step 0.95 -> 0.83 ms only --
 // 32 scalar row loads (8 KB) per step and wavefront are 80 B/clk per CU at the MFMA rate, more than the 64 B/clk the
 // vector memory path delivers; a wider tile per wavefront (or LDS staging shared by the workgroup) is what it needs next.
-typedef __attribute__((ext_vector_type(8))) __bf16 wg_bf16x8;
-typedef __attribute__((ext_vector_type(4))) uint32_t wg_u32x4;
-
-__device__ __forceinline__ uint32_t wg_cvt_pk_bf16(float lo, float hi) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-__device__ __forceinline__ void wg_split8(const float (&v)[8], wg_u32x4& h, wg_u32x4& m, wg_u32x4& l) {
+__device__ __forceinline__ void wg_split8(const float (&v)[8], u32x4& h, u32x4& m, u32x4& l) {
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
-    const float x0 = v[2 * p], x1 = v[2 * p + 1];
-    const uint32_t hh = wg_cvt_pk_bf16(x0, x1);
-    float r0 = x0 - __uint_as_float(hh << 16);
-    float r1 = x1 - __uint_as_float(hh & 0xffff0000u);
-    const uint32_t mm = wg_cvt_pk_bf16(r0, r1);
-    r0 -= __uint_as_float(mm << 16);
-    r1 -= __uint_as_float(mm & 0xffff0000u);
+    uint32_t hh, mm, ll;
+    split_pair(v[2 * p], v[2 * p + 1], hh, mm, ll);
     h[p] = hh;
     m[p] = mm;
-    l[p] = wg_cvt_pk_bf16(r0, r1);
+    l[p] = ll;
   }
-}
-__device__ __forceinline__ wg_f16 wg_mfma_bf16(const wg_u32x4& a, const wg_u32x4& b, const wg_f16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wg_bf16x8, a), __builtin_bit_cast(wg_bf16x8, b), c, 0,
-                                                 0, 0);
 }
 
 constexpr int kWgRows = 16;  // rows per pipeline step of the split form
@@ -288,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a) 
   }
   const uint32_t lda4 = 4u * (uint32_t)a.lda, ldb4 = 4u * (uint32_t)a.ldb;
 
-  wg_f16 acc[RB][2];
+  f32x16 acc[RB][2];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -321,7 +303,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a) 
     }
   };
   auto mfma_all = [&](int buf) __attribute__((always_inline)) {
-    wg_u32x4 bh[2], bm[2], bl[2];
+    u32x4 bh[2], bm[2], bl[2];
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) wg_split8(bv[buf][cb], bh[cb], bm[cb], bl[cb]);
 #pragma unroll
@@ -330,16 +312,16 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a) 
 #pragma unroll
       for (int tt = 0; tt < 8; ++tt)
         x[tt] = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, av[buf][rb][tt]) & msk[buf][tt] & amask[rb]);
-      wg_u32x4 ah, am, al;
+      u32x4 ah, am, al;
       wg_split8(x, ah, am, al);
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {
-        acc[rb][cb] = wg_mfma_bf16(am, bm[cb], acc[rb][cb]);
-        acc[rb][cb] = wg_mfma_bf16(ah, bl[cb], acc[rb][cb]);
-        acc[rb][cb] = wg_mfma_bf16(al, bh[cb], acc[rb][cb]);
-        acc[rb][cb] = wg_mfma_bf16(ah, bm[cb], acc[rb][cb]);
-        acc[rb][cb] = wg_mfma_bf16(am, bh[cb], acc[rb][cb]);
-        acc[rb][cb] = wg_mfma_bf16(ah, bh[cb], acc[rb][cb]);
+        acc[rb][cb] = mfma_bf16(am, bm[cb], acc[rb][cb]);
+        acc[rb][cb] = mfma_bf16(ah, bl[cb], acc[rb][cb]);
+        acc[rb][cb] = mfma_bf16(al, bh[cb], acc[rb][cb]);
+        acc[rb][cb] = mfma_bf16(ah, bm[cb], acc[rb][cb]);
+        acc[rb][cb] = mfma_bf16(am, bh[cb], acc[rb][cb]);
+        acc[rb][cb] = mfma_bf16(ah, bh[cb], acc[rb][cb]);
       }
     }
   };
@@ -414,7 +396,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a) 
 }
 
 }  // namespace nqa
-
 
 using namespace nqa;
 

@@ -34,8 +34,7 @@ NEIGHBORLIST_BACKEND_NEQUIP_AMD: Final[str] = "nequip_amd"
 DEFAULT_NEIGHBORLIST_BACKEND: Final[str] = NEIGHBORLIST_BACKEND_NEQUIP_AMD
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p()
+_ptr = _lib.ptr
 
 
 def _complete_cell_host(cell64: torch.Tensor, pbc: Tuple[bool, bool, bool]) -> torch.Tensor:

@@ -9,17 +9,13 @@ readout module consumes it and marks the per-atom energies as already scaled, ``
 
 from __future__ import annotations
 
-import ctypes
-from typing import Optional
-
 import torch
 
 from .. import _lib
 from ..utils import ktimer
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p()
+_ptr = _lib.ptr
 
 
 def _launch(backward: int, h, w, scales, shifts, types, g_e, out, act: int, cst: float):
@@ -30,7 +26,7 @@ def _launch(backward: int, h, w, scales, shifts, types, g_e, out, act: int, cst:
     with torch.cuda.device(h.device), ktimer.region("energy_head", 4.0 * N * D * (2 if backward else 1) + 8.0 * N):
         rc = lib.nqa_energy_head(backward, _ptr(h), _ptr(w), _ptr(scales), ns, _ptr(shifts), nh, _ptr(types), _ptr(g_e),
                                  _ptr(out), D, act, float(cst), N,
-                                 ctypes.c_void_p(torch.cuda.current_stream(h.device).cuda_stream))
+                                 _lib.stream_ptr(h.device))
     _lib.check(rc, "nqa_energy_head")
 
 

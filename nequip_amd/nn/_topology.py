@@ -9,7 +9,6 @@ device by ``nqa_csr_build`` and reused by the three convolution layers and their
 
 from __future__ import annotations
 
-import ctypes
 import contextlib
 import os
 import weakref
@@ -20,12 +19,7 @@ import torch
 from .. import _lib
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p()
-
-
-def current_stream_ptr(device: torch.device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+_ptr, current_stream_ptr = _lib.ptr, _lib.stream_ptr
 
 
 class EdgeTopology:

@@ -70,43 +70,53 @@ class _WeightImages:
         return self.images[(mode, backward)], hit
 
 
+_P = _lib.ptr
+
+
+def _launch(name: str, *, region: str, nbytes: float, flops: float, resolve, mode: int, backward: int, w1,
+            cache: _WeightImages, rows: int, device, alloc, call):
+    """One launch of the fused MLP's C entry point ``name``.  Owns the mode of the launch (``resolve``: ``forward_mode`` /
+    ``backward_mode``, or None for a fixed mode), the weight image of (mode, direction) from ``cache``, the timer region
+    with the caller's byte and FLOP counts, and the return code.  ``alloc()`` returns the output tensors (called after the
+    workspace is there); ``call(fn, mode, outs, *ws)`` spells the C call, ``ws`` being its last four arguments
+    (workspace, workspace_bytes, workspace_ready, stream).  Returns the outputs."""
+    lib = _lib.load()
+    H, W = w1.shape
+    if resolve is not None:
+        mode = resolve(mode)
+    ws_bytes = lib.nqa_radial_mlp_workspace_bytes(mode, backward, H, W)
+    ws, ready = cache.get(w1, mode, backward, ws_bytes, rows)
+    outs = alloc()
+    with torch.cuda.device(device), ktimer.region(region, nbytes, flops):
+        rc = call(getattr(lib, name), mode, outs, _P(ws), ws_bytes, int(ready), _lib.stream_ptr(device))
+    _lib.check(rc, name)
+    return outs
+
+
 def _launch_fwd(emb, w0, w1, alpha0: float, alpha1: float, mode: int, cache: _WeightImages):
     """``silu(emb @ (w0 alpha0)) @ (w1 alpha1)`` in one fused MFMA launch (``nqa_radial_mlp_fwd``)."""
-    from ._topology import _ptr, current_stream_ptr
-
-    lib = _lib.load()
     E, nb = emb.shape
     H, W = w1.shape
     out = torch.empty((E, W), dtype=emb.dtype, device=emb.device)
-    flops = 2.0 * E * (nb * H + H * W)
-    mode = forward_mode(mode)
-    ws_bytes = lib.nqa_radial_mlp_workspace_bytes(mode, 0, H, W)
-    ws, ready = cache.get(w1, mode, 0, ws_bytes, E)
-    with torch.cuda.device(emb.device), ktimer.region("radial_mlp_fwd", 4.0 * E * (nb + W), flops):
-        rc = lib.nqa_radial_mlp_fwd(_lib.NQA_F32, mode, _ptr(emb), _ptr(w0), alpha0, _ptr(w1), alpha1, nb, H, W, E,
-                                    _ptr(out), _ptr(ws), ws_bytes, int(ready), current_stream_ptr(emb.device))
-    _lib.check(rc, "nqa_radial_mlp_fwd")
+    _launch("nqa_radial_mlp_fwd", region="radial_mlp_fwd", nbytes=4.0 * E * (nb + W), flops=2.0 * E * (nb * H + H * W),
+            resolve=forward_mode, mode=mode, backward=0, w1=w1, cache=cache, rows=E, device=emb.device, alloc=lambda: (out,),
+            call=lambda fn, m, outs, *ws: fn(_lib.NQA_F32, m, _P(emb), _P(w0), alpha0, _P(w1), alpha1, nb, H, W, E, _P(out),
+                                             *ws))
     return out
 
 
 def _launch_bwd(emb, w0, w1, alpha0: float, alpha1: float, g_w, mode: int, cache: _WeightImages, device_idle: bool = False):
     """Gradient of the fused MLP w.r.t. the edge embedding (``nqa_radial_mlp_bwd``; hidden layer recomputed on chip).
     ``device_idle``: the launch has the device to itself (``NQA_MLP_HINT_DEVICE_IS_IDLE``, include/nequip_amd.h)."""
-    from ._topology import _ptr, current_stream_ptr
-
-    lib = _lib.load()
     E, nb = emb.shape
     H, W = w1.shape
     g_emb = torch.empty_like(emb)
-    flops = 2.0 * E * (nb * H * 2 + H * W)
-    mode = backward_mode(mode)
-    ws_bytes = lib.nqa_radial_mlp_workspace_bytes(mode, 1, H, W)
-    ws, ready = cache.get(w1, mode, 1, ws_bytes, E)
-    with torch.cuda.device(emb.device), ktimer.region("radial_mlp_bwd", 4.0 * E * (2 * nb + W), flops):
-        rc = lib.nqa_radial_mlp_bwd(_lib.NQA_F32, mode | (_lib.NQA_MLP_HINT_DEVICE_IS_IDLE if device_idle else 0), _ptr(emb),
-                                    _ptr(w0), alpha0, _ptr(w1), alpha1, _ptr(g_w), nb, H, W, E, _ptr(g_emb), _ptr(ws), ws_bytes,
-                                    int(ready), current_stream_ptr(emb.device))
-    _lib.check(rc, "nqa_radial_mlp_bwd")
+    hint = _lib.NQA_MLP_HINT_DEVICE_IS_IDLE if device_idle else 0
+    _launch("nqa_radial_mlp_bwd", region="radial_mlp_bwd", nbytes=4.0 * E * (2 * nb + W),
+            flops=2.0 * E * (nb * H * 2 + H * W), resolve=backward_mode, mode=mode, backward=1, w1=w1, cache=cache, rows=E,
+            device=emb.device, alloc=lambda: (g_emb,),
+            call=lambda fn, m, outs, *ws: fn(_lib.NQA_F32, m | hint, _P(emb), _P(w0), alpha0, _P(w1), alpha1, _P(g_w), nb, H,
+                                             W, E, _P(g_emb), *ws))
     return g_emb
 
 
@@ -114,63 +124,44 @@ def _launch_bwd_train(emb, w0, w1, alpha0: float, alpha1: float, g_w, cot, mode:
     """``nqa_radial_mlp_bwd_train``: the embedding-side gradient plus the on-chip pieces of the parameter gradients.
     ``cot is None``: (g_emb, silu(P), dW0 / alpha0); second order (``cot`` = cotangent of g_emb): (d<cot,g_emb>/d emb,
     Q silu'(P), d<cot,g_emb>/dW0 / alpha0) -- see include/nequip_amd.h."""
-    from ._topology import _ptr, current_stream_ptr
-
-    lib = _lib.load()
     E, nb = emb.shape
     H, W = w1.shape
     g_emb = torch.empty_like(emb)
     hid = torch.empty((E, H), dtype=emb.dtype, device=emb.device)
-    tiles = lib.nqa_radial_mlp_train_tiles(E)
+    tiles = _lib.load().nqa_radial_mlp_train_tiles(E)
     parts = torch.empty((tiles, nb, H), dtype=emb.dtype, device=emb.device)
-    flops = 2.0 * E * (nb * H * (3 if cot is None else 5) + H * W)
-    mode = backward_mode(mode)
-    ws_bytes = lib.nqa_radial_mlp_workspace_bytes(mode, 1, H, W)
-    ws, ready = cache.get(w1, mode, 1, ws_bytes, E)
-    with torch.cuda.device(emb.device), ktimer.region("radial_mlp_bwd_train", 4.0 * E * (3 * nb + W + H), flops):
-        rc = lib.nqa_radial_mlp_bwd_train(_lib.NQA_F32, mode, _ptr(emb), _ptr(cot), _ptr(w0), alpha0, _ptr(w1), alpha1,
-                                          _ptr(g_w), nb, H, W, E, _ptr(g_emb), _ptr(hid), _ptr(parts), _ptr(ws),
-                                          ws_bytes, int(ready), current_stream_ptr(emb.device))
-    _lib.check(rc, "nqa_radial_mlp_bwd_train")
+    _launch("nqa_radial_mlp_bwd_train", region="radial_mlp_bwd_train", nbytes=4.0 * E * (3 * nb + W + H),
+            flops=2.0 * E * (nb * H * (3 if cot is None else 5) + H * W), resolve=backward_mode, mode=mode, backward=1, w1=w1,
+            cache=cache, rows=E, device=emb.device, alloc=lambda: (g_emb, hid, parts),
+            call=lambda fn, m, outs, *ws: fn(_lib.NQA_F32, m, _P(emb), _P(cot), _P(w0), alpha0, _P(w1), alpha1, _P(g_w), nb, H,
+                                             W, E, _P(g_emb), _P(hid), _P(parts), *ws))
     return g_emb, hid, parts.sum(0)
 
 
 def _launch_fwd_tangent(emb, cot, w0, w1, alpha0: float, alpha1: float, mode: int, cache: _WeightImages):
     """``((cot W0) silu'(emb W0)) W1`` (``nqa_radial_mlp_fwd_tangent``): gradient of <cot, g_emb> w.r.t. grad_out."""
-    from ._topology import _ptr, current_stream_ptr
-
-    lib = _lib.load()
     E, nb = emb.shape
     H, W = w1.shape
     out = torch.empty((E, W), dtype=emb.dtype, device=emb.device)
-    ws_bytes = lib.nqa_radial_mlp_workspace_bytes(mode, 0, H, W)
-    ws, ready = cache.get(w1, mode, 0, ws_bytes, E)
-    with torch.cuda.device(emb.device), ktimer.region("radial_mlp_fwd", 4.0 * E * (2 * nb + W), 2.0 * E * (2 * nb * H + H * W)):
-        rc = lib.nqa_radial_mlp_fwd_tangent(_lib.NQA_F32, mode, _ptr(emb), _ptr(cot), _ptr(w0), alpha0, _ptr(w1),
-                                            alpha1, nb, H, W, E, _ptr(out), _ptr(ws), ws_bytes, int(ready),
-                                            current_stream_ptr(emb.device))
-    _lib.check(rc, "nqa_radial_mlp_fwd_tangent")
+    _launch("nqa_radial_mlp_fwd_tangent", region="radial_mlp_fwd", nbytes=4.0 * E * (2 * nb + W),
+            flops=2.0 * E * (2 * nb * H + H * W), resolve=None, mode=mode, backward=0, w1=w1, cache=cache, rows=E,
+            device=emb.device, alloc=lambda: (out,),
+            call=lambda fn, m, outs, *ws: fn(_lib.NQA_F32, m, _P(emb), _P(cot), _P(w0), alpha0, _P(w1), alpha1, nb, H, W, E,
+                                             _P(out), *ws))
     return out
 
 
 def _launch_bwd_paired(emb, w0, w1, alpha0: float, alpha1: float, g_a, g_b, mode: int, cache: _WeightImages):
     """``_launch_bwd`` for a gradient given as two row streams ``g_a + g_b`` (``nqa_radial_mlp_bwd_paired``)."""
-    from ._topology import _ptr, current_stream_ptr
-
-    lib = _lib.load()
     E, nb = emb.shape
     H, W = w1.shape
     assert g_a.shape == (E, W) and g_b.shape == (E, W) and g_a.is_contiguous() and g_b.is_contiguous()
     g_emb = torch.empty_like(emb)
-    flops = 2.0 * E * (nb * H * 2 + H * W)
-    mode = backward_mode(mode)
-    ws_bytes = lib.nqa_radial_mlp_workspace_bytes(mode, 1, H, W)
-    ws, ready = cache.get(w1, mode, 1, ws_bytes, E)
-    with torch.cuda.device(emb.device), ktimer.region("radial_mlp_bwd", 4.0 * E * (2 * nb + 2 * W), flops):
-        rc = lib.nqa_radial_mlp_bwd_paired(_lib.NQA_F32, mode, _ptr(emb), _ptr(w0), alpha0, _ptr(w1), alpha1, _ptr(g_a),
-                                           _ptr(g_b), nb, H, W, E, _ptr(g_emb), _ptr(ws), ws_bytes, int(ready),
-                                           current_stream_ptr(emb.device))
-    _lib.check(rc, "nqa_radial_mlp_bwd_paired")
+    _launch("nqa_radial_mlp_bwd_paired", region="radial_mlp_bwd", nbytes=4.0 * E * (2 * nb + 2 * W),
+            flops=2.0 * E * (nb * H * 2 + H * W), resolve=backward_mode, mode=mode, backward=1, w1=w1, cache=cache, rows=E,
+            device=emb.device, alloc=lambda: (g_emb,),
+            call=lambda fn, m, outs, *ws: fn(_lib.NQA_F32, m, _P(emb), _P(w0), alpha0, _P(w1), alpha1, _P(g_a), _P(g_b), nb,
+                                             H, W, E, _P(g_emb), *ws))
     return g_emb
 
 
@@ -206,29 +197,17 @@ class _RadialMLPFn(torch.autograd.Function):
 def _launch_last(pre, w, alpha: float, cache: _WeightImages, g=None):
     """The last layer of a deeper MLP on the fused kernels' GEMM cores: ``silu(pre) @ (w alpha)`` (``g is None``,
     ``nqa_radial_mlp_last_fwd``) or ``(g @ (w alpha)^T) * silu'(pre)`` (``nqa_radial_mlp_last_bwd``)."""
-    from ._topology import _ptr, current_stream_ptr
-
-    lib = _lib.load()
     E, H = pre.shape
     W = w.shape[1]
-    mode = _lib.NQA_MLP_F16X3
-    backward = 0 if g is None else 1
-    ws_bytes = lib.nqa_radial_mlp_workspace_bytes(mode, backward, H, W)
-    ws, ready = cache.get(w, mode, backward, ws_bytes, E)
-    flops = 2.0 * E * H * W
+    common = dict(flops=2.0 * E * H * W, resolve=None, mode=_lib.NQA_MLP_F16X3, w1=w, cache=cache, rows=E, device=pre.device)
     if g is None:
-        out = torch.empty((E, W), dtype=pre.dtype, device=pre.device)
-        with torch.cuda.device(pre.device), ktimer.region("radial_mlp_fwd", 4.0 * E * (H + W), flops):
-            rc = lib.nqa_radial_mlp_last_fwd(_lib.NQA_F32, mode, _ptr(pre), _ptr(w), alpha, H, W, E, _ptr(out), _ptr(ws),
-                                             ws_bytes, int(ready), current_stream_ptr(pre.device))
-        _lib.check(rc, "nqa_radial_mlp_last_fwd")
-        return out
-    out = torch.empty_like(pre)
-    with torch.cuda.device(pre.device), ktimer.region("radial_mlp_bwd", 4.0 * E * (2 * H + W), flops):
-        rc = lib.nqa_radial_mlp_last_bwd(_lib.NQA_F32, mode, _ptr(pre), _ptr(w), alpha, _ptr(g), None, H, W, E, _ptr(out),
-                                         _ptr(ws), ws_bytes, int(ready), current_stream_ptr(pre.device))
-    _lib.check(rc, "nqa_radial_mlp_last_bwd")
-    return out
+        return _launch("nqa_radial_mlp_last_fwd", region="radial_mlp_fwd", nbytes=4.0 * E * (H + W), backward=0, **common,
+                       alloc=lambda: (torch.empty((E, W), dtype=pre.dtype, device=pre.device),),
+                       call=lambda fn, m, outs, *ws: fn(_lib.NQA_F32, m, _P(pre), _P(w), alpha, H, W, E, _P(outs[0]), *ws))[0]
+    return _launch("nqa_radial_mlp_last_bwd", region="radial_mlp_bwd", nbytes=4.0 * E * (2 * H + W), backward=1, **common,
+                   alloc=lambda: (torch.empty_like(pre),),
+                   call=lambda fn, m, outs, *ws: fn(_lib.NQA_F32, m, _P(pre), _P(w), alpha, _P(g), None, H, W, E,
+                                                    _P(outs[0]), *ws))[0]
 
 
 class _RadialMLPLastFn(torch.autograd.Function):

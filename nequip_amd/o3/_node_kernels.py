@@ -26,12 +26,7 @@ from ..utils import wgrad as _wgrad
 from .irreps import Irreps
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p()
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+_ptr, _stream = _lib.ptr, _lib.stream_ptr
 
 
 def _dt(dtype):
