@@ -114,22 +114,6 @@ SIGNATURES = {
     "nqa_pair_owner_lists_guard": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "nqa_pair_gather": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "nqa_pair_expand": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
-    "nqa_tp_scatter_fwd_paired": (
-        c_int32,
-        [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        + [c_int64, c_int64, c_void_p, c_int64, c_void_p],
-    ),
-    "nqa_tp_scatter_bwd_edge_paired": (
-        c_int32,
-        [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        + [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p],
-    ),
-    "nqa_tp_scatter_bwd_fused_paired": (
-        c_int32,
-        [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
-        + [c_void_p] * 5
-        + [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p],
-    ),
     "nqa_tp_bwd_pairs_workspace_bytes": (c_int64, [c_void_p, c_int32, c_int64]),
     "nqa_tp_scatter_bwd_pairs": (
         c_int32,
@@ -154,11 +138,6 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_int32] + [c_void_p] * 7  # plan, image, dtype, x, x_cot, y, y_cot, w, w_cot, grad_out
         + [c_void_p] * 5  # owner_rowptr, pair_other, pair_row, pair_edge_in, pair_edge_out
         + [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p],
-    ),
-    "nqa_tp_scatter_bwd_x_paired": (
-        c_int32,
-        [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        + [c_int64, c_int64, c_void_p, c_int64, c_void_p],
     ),
     "nqa_edge_vectors_fwd": (
         c_int32,
@@ -324,6 +303,11 @@ SIGNATURES = {
          c_void_p, c_void_p],
     ),
 }
+
+# nqa_tp_scatter_<family>_paired: the family's arguments with (weight_rows, num_pairs) before the stream
+for _family in ("fwd", "bwd_edge", "bwd_fused", "bwd_x"):
+    _res, _args = SIGNATURES[f"nqa_tp_scatter_{_family}"]
+    SIGNATURES[f"nqa_tp_scatter_{_family}_paired"] = (_res, _args[:-1] + [c_void_p, c_int64, c_void_p])
 
 _lock = threading.Lock()
 _lib = None

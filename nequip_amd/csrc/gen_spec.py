@@ -1717,85 +1717,111 @@ def emit_gx_kernels(p: Plan) -> List[str]:
 
 
 def emit_launcher(p: Plan) -> List[str]:
-    """launch<WPN>(which, ...) for every entry point of tp_spec.h, and the structure's registration (closes the namespaces)."""
+    """launch<WPN>(SpecKernel, ...) for every member of tp_spec.h's SpecKernel, and the structure's registration (closes the
+    namespaces).  The launcher reads no environment: what the dispatcher decided arrives in SpecLaunchOpts."""
     st = p.st
     L = []
     A = L.append
+    pair_operands = "a.gw == nullptr || a.gy == nullptr || a.eid2 == nullptr"
     # (NQA_LAB: scripts/micro/pair_lab.hip includes a generated file and launches single instantiations itself)
     A("#ifndef NQA_LAB")
     A("template <int WPN>")
-    A("static int launch(int which, const SpecArgs<float>& a, hipStream_t stream) {")
+    A("static int launch(SpecKernel which, const SpecLaunchOpts& o, const SpecArgs<float>& a, hipStream_t stream) {")
     A("  const int nchunk = (a.mul + 63) / 64;")
     A("  const int64_t items = (int64_t)a.N * nchunk;")
     # FULL for EVERY multiplicity: a lane beyond the last channel works on the clamped channel -- same loads, same
     # arithmetic, and it rewrites its twin's stores with identical values; only the wave reductions (grad_y) mask it out
     # (spec_mask_dup) and the owner-side stores use the clamped channel.  The FULL = false instantiations (one exec-mask
     # branch region per store: 155 spilled registers in the l_max = 3 split pair kernel that the 32-channel segments of the
-    # L preset ran) remain behind NQA_SPEC_MASKED=1.
-    A("  static const bool masked_ = [] { const char* v = std::getenv(\"NQA_SPEC_MASKED\"); return v != nullptr && v[0] == '1'; }();")
-    A("  const bool full = (a.mul & 63) == 0 || !masked_;")
+    # L preset ran) remain behind NQA_SPEC_MASKED=1 (SpecLaunchOpts::masked).
+    A("  const bool full = (a.mul & 63) == 0 || !o.masked;")
     A("  if (items == 0) return 0;")
-    A("  if (which == 1) {")
-    A("    const int64_t blocks = (items * WPN + 3) / 4;")
-    A("    const dim3 grid((unsigned)blocks), blk(256);")
-    A("    if (a.gxe != nullptr) {")
-    A("      if (a.gw == nullptr || a.gy == nullptr) return 1;")
+    A("  const dim3 blk(256);")
+    A("  const dim3 node_grid((unsigned)(WPN == 1 ? (items + 3) / 4 : items));  // fwd / bwd_x: a block per item when split")
+    A("  const dim3 edge_grid((unsigned)((items * WPN + 3) / 4));")
+    A("  const dim3 rows_grid((unsigned)((items + 3) / 4));")
+    A("  const size_t smem_out = WPN > 1 ? (size_t)(WPN - 1) * kOD * 64 * sizeof(float) : 0;")
+    A("  const size_t smem_x = WPN > 1 ? (size_t)(WPN - 1) * kXD * 64 * sizeof(float) : 0;")
+    A("  switch (which) {")
+    A("    case SpecKernel::Fwd:")
+    A("      hipLaunchKernelGGL((fwd_kernel<float, WPN, false>), node_grid, blk, smem_out, stream, a);")
+    A("      return 0;")
+    A("    case SpecKernel::FwdJvp:  // out = F(x2, y, w) + F(x, y2, w) + F(x, y, w2)")
+    A("      hipLaunchKernelGGL((fwd_kernel<float, WPN, true>), node_grid, blk, smem_out, stream, a);")
+    A("      return 0;")
+    A("    case SpecKernel::BwdX:")
+    A("      hipLaunchKernelGGL((bwd_x_kernel<float, WPN, false>), node_grid, blk, smem_x, stream, a);")
+    A("      return 0;")
+    A("    case SpecKernel::BwdXDual:  // out = Bx(y2, w, g) + Bx(y, w2, g)")
+    A("      if (a.y2 == nullptr || a.w2 == nullptr) return 1;")
+    A("      hipLaunchKernelGGL((bwd_x_kernel<float, WPN, true>), node_grid, blk, smem_x, stream, a);")
+    A("      return 0;")
+    A("    case SpecKernel::BwdEdge:")
+    A("      if (a.gxe != nullptr) {")
+    A("        if (a.gw == nullptr || a.gy == nullptr) return 1;")
     for cond, flags in ((None, "true, true, true"), ("a.gw != nullptr && a.gy != nullptr", "false, true, true"),
                         ("a.gw != nullptr", "false, true, false"), ("a.gy != nullptr", "false, false, true")):
         if cond is not None:
-            A(f"    }} else if ({cond}) {{")
-        A(f"      if (full) hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, {flags}, true>), grid, blk, 0, stream, a); "
-          f"else hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, {flags}, false>), grid, blk, 0, stream, a);")
-    A("    }")
-    A("    return 0;")
-    A("  }")
-    A("  if (which == 3) {")
-    A("    hipLaunchKernelGGL((gx_rows_sum_kernel<float, false>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, a);")
-    A("    return 0;")
-    A("  }")
-    A("  if (which == 4) {  // pair-centric backward (owner CSR in rowptr / nbr / wid / eid / eid2)")
+            A(f"      }} else if ({cond}) {{")
+        A(f"        if (full) hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, {flags}, true>), edge_grid, blk, 0, stream, a); "
+          f"else hipLaunchKernelGGL((bwd_edge_kernel<float, WPN, {flags}, false>), edge_grid, blk, 0, stream, a);")
+    A("      }")
+    A("      return 0;")
+    A("    case SpecKernel::RowsSumSrc:")
+    A("      hipLaunchKernelGGL((gx_rows_sum_kernel<float, false>), rows_grid, blk, 0, stream, a);")
+    A("      return 0;")
+    A("    case SpecKernel::RowsSumPairs:  // grad_x += rows of the pairs in which the node is not the owner")
+    A("      hipLaunchKernelGGL((gx_rows_sum_kernel<float, true>), rows_grid, blk, 0, stream, a);")
+    A("      return 0;")
+    A("    case SpecKernel::AccFinish:  // grad_x += the accumulator rows of the atomic form of the pair kernels")
+    if p.pair_parts:
+        A("      hipLaunchKernelGGL(gx_acc_finish_kernel, dim3((unsigned)(((int64_t)a.N * a.mul + 255) / 256)), blk, 0, stream, a);")
+        A("      return 0;")
+    else:
+        A("      return 1;")
+    A("    case SpecKernel::BwdPairsDual:  // see bwd_pair_kernel<DUAL>")
     if p.pair_ok:
-        A("    if (a.gw == nullptr || a.gy == nullptr || a.eid2 == nullptr || (a.out != nullptr && a.gxe == nullptr)) return 1;")
+        A(f"      if ({pair_operands} || a.x2 == nullptr || a.y2 == nullptr) return 1;")
+        A("      if (full) hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, true, false, true>), edge_grid, blk, 0, stream, a);")
+        A("      else hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, false, false, true>), edge_grid, blk, 0, stream, a);")
+        A("      return 0;")
+    else:
+        A("      return 1;")
+    A("    case SpecKernel::BwdPairs: {  // owner CSR in rowptr / nbr / wid / eid / eid2")
+    if p.pair_ok:
+        A(f"      if ({pair_operands} || (a.out != nullptr && a.gxe == nullptr)) return 1;")
         if p.ring is not None:
-            A("    // LDS-ring kernel (round 6): multiples of 64 channels; one wavefront per (node, chunk) when that fills the chip")
-            A("    // (read at every launch: the tests switch kernels within one process)")
-            A("    const bool ring_ = [] { const char* v = std::getenv(\"NQA_PAIR_RING\"); return v == nullptr || v[0] != '0'; }();")
-            A("    if (ring_ && (a.mul & 63) == 0) {")
-            A("      const int rw = items >= 6144 ? 1 : (items >= 3072 ? 2 : 4);")
-            A("      const size_t rsmem = (size_t)4 * kRingWaveBytes;")
-            A("      const dim3 rgrid((unsigned)((items * rw + 3) / 4)), rblk(256);")
+            A("      // LDS-ring kernel: multiples of 64 channels; one wavefront per (node, chunk) when that fills the chip")
+            A("      if (o.ring && (a.mul & 63) == 0) {")
+            A("        const int rw = items >= 6144 ? 1 : (items >= 3072 ? 2 : 4);")
+            A("        const size_t rsmem = (size_t)4 * kRingWaveBytes;")
+            A("        const dim3 rgrid((unsigned)((items * rw + 3) / 4));")
             A("#define NQA_RING_LAUNCH(W, GX_, AT_) do { \\")
-            A("        static bool lds_ok_[64] = {}; \\")
-            A("        if (!spec_allow_lds((const void*)bwd_pair_ring_kernel<W, GX_, AT_>, 4 * kRingWaveBytes, lds_ok_)) return 1; \\")
-            A("        hipLaunchKernelGGL((bwd_pair_ring_kernel<W, GX_, AT_>), rgrid, rblk, rsmem, stream, a); } while (0)")
+            A("          static bool lds_ok_[64] = {}; \\")
+            A("          if (!spec_allow_lds((const void*)bwd_pair_ring_kernel<W, GX_, AT_>, 4 * kRingWaveBytes, lds_ok_)) return 1; \\")
+            A("          hipLaunchKernelGGL((bwd_pair_ring_kernel<W, GX_, AT_>), rgrid, blk, rsmem, stream, a); } while (0)")
             A("#define NQA_RING_WPN(GX_, AT_) do { if (rw == 1) NQA_RING_LAUNCH(1, GX_, AT_); else if (rw == 2) NQA_RING_LAUNCH(2, GX_, AT_); else NQA_RING_LAUNCH(4, GX_, AT_); } while (0)")
-            A("      if (a.out == nullptr) NQA_RING_WPN(false, false);")
-            A("      else if (a.gx_atomic) NQA_RING_WPN(true, true);")
-            A("      else NQA_RING_WPN(true, false);")
+            A("        if (a.out == nullptr) NQA_RING_WPN(false, false);")
+            A("        else if (a.gx_atomic) NQA_RING_WPN(true, true);")
+            A("        else NQA_RING_WPN(true, false);")
             A("#undef NQA_RING_WPN")
             A("#undef NQA_RING_LAUNCH")
-            A("      return 0;")
-            A("    }")
-        A("    if (a.gx_atomic) return 1;  // (the caller asked for the accumulator form, which only the ring kernel has)")
-        A("    const int64_t blocks = (items * WPN + 3) / 4;")
-        A("    const size_t smem = WPN > 1 ? (size_t)(WPN - 1) * kXD * 64 * sizeof(float) : 0;")
-        A("    const dim3 grid((unsigned)blocks), blk(256);")
-        A("    if (a.out != nullptr) {")
-        A("      if (full) hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, true, true>), grid, blk, smem, stream, a);")
-        A("      else hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, false, true>), grid, blk, smem, stream, a);")
-        A("    } else {")
-        A("      if (full) hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, true, false>), grid, blk, 0, stream, a);")
-        A("      else hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, false, false>), grid, blk, 0, stream, a);")
-        A("    }")
-        A("    return 0;")
+            A("        return 0;")
+            A("      }")
+        A("      if (a.gx_atomic || a.gy_atomic) return 1;  // (the accumulator forms, which only the ring kernel has)")
+        A("      if (a.out != nullptr) {")
+        A("        if (full) hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, true, true>), edge_grid, blk, smem_x, stream, a);")
+        A("        else hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, false, true>), edge_grid, blk, smem_x, stream, a);")
+        A("      } else {")
+        A("        if (full) hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, true, false>), edge_grid, blk, 0, stream, a);")
+        A("        else hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, false, false>), edge_grid, blk, 0, stream, a);")
+        A("      }")
+        A("      return 0;")
     elif p.pair_parts > 1:
-        A("    if (a.gw == nullptr || a.gy == nullptr || a.eid2 == nullptr || (a.out != nullptr && a.gxe == nullptr)) return 1;")
-        A("    const int64_t witems = items * kPairParts;  // one wavefront per (node, chunk, part)")
-        A("    const dim3 grid((unsigned)((witems + 3) / 4)), blk(256);")
-        A("    if (a.out != nullptr) {")
-        A("      // LDS-ring form (round 6): multiples of 64 channels; NQA_PAIR_RING=0 keeps the plain loop")
-        A("      const bool sring_ = [] { const char* v = std::getenv(\"NQA_PAIR_RING\"); return v == nullptr || v[0] != '0'; }();")
-        A("      if (sring_ && (a.mul & 63) == 0) {")
+        A(f"      if ({pair_operands} || (a.out != nullptr && a.gxe == nullptr)) return 1;")
+        A("      const dim3 grid((unsigned)((items * kPairParts + 3) / 4));  // one wavefront per (node, chunk, part)")
+        A("      // LDS-ring form: multiples of 64 channels, with grad_x; otherwise the plain loop")
+        A("      if (a.out != nullptr && o.ring && (a.mul & 63) == 0) {")
         A(f"        const size_t rsmem = (size_t)4 * {RING_WAVE_BYTES};")
         A("#define NQA_SRING_LAUNCH(GX_, AT_) do { \\")
         A("          static bool lds_ok_[64] = {}; \\")
@@ -1805,67 +1831,27 @@ def emit_launcher(p: Plan) -> List[str]:
         A("#undef NQA_SRING_LAUNCH")
         A("        return 0;")
         A("      }")
-        A("      if (a.gx_atomic && (a.mul & 63) != 0) return 1;")
-        A("      if (a.gx_atomic) hipLaunchKernelGGL((bwd_pair_split_kernel<float, true, true, true>), grid, blk, 0, stream, a);")
-        A("      else if (full) hipLaunchKernelGGL((bwd_pair_split_kernel<float, true, true>), grid, blk, 0, stream, a);")
-        A("      else hipLaunchKernelGGL((bwd_pair_split_kernel<float, false, true>), grid, blk, 0, stream, a);")
-        A("    } else {")
-        A("      if (full) hipLaunchKernelGGL((bwd_pair_split_kernel<float, true, false>), grid, blk, 0, stream, a);")
-        A("      else hipLaunchKernelGGL((bwd_pair_split_kernel<float, false, false>), grid, blk, 0, stream, a);")
-        A("    }")
-        A("    return 0;")
+        A("      if (a.gy_atomic) return 1;  // (only the ring kernel adds into grad_y)")
+        A("      if (a.out != nullptr) {")
+        A("        if (a.gx_atomic && (a.mul & 63) != 0) return 1;")
+        A("        if (a.gx_atomic) hipLaunchKernelGGL((bwd_pair_split_kernel<float, true, true, true>), grid, blk, 0, stream, a);")
+        A("        else if (full) hipLaunchKernelGGL((bwd_pair_split_kernel<float, true, true>), grid, blk, 0, stream, a);")
+        A("        else hipLaunchKernelGGL((bwd_pair_split_kernel<float, false, true>), grid, blk, 0, stream, a);")
+        A("      } else {")
+        A("        if (full) hipLaunchKernelGGL((bwd_pair_split_kernel<float, true, false>), grid, blk, 0, stream, a);")
+        A("        else hipLaunchKernelGGL((bwd_pair_split_kernel<float, false, false>), grid, blk, 0, stream, a);")
+        A("      }")
+        A("      return 0;")
     else:
-        A("    return 1;  // not generated for this structure (register budget)")
+        A("      return 1;  // not generated for this structure (register budget)")
+    A("    }")
     A("  }")
-    A("  if (which == 8) {  // dual bwd_x (second-order backward): out = Bx(y2, w, g) + Bx(y, w2, g)")
-    A("    if (a.y2 == nullptr || a.w2 == nullptr) return 1;")
-    A("    const int64_t blocks8 = WPN == 1 ? (items + 3) / 4 : items;")
-    A("    const size_t smem8 = WPN > 1 ? (size_t)(WPN - 1) * kXD * 64 * sizeof(float) : 0;")
-    A("    hipLaunchKernelGGL((bwd_x_kernel<float, WPN, true>), dim3((unsigned)blocks8), dim3(256), smem8, stream, a);")
-    A("    return 0;")
-    A("  }")
-    A("  if (which == 7) {  // forward JVP (second-order backward): out = F(x2, y, w) + F(x, y2, w) + F(x, y, w2)")
-    A("    const int64_t blocks7 = WPN == 1 ? (items + 3) / 4 : items;")
-    A("    const size_t smem7 = WPN > 1 ? (size_t)(WPN - 1) * kOD * 64 * sizeof(float) : 0;")
-    A("    hipLaunchKernelGGL((fwd_kernel<float, WPN, true>), dim3((unsigned)blocks7), dim3(256), smem7, stream, a);")
-    A("    return 0;")
-    A("  }")
-    A("  if (which == 6) {  // dual pair-centric edge gradients (second-order backward), see bwd_pair_kernel<DUAL>")
-    if p.pair_ok:
-        A("    if (a.gw == nullptr || a.gy == nullptr || a.eid2 == nullptr || a.x2 == nullptr || a.y2 == nullptr) return 1;")
-        A("    const dim3 grid((unsigned)((items * WPN + 3) / 4)), blk(256);")
-        A("    if (full) hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, true, false, true>), grid, blk, 0, stream, a);")
-        A("    else hipLaunchKernelGGL((bwd_pair_kernel<float, WPN, false, false, true>), grid, blk, 0, stream, a);")
-        A("    return 0;")
-    else:
-        A("    return 1;")
-    A("  }")
-    A("  if (which == 9) {  // grad_x += the accumulator rows of the atomic form of the pair kernels")
-    if p.pair_parts:
-        A("    const int64_t threads = (int64_t)a.N * a.mul;")
-        A("    hipLaunchKernelGGL(gx_acc_finish_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, a);")
-        A("    return 0;")
-    else:
-        A("    return 1;")
-    A("  }")
-    A("  if (which == 5) {  // grad_x += rows of the pairs in which the node is not the owner")
-    A("    hipLaunchKernelGGL((gx_rows_sum_kernel<float, true>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, stream, a);")
-    A("    return 0;")
-    A("  }")
-    A("  const int64_t blocks = WPN == 1 ? (items + 3) / 4 : items;")
-    A("  if (which == 0) {")
-    A("    const size_t smem = WPN > 1 ? (size_t)(WPN - 1) * kOD * 64 * sizeof(float) : 0;")
-    A("    hipLaunchKernelGGL((fwd_kernel<float, WPN, false>), dim3((unsigned)blocks), dim3(256), smem, stream, a);")
-    A("  } else {")
-    A("    const size_t smem = WPN > 1 ? (size_t)(WPN - 1) * kXD * 64 * sizeof(float) : 0;")
-    A("    hipLaunchKernelGGL((bwd_x_kernel<float, WPN, false>), dim3((unsigned)blocks), dim3(256), smem, stream, a);")
-    A("  }")
-    A("  return 0;")
+    A("  return 1;")
     A("}")
-    A("static int launch_any(int which, int wpn, const SpecArgs<float>& a, hipStream_t stream) {")
+    A("static int launch_any(SpecKernel which, const SpecLaunchOpts& o, const SpecArgs<float>& a, hipStream_t stream) {")
     A("  // LDS budget of the 4-way split: (WPN-1) * accumulators * 256 B per block")
-    A("  if (wpn >= 4 && kOD <= 64) return launch<4>(which, a, stream);")
-    A("  return launch<1>(which, a, stream);")
+    A("  if (o.wpn >= 4 && kOD <= 64) return launch<4>(which, o, a, stream);")
+    A("  return launch<1>(which, o, a, stream);")
     A("}")
     A(f'static SpecRegistrar reg_{st.tag()}("{st.key()}", &launch_any, kXD, kS, kOD, kNP, {p.pair_parts}, {p.ring_flag});')
     A("#endif  // NQA_LAB")

@@ -4,6 +4,7 @@
 #pragma once
 
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -76,4 +77,21 @@ struct nqa_plan {
 
 namespace nqa {
 void set_error(const std::string& msg);
+
+// Environment switches of the host drivers.  A flag that defaults to on is switched off by a leading '0', one that
+// defaults to off is switched on by a leading '1'.  Whether a switch is read at every call or once per process is
+// stated where it is used.
+inline bool env_flag(const char* name, bool dflt) {
+  const char* v = std::getenv(name);
+  return v == nullptr ? dflt : (dflt ? v[0] != '0' : v[0] == '1');
 }
+// A switch that the Python side reads as well: on for any value but "" or one with a leading '0'.
+inline bool env_set(const char* name) {
+  const char* v = std::getenv(name);
+  return v != nullptr && v[0] != '\0' && v[0] != '0';
+}
+inline int env_int(const char* name, int dflt) {
+  const char* v = std::getenv(name);
+  return v ? std::atoi(v) : dflt;
+}
+}  // namespace nqa

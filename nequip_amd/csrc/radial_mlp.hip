@@ -1412,17 +1412,8 @@ using namespace nqa;
 // ---- host side ---------------------------------------------------------------------------------------------------------
 namespace {
 
-// Switches.  Every one is read at every call, because the tests select kernel forms within one process; only the CU
-// count is looked up once.  A flag that defaults to on is switched off by a leading '0', one that defaults to off is
-// switched on by a leading '1'.
-bool env_flag(const char* name, bool dflt) {
-  const char* v = std::getenv(name);
-  return v == nullptr ? dflt : (dflt ? v[0] != '0' : v[0] == '1');
-}
-int env_int(const char* name, int dflt) {
-  const char* v = std::getenv(name);
-  return v ? std::atoi(v) : dflt;
-}
+// Switches (env_flag / env_int of plan.h).  Every one is read at every call, because the tests select kernel forms
+// within one process; only the CU count is looked up once.
 int mlp_num_cus() {
   static const int num_cus = [] {
     int dev = 0, n = 0;

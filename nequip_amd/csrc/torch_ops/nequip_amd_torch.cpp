@@ -545,6 +545,93 @@ Tensor tp_scatter_fwd(const Tensor& x_, const Tensor& y_, const Tensor& w_, cons
   return out;
 }
 
+// The backward of one tensor-product scatter: output allocation, workspace allocation and the choice between the
+// pair-centric pass, the fused pass and bwd_x + bwd_edge.  With per-edge weights (`pr` NULL) it mirrors
+// _TPScatterBwdFn.forward (nequip_amd/nn/_tp_scatter_base.py), with paired ones (`w` = one row per pair) the choices of
+// _PairedRadialTPFn.backward (nequip_amd/nn/_paired_radial.py); `allow_pairs`: its _pair_backward_pays.
+struct TpGrads {
+  Tensor gx, gy, gw;    // an empty tensor where not asked for
+  bool folded = false;  // paired: gw is [P, W], summed over the two directed edges of every pair; else its halves [2 P, W]
+};
+
+// fn(args..., stream), or with a pairing fn_paired(args..., slots, num_pairs, stream)
+#define NQA_TP_CALL(fn, slots, ...)                                                                       \
+  do {                                                                                                    \
+    if (pr) NQA_CALL(fn##_paired(__VA_ARGS__, i32(slots(topo, *pr)), pr->P, stream_of(x)), #fn "_paired"); \
+    else NQA_CALL(fn(__VA_ARGS__, stream_of(x)), #fn);                                                    \
+  } while (0)
+
+TpGrads tp_backward(Plan& P, Topology& topo, Pairing* pr, const Tensor& g, const Tensor& x, const Tensor& y, const Tensor& w,
+                    bool need_x, bool need_y, bool need_w, bool allow_pairs) {
+  const int64_t N = x.size(0), E = y.size(0), W = P.weight_numel;
+  const int32_t dt = nqa_dtype(x, "tp_scatter_bwd");
+  Tensor image = plan_image(P, x.device());
+  auto workspace = [&](int64_t n) { return at::empty({std::max<int64_t>(n, 1)}, x.options().dtype(at::kByte)); };
+  const int64_t gw_rows = pr ? 2 * pr->P : E;
+  TpGrads r;
+  r.gx = r.gy = r.gw = at::empty({0}, x.options());
+  auto run_pairs = [&](bool with_gx) -> bool {
+    if (!allow_pairs) return false;
+    const int64_t ws_bytes = nqa_tp_bwd_pairs_workspace_bytes(P.handle, dt, E);
+    if (ws_bytes < 0) return false;
+    owner_lists(topo, *pr);
+    if (with_gx) r.gx = at::empty({N, P.dim_in1}, x.options());
+    r.gw = at::empty({pr->P, W}, x.options());
+    r.gy = at::empty({E, P.dim_in2}, x.options());
+    Tensor ws = workspace(ws_bytes);
+    NQA_CALL(nqa_tp_scatter_bwd_pairs(P.handle, image.data_ptr(), dt, x.data_ptr(), y.data_ptr(), w.data_ptr(), g.data_ptr(),
+                                      i32(pr->owner[0]), i32(pr->owner[1]), i32(pr->owner[2]), i32(pr->owner[3]),
+                                      i32(pr->owner[4]), i32(pr->owner[5]), i32(pr->owner[6]), r.gw.data_ptr(),
+                                      r.gy.data_ptr(), with_gx ? r.gx.data_ptr() : nullptr, ws.data_ptr(), ws_bytes, N, E,
+                                      stream_of(x)),
+             "nqa_tp_scatter_bwd_pairs");
+    r.folded = true;
+    return true;
+  };
+  // (NQA_NO_FUSED_BWD: the paired caller's switch only -- the dispatcher op with per-edge weights never read it)
+  if (need_x && need_y && need_w && P.prefer_fused_bwd && !(pr && env_on("NQA_NO_FUSED_BWD"))) {
+    if (run_pairs(true)) return r;
+    const int64_t ws_bytes = P.fused_rows_ok ? nqa_tp_bwd_fused_workspace_bytes(P.handle, dt, E) : -1;
+    if (ws_bytes >= 0) {  // structure-specialised float32 kernels exist for this plan
+      const Csr& cd = by_dst(topo);
+      const Csr& cs = by_src(topo);
+      r.gx = at::empty({N, P.dim_in1}, x.options());
+      r.gw = at::empty({gw_rows, W}, x.options());
+      r.gy = at::empty({E, P.dim_in2}, x.options());
+      Tensor ws = workspace(ws_bytes);
+      NQA_TP_CALL(nqa_tp_scatter_bwd_fused, slots_dst, P.handle, image.data_ptr(), dt, x.data_ptr(), y.data_ptr(),
+                  w.data_ptr(), g.data_ptr(), i32(cd.rowptr), i32(cd.edge_id), i32(cd.other), i32(cs.rowptr),
+                  i32(cs.edge_id), r.gw.data_ptr(), r.gy.data_ptr(), r.gx.data_ptr(), ws.data_ptr(), ws_bytes, N, E);
+      return r;
+    }
+  }
+  if (need_x) {
+    const Csr& cs = by_src(topo);
+    r.gx = at::empty({N, P.dim_in1}, x.options());
+    NQA_TP_CALL(nqa_tp_scatter_bwd_x, slots_src, P.handle, image.data_ptr(), dt, y.data_ptr(), w.data_ptr(), g.data_ptr(),
+                i32(cs.rowptr), i32(cs.edge_id), i32(cs.other), r.gx.data_ptr(), N, E);
+  }
+  if (need_w && need_y && run_pairs(false)) return r;  // (the edge gradients only: gx stays bwd_x's)
+  if (need_w || need_y) {
+    const Csr& cd = by_dst(topo);
+    if (need_w) r.gw = at::empty({gw_rows, W}, x.options());
+    if (need_y) r.gy = at::empty({E, P.dim_in2}, x.options());
+    int64_t ws_bytes = 0;
+    Tensor ws;
+    if (need_y) {
+      ws_bytes = nqa_tp_bwd_edge_workspace_bytes(P.handle, dt, E);
+      TORCH_CHECK(ws_bytes >= 0, "nequip_amd: nqa_tp_bwd_edge_workspace_bytes failed");
+      ws = workspace(ws_bytes);
+    }
+    NQA_TP_CALL(nqa_tp_scatter_bwd_edge, slots_dst, P.handle, image.data_ptr(), dt, x.data_ptr(), y.data_ptr(),
+                w.data_ptr(), g.data_ptr(), i32(cd.rowptr), i32(cd.edge_id), i32(cd.other),
+                need_w ? r.gw.data_ptr() : nullptr, need_y ? r.gy.data_ptr() : nullptr, need_y ? ws.data_ptr() : nullptr,
+                ws_bytes, N, E);
+  }
+  return r;
+}
+#undef NQA_TP_CALL
+
 std::tuple<Tensor, Tensor, Tensor> tp_scatter_bwd(const Tensor& g_, const Tensor& x_, const Tensor& y_, const Tensor& w_,
                                                   const Tensor& edge_dst, const Tensor& edge_src, std::string plan,
                                                   bool need_x, bool need_y, bool need_w) {
@@ -555,54 +642,9 @@ std::tuple<Tensor, Tensor, Tensor> tp_scatter_bwd(const Tensor& g_, const Tensor
   const int64_t N = x.size(0), E = edge_dst.numel();
   check_tp_operands(P, &x, y, w, N, E);
   TORCH_CHECK(g.dim() == 2 && g.size(0) == N && g.size(1) == P.dim_out, "nequip_amd: grad_out must be [", N, ", ", P.dim_out, "]");
-  const int32_t dt = nqa_dtype(x, "tp_scatter_bwd");
   auto topo = topology_of(edge_dst, edge_src, N);
-  Tensor image = plan_image(P, x.device());
-  const Tensor empty = at::empty({0}, x.options());
-  const auto bytes = x.options().dtype(at::kByte);
-  Tensor gx = empty, gy = empty, gw = empty;
-  if (need_x && need_y && need_w && P.prefer_fused_bwd && P.fused_rows_ok) {
-    const int64_t ws_bytes = nqa_tp_bwd_fused_workspace_bytes(P.handle, dt, E);
-    if (ws_bytes >= 0) {  // structure-specialised float32 kernels exist for this plan
-      const Csr& cd = by_dst(*topo);
-      const Csr& cs = by_src(*topo);
-      gx = at::empty({N, P.dim_in1}, x.options());
-      gw = at::empty({E, P.weight_numel}, x.options());
-      gy = at::empty({E, P.dim_in2}, x.options());
-      Tensor ws = at::empty({std::max<int64_t>(ws_bytes, 1)}, bytes);
-      NQA_CALL(nqa_tp_scatter_bwd_fused(P.handle, image.data_ptr(), dt, x.data_ptr(), y.data_ptr(), w.data_ptr(),
-                                        g.data_ptr(), i32(cd.rowptr), i32(cd.edge_id), i32(cd.other), i32(cs.rowptr),
-                                        i32(cs.edge_id), gw.data_ptr(), gy.data_ptr(), gx.data_ptr(), ws.data_ptr(),
-                                        ws_bytes, N, E, stream_of(x)),
-               "nqa_tp_scatter_bwd_fused");
-      return std::make_tuple(gx, gy, gw);
-    }
-  }
-  if (need_x) {
-    const Csr& cs = by_src(*topo);
-    gx = at::empty({N, P.dim_in1}, x.options());
-    NQA_CALL(nqa_tp_scatter_bwd_x(P.handle, image.data_ptr(), dt, y.data_ptr(), w.data_ptr(), g.data_ptr(), i32(cs.rowptr),
-                                  i32(cs.edge_id), i32(cs.other), gx.data_ptr(), N, E, stream_of(x)),
-             "nqa_tp_scatter_bwd_x");
-  }
-  if (need_w || need_y) {
-    const Csr& cd = by_dst(*topo);
-    if (need_w) gw = at::empty({E, P.weight_numel}, x.options());
-    if (need_y) gy = at::empty({E, P.dim_in2}, x.options());
-    int64_t ws_bytes = 0;
-    Tensor ws;
-    if (need_y) {
-      ws_bytes = nqa_tp_bwd_edge_workspace_bytes(P.handle, dt, E);
-      TORCH_CHECK(ws_bytes >= 0, "nequip_amd: nqa_tp_bwd_edge_workspace_bytes failed");
-      ws = at::empty({std::max<int64_t>(ws_bytes, 1)}, bytes);
-    }
-    NQA_CALL(nqa_tp_scatter_bwd_edge(P.handle, image.data_ptr(), dt, x.data_ptr(), y.data_ptr(), w.data_ptr(),
-                                     g.data_ptr(), i32(cd.rowptr), i32(cd.edge_id), i32(cd.other),
-                                     need_w ? gw.data_ptr() : nullptr, need_y ? gy.data_ptr() : nullptr,
-                                     need_y ? ws.data_ptr() : nullptr, ws_bytes, N, E, stream_of(x)),
-             "nqa_tp_scatter_bwd_edge");
-  }
-  return std::make_tuple(gx, gy, gw);
+  TpGrads r = tp_backward(P, *topo, nullptr, g, x, y, w, need_x, need_y, need_w, false);
+  return std::make_tuple(r.gx, r.gy, r.gw);
 }
 
 // ---- edge vectors ----------------------------------------------------------------------------------------------------
@@ -874,105 +916,29 @@ std::tuple<Tensor, Tensor, Tensor> radial_tp_bwd(const Tensor& g_, const Tensor&
               "nequip_amd::radial_tp_bwd: grad_out must be float32 [", N, ", ", P.dim_out, "]");
   auto topo = topology_of(edge_dst, edge_src, N);
   auto pairing = radial_tp_pairing(P, *topo, edge_shift);
-  const Tensor empty = at::empty({0}, x.options());
-  if (!pairing) {  // the per-edge kernels; the weight rows were not kept (w_rows is a placeholder): one more MLP forward
-    const Tensor w = radial_mlp_fwd(emb, w0, w1, alpha0, alpha1);
-    auto r = tp_scatter_bwd(g, x, y, w, edge_dst, edge_src, plan, need_x, need_y, need_emb);
-    Tensor g_emb = need_emb ? radial_mlp_bwd(emb, w0, w1, std::get<2>(r), alpha0, alpha1) : empty;
-    return std::make_tuple(g_emb, std::get<0>(r), std::get<1>(r));
+  Pairing* pr = pairing.get();
+  Tensor w;
+  if (pr == nullptr) {  // the per-edge kernels; the weight rows were not kept (w_rows is a placeholder): one more MLP forward
+    w = radial_mlp_fwd(emb, w0, w1, alpha0, alpha1);
+  } else {
+    TORCH_CHECK(w_rows_.numel() == pr->P * W, "nequip_amd::radial_tp_bwd: w_rows is not the forward's [E / 2, W] rows");
+    w = w_rows_.contiguous().view({pr->P, W});
   }
-  Pairing& pr = *pairing;
-  const int64_t Pn = pr.P;
-  TORCH_CHECK(w_rows_.numel() == Pn * W, "nequip_amd::radial_tp_bwd: w_rows is not the forward's [E / 2, W] rows");
-  const Tensor w_rows = w_rows_.contiguous().view({Pn, W});
-  Tensor image = plan_image(P, x.device());
-  const auto bytes = x.options().dtype(at::kByte);
-  Tensor gx = empty, gy = empty, G;
-  bool folded = false, done = false;
-  // the choices of _PairedRadialTPFn.backward (nequip_amd/nn/_paired_radial.py)
-  auto run_pairs = [&](bool with_gx) -> bool {
-    const int64_t ws_bytes = nqa_tp_bwd_pairs_workspace_bytes(P.handle, NQA_F32, E);
-    if (ws_bytes < 0) return false;
-    owner_lists(*topo, pr);
-    if (with_gx) gx = at::empty({N, P.dim_in1}, x.options());
-    G = at::empty({Pn, W}, x.options());
-    gy = at::empty({E, P.dim_in2}, x.options());
-    Tensor ws = at::empty({std::max<int64_t>(ws_bytes, 1)}, bytes);
-    NQA_CALL(nqa_tp_scatter_bwd_pairs(P.handle, image.data_ptr(), NQA_F32, x.data_ptr(), y.data_ptr(), w_rows.data_ptr(),
-                                      g.data_ptr(), i32(pr.owner[0]), i32(pr.owner[1]), i32(pr.owner[2]), i32(pr.owner[3]),
-                                      i32(pr.owner[4]), i32(pr.owner[5]), i32(pr.owner[6]), G.data_ptr(), gy.data_ptr(),
-                                      with_gx ? gx.data_ptr() : nullptr, ws.data_ptr(), ws_bytes, N, E, stream_of(x)),
-             "nqa_tp_scatter_bwd_pairs");
-    return true;
-  };
-  if (need_emb && need_x && need_y && P.prefer_fused_bwd && !env_on("NQA_NO_FUSED_BWD")) {
-    if (pair_backward_pays(g) && run_pairs(true)) {
-      folded = done = true;
-    } else if (P.fused_rows_ok) {
-      const int64_t ws_bytes = nqa_tp_bwd_fused_workspace_bytes(P.handle, NQA_F32, E);
-      if (ws_bytes >= 0) {
-        const Csr& cd = by_dst(*topo);
-        const Csr& cs = by_src(*topo);
-        const Tensor& slots = slots_dst(*topo, pr);
-        gx = at::empty({N, P.dim_in1}, x.options());
-        G = at::empty({2 * Pn, W}, x.options());
-        gy = at::empty({E, P.dim_in2}, x.options());
-        Tensor ws = at::empty({std::max<int64_t>(ws_bytes, 1)}, bytes);
-        NQA_CALL(nqa_tp_scatter_bwd_fused_paired(P.handle, image.data_ptr(), NQA_F32, x.data_ptr(), y.data_ptr(),
-                                                 w_rows.data_ptr(), g.data_ptr(), i32(cd.rowptr), i32(cd.edge_id),
-                                                 i32(cd.other), i32(cs.rowptr), i32(cs.edge_id), G.data_ptr(), gy.data_ptr(),
-                                                 gx.data_ptr(), ws.data_ptr(), ws_bytes, N, E, i32(slots), Pn, stream_of(x)),
-                 "nqa_tp_scatter_bwd_fused_paired");
-        done = true;
-      }
-    }
-  }
-  if (!done) {
-    if (need_x) {
-      const Csr& cs = by_src(*topo);
-      const Tensor& slots = slots_src(*topo, pr);
-      gx = at::empty({N, P.dim_in1}, x.options());
-      NQA_CALL(nqa_tp_scatter_bwd_x_paired(P.handle, image.data_ptr(), NQA_F32, y.data_ptr(), w_rows.data_ptr(), g.data_ptr(),
-                                           i32(cs.rowptr), i32(cs.edge_id), i32(cs.other), gx.data_ptr(), N, E, i32(slots),
-                                           Pn, stream_of(x)),
-               "nqa_tp_scatter_bwd_x_paired");
-    }
-    Tensor gx_keep = gx;
-    if (need_emb && need_y && pair_backward_pays(g) && run_pairs(false)) {
-      folded = true;
-      gx = gx_keep;
-    } else if (need_emb || need_y) {
-      const Csr& cd = by_dst(*topo);
-      const Tensor& slots = slots_dst(*topo, pr);
-      if (need_emb) G = at::empty({2 * Pn, W}, x.options());
-      if (need_y) gy = at::empty({E, P.dim_in2}, x.options());
-      int64_t ws_bytes = 0;
-      Tensor ws;
-      if (need_y) {
-        ws_bytes = nqa_tp_bwd_edge_workspace_bytes(P.handle, NQA_F32, E);
-        TORCH_CHECK(ws_bytes >= 0, "nequip_amd: nqa_tp_bwd_edge_workspace_bytes failed");
-        ws = at::empty({std::max<int64_t>(ws_bytes, 1)}, bytes);
-      }
-      NQA_CALL(nqa_tp_scatter_bwd_edge_paired(P.handle, image.data_ptr(), NQA_F32, x.data_ptr(), y.data_ptr(),
-                                              w_rows.data_ptr(), g.data_ptr(), i32(cd.rowptr), i32(cd.edge_id), i32(cd.other),
-                                              need_emb ? G.data_ptr() : nullptr, need_y ? gy.data_ptr() : nullptr,
-                                              need_y ? ws.data_ptr() : nullptr, ws_bytes, N, E, i32(slots), Pn, stream_of(x)),
-               "nqa_tp_scatter_bwd_edge_paired");
-    }
-  }
-  Tensor g_emb = empty;
-  if (need_emb) {
-    const Tensor emb_half = pair_rows(emb, pr);
-    const Tensor g_half = folded ? radial_mlp_bwd(emb_half, w0, w1, G, alpha0, alpha1)
-                                 : radial_mlp_bwd_impl(emb_half, w0, w1, G.slice(0, 0, Pn), G.slice(0, Pn, 2 * Pn), alpha0,
-                                                         alpha1);
+  TpGrads r = tp_backward(P, *topo, pr, g, x, y, w, need_x, need_y, need_emb, pr != nullptr && pair_backward_pays(g));
+  Tensor g_emb = at::empty({0}, x.options());
+  if (need_emb && pr == nullptr) {
+    g_emb = radial_mlp_bwd(emb, w0, w1, r.gw, alpha0, alpha1);
+  } else if (need_emb) {
+    const int64_t Pn = pr->P;
+    const Tensor emb_half = pair_rows(emb, *pr);
+    const Tensor g_half = r.folded ? radial_mlp_bwd(emb_half, w0, w1, r.gw, alpha0, alpha1)
+                                   : radial_mlp_bwd_impl(emb_half, w0, w1, r.gw.slice(0, 0, Pn), r.gw.slice(0, Pn, 2 * Pn),
+                                                         alpha0, alpha1);
     g_emb = at::empty_like(emb);
-    NQA_CALL(nqa_pair_expand(g_half.data_ptr(), i32(pr.rows), E, Pn, (int32_t)emb.size(1), g_emb.data_ptr(), stream_of(emb)),
+    NQA_CALL(nqa_pair_expand(g_half.data_ptr(), i32(pr->rows), E, Pn, (int32_t)emb.size(1), g_emb.data_ptr(), stream_of(emb)),
              "nqa_pair_expand");
   }
-  if (!need_x) gx = empty;
-  if (!need_y) gy = empty;
-  return std::make_tuple(g_emb, gx, gy);
+  return std::make_tuple(g_emb, r.gx, r.gy);
 }
 
 // ---- force / virial tail (nequip_amd/nn/_force_ops.py) ------------------------------------------------------------------------

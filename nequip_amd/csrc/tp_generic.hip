@@ -18,13 +18,12 @@
 // re-read through L2/MALL.  Roofline: HBM-bound.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "generated/cg_generated.h"
 #include "plan.h"
 #include "tp_spec.h"
-
-#include <cstdlib>
 
 namespace nqa {
 
@@ -298,23 +297,6 @@ __global__ __launch_bounds__(kBlock) void tp_bwd_x_kernel(const TPArgs<T> a) {
 // ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-static void fill_tables(TPArgs<T>& a, const nqa_plan* P, const void* image) {
-  const char* base = static_cast<const char*>(image);
-  a.instr = reinterpret_cast<const InstrDev*>(base + P->layout.off_instr);
-  a.chunks = reinterpret_cast<const ChunkDev*>(base + P->layout.off_chunks);
-  a.blks = reinterpret_cast<const BlkDev*>(base + P->layout.off_blks);
-  a.blk_instr = reinterpret_cast<const int32_t*>(base + P->layout.off_blk_instr);
-  a.xchunks = reinterpret_cast<const XChunkDev*>(base + P->layout.off_xchunks);
-  a.n_chunks = (int32_t)P->chunks.size();
-  a.n_xchunks = (int32_t)P->xchunks.size();
-  a.dim_in1 = P->dim_in1;
-  a.dim_in2 = P->dim_in2;
-  a.dim_out = P->dim_out;
-  a.wnumel = P->weight_numel;
-  a.ypw = P->ypart_width;
-}
-
 static int check_launch(const char* what) {
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) {
@@ -334,20 +316,57 @@ static int grid_for(int64_t items, unsigned* grid) {
   return NQA_OK;
 }
 
+// The operands of one call as the C ABI hands them over; a kernel family reads the ones it needs, the rest stay NULL.
+struct Values {
+  const void *x, *y, *w, *g;
+};
+struct EdgeCsr {  // edges grouped by node: nqa_csr_build's (rowptr, edge id per slot, the other node per slot)
+  const int32_t *rowptr, *eid, *nbr;
+};
+struct PairedRows {  // nqa_tp_scatter_*_paired: the weight row of every CSR slot, w has num_pairs rows
+  const int32_t* rows;
+  int64_t num_pairs;
+};
+struct OwnerCsr {  // nqa_pair_owner_lists: pairs grouped by their owner node
+  const int32_t *rowptr, *other, *row, *edge_in, *edge_out;
+};
+
+// ---- generic (any irreps) kernels ----
 template <typename T>
-static int launch_fwd(const nqa_plan* P, const void* image, const void* x, const void* y, const void* w,
-                      const int32_t* rowptr, const int32_t* eid, const int32_t* nbr, void* out, int64_t N, int64_t E,
-                      hipStream_t stream) {
-  (void)E;
+static TPArgs<T> generic_args(const nqa_plan* P, const void* image, const Values& v, const EdgeCsr& c) {
   TPArgs<T> a{};
-  fill_tables(a, P, image);
-  a.x = static_cast<const T*>(x);
-  a.y = static_cast<const T*>(y);
-  a.w = static_cast<const T*>(w);
+  const char* base = static_cast<const char*>(image);
+  a.instr = reinterpret_cast<const InstrDev*>(base + P->layout.off_instr);
+  a.chunks = reinterpret_cast<const ChunkDev*>(base + P->layout.off_chunks);
+  a.blks = reinterpret_cast<const BlkDev*>(base + P->layout.off_blks);
+  a.blk_instr = reinterpret_cast<const int32_t*>(base + P->layout.off_blk_instr);
+  a.xchunks = reinterpret_cast<const XChunkDev*>(base + P->layout.off_xchunks);
+  a.n_chunks = (int32_t)P->chunks.size();
+  a.n_xchunks = (int32_t)P->xchunks.size();
+  a.dim_in1 = P->dim_in1;
+  a.dim_in2 = P->dim_in2;
+  a.dim_out = P->dim_out;
+  a.wnumel = P->weight_numel;
+  a.ypw = P->ypart_width;
+  a.x = static_cast<const T*>(v.x);
+  a.y = static_cast<const T*>(v.y);
+  a.w = static_cast<const T*>(v.w);
+  a.g = static_cast<const T*>(v.g);
+  a.rowptr = c.rowptr;
+  a.eid = c.eid;
+  a.nbr = c.nbr;
+  return a;
+}
+
+// f(T{}) with T the element type of `dtype` (checked by check_common)
+template <typename F>
+static int by_dtype(int32_t dtype, F&& f) {
+  return dtype == NQA_F32 ? f(float{}) : f(double{});
+}
+
+template <typename T>
+static int launch_fwd(TPArgs<T> a, void* out, int64_t N, hipStream_t stream) {
   a.out = static_cast<T*>(out);
-  a.rowptr = rowptr;
-  a.eid = eid;
-  a.nbr = nbr;
   a.n_items = N * (int64_t)a.n_chunks;
   if (a.n_items == 0) return NQA_OK;
   unsigned grid;
@@ -358,20 +377,10 @@ static int launch_fwd(const nqa_plan* P, const void* image, const void* x, const
 }
 
 template <typename T>
-static int launch_bwd_edge(const nqa_plan* P, const void* image, const void* x, const void* y, const void* w,
-                           const void* g, const int32_t* rowptr, const int32_t* eid, const int32_t* nbr, void* gw,
-                           void* gy, void* workspace, int64_t N, int64_t E, hipStream_t stream) {
-  TPArgs<T> a{};
-  fill_tables(a, P, image);
-  a.x = static_cast<const T*>(x);
-  a.y = static_cast<const T*>(y);
-  a.w = static_cast<const T*>(w);
-  a.g = static_cast<const T*>(g);
+static int launch_bwd_edge(TPArgs<T> a, const nqa_plan* P, const void* image, void* gw, void* gy, void* workspace,
+                           int64_t N, int64_t E, hipStream_t stream) {
   a.gw = static_cast<T*>(gw);
   a.ypart = gy ? static_cast<T*>(workspace) : nullptr;
-  a.rowptr = rowptr;
-  a.eid = eid;
-  a.nbr = nbr;
   a.n_items = N * (int64_t)a.n_chunks;
   if (a.n_items > 0 && E > 0) {
     unsigned grid;
@@ -396,19 +405,8 @@ static int launch_bwd_edge(const nqa_plan* P, const void* image, const void* x, 
 }
 
 template <typename T>
-static int launch_bwd_x(const nqa_plan* P, const void* image, const void* y, const void* w, const void* g,
-                        const int32_t* rowptr, const int32_t* eid, const int32_t* nbr, void* gx, int64_t N,
-                        int64_t E, hipStream_t stream) {
-  (void)E;
-  TPArgs<T> a{};
-  fill_tables(a, P, image);
-  a.y = static_cast<const T*>(y);
-  a.w = static_cast<const T*>(w);
-  a.g = static_cast<const T*>(g);
+static int launch_bwd_x(TPArgs<T> a, void* gx, int64_t N, hipStream_t stream) {
   a.out = static_cast<T*>(gx);
-  a.rowptr = rowptr;
-  a.eid = eid;
-  a.nbr = nbr;
   a.n_items = N * (int64_t)a.n_xchunks;
   if (a.n_items == 0) return NQA_OK;
   unsigned grid;
@@ -419,11 +417,19 @@ static int launch_bwd_x(const nqa_plan* P, const void* image, const void* y, con
 }
 
 // ---- structure-specialised ("edge-outer") kernels: used for float32 when prebuilt for the plan's structure ----
+// Switches (env_flag / env_int of plan.h).  Each one's policy:
+//   NQA_FORCE_GENERIC     once per process: the tests and the Python side's cached queries rely on one answer per plan
+//                         (env_set: on for any value but "" or a leading '0', as the tests' own reading of it)
+//   NQA_SPEC_MASKED=1     once per process: the exec-masked instantiations for partial channel chunks
+//   NQA_SPEC_WPN=1|4      every call: a test forces the large-box launch shape on a box the oracle can evaluate
+//   NQA_PAIR_RING=0       every call: the tests switch between the pair kernels within one process (pair_form)
+//   NQA_PAIR_GX_ATOMIC=0  every call: likewise (pair_form)
 static bool force_generic() {
-  static const bool v = [] {
-    const char* e = std::getenv("NQA_FORCE_GENERIC");
-    return e != nullptr && e[0] != '\0' && e[0] != '0';
-  }();
+  static const bool v = env_set("NQA_FORCE_GENERIC");
+  return v;
+}
+static bool spec_masked() {
+  static const bool v = env_flag("NQA_SPEC_MASKED", false);
   return v;
 }
 
@@ -431,15 +437,21 @@ static bool use_spec(const nqa_plan* P, int32_t dtype) {
   return P->spec != nullptr && dtype == NQA_F32 && !force_generic();
 }
 
+static int spec_chunks(const nqa_plan* P) { return (P->uniform_mul + 63) / 64; }
+
 static int spec_wpn(const nqa_plan* P, int64_t N) {
   // few (node, chunk) items -> split each node's edges over 4 wavefronts to fill the 256 CUs
-  const int64_t items = N * (int64_t)((P->uniform_mul + 63) / 64);
-  // experiment / test switch: 1 or 4 wavefronts per (node, chunk); measured: 4 wins at cfg-3 (2 was tried: slower).  Read at
-  // every call (a getenv is ~100 ns) so that a test can force the large-box launch shape on a box the oracle can evaluate.
-  const char* v = std::getenv("NQA_SPEC_WPN");
-  const int forced = v ? std::atoi(v) : 0;
+  const int64_t items = N * (int64_t)spec_chunks(P);
+  // experiment / test switch: 1 or 4 wavefronts per (node, chunk); measured: 4 wins at cfg-3 (2 was tried: slower)
+  const int forced = env_int("NQA_SPEC_WPN", 0);
   if (forced == 1 || forced == 4) return forced;
   return items < 49152 ? 4 : 1;
+}
+
+// The structure's launcher with this call's choices; `ring` is pair_form's (only BwdPairs reads it).
+static int spec_launch(const nqa_plan* P, SpecKernel which, const SpecArgs<float>& a, hipStream_t stream, bool ring = false) {
+  const bool sums = which == SpecKernel::RowsSumSrc || which == SpecKernel::RowsSumPairs || which == SpecKernel::AccFinish;
+  return P->spec->launch(which, SpecLaunchOpts{sums ? 1 : spec_wpn(P, a.N), ring, spec_masked()}, a, stream);
 }
 
 __global__ __launch_bounds__(256) void spec_gy_reduce_kernel(const float* __restrict__ part, float* __restrict__ gy,
@@ -453,13 +465,136 @@ __global__ __launch_bounds__(256) void spec_gy_reduce_kernel(const float* __rest
   gy[t] = r;
 }
 
-static void spec_fill(SpecArgs<float>& a, const nqa_plan* P, int64_t N) {
+static SpecArgs<float> spec_node_operands(const nqa_plan* P, int64_t N) {
+  SpecArgs<float> a{};
   a.N = (int32_t)N;
   a.mul = P->uniform_mul;
   a.din = P->dim_in1;
   a.dout = P->dim_out;
   a.wn = P->weight_numel;
   a.gy_stride = P->dim_in2;
+  return a;
+}
+
+// The operands every edge kernel reads.  The only place that decides which row of w / grad_w a CSR slot uses: its own
+// edge's, or with paired weights the row `paired->rows` names (SpecArgs::wid / wP).
+static SpecArgs<float> spec_edge_operands(const nqa_plan* P, int64_t N, const Values& v, const EdgeCsr& c,
+                                          const PairedRows* paired) {
+  SpecArgs<float> a = spec_node_operands(P, N);
+  a.x = static_cast<const float*>(v.x);
+  a.y = static_cast<const float*>(v.y);
+  a.w = static_cast<const float*>(v.w);
+  a.g = static_cast<const float*>(v.g);
+  a.rowptr = c.rowptr;
+  a.eid = c.eid;
+  a.nbr = c.nbr;
+  a.wid = paired ? paired->rows : c.eid;
+  a.wP = paired ? (int32_t)paired->num_pairs : INT32_MAX;
+  return a;
+}
+
+// Owner-CSR variant (pair-centric kernels): a slot is a pair, its weight row is the pair's own (no second half: wP stays
+// INT32_MAX), eid / eid2 are its two directed edges.
+static SpecArgs<float> spec_owner_operands(const nqa_plan* P, int64_t N, const Values& v, const OwnerCsr& c) {
+  const PairedRows own_rows{c.row, INT32_MAX};
+  SpecArgs<float> a = spec_edge_operands(P, N, v, EdgeCsr{c.rowptr, c.edge_in, c.other}, &own_rows);
+  a.eid2 = c.edge_out;
+  return a;
+}
+
+// ---- workspace: [grad_y partial rows | pad to 256 B | per-edge (fused) or per-pair (pairs) grad_x rows] ----
+enum class TpWs { Edge, Fused, Pairs };
+struct TpWsLayout {
+  int64_t total;      // bytes; -1: this plan / dtype / edge count has no such kernel
+  int32_t nchunk;     // grad_y partials per edge that the specialised kernels write (1: straight into grad_y)
+  int32_t gy_stride;  // floats per edge of the partial rows
+  int64_t gxe_off;    // byte offset of the grad_x rows (Fused, Pairs)
+};
+
+static TpWsLayout tp_ws_layout(const nqa_plan* plan, int32_t dtype, TpWs kind, int64_t num_edges) {
+  TpWsLayout l{-1, 1, 0, 0};
+  if (plan == nullptr || num_edges < 0) return l;
+  const bool spec = use_spec(plan, dtype);
+  if (kind != TpWs::Edge && !spec) return l;
+  if (kind == TpWs::Pairs && ((num_edges & 1) || !plan->spec->pair)) return l;
+  if (spec) {
+    // (the split pair kernel: one partial per channel chunk and input-block part)
+    l.nchunk = spec_chunks(plan) * (kind == TpWs::Pairs ? plan->spec->pair : 1);
+    l.gy_stride = plan->dim_in2 * l.nchunk;
+  }
+  if (kind == TpWs::Edge) {
+    // generic kernels: one partial per (instruction, 64-channel chunk) and component of its in2 irrep (ypart_width);
+    // structure-specialised kernels: dim_in2 partials per channel chunk.  The larger of the two: for a structure with few
+    // paths the second exceeds the first (one 0e x 0e path, l_max = 1 harmonics, 128 channels: 8 floats per edge against
+    // 2) -- found when the truncated-input structures of the channel segments were added; no round-2 structure hit it.
+    const int64_t per_edge = std::max<int64_t>(plan->ypart_width, spec ? l.gy_stride : 0);
+    l.total = num_edges * per_edge * (dtype == NQA_F64 ? 8 : 4);
+    return l;
+  }
+  const int64_t ypart = l.nchunk > 1 ? num_edges * (int64_t)l.gy_stride * 4 : 0;
+  const int64_t rows = kind == TpWs::Pairs ? num_edges / 2 : num_edges;
+  l.gxe_off = (ypart + 255) & ~(int64_t)255;
+  l.total = l.gxe_off + rows * (int64_t)plan->dim_in1 * 4;
+  return l;
+}
+
+struct TpWsView {
+  float* ypart;
+  float* gxe;
+};
+static TpWsView tp_ws_view(void* workspace, const TpWsLayout& l) {
+  return {static_cast<float*>(workspace), reinterpret_cast<float*>(static_cast<char*>(workspace) + l.gxe_off)};
+}
+
+// ---- grad_y of the specialised kernels ----
+enum class GyMode {
+  Direct,   // one partial per edge: the kernel writes grad_y itself
+  Partial,  // nchunk partial rows per edge in the workspace, summed by spec_gy_reduce_kernel (finish_gy)
+  Atomic,   // the ring pair kernels add every partial to the zeroed grad_y
+};
+
+static void route_gy(SpecArgs<float>& a, const TpWsLayout& l, void* grad_y, void* workspace, GyMode mode) {
+  if (mode == GyMode::Partial) {
+    a.gy = tp_ws_view(workspace, l).ypart;
+    a.gy_stride = l.gy_stride;
+  } else {
+    a.gy = static_cast<float*>(grad_y);
+    a.gy_atomic = mode == GyMode::Atomic;
+  }
+}
+
+static int finish_gy(const nqa_plan* plan, const TpWsLayout& l, void* grad_y, void* workspace, GyMode mode,
+                     int64_t num_edges, const char* label, hipStream_t s) {
+  if (mode != GyMode::Partial || num_edges == 0) return NQA_OK;
+  const int64_t total = num_edges * (int64_t)plan->dim_in2;
+  hipLaunchKernelGGL(spec_gy_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
+                     tp_ws_view(workspace, l).ypart, static_cast<float*>(grad_y), plan->dim_in2, l.nchunk, total);
+  return check_launch(label);
+}
+
+// ---- which pair-centric backward runs ----
+// Decided here, once per call, for the host (the two memsets, SpecArgs::gx_atomic / gy_atomic) AND the launcher
+// (SpecLaunchOpts::ring), so the accumulator forms cannot be asked of a kernel that was not selected.
+//   R = NQA_PAIR_RING is not 0, A = NQA_PAIR_GX_ATOMIC is not 0, ring = the structure's SpecEntry::ring
+//   fits = (mul & 63) == 0 && E / 2 >= N    (ring kernels take whole 64-channel chunks; the accumulator [N, dim_in1] lives in
+//                                            the rows' workspace [E / 2, dim_in1] -- every list this is worth running on)
+//   ring  R  A  fits | grad_x accumulator (when grad_x is wanted)       | grad_y accumulated (when nchunk > 1 and E > 0)
+//    0    .  .   .   | no                                               | no
+//    1    1  1   1   | yes (LDS-ring kernel)                            | yes
+//    2    1  1   1   | yes (split ring kernel)                          | yes when grad_x is wanted (else the plain split
+//                    |                                                  |   kernel runs: partial rows)
+//    2    0  1   1   | yes (the plain split kernel has the form itself) | no
+//    otherwise       | no (rows, summed in a fixed order)               | no (partial rows + reduce, or direct)
+struct PairForm {
+  bool ring, gx_atomic, gy_atomic;
+};
+static PairForm pair_form(const nqa_plan* plan, const TpWsLayout& l, int64_t N, int64_t E, bool want_gx) {
+  const bool R = env_flag("NQA_PAIR_RING", true), A = env_flag("NQA_PAIR_GX_ATOMIC", true);
+  const int ring = plan->spec->ring;
+  const bool fits = (plan->uniform_mul & 63) == 0 && E / 2 >= N;
+  const bool acc = A && fits && (ring == 2 || (ring == 1 && R));
+  const bool many = l.nchunk > 1 && E > 0;  // (the caller's layout: the nchunk that route_gy uses)
+  return {R, acc && want_gx, acc && R && many && (ring == 1 || want_gx)};
 }
 
 static int check_common(const nqa_plan* P, const void* image, int32_t dtype, const char* fn) {
@@ -474,263 +609,157 @@ static int check_common(const nqa_plan* P, const void* image, int32_t dtype, con
   return NQA_OK;
 }
 
+static int fail(int code, const char* fn, const char* what) {
+  set_error(std::string(fn) + what);
+  return code;
+}
+static const char kNullOperand[] = ": NULL operand";
+static const char kNoSpec[] = ": no structure-specialised float32 kernel for this plan";
+static const char kNoSpecPaired[] = "_paired: no structure-specialised float32 kernel for this plan";
+static const char kWorkspace[] = ": workspace missing or too small";
+
+static int check_paired(const char* fn, const int32_t* rows, int64_t num_pairs) {
+  if (rows == nullptr || num_pairs <= 0 || num_pairs > 1073741823)
+    return fail(NQA_ERR_INVALID, fn, "_paired: weight_rows / num_pairs missing or out of range");
+  return NQA_OK;
+}
+
+// ---- one driver per family; `paired` is NULL for the per-edge weights ----
+static int tp_fwd(const nqa_plan* plan, const void* image, int32_t dtype, const Values& v, const EdgeCsr& dst, void* out,
+                  int64_t N, int64_t E, const PairedRows* paired, hipStream_t s) {
+  const char* fn = "nqa_tp_scatter_fwd";
+  int rc = check_common(plan, image, dtype, fn);
+  if (rc != NQA_OK) return rc;
+  if (N < 0 || E < 0 || (N > 0 && (!out || !dst.rowptr)) || (E > 0 && (!v.x || !v.y || !v.w || !dst.eid || !dst.nbr)))
+    return fail(NQA_ERR_INVALID, fn, kNullOperand);
+  if (use_spec(plan, dtype)) {
+    if (N == 0) return NQA_OK;
+    SpecArgs<float> a = spec_edge_operands(plan, N, v, dst, paired);
+    a.out = static_cast<float*>(out);
+    spec_launch(plan, SpecKernel::Fwd, a, s);
+    return check_launch("nqa_tp_scatter_fwd(spec)");
+  }
+  if (paired != nullptr) return fail(NQA_ERR_UNSUPPORTED, fn, kNoSpecPaired);
+  return by_dtype(dtype, [&](auto t) { return launch_fwd(generic_args<decltype(t)>(plan, image, v, dst), out, N, s); });
+}
+
+static int tp_bwd_edge(const nqa_plan* plan, const void* image, int32_t dtype, const Values& v, const EdgeCsr& dst,
+                       void* grad_w, void* grad_y, void* workspace, int64_t workspace_bytes, int64_t N, int64_t E,
+                       const PairedRows* paired, hipStream_t s) {
+  const char* fn = "nqa_tp_scatter_bwd_edge";
+  int rc = check_common(plan, image, dtype, fn);
+  if (rc != NQA_OK) return rc;
+  if (grad_w == nullptr && grad_y == nullptr) return NQA_OK;
+  if (E > 0 && (!v.x || !v.y || !v.w || !v.g || !dst.rowptr || !dst.eid || !dst.nbr))
+    return fail(NQA_ERR_INVALID, fn, kNullOperand);
+  const TpWsLayout l = tp_ws_layout(plan, dtype, TpWs::Edge, E);
+  if (grad_y != nullptr && E > 0 && (workspace == nullptr || workspace_bytes < l.total))
+    return fail(NQA_ERR_WORKSPACE, fn, kWorkspace);
+  if (use_spec(plan, dtype)) {
+    if (N == 0 || E == 0) return NQA_OK;
+    SpecArgs<float> a = spec_edge_operands(plan, N, v, dst, paired);
+    a.gw = static_cast<float*>(grad_w);
+    const GyMode mode = l.nchunk == 1 || grad_y == nullptr ? GyMode::Direct : GyMode::Partial;
+    route_gy(a, l, grad_y, workspace, mode);
+    spec_launch(plan, SpecKernel::BwdEdge, a, s);
+    rc = check_launch("nqa_tp_scatter_bwd_edge(spec)");
+    if (rc != NQA_OK) return rc;
+    return finish_gy(plan, l, grad_y, workspace, mode, E, "nqa_tp_scatter_bwd_edge(spec reduce)", s);
+  }
+  if (paired != nullptr) return fail(NQA_ERR_UNSUPPORTED, fn, kNoSpecPaired);
+  return by_dtype(dtype, [&](auto t) {
+    return launch_bwd_edge(generic_args<decltype(t)>(plan, image, v, dst), plan, image, grad_w, grad_y, workspace, N, E, s);
+  });
+}
+
+static int tp_bwd_fused(const nqa_plan* plan, const void* image, int32_t dtype, const Values& v, const EdgeCsr& dst,
+                        const EdgeCsr& src, void* grad_w, void* grad_y, void* grad_x, void* workspace,
+                        int64_t workspace_bytes, int64_t N, int64_t E, const PairedRows* paired, hipStream_t s) {
+  const char* fn = "nqa_tp_scatter_bwd_fused";
+  int rc = check_common(plan, image, dtype, fn);
+  if (rc != NQA_OK) return rc;
+  if (!use_spec(plan, dtype)) return fail(NQA_ERR_UNSUPPORTED, fn, kNoSpec);
+  if ((N > 0 && (!grad_x || !dst.rowptr || !src.rowptr)) ||
+      (E > 0 && (!v.x || !v.y || !v.w || !v.g || !dst.eid || !dst.nbr || !src.eid || !grad_w || !grad_y)))
+    return fail(NQA_ERR_INVALID, fn, kNullOperand);
+  const TpWsLayout l = tp_ws_layout(plan, dtype, TpWs::Fused, E);
+  if (E > 0 && (workspace == nullptr || workspace_bytes < l.total)) return fail(NQA_ERR_WORKSPACE, fn, kWorkspace);
+  if (N == 0) return NQA_OK;
+  float* gxe = tp_ws_view(workspace, l).gxe;
+  if (E > 0) {
+    SpecArgs<float> a = spec_edge_operands(plan, N, v, dst, paired);
+    a.gw = static_cast<float*>(grad_w);
+    a.gxe = gxe;
+    const GyMode mode = l.nchunk == 1 ? GyMode::Direct : GyMode::Partial;
+    route_gy(a, l, grad_y, workspace, mode);
+    spec_launch(plan, SpecKernel::BwdEdge, a, s);
+    rc = check_launch("nqa_tp_scatter_bwd_fused(edge)");
+    if (rc != NQA_OK) return rc;
+    rc = finish_gy(plan, l, grad_y, workspace, mode, E, "nqa_tp_scatter_bwd_fused(reduce)", s);
+    if (rc != NQA_OK) return rc;
+  }
+  SpecArgs<float> b = spec_node_operands(plan, N);
+  b.gxe = gxe;
+  b.out = static_cast<float*>(grad_x);
+  b.rowptr = src.rowptr;
+  b.eid = src.eid;
+  spec_launch(plan, SpecKernel::RowsSumSrc, b, s);
+  return check_launch("nqa_tp_scatter_bwd_fused(sum)");
+}
+
+static int tp_bwd_x(const nqa_plan* plan, const void* image, int32_t dtype, const Values& v, const EdgeCsr& src,
+                    void* grad_x, int64_t N, int64_t E, const PairedRows* paired, hipStream_t s) {
+  const char* fn = "nqa_tp_scatter_bwd_x";
+  int rc = check_common(plan, image, dtype, fn);
+  if (rc != NQA_OK) return rc;
+  if ((N > 0 && (!grad_x || !src.rowptr)) || (E > 0 && (!v.y || !v.w || !v.g || !src.eid || !src.nbr)))
+    return fail(NQA_ERR_INVALID, fn, kNullOperand);
+  if (use_spec(plan, dtype)) {
+    if (N == 0) return NQA_OK;
+    SpecArgs<float> a = spec_edge_operands(plan, N, v, src, paired);
+    a.out = static_cast<float*>(grad_x);
+    spec_launch(plan, SpecKernel::BwdX, a, s);
+    return check_launch("nqa_tp_scatter_bwd_x(spec)");
+  }
+  if (paired != nullptr) return fail(NQA_ERR_UNSUPPORTED, fn, kNoSpecPaired);
+  return by_dtype(dtype, [&](auto t) { return launch_bwd_x(generic_args<decltype(t)>(plan, image, v, src), grad_x, N, s); });
+}
+
 }  // namespace nqa
 
 using namespace nqa;
 
 extern "C" {
 
-static int nqa_tp_scatter_fwd_impl(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x, const void* y,
-                       const void* w, const int32_t* rowptr_dst, const int32_t* edge_id_dst,
-                       const int32_t* src_sorted, void* out, int64_t num_nodes, int64_t num_edges,
-                       nqa_stream stream, const int32_t* weight_rows, int64_t num_pairs) {
-  int rc = check_common(plan, plan_image, dtype, "nqa_tp_scatter_fwd");
-  if (rc != NQA_OK) return rc;
-  if (num_nodes < 0 || num_edges < 0 || (num_nodes > 0 && (!out || !rowptr_dst)) ||
-      (num_edges > 0 && (!x || !y || !w || !edge_id_dst || !src_sorted))) {
-    set_error("nqa_tp_scatter_fwd: NULL operand");
-    return NQA_ERR_INVALID;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (use_spec(plan, dtype)) {
-    if (num_nodes == 0) return NQA_OK;
-    SpecArgs<float> a{};
-    spec_fill(a, plan, num_nodes);
-    a.x = static_cast<const float*>(x);
-    a.y = static_cast<const float*>(y);
-    a.w = static_cast<const float*>(w);
-    a.out = static_cast<float*>(out);
-    a.rowptr = rowptr_dst;
-    a.eid = edge_id_dst;
-    a.nbr = src_sorted;
-    a.wid = weight_rows ? weight_rows : edge_id_dst;
-    a.wP = weight_rows ? (int32_t)num_pairs : 2147483647;
-    plan->spec->launch(0, spec_wpn(plan, num_nodes), a, s);
-    return check_launch("nqa_tp_scatter_fwd(spec)");
-  }
-  if (weight_rows != nullptr) {
-    set_error("nqa_tp_scatter_fwd_paired: no structure-specialised float32 kernel for this plan");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  return dtype == NQA_F32
-             ? launch_fwd<float>(plan, plan_image, x, y, w, rowptr_dst, edge_id_dst, src_sorted, out, num_nodes,
-                                 num_edges, s)
-             : launch_fwd<double>(plan, plan_image, x, y, w, rowptr_dst, edge_id_dst, src_sorted, out, num_nodes,
-                                  num_edges, s);
-}
-
 int64_t nqa_tp_bwd_edge_workspace_bytes(const nqa_plan* plan, int32_t dtype, int64_t num_edges) {
-  if (plan == nullptr || num_edges < 0) return -1;
-  const int64_t es = dtype == NQA_F64 ? 8 : 4;
-  // generic kernels: one partial per (instruction, 64-channel chunk) and component of its in2 irrep (ypart_width);
-  // structure-specialised kernels: dim_in2 partials per channel chunk.  The larger of the two: for a structure with few
-  // paths the second exceeds the first (one 0e x 0e path, l_max = 1 harmonics, 128 channels: 8 floats per edge against
-  // 2) -- found when the truncated-input structures of the channel segments were added; no round-2 structure hit it.
-  int64_t per_edge = plan->ypart_width;
-  if (use_spec(plan, dtype)) {
-    const int64_t spec_w = (int64_t)plan->dim_in2 * ((plan->uniform_mul + 63) / 64);
-    if (spec_w > per_edge) per_edge = spec_w;
-  }
-  return num_edges * per_edge * es;
-}
-
-static int nqa_tp_scatter_bwd_edge_impl(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x,
-                            const void* y, const void* w, const void* grad_out, const int32_t* rowptr_dst,
-                            const int32_t* edge_id_dst, const int32_t* src_sorted, void* grad_w, void* grad_y,
-                            void* workspace, int64_t workspace_bytes, int64_t num_nodes, int64_t num_edges,
-                            nqa_stream stream, const int32_t* weight_rows, int64_t num_pairs) {
-  int rc = check_common(plan, plan_image, dtype, "nqa_tp_scatter_bwd_edge");
-  if (rc != NQA_OK) return rc;
-  if (grad_w == nullptr && grad_y == nullptr) return NQA_OK;
-  if (num_edges > 0 && (!x || !y || !w || !grad_out || !rowptr_dst || !edge_id_dst || !src_sorted)) {
-    set_error("nqa_tp_scatter_bwd_edge: NULL operand");
-    return NQA_ERR_INVALID;
-  }
-  if (grad_y != nullptr && num_edges > 0 &&
-      (workspace == nullptr || workspace_bytes < nqa_tp_bwd_edge_workspace_bytes(plan, dtype, num_edges))) {
-    set_error("nqa_tp_scatter_bwd_edge: workspace missing or too small");
-    return NQA_ERR_WORKSPACE;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (use_spec(plan, dtype)) {
-    if (num_nodes == 0 || num_edges == 0) return NQA_OK;
-    SpecArgs<float> a{};
-    spec_fill(a, plan, num_nodes);
-    const int nchunk = (plan->uniform_mul + 63) / 64;
-    a.x = static_cast<const float*>(x);
-    a.y = static_cast<const float*>(y);
-    a.w = static_cast<const float*>(w);
-    a.g = static_cast<const float*>(grad_out);
-    a.gw = static_cast<float*>(grad_w);
-    a.rowptr = rowptr_dst;
-    a.eid = edge_id_dst;
-    a.nbr = src_sorted;
-    a.wid = weight_rows ? weight_rows : edge_id_dst;
-    a.wP = weight_rows ? (int32_t)num_pairs : 2147483647;
-    if (grad_y != nullptr) {
-      if (nchunk == 1) {
-        a.gy = static_cast<float*>(grad_y);
-        a.gy_stride = plan->dim_in2;
-      } else {
-        a.gy = static_cast<float*>(workspace);
-        a.gy_stride = plan->dim_in2 * nchunk;
-      }
-    }
-    plan->spec->launch(1, spec_wpn(plan, num_nodes), a, s);
-    rc = check_launch("nqa_tp_scatter_bwd_edge(spec)");
-    if (rc != NQA_OK) return rc;
-    if (grad_y != nullptr && nchunk > 1) {
-      const int64_t total = num_edges * (int64_t)plan->dim_in2;
-      hipLaunchKernelGGL(spec_gy_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                         static_cast<const float*>(workspace), static_cast<float*>(grad_y), plan->dim_in2, nchunk,
-                         total);
-      return check_launch("nqa_tp_scatter_bwd_edge(spec reduce)");
-    }
-    return NQA_OK;
-  }
-  if (weight_rows != nullptr) {
-    set_error("nqa_tp_scatter_bwd_edge_paired: no structure-specialised float32 kernel for this plan");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  return dtype == NQA_F32 ? launch_bwd_edge<float>(plan, plan_image, x, y, w, grad_out, rowptr_dst, edge_id_dst,
-                                                   src_sorted, grad_w, grad_y, workspace, num_nodes, num_edges, s)
-                          : launch_bwd_edge<double>(plan, plan_image, x, y, w, grad_out, rowptr_dst, edge_id_dst,
-                                                    src_sorted, grad_w, grad_y, workspace, num_nodes, num_edges, s);
+  return tp_ws_layout(plan, dtype, TpWs::Edge, num_edges).total;
 }
 
 int64_t nqa_tp_bwd_fused_workspace_bytes(const nqa_plan* plan, int32_t dtype, int64_t num_edges) {
-  if (plan == nullptr || num_edges < 0 || !use_spec(plan, dtype)) return -1;
-  const int nchunk = (plan->uniform_mul + 63) / 64;
-  const int64_t ypart = nchunk > 1 ? num_edges * (int64_t)plan->dim_in2 * nchunk * 4 : 0;
-  return ((ypart + 255) & ~(int64_t)255) + num_edges * (int64_t)plan->dim_in1 * 4;
+  return tp_ws_layout(plan, dtype, TpWs::Fused, num_edges).total;
 }
 
-static int nqa_tp_scatter_bwd_fused_impl(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x,
-                             const void* y, const void* w, const void* grad_out, const int32_t* rowptr_dst,
-                             const int32_t* edge_id_dst, const int32_t* src_sorted, const int32_t* rowptr_src,
-                             const int32_t* edge_id_src, void* grad_w, void* grad_y, void* grad_x, void* workspace,
-                             int64_t workspace_bytes, int64_t num_nodes, int64_t num_edges, nqa_stream stream, const int32_t* weight_rows, int64_t num_pairs) {
-  int rc = check_common(plan, plan_image, dtype, "nqa_tp_scatter_bwd_fused");
-  if (rc != NQA_OK) return rc;
-  if (!use_spec(plan, dtype)) {
-    set_error("nqa_tp_scatter_bwd_fused: no structure-specialised float32 kernel for this plan");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  if ((num_nodes > 0 && (!grad_x || !rowptr_dst || !rowptr_src)) ||
-      (num_edges > 0 &&
-       (!x || !y || !w || !grad_out || !edge_id_dst || !src_sorted || !edge_id_src || !grad_w || !grad_y))) {
-    set_error("nqa_tp_scatter_bwd_fused: NULL operand");
-    return NQA_ERR_INVALID;
-  }
-  if (num_edges > 0 &&
-      (workspace == nullptr || workspace_bytes < nqa_tp_bwd_fused_workspace_bytes(plan, dtype, num_edges))) {
-    set_error("nqa_tp_scatter_bwd_fused: workspace missing or too small");
-    return NQA_ERR_WORKSPACE;
-  }
-  if (num_nodes == 0) return NQA_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  SpecArgs<float> a{};
-  spec_fill(a, plan, num_nodes);
-  const int nchunk = (plan->uniform_mul + 63) / 64;
-  const int64_t ypart = nchunk > 1 ? num_edges * (int64_t)plan->dim_in2 * nchunk * 4 : 0;
-  float* gxe = reinterpret_cast<float*>(static_cast<char*>(workspace) + ((ypart + 255) & ~(int64_t)255));
-  if (num_edges > 0) {
-    a.x = static_cast<const float*>(x);
-    a.y = static_cast<const float*>(y);
-    a.w = static_cast<const float*>(w);
-    a.g = static_cast<const float*>(grad_out);
-    a.gw = static_cast<float*>(grad_w);
-    a.gxe = gxe;
-    a.rowptr = rowptr_dst;
-    a.eid = edge_id_dst;
-    a.nbr = src_sorted;
-    a.wid = weight_rows ? weight_rows : edge_id_dst;
-    a.wP = weight_rows ? (int32_t)num_pairs : 2147483647;
-    if (grad_y != nullptr) {
-      if (nchunk == 1) {
-        a.gy = static_cast<float*>(grad_y);
-        a.gy_stride = plan->dim_in2;
-      } else {
-        a.gy = static_cast<float*>(workspace);
-        a.gy_stride = plan->dim_in2 * nchunk;
-      }
-    }
-    plan->spec->launch(1, spec_wpn(plan, num_nodes), a, s);
-    rc = check_launch("nqa_tp_scatter_bwd_fused(edge)");
-    if (rc != NQA_OK) return rc;
-    if (grad_y != nullptr && nchunk > 1) {
-      const int64_t total = num_edges * (int64_t)plan->dim_in2;
-      hipLaunchKernelGGL(spec_gy_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                         static_cast<const float*>(workspace), static_cast<float*>(grad_y), plan->dim_in2, nchunk,
-                         total);
-      rc = check_launch("nqa_tp_scatter_bwd_fused(reduce)");
-      if (rc != NQA_OK) return rc;
-    }
-  }
-  SpecArgs<float> b{};
-  spec_fill(b, plan, num_nodes);
-  b.gxe = gxe;
-  b.out = static_cast<float*>(grad_x);
-  b.rowptr = rowptr_src;
-  b.eid = edge_id_src;
-  plan->spec->launch(3, 1, b, s);
-  return check_launch("nqa_tp_scatter_bwd_fused(sum)");
-}
-
-static int nqa_tp_scatter_bwd_x_impl(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* y, const void* w,
-                         const void* grad_out, const int32_t* rowptr_src, const int32_t* edge_id_src,
-                         const int32_t* dst_sorted, void* grad_x, int64_t num_nodes, int64_t num_edges,
-                         nqa_stream stream, const int32_t* weight_rows, int64_t num_pairs) {
-  int rc = check_common(plan, plan_image, dtype, "nqa_tp_scatter_bwd_x");
-  if (rc != NQA_OK) return rc;
-  if ((num_nodes > 0 && (!grad_x || !rowptr_src)) ||
-      (num_edges > 0 && (!y || !w || !grad_out || !edge_id_src || !dst_sorted))) {
-    set_error("nqa_tp_scatter_bwd_x: NULL operand");
-    return NQA_ERR_INVALID;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (use_spec(plan, dtype)) {
-    if (num_nodes == 0) return NQA_OK;
-    SpecArgs<float> a{};
-    spec_fill(a, plan, num_nodes);
-    a.y = static_cast<const float*>(y);
-    a.w = static_cast<const float*>(w);
-    a.g = static_cast<const float*>(grad_out);
-    a.out = static_cast<float*>(grad_x);
-    a.rowptr = rowptr_src;
-    a.eid = edge_id_src;
-    a.nbr = dst_sorted;
-    a.wid = weight_rows ? weight_rows : edge_id_src;
-    a.wP = weight_rows ? (int32_t)num_pairs : 2147483647;
-    plan->spec->launch(2, spec_wpn(plan, num_nodes), a, s);
-    return check_launch("nqa_tp_scatter_bwd_x(spec)");
-  }
-  if (weight_rows != nullptr) {
-    set_error("nqa_tp_scatter_bwd_x_paired: no structure-specialised float32 kernel for this plan");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  return dtype == NQA_F32 ? launch_bwd_x<float>(plan, plan_image, y, w, grad_out, rowptr_src, edge_id_src,
-                                                dst_sorted, grad_x, num_nodes, num_edges, s)
-                          : launch_bwd_x<double>(plan, plan_image, y, w, grad_out, rowptr_src, edge_id_src,
-                                                 dst_sorted, grad_x, num_nodes, num_edges, s);
+int64_t nqa_tp_bwd_pairs_workspace_bytes(const nqa_plan* plan, int32_t dtype, int64_t num_edges) {
+  return tp_ws_layout(plan, dtype, TpWs::Pairs, num_edges).total;
 }
 
 int nqa_tp_scatter_fwd(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x, const void* y,
                        const void* w, const int32_t* rowptr_dst, const int32_t* edge_id_dst,
                        const int32_t* src_sorted, void* out, int64_t num_nodes, int64_t num_edges,
                        nqa_stream stream) {
-  return nqa_tp_scatter_fwd_impl(plan, plan_image, dtype, x, y, w, rowptr_dst, edge_id_dst, src_sorted, out, num_nodes, num_edges, stream, nullptr, 0);
+  return tp_fwd(plan, plan_image, dtype, {x, y, w, nullptr}, {rowptr_dst, edge_id_dst, src_sorted}, out, num_nodes,
+                num_edges, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int nqa_tp_scatter_fwd_paired(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x, const void* y,
-                       const void* w, const int32_t* rowptr_dst, const int32_t* edge_id_dst,
-                       const int32_t* src_sorted, void* out, int64_t num_nodes, int64_t num_edges,
-                       const int32_t* weight_rows, int64_t num_pairs, nqa_stream stream) {
-  if (weight_rows == nullptr || num_pairs <= 0 || num_pairs > 1073741823) {
-    set_error("nqa_tp_scatter_fwd_paired: weight_rows / num_pairs missing or out of range");
-    return NQA_ERR_INVALID;
-  }
-  return nqa_tp_scatter_fwd_impl(plan, plan_image, dtype, x, y, w, rowptr_dst, edge_id_dst, src_sorted, out, num_nodes, num_edges, stream, weight_rows, num_pairs);
+                              const void* w, const int32_t* rowptr_dst, const int32_t* edge_id_dst,
+                              const int32_t* src_sorted, void* out, int64_t num_nodes, int64_t num_edges,
+                              const int32_t* weight_rows, int64_t num_pairs, nqa_stream stream) {
+  const PairedRows paired{weight_rows, num_pairs};
+  int rc = check_paired("nqa_tp_scatter_fwd", weight_rows, num_pairs);
+  if (rc != NQA_OK) return rc;
+  return tp_fwd(plan, plan_image, dtype, {x, y, w, nullptr}, {rowptr_dst, edge_id_dst, src_sorted}, out, num_nodes,
+                num_edges, &paired, static_cast<hipStream_t>(stream));
 }
 
 int nqa_tp_scatter_bwd_edge(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x,
@@ -738,19 +767,20 @@ int nqa_tp_scatter_bwd_edge(const nqa_plan* plan, const void* plan_image, int32_
                             const int32_t* edge_id_dst, const int32_t* src_sorted, void* grad_w, void* grad_y,
                             void* workspace, int64_t workspace_bytes, int64_t num_nodes, int64_t num_edges,
                             nqa_stream stream) {
-  return nqa_tp_scatter_bwd_edge_impl(plan, plan_image, dtype, x, y, w, grad_out, rowptr_dst, edge_id_dst, src_sorted, grad_w, grad_y, workspace, workspace_bytes, num_nodes, num_edges, stream, nullptr, 0);
+  return tp_bwd_edge(plan, plan_image, dtype, {x, y, w, grad_out}, {rowptr_dst, edge_id_dst, src_sorted}, grad_w, grad_y,
+                     workspace, workspace_bytes, num_nodes, num_edges, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int nqa_tp_scatter_bwd_edge_paired(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x,
-                            const void* y, const void* w, const void* grad_out, const int32_t* rowptr_dst,
-                            const int32_t* edge_id_dst, const int32_t* src_sorted, void* grad_w, void* grad_y,
-                            void* workspace, int64_t workspace_bytes, int64_t num_nodes, int64_t num_edges,
-                            const int32_t* weight_rows, int64_t num_pairs, nqa_stream stream) {
-  if (weight_rows == nullptr || num_pairs <= 0 || num_pairs > 1073741823) {
-    set_error("nqa_tp_scatter_bwd_edge_paired: weight_rows / num_pairs missing or out of range");
-    return NQA_ERR_INVALID;
-  }
-  return nqa_tp_scatter_bwd_edge_impl(plan, plan_image, dtype, x, y, w, grad_out, rowptr_dst, edge_id_dst, src_sorted, grad_w, grad_y, workspace, workspace_bytes, num_nodes, num_edges, stream, weight_rows, num_pairs);
+                                   const void* y, const void* w, const void* grad_out, const int32_t* rowptr_dst,
+                                   const int32_t* edge_id_dst, const int32_t* src_sorted, void* grad_w, void* grad_y,
+                                   void* workspace, int64_t workspace_bytes, int64_t num_nodes, int64_t num_edges,
+                                   const int32_t* weight_rows, int64_t num_pairs, nqa_stream stream) {
+  const PairedRows paired{weight_rows, num_pairs};
+  int rc = check_paired("nqa_tp_scatter_bwd_edge", weight_rows, num_pairs);
+  if (rc != NQA_OK) return rc;
+  return tp_bwd_edge(plan, plan_image, dtype, {x, y, w, grad_out}, {rowptr_dst, edge_id_dst, src_sorted}, grad_w, grad_y,
+                     workspace, workspace_bytes, num_nodes, num_edges, &paired, static_cast<hipStream_t>(stream));
 }
 
 int nqa_tp_scatter_bwd_fused(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x,
@@ -758,57 +788,42 @@ int nqa_tp_scatter_bwd_fused(const nqa_plan* plan, const void* plan_image, int32
                              const int32_t* edge_id_dst, const int32_t* src_sorted, const int32_t* rowptr_src,
                              const int32_t* edge_id_src, void* grad_w, void* grad_y, void* grad_x, void* workspace,
                              int64_t workspace_bytes, int64_t num_nodes, int64_t num_edges, nqa_stream stream) {
-  return nqa_tp_scatter_bwd_fused_impl(plan, plan_image, dtype, x, y, w, grad_out, rowptr_dst, edge_id_dst, src_sorted, rowptr_src, edge_id_src, grad_w, grad_y, grad_x, workspace, workspace_bytes, num_nodes, num_edges, stream, nullptr, 0);
+  return tp_bwd_fused(plan, plan_image, dtype, {x, y, w, grad_out}, {rowptr_dst, edge_id_dst, src_sorted},
+                      {rowptr_src, edge_id_src, nullptr}, grad_w, grad_y, grad_x, workspace, workspace_bytes, num_nodes,
+                      num_edges, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int nqa_tp_scatter_bwd_fused_paired(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x,
-                             const void* y, const void* w, const void* grad_out, const int32_t* rowptr_dst,
-                             const int32_t* edge_id_dst, const int32_t* src_sorted, const int32_t* rowptr_src,
-                             const int32_t* edge_id_src, void* grad_w, void* grad_y, void* grad_x, void* workspace,
-                             int64_t workspace_bytes, int64_t num_nodes, int64_t num_edges, const int32_t* weight_rows, int64_t num_pairs, nqa_stream stream) {
-  if (weight_rows == nullptr || num_pairs <= 0 || num_pairs > 1073741823) {
-    set_error("nqa_tp_scatter_bwd_fused_paired: weight_rows / num_pairs missing or out of range");
-    return NQA_ERR_INVALID;
-  }
-  return nqa_tp_scatter_bwd_fused_impl(plan, plan_image, dtype, x, y, w, grad_out, rowptr_dst, edge_id_dst, src_sorted, rowptr_src, edge_id_src, grad_w, grad_y, grad_x, workspace, workspace_bytes, num_nodes, num_edges, stream, weight_rows, num_pairs);
+                                    const void* y, const void* w, const void* grad_out, const int32_t* rowptr_dst,
+                                    const int32_t* edge_id_dst, const int32_t* src_sorted, const int32_t* rowptr_src,
+                                    const int32_t* edge_id_src, void* grad_w, void* grad_y, void* grad_x, void* workspace,
+                                    int64_t workspace_bytes, int64_t num_nodes, int64_t num_edges,
+                                    const int32_t* weight_rows, int64_t num_pairs, nqa_stream stream) {
+  const PairedRows paired{weight_rows, num_pairs};
+  int rc = check_paired("nqa_tp_scatter_bwd_fused", weight_rows, num_pairs);
+  if (rc != NQA_OK) return rc;
+  return tp_bwd_fused(plan, plan_image, dtype, {x, y, w, grad_out}, {rowptr_dst, edge_id_dst, src_sorted},
+                      {rowptr_src, edge_id_src, nullptr}, grad_w, grad_y, grad_x, workspace, workspace_bytes, num_nodes,
+                      num_edges, &paired, static_cast<hipStream_t>(stream));
 }
 
 int nqa_tp_scatter_bwd_x(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* y, const void* w,
                          const void* grad_out, const int32_t* rowptr_src, const int32_t* edge_id_src,
                          const int32_t* dst_sorted, void* grad_x, int64_t num_nodes, int64_t num_edges,
                          nqa_stream stream) {
-  return nqa_tp_scatter_bwd_x_impl(plan, plan_image, dtype, y, w, grad_out, rowptr_src, edge_id_src, dst_sorted, grad_x, num_nodes, num_edges, stream, nullptr, 0);
+  return tp_bwd_x(plan, plan_image, dtype, {nullptr, y, w, grad_out}, {rowptr_src, edge_id_src, dst_sorted}, grad_x,
+                  num_nodes, num_edges, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int nqa_tp_scatter_bwd_x_paired(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* y, const void* w,
-                         const void* grad_out, const int32_t* rowptr_src, const int32_t* edge_id_src,
-                         const int32_t* dst_sorted, void* grad_x, int64_t num_nodes, int64_t num_edges,
-                         const int32_t* weight_rows, int64_t num_pairs, nqa_stream stream) {
-  if (weight_rows == nullptr || num_pairs <= 0 || num_pairs > 1073741823) {
-    set_error("nqa_tp_scatter_bwd_x_paired: weight_rows / num_pairs missing or out of range");
-    return NQA_ERR_INVALID;
-  }
-  return nqa_tp_scatter_bwd_x_impl(plan, plan_image, dtype, y, w, grad_out, rowptr_src, edge_id_src, dst_sorted, grad_x, num_nodes, num_edges, stream, weight_rows, num_pairs);
-}
-
-int64_t nqa_tp_bwd_pairs_workspace_bytes(const nqa_plan* plan, int32_t dtype, int64_t num_edges) {
-  if (plan == nullptr || num_edges < 0 || (num_edges & 1) || !use_spec(plan, dtype) || !plan->spec->pair) return -1;
-  const int nchunk = ((plan->uniform_mul + 63) / 64) * plan->spec->pair;  // grad_y partials per edge
-  const int64_t ypart = nchunk > 1 ? num_edges * (int64_t)plan->dim_in2 * nchunk * 4 : 0;
-  return ((ypart + 255) & ~(int64_t)255) + (num_edges / 2) * (int64_t)plan->dim_in1 * 4;
-}
-
-// The ring kernel's atomic grad_x form (round 6): one zeroed [N, dim_in1] accumulator instead of a row per pair.  On by
-// default where the structure has the ring kernel; NQA_PAIR_GX_ATOMIC=0 keeps the rows (sums in a fixed order: results
-// reproducible to the bit), NQA_PAIR_RING=0 the register kernel.
-static bool pair_gx_atomic(const nqa_plan* plan, int64_t num_nodes, int64_t num_edges) {
-  const char* ea = std::getenv("NQA_PAIR_GX_ATOMIC");  // (read at every call: the tests switch forms within one process)
-  const char* er = std::getenv("NQA_PAIR_RING");
-  // (the split kernel of the l_max = 3 structures has the accumulator form itself: spec->ring == 2)
-  const bool on = (ea == nullptr || ea[0] != '0') && (plan->spec->ring == 2 || er == nullptr || er[0] != '0');
-  // (the accumulator lives in the rows' workspace: [P, dim_in1] holds [N, dim_in1] whenever there are at least as many pairs
-  // as nodes -- every list this is worth running on)
-  return on && plan->spec->ring && (plan->uniform_mul & 63) == 0 && num_edges / 2 >= num_nodes;
+                                const void* grad_out, const int32_t* rowptr_src, const int32_t* edge_id_src,
+                                const int32_t* dst_sorted, void* grad_x, int64_t num_nodes, int64_t num_edges,
+                                const int32_t* weight_rows, int64_t num_pairs, nqa_stream stream) {
+  const PairedRows paired{weight_rows, num_pairs};
+  int rc = check_paired("nqa_tp_scatter_bwd_x", weight_rows, num_pairs);
+  if (rc != NQA_OK) return rc;
+  return tp_bwd_x(plan, plan_image, dtype, {nullptr, y, w, grad_out}, {rowptr_src, edge_id_src, dst_sorted}, grad_x,
+                  num_nodes, num_edges, &paired, static_cast<hipStream_t>(stream));
 }
 
 int nqa_tp_scatter_bwd_pairs(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x, const void* y,
@@ -817,105 +832,53 @@ int nqa_tp_scatter_bwd_pairs(const nqa_plan* plan, const void* plan_image, int32
                              const int32_t* pair_edge_out, const int32_t* other_rowptr, const int32_t* other_slot,
                              void* grad_w, void* grad_y, void* grad_x, void* workspace, int64_t workspace_bytes,
                              int64_t num_nodes, int64_t num_edges, nqa_stream stream) {
-  int rc = check_common(plan, plan_image, dtype, "nqa_tp_scatter_bwd_pairs");
+  const char* fn = "nqa_tp_scatter_bwd_pairs";
+  int rc = check_common(plan, plan_image, dtype, fn);
   if (rc != NQA_OK) return rc;
-  const int64_t need = nqa_tp_bwd_pairs_workspace_bytes(plan, dtype, num_edges);
-  if (need < 0) {
-    set_error("nqa_tp_scatter_bwd_pairs: no pair-centric float32 kernel for this plan (or an odd edge count)");
-    return NQA_ERR_UNSUPPORTED;
-  }
+  const TpWsLayout l = tp_ws_layout(plan, dtype, TpWs::Pairs, num_edges);
+  if (l.total < 0)
+    return fail(NQA_ERR_UNSUPPORTED, fn, ": no pair-centric float32 kernel for this plan (or an odd edge count)");
   if ((num_nodes > 0 && (!owner_rowptr || (grad_x && !other_rowptr))) ||
       (num_edges > 0 && (!x || !y || !w || !grad_out || !pair_other || !pair_row || !pair_edge_in || !pair_edge_out ||
-                         (grad_x && !other_slot) || !grad_w || !grad_y))) {
-    set_error("nqa_tp_scatter_bwd_pairs: NULL operand");
-    return NQA_ERR_INVALID;
-  }
-  if (num_edges > 0 && (workspace == nullptr || workspace_bytes < need)) {
-    set_error("nqa_tp_scatter_bwd_pairs: workspace missing or too small");
-    return NQA_ERR_WORKSPACE;
-  }
+                         (grad_x && !other_slot) || !grad_w || !grad_y)))
+    return fail(NQA_ERR_INVALID, fn, kNullOperand);
+  if (num_edges > 0 && (workspace == nullptr || workspace_bytes < l.total)) return fail(NQA_ERR_WORKSPACE, fn, kWorkspace);
   if (num_nodes == 0) return NQA_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  SpecArgs<float> a{};
-  spec_fill(a, plan, num_nodes);
-  const int nchunk = ((plan->uniform_mul + 63) / 64) * plan->spec->pair;  // grad_y partials per edge
-  const int64_t ypart = nchunk > 1 ? num_edges * (int64_t)plan->dim_in2 * nchunk * 4 : 0;
-  float* gxe = reinterpret_cast<float*>(static_cast<char*>(workspace) + ((ypart + 255) & ~(int64_t)255));
-  a.x = static_cast<const float*>(x);
-  a.y = static_cast<const float*>(y);
-  a.w = static_cast<const float*>(w);
-  a.g = static_cast<const float*>(grad_out);
+  const PairForm form = pair_form(plan, l, num_nodes, num_edges, grad_x != nullptr);
+  float* gxe = tp_ws_view(workspace, l).gxe;  // the pair rows, or the accumulator [N, dim_in1] in their place
+  SpecArgs<float> a = spec_owner_operands(plan, num_nodes, {x, y, w, grad_out},
+                                          {owner_rowptr, pair_other, pair_row, pair_edge_in, pair_edge_out});
   a.gw = static_cast<float*>(grad_w);
   a.gxe = grad_x ? gxe : nullptr;
   a.out = static_cast<float*>(grad_x);  // NULL: grad_w and grad_y only
-  a.rowptr = owner_rowptr;
-  a.nbr = pair_other;
-  a.wid = pair_row;
-  a.eid = pair_edge_in;
-  a.eid2 = pair_edge_out;
-  a.wP = 2147483647;
-  const bool atomic = grad_x != nullptr && pair_gx_atomic(plan, num_nodes, num_edges);
-  if (atomic) {
-    a.gx_atomic = 1;
-    if (hipMemsetAsync(gxe, 0, (size_t)num_nodes * plan->dim_in1 * 4, s) != hipSuccess) {
-      set_error("nqa_tp_scatter_bwd_pairs: hipMemsetAsync of the grad_x accumulator failed");
-      return NQA_ERR_LAUNCH;
-    }
-  }
-  // round 6: with more than one (channel chunk, part) per edge the ring kernels add their grad_y sums straight into the
-  // zeroed grad_y (same switch and same caveat as the grad_x accumulator: sums in arrival order) -- no [E, S x chunks] partial
-  // rows, no reduce pass.  Only where a ring kernel is what runs: the unsplit one for either request, the split one with grad_x.
-  const bool gy_atomic = nchunk > 1 && num_edges > 0 && pair_gx_atomic(plan, num_nodes, num_edges) &&
-                         (plan->spec->ring == 1 || (plan->spec->ring == 2 && grad_x != nullptr)) && [] {
-                           const char* er = std::getenv("NQA_PAIR_RING");
-                           return er == nullptr || er[0] != '0';
-                         }();
-  if (nchunk == 1) {
-    a.gy = static_cast<float*>(grad_y);
-    a.gy_stride = plan->dim_in2;
-  } else if (gy_atomic) {
-    if (hipMemsetAsync(grad_y, 0, (size_t)num_edges * plan->dim_in2 * 4, s) != hipSuccess) {
-      set_error("nqa_tp_scatter_bwd_pairs: hipMemsetAsync of grad_y failed");
-      return NQA_ERR_LAUNCH;
-    }
-    a.gy = static_cast<float*>(grad_y);
-    a.gy_stride = plan->dim_in2;
-    a.gy_atomic = 1;
-  } else {
-    a.gy = static_cast<float*>(workspace);
-    a.gy_stride = plan->dim_in2 * nchunk;
-  }
-  if (plan->spec->launch(4, spec_wpn(plan, num_nodes), a, s) != 0) {
-    set_error("nqa_tp_scatter_bwd_pairs: kernel not available");
-    return NQA_ERR_UNSUPPORTED;
-  }
+  a.gx_atomic = form.gx_atomic;
+  if (form.gx_atomic && hipMemsetAsync(gxe, 0, (size_t)num_nodes * plan->dim_in1 * 4, s) != hipSuccess)
+    return fail(NQA_ERR_LAUNCH, fn, ": hipMemsetAsync of the grad_x accumulator failed");
+  // with more than one (channel chunk, part) per edge the ring kernels add their grad_y sums straight into the zeroed grad_y
+  // (sums in arrival order, as the grad_x accumulator) -- no [E, S x chunks] partial rows, no reduce pass
+  const GyMode mode = l.nchunk == 1 ? GyMode::Direct : (form.gy_atomic ? GyMode::Atomic : GyMode::Partial);
+  if (mode == GyMode::Atomic && hipMemsetAsync(grad_y, 0, (size_t)num_edges * plan->dim_in2 * 4, s) != hipSuccess)
+    return fail(NQA_ERR_LAUNCH, fn, ": hipMemsetAsync of grad_y failed");
+  route_gy(a, l, grad_y, workspace, mode);
+  if (spec_launch(plan, SpecKernel::BwdPairs, a, s, form.ring) != 0) return fail(NQA_ERR_UNSUPPORTED, fn, ": kernel not available");
   rc = check_launch("nqa_tp_scatter_bwd_pairs(pairs)");
   if (rc != NQA_OK) return rc;
-  if (nchunk > 1 && num_edges > 0 && !gy_atomic) {
-    const int64_t total = num_edges * (int64_t)plan->dim_in2;
-    hipLaunchKernelGGL(spec_gy_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                       static_cast<const float*>(workspace), static_cast<float*>(grad_y), plan->dim_in2, nchunk, total);
-    rc = check_launch("nqa_tp_scatter_bwd_pairs(reduce)");
-    if (rc != NQA_OK) return rc;
-  }
+  rc = finish_gy(plan, l, grad_y, workspace, mode, num_edges, "nqa_tp_scatter_bwd_pairs(reduce)", s);
+  if (rc != NQA_OK) return rc;
   if (grad_x == nullptr) return NQA_OK;
-  SpecArgs<float> b{};
-  spec_fill(b, plan, num_nodes);
+  SpecArgs<float> b = spec_node_operands(plan, num_nodes);
   b.gxe = gxe;
   b.out = static_cast<float*>(grad_x);
-  if (atomic) {
-    if (plan->spec->launch(9, 1, b, s) != 0) {
-      set_error("nqa_tp_scatter_bwd_pairs: this structure has no accumulator kernel");
-      return NQA_ERR_UNSUPPORTED;
-    }
+  if (form.gx_atomic) {
+    if (spec_launch(plan, SpecKernel::AccFinish, b, s) != 0)
+      return fail(NQA_ERR_UNSUPPORTED, fn, ": this structure has no accumulator kernel");
     return check_launch("nqa_tp_scatter_bwd_pairs(accumulator)");
   }
   b.rowptr = other_rowptr;
   b.eid = other_slot;
-  if (plan->spec->launch(5, 1, b, s) != 0) {
-    set_error("nqa_tp_scatter_bwd_pairs: this structure has no grad_x row-sum kernel");
-    return NQA_ERR_UNSUPPORTED;
-  }
+  if (spec_launch(plan, SpecKernel::RowsSumPairs, b, s) != 0)
+    return fail(NQA_ERR_UNSUPPORTED, fn, ": this structure has no grad_x row-sum kernel");
   return check_launch("nqa_tp_scatter_bwd_pairs(sum)");
 }
 
@@ -929,66 +892,40 @@ int nqa_tp_scatter_bwd_pairs_dual(const nqa_plan* plan, const void* plan_image, 
                                   const int32_t* pair_row, const int32_t* pair_edge_in, const int32_t* pair_edge_out,
                                   void* grad_w, void* grad_y, void* workspace, int64_t workspace_bytes,
                                   int64_t num_nodes, int64_t num_edges, nqa_stream stream) {
-  int rc = check_common(plan, plan_image, dtype, "nqa_tp_scatter_bwd_pairs_dual");
+  const char* fn = "nqa_tp_scatter_bwd_pairs_dual";
+  int rc = check_common(plan, plan_image, dtype, fn);
   if (rc != NQA_OK) return rc;
-  if (!nqa_tp_bwd_pairs_dual_supported(plan, dtype) || (num_edges & 1)) {
-    set_error("nqa_tp_scatter_bwd_pairs_dual: no dual pair-centric kernel for this plan (or an odd edge count)");
-    return NQA_ERR_UNSUPPORTED;
-  }
-  const int64_t need = nqa_tp_bwd_pairs_workspace_bytes(plan, dtype, num_edges);
+  if (!nqa_tp_bwd_pairs_dual_supported(plan, dtype) || (num_edges & 1))
+    return fail(NQA_ERR_UNSUPPORTED, fn, ": no dual pair-centric kernel for this plan (or an odd edge count)");
+  const TpWsLayout l = tp_ws_layout(plan, dtype, TpWs::Pairs, num_edges);  // (pair == 1: nchunk is the channel chunks)
   if ((num_nodes > 0 && !owner_rowptr) ||
       (num_edges > 0 && (!x || !x_cot || !y || !y_cot || !w || !grad_out || !pair_other || !pair_row || !pair_edge_in ||
-                         !pair_edge_out || !grad_w || !grad_y))) {
-    set_error("nqa_tp_scatter_bwd_pairs_dual: NULL operand");
-    return NQA_ERR_INVALID;
-  }
-  if (num_edges > 0 && (workspace == nullptr || workspace_bytes < need)) {
-    set_error("nqa_tp_scatter_bwd_pairs_dual: workspace missing or too small");
-    return NQA_ERR_WORKSPACE;
-  }
+                         !pair_edge_out || !grad_w || !grad_y)))
+    return fail(NQA_ERR_INVALID, fn, kNullOperand);
+  if (num_edges > 0 && (workspace == nullptr || workspace_bytes < l.total)) return fail(NQA_ERR_WORKSPACE, fn, kWorkspace);
   if (num_nodes == 0 || num_edges == 0) return NQA_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  SpecArgs<float> a{};
-  spec_fill(a, plan, num_nodes);
-  const int nchunk = (plan->uniform_mul + 63) / 64;
-  a.x = static_cast<const float*>(x);
+  SpecArgs<float> a = spec_owner_operands(plan, num_nodes, {x, y, w, grad_out},
+                                          {owner_rowptr, pair_other, pair_row, pair_edge_in, pair_edge_out});
   a.x2 = static_cast<const float*>(x_cot);
-  a.y = static_cast<const float*>(y);
   a.y2 = static_cast<const float*>(y_cot);
-  a.w = static_cast<const float*>(w);
   a.w2 = static_cast<const float*>(w_cot);  // optional: grad_y += By(x, w_cot, grad_out)
-  a.g = static_cast<const float*>(grad_out);
   a.gw = static_cast<float*>(grad_w);
-  a.rowptr = owner_rowptr;
-  a.nbr = pair_other;
-  a.wid = pair_row;
-  a.eid = pair_edge_in;
-  a.eid2 = pair_edge_out;
-  a.wP = 2147483647;
-  if (nchunk == 1) {
-    a.gy = static_cast<float*>(grad_y);
-    a.gy_stride = plan->dim_in2;
-  } else {
-    a.gy = static_cast<float*>(workspace);
-    a.gy_stride = plan->dim_in2 * nchunk;
-  }
-  if (plan->spec->launch(6, spec_wpn(plan, num_nodes), a, s) != 0) {
-    set_error("nqa_tp_scatter_bwd_pairs_dual: kernel not available");
-    return NQA_ERR_UNSUPPORTED;
-  }
+  const GyMode mode = l.nchunk == 1 ? GyMode::Direct : GyMode::Partial;
+  route_gy(a, l, grad_y, workspace, mode);
+  if (spec_launch(plan, SpecKernel::BwdPairsDual, a, s) != 0) return fail(NQA_ERR_UNSUPPORTED, fn, ": kernel not available");
   rc = check_launch("nqa_tp_scatter_bwd_pairs_dual");
   if (rc != NQA_OK) return rc;
-  if (nchunk > 1) {
-    const int64_t total = num_edges * (int64_t)plan->dim_in2;
-    hipLaunchKernelGGL(spec_gy_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                       static_cast<const float*>(workspace), static_cast<float*>(grad_y), plan->dim_in2, nchunk, total);
-    rc = check_launch("nqa_tp_scatter_bwd_pairs_dual(reduce)");
-  }
-  return rc;
+  return finish_gy(plan, l, grad_y, workspace, mode, num_edges, "nqa_tp_scatter_bwd_pairs_dual(reduce)", s);
 }
 
 int32_t nqa_tp_fwd_jvp_supported(const nqa_plan* plan, int32_t dtype) {
   return (plan != nullptr && use_spec(plan, dtype)) ? 1 : 0;
+}
+
+// (fwd_jvp, bwd_x_dual: weight_rows is optional, and its range check is part of the NULL-operand check)
+static bool bad_optional_rows(const int32_t* weight_rows, int64_t num_pairs) {
+  return weight_rows != nullptr && (num_pairs <= 0 || num_pairs > 1073741823);
 }
 
 int nqa_tp_scatter_fwd_jvp(const nqa_plan* plan, const void* plan_image, int32_t dtype, const void* x, const void* y,
@@ -996,45 +933,30 @@ int nqa_tp_scatter_fwd_jvp(const nqa_plan* plan, const void* plan_image, int32_t
                            const int32_t* rowptr_dst, const int32_t* edge_id_dst, const int32_t* src_sorted, void* out,
                            int64_t num_nodes, int64_t num_edges, const int32_t* weight_rows, int64_t num_pairs,
                            nqa_stream stream) {
-  int rc = check_common(plan, plan_image, dtype, "nqa_tp_scatter_fwd_jvp");
+  const char* fn = "nqa_tp_scatter_fwd_jvp";
+  int rc = check_common(plan, plan_image, dtype, fn);
   if (rc != NQA_OK) return rc;
-  if (!use_spec(plan, dtype)) {
-    set_error("nqa_tp_scatter_fwd_jvp: no structure-specialised float32 kernel for this plan");
-    return NQA_ERR_UNSUPPORTED;
-  }
+  if (!use_spec(plan, dtype)) return fail(NQA_ERR_UNSUPPORTED, fn, kNoSpec);
   if (num_nodes < 0 || num_edges < 0 || (num_nodes > 0 && (!out || !rowptr_dst)) ||
       (num_edges > 0 && (!x || !y || !w || !edge_id_dst || !src_sorted || (!x_cot && !y_cot && !w_cot))) ||
-      (weight_rows != nullptr && (num_pairs <= 0 || num_pairs > 1073741823))) {
-    set_error("nqa_tp_scatter_fwd_jvp: NULL operand (at least one cotangent is required)");
-    return NQA_ERR_INVALID;
-  }
+      bad_optional_rows(weight_rows, num_pairs))
+    return fail(NQA_ERR_INVALID, fn, ": NULL operand (at least one cotangent is required)");
   if (num_nodes == 0) return NQA_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (num_edges == 0) {  // no terms: the edge operands (cotangents included) are empty and may be NULL
-    if (hipMemsetAsync(out, 0, (size_t)num_nodes * plan->dim_out * 4, s) != hipSuccess) {
-      set_error("nqa_tp_scatter_fwd_jvp: hipMemsetAsync failed");
-      return NQA_ERR_LAUNCH;
-    }
+    if (hipMemsetAsync(out, 0, (size_t)num_nodes * plan->dim_out * 4, s) != hipSuccess)
+      return fail(NQA_ERR_LAUNCH, fn, ": hipMemsetAsync failed");
     return NQA_OK;
   }
-  SpecArgs<float> a{};
-  spec_fill(a, plan, num_nodes);
-  a.x = static_cast<const float*>(x);
-  a.y = static_cast<const float*>(y);
-  a.w = static_cast<const float*>(w);
+  const PairedRows paired{weight_rows, num_pairs};
+  SpecArgs<float> a = spec_edge_operands(plan, num_nodes, {x, y, w, nullptr}, {rowptr_dst, edge_id_dst, src_sorted},
+                                         weight_rows ? &paired : nullptr);
   a.x2 = static_cast<const float*>(x_cot);
   a.y2 = static_cast<const float*>(y_cot);
   a.w2 = static_cast<const float*>(w_cot);
   a.out = static_cast<float*>(out);
-  a.rowptr = rowptr_dst;
-  a.eid = edge_id_dst;
-  a.nbr = src_sorted;
-  a.wid = weight_rows ? weight_rows : edge_id_dst;
-  a.wP = weight_rows ? (int32_t)num_pairs : 2147483647;
-  if (plan->spec->launch(7, spec_wpn(plan, num_nodes), a, s) != 0) {
-    set_error("nqa_tp_scatter_fwd_jvp: this structure has no forward-JVP kernel");
-    return NQA_ERR_UNSUPPORTED;
-  }
+  if (spec_launch(plan, SpecKernel::FwdJvp, a, s) != 0)
+    return fail(NQA_ERR_UNSUPPORTED, fn, ": this structure has no forward-JVP kernel");
   return check_launch("nqa_tp_scatter_fwd_jvp");
 }
 
@@ -1042,49 +964,29 @@ int nqa_tp_scatter_bwd_x_dual(const nqa_plan* plan, const void* plan_image, int3
                               const void* y_cot, const void* w_cot, const void* grad_out, const int32_t* rowptr_src,
                               const int32_t* edge_id_src, const int32_t* dst_sorted, void* grad_x, int64_t num_nodes,
                               int64_t num_edges, const int32_t* weight_rows, int64_t num_pairs, nqa_stream stream) {
-  int rc = check_common(plan, plan_image, dtype, "nqa_tp_scatter_bwd_x_dual");
+  const char* fn = "nqa_tp_scatter_bwd_x_dual";
+  int rc = check_common(plan, plan_image, dtype, fn);
   if (rc != NQA_OK) return rc;
-  if (!use_spec(plan, dtype)) {
-    set_error("nqa_tp_scatter_bwd_x_dual: no structure-specialised float32 kernel for this plan");
-    return NQA_ERR_UNSUPPORTED;
-  }
+  if (!use_spec(plan, dtype)) return fail(NQA_ERR_UNSUPPORTED, fn, kNoSpec);
   if ((num_nodes > 0 && (!grad_x || !rowptr_src)) ||
       (num_edges > 0 && (!y || !w || !y_cot || !w_cot || !grad_out || !edge_id_src || !dst_sorted)) ||
-      (weight_rows != nullptr && (num_pairs <= 0 || num_pairs > 1073741823))) {
-    set_error("nqa_tp_scatter_bwd_x_dual: NULL operand");
-    return NQA_ERR_INVALID;
-  }
+      bad_optional_rows(weight_rows, num_pairs))
+    return fail(NQA_ERR_INVALID, fn, kNullOperand);
   if (num_nodes == 0) return NQA_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (num_edges == 0) {  // no terms: the edge operands (cotangents included) are empty and may be NULL
-    if (hipMemsetAsync(grad_x, 0, (size_t)num_nodes * plan->dim_in1 * 4, s) != hipSuccess) {
-      set_error("nqa_tp_scatter_bwd_x_dual: hipMemsetAsync failed");
-      return NQA_ERR_LAUNCH;
-    }
+    if (hipMemsetAsync(grad_x, 0, (size_t)num_nodes * plan->dim_in1 * 4, s) != hipSuccess)
+      return fail(NQA_ERR_LAUNCH, fn, ": hipMemsetAsync failed");
     return NQA_OK;
   }
-  SpecArgs<float> a{};
-  spec_fill(a, plan, num_nodes);
-  a.y = static_cast<const float*>(y);
-  a.w = static_cast<const float*>(w);
+  const PairedRows paired{weight_rows, num_pairs};
+  SpecArgs<float> a = spec_edge_operands(plan, num_nodes, {nullptr, y, w, grad_out}, {rowptr_src, edge_id_src, dst_sorted},
+                                         weight_rows ? &paired : nullptr);
   a.y2 = static_cast<const float*>(y_cot);
   a.w2 = static_cast<const float*>(w_cot);
-  a.g = static_cast<const float*>(grad_out);
   a.out = static_cast<float*>(grad_x);
-  a.rowptr = rowptr_src;
-  a.eid = edge_id_src;
-  a.nbr = dst_sorted;
-  a.wid = weight_rows ? weight_rows : edge_id_src;
-  a.wP = weight_rows ? (int32_t)num_pairs : 2147483647;
-  if (plan->spec->launch(8, spec_wpn(plan, num_nodes), a, s) != 0) {
-    set_error("nqa_tp_scatter_bwd_x_dual: kernel not available");
-    return NQA_ERR_UNSUPPORTED;
-  }
+  if (spec_launch(plan, SpecKernel::BwdXDual, a, s) != 0) return fail(NQA_ERR_UNSUPPORTED, fn, ": kernel not available");
   return check_launch("nqa_tp_scatter_bwd_x_dual");
 }
 
 }  // extern "C"
-
-
-
-

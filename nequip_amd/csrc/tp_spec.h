@@ -12,9 +12,9 @@ namespace nqa {
 template <typename T>
 struct SpecArgs {
   const T* __restrict__ x;   // [N, din]        (fwd, bwd_edge)
-  const T* __restrict__ x2;  // [N, din] / y2 [E, S]: second operand set of the dual pair kernel (which = 6)
+  const T* __restrict__ x2;  // [N, din] / y2 [E, S]: second operand set of the dual pair kernel (BwdPairsDual)
   const T* __restrict__ y2;
-  const T* __restrict__ w2;  // forward JVP (which = 7): cotangent of the weights, rows as w
+  const T* __restrict__ w2;  // forward JVP (FwdJvp): cotangent of the weights, rows as w
   const T* __restrict__ y;   // [E, S]
   const T* __restrict__ w;   // [E, wn]
   const T* __restrict__ g;   // [N, dout]       (bwd_edge, bwd_x)
@@ -34,23 +34,42 @@ struct SpecArgs {
   int32_t mul;
   int32_t din, dout, wn;
   int32_t gy_stride;
-  int32_t gx_atomic;  // which = 4: the other node's grad_x goes into the zeroed accumulator gxe [N, din] by atomics (ring kernel)
-  int32_t gy_atomic;  // which = 4, ring kernels, more than one (chunk, part) per edge: gy is the zeroed grad_y [E, S] itself and
+  int32_t gx_atomic;  // BwdPairs: the other node's grad_x goes into the zeroed accumulator gxe [N, din] by atomics (ring kernel)
+  int32_t gy_atomic;  // BwdPairs, ring kernels, more than one (chunk, part) per edge: gy is the zeroed grad_y [E, S] itself and
                       // every wavefront adds its sums to it (no partial rows, no reduce pass)
 };
 
-// which: 0 = fwd, 1 = bwd_edge (+ gxe rows when a.gxe != null), 2 = bwd_x, 3 = per-source sum of the gxe rows,
-// 4 = pair-centric backward (owner CSR), 5 = out += per-node sum of the pair rows, 6 = dual pair-centric edge gradients, 7 = forward JVP, 8 = dual bwd_x,
-// 9 = out += accumulator rows (a.gx_atomic form of 4);  wpn: requested wavefronts per (node, chunk)
-using SpecLaunchFn = int (*)(int which, int wpn, const SpecArgs<float>& a, hipStream_t stream);
+// What a structure's launcher can be asked for.
+enum class SpecKernel {
+  Fwd,
+  BwdEdge,       // (+ the gxe rows when a.gxe != null)
+  BwdX,
+  RowsSumSrc,    // out = per-source sum of the gxe rows
+  BwdPairs,      // pair-centric backward (owner CSR)
+  RowsSumPairs,  // out += per-node sum of the pair rows
+  BwdPairsDual,  // dual pair-centric edge gradients
+  FwdJvp,
+  BwdXDual,
+  AccFinish,     // out += accumulator rows (the a.gx_atomic form of BwdPairs)
+};
+
+// Host-only launch choices, decided once per call by the dispatcher (the generated launchers read no environment).
+struct SpecLaunchOpts {
+  int wpn;      // requested wavefronts per (node, chunk)
+  bool ring;    // BwdPairs: the LDS-ring kernel where the structure has one (a.gx_atomic / a.gy_atomic need it)
+  bool masked;  // partial chunks on the exec-masked instantiations instead of the all-lanes ones
+};
+
+// Returns 0 after a launch, 1 for a request this structure cannot serve (nothing launched).
+using SpecLaunchFn = int (*)(SpecKernel which, const SpecLaunchOpts& opts, const SpecArgs<float>& a, hipStream_t stream);
 
 struct SpecEntry {
   std::string key;
   SpecLaunchFn launch;
   int xd, s, od, np;
-  int pair;  // pair-centric backward (which = 4 / 5): 0 not generated, 1 one wavefront per (node, chunk), n > 1 split
+  int pair;  // pair-centric backward (BwdPairs / RowsSumPairs): 0 not generated, 1 one wavefront per (node, chunk), n > 1 split
              // over n wavefronts by input block (grad_y partials: nchunk * n per edge)
-  int ring;  // the accumulator (atomic) form of the pair kernel's grad_x and its last step (which = 9) exist for multiples of
+  int ring;  // the accumulator (atomic) form of the pair kernel's grad_x and its last step (AccFinish) exist for multiples of
              // 64 channels: 1 = in the LDS-ring kernel, 2 = in the split kernel; 0 = rows only
   SpecEntry* next;
 };

@@ -18,7 +18,6 @@ three kernels.
 
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import Optional, Tuple
 
@@ -39,8 +38,13 @@ def _nqa_dtype(dtype: torch.dtype) -> int:
     raise RuntimeError(f"nequip_amd kernels support float32/float64 model dtypes, got {dtype}")
 
 
+def _switched_off(name: str) -> bool:
+    """An ``NQA_NO_...`` switch is set (to anything but the empty string or ``0``)?"""
+    return os.environ.get(name, "") not in ("", "0")
+
+
 class _Kernels:
-    """Thin launcher around the three native entry points for one plan."""
+    """Thin launcher around the native tensor-product entry points for one plan."""
 
     def __init__(self, plan: NativePlan, image: torch.Tensor):
         self.plan = plan
@@ -56,13 +60,45 @@ class _Kernels:
         # ... and only while the kernel's per-channel operands fit the register file (the pair-centric kernel, which is
         # split by input block for the wide structures, is not bound by this)
         self.fused_rows_ok = bool(plan.query(_lib.NQA_PLAN_FUSED_ROWS_OK))
+        self._support = {}
+
+    def _supports(self, kind: str, dtype: torch.dtype) -> bool:
+        """Cached answer of the library for this plan: ``spec`` structure-specialised kernels (float32, uniform-mul NequIP
+        shapes), ``pairs`` the pair-centric backward, ``jvp`` the one-pass second-order kernels, ``dual`` the dual
+        pair-centric edge gradients."""
+        if (kind, dtype) not in self._support:
+            lib, h, dt = _lib.load(), self.plan.handle, _nqa_dtype(dtype)
+            self._support[kind, dtype] = {
+                "spec": lambda: lib.nqa_tp_bwd_fused_workspace_bytes(h, dt, 0) >= 0,
+                "pairs": lambda: lib.nqa_tp_bwd_pairs_workspace_bytes(h, dt, 0) >= 0,
+                "jvp": lambda: bool(lib.nqa_tp_fwd_jvp_supported(h, dt)),
+                "dual": lambda: bool(lib.nqa_tp_bwd_pairs_dual_supported(h, dt)),
+            }[kind]()
+        return self._support[kind, dtype]
 
     def has_spec(self, dtype: torch.dtype) -> bool:
-        """Structure-specialised kernels available (float32, uniform-mul NequIP shapes)?"""
-        cache = self.__dict__.setdefault("_has_spec", {})
-        if dtype not in cache:
-            cache[dtype] = _lib.load().nqa_tp_bwd_fused_workspace_bytes(self.plan.handle, _nqa_dtype(dtype), 0) >= 0
-        return cache[dtype]
+        return self._supports("spec", dtype)
+
+    def has_pairs_kernel(self, dtype: torch.dtype) -> bool:
+        return self._supports("pairs", dtype)
+
+    def has_fwd_jvp(self, dtype: torch.dtype) -> bool:
+        return self._supports("jvp", dtype)
+
+    def has_dual_pairs_kernel(self, dtype: torch.dtype) -> bool:
+        return self._supports("dual", dtype)
+
+    def _call(self, name: str, pairing, slots: Optional[str], ref: torch.Tensor, *args) -> None:
+        """``nqa_tp_scatter_<name>(plan, image, dtype, *args, stream)`` on ``ref``'s dtype and stream; tensors (or None)
+        in ``args`` go by address, integers as they are.  With ``pairing``: the ``_paired`` entry point, which takes
+        ``(pairing.<slots>, num_pairs)`` -- the weight row of every CSR slot -- before the stream."""
+        fn = f"nqa_tp_scatter_{name}"
+        argv = [self.plan.handle, _ptr(self.image), _nqa_dtype(ref.dtype)]
+        argv += [a if isinstance(a, int) else _ptr(a) for a in args]
+        if pairing is not None:
+            argv += [_ptr(getattr(pairing, slots)), pairing.num_pairs]
+        rc = getattr(_lib.load(), fn + ("_paired" if pairing is not None else ""))(*argv, current_stream_ptr(ref.device))
+        _lib.check(rc, fn)
 
     def _check(self, x, y, w, topo: EdgeTopology, pairing=None):
         N, E = topo.num_nodes, topo.num_edges
@@ -79,29 +115,17 @@ class _Kernels:
     def fwd(self, x, y, w, topo: EdgeTopology, pairing=None) -> torch.Tensor:
         """``pairing`` (``EdgePairing``): ``w`` holds one row per reverse-edge pair (``nqa_tp_scatter_fwd_paired``)."""
         self._check(x, y, w, topo, pairing)
-        lib = _lib.load()
         alloc = torch.zeros if self.out_needs_zero else torch.empty
         out = alloc((topo.num_nodes, self.dim_out), dtype=x.dtype, device=x.device)
-        rowptr, eid, nbr = topo.by_dst
+        csr = topo.by_dst
         es = x.element_size()
         nbytes = topo.num_edges * (es * (self.weight_numel + self.dim_in2) + 16) + topo.num_nodes * es * (
             self.dim_in1 + self.dim_out
         )
         with torch.cuda.device(x.device), ktimer.region("tp_fwd", nbytes, 0.0, topo.num_edges * es * self.weight_numel,
                                                         self.weight_numel):
-            if pairing is None:
-                rc = lib.nqa_tp_scatter_fwd(
-                    self.plan.handle, _ptr(self.image), _nqa_dtype(x.dtype), _ptr(x), _ptr(y), _ptr(w),
-                    _ptr(rowptr), _ptr(eid), _ptr(nbr), _ptr(out), topo.num_nodes, topo.num_edges,
-                    current_stream_ptr(x.device),
-                )  # fmt: skip
-            else:
-                rc = lib.nqa_tp_scatter_fwd_paired(
-                    self.plan.handle, _ptr(self.image), _nqa_dtype(x.dtype), _ptr(x), _ptr(y), _ptr(w),
-                    _ptr(rowptr), _ptr(eid), _ptr(nbr), _ptr(out), topo.num_nodes, topo.num_edges,
-                    _ptr(pairing.slots_dst), pairing.num_pairs, current_stream_ptr(x.device),
-                )  # fmt: skip
-        _lib.check(rc, "nqa_tp_scatter_fwd")
+            self._call("fwd", pairing, "slots_dst", x, x, y, w, *csr, out,
+                       topo.num_nodes, topo.num_edges)
         return out
 
     def bwd_edge(self, x, y, w, g, topo: EdgeTopology, need_gw: bool, need_gy: bool, pairing=None, gw_out=None):
@@ -126,7 +150,7 @@ class _Kernels:
         if need_gy:
             ws_bytes = lib.nqa_tp_bwd_edge_workspace_bytes(self.plan.handle, _nqa_dtype(x.dtype), E)
             ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
-        rowptr, eid, nbr = topo.by_dst
+        csr = topo.by_dst
         es = x.element_size()
         nbytes = E * (es * (self.weight_numel + self.dim_in2) + 16) + topo.num_nodes * es * (
             self.dim_in1 + self.dim_out
@@ -134,19 +158,8 @@ class _Kernels:
         nbytes += E * es * ((self.weight_numel if need_gw else 0) + (self.dim_in2 if need_gy else 0))
         with torch.cuda.device(x.device), ktimer.region("tp_bwd_edge", nbytes, 0.0,
                                                         E * es * self.weight_numel * (2 if need_gw else 1), self.weight_numel):
-            if pairing is None:
-                rc = lib.nqa_tp_scatter_bwd_edge(
-                    self.plan.handle, _ptr(self.image), _nqa_dtype(x.dtype), _ptr(x), _ptr(y), _ptr(w), _ptr(g),
-                    _ptr(rowptr), _ptr(eid), _ptr(nbr), _ptr(gw), _ptr(gy), _ptr(ws), ws_bytes,
-                    topo.num_nodes, E, current_stream_ptr(x.device),
-                )  # fmt: skip
-            else:
-                rc = lib.nqa_tp_scatter_bwd_edge_paired(
-                    self.plan.handle, _ptr(self.image), _nqa_dtype(x.dtype), _ptr(x), _ptr(y), _ptr(w), _ptr(g),
-                    _ptr(rowptr), _ptr(eid), _ptr(nbr), _ptr(gw), _ptr(gy), _ptr(ws), ws_bytes,
-                    topo.num_nodes, E, _ptr(pairing.slots_dst), pairing.num_pairs, current_stream_ptr(x.device),
-                )  # fmt: skip
-        _lib.check(rc, "nqa_tp_scatter_bwd_edge")
+            self._call("bwd_edge", pairing, "slots_dst", x, x, y, w, g, *csr, gw, gy, ws,
+                       ws_bytes, topo.num_nodes, E)
         return gw, gy
 
     def bwd_fused(self, x, y, w, g, topo: EdgeTopology, need_gw: bool = True, need_gy: bool = True, pairing=None):
@@ -163,7 +176,7 @@ class _Kernels:
         gw = torch.empty((gw_rows, self.weight_numel), dtype=x.dtype, device=x.device) if need_gw else None
         gy = torch.empty((E, self.dim_in2), dtype=x.dtype, device=x.device) if need_gy else None
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
-        rowptr, eid, nbr = topo.by_dst
+        csr = topo.by_dst
         rowptr_s, eid_s, _ = topo.by_src
         es = x.element_size()
         # algorithmic bytes: operands and results once (w, y, gw, gy per edge; x, g, gx per node) -- the intermediate
@@ -172,27 +185,9 @@ class _Kernels:
         nbytes += E * es * ((self.weight_numel if need_gw else 0) + (self.dim_in2 if need_gy else 0))
         with torch.cuda.device(x.device), ktimer.region("tp_bwd_fused", nbytes, 0.0,
                                                         E * es * self.weight_numel * (2 if need_gw else 1), self.weight_numel):
-            if pairing is None:
-                rc = lib.nqa_tp_scatter_bwd_fused(
-                    self.plan.handle, _ptr(self.image), _nqa_dtype(x.dtype), _ptr(x), _ptr(y), _ptr(w), _ptr(g),
-                    _ptr(rowptr), _ptr(eid), _ptr(nbr), _ptr(rowptr_s), _ptr(eid_s), _ptr(gw), _ptr(gy), _ptr(gx),
-                    _ptr(ws), ws_bytes, N, E, current_stream_ptr(x.device),
-                )  # fmt: skip
-            else:
-                rc = lib.nqa_tp_scatter_bwd_fused_paired(
-                    self.plan.handle, _ptr(self.image), _nqa_dtype(x.dtype), _ptr(x), _ptr(y), _ptr(w), _ptr(g),
-                    _ptr(rowptr), _ptr(eid), _ptr(nbr), _ptr(rowptr_s), _ptr(eid_s), _ptr(gw), _ptr(gy), _ptr(gx),
-                    _ptr(ws), ws_bytes, N, E, _ptr(pairing.slots_dst), pairing.num_pairs,
-                    current_stream_ptr(x.device),
-                )  # fmt: skip
-        _lib.check(rc, "nqa_tp_scatter_bwd_fused")
+            self._call("bwd_fused", pairing, "slots_dst", x, x, y, w, g, *csr, rowptr_s, eid_s,
+                       gw, gy, gx, ws, ws_bytes, N, E)
         return gx, gw, gy
-
-    def has_pairs_kernel(self, dtype: torch.dtype) -> bool:
-        cache = self.__dict__.setdefault("_has_pairs", {})
-        if dtype not in cache:
-            cache[dtype] = _lib.load().nqa_tp_bwd_pairs_workspace_bytes(self.plan.handle, _nqa_dtype(dtype), 0) >= 0
-        return cache[dtype]
 
     def bwd_pairs(self, x, y, w, g, topo: EdgeTopology, pairing, need_gx: bool = True):
         """(gx, gw, gy) with ``gw = [num_pairs, weight_numel]`` already summed over the two directed edges of every pair
@@ -209,77 +204,48 @@ class _Kernels:
         gw = torch.empty((P, self.weight_numel), dtype=x.dtype, device=x.device)
         gy = torch.empty((E, self.dim_in2), dtype=x.dtype, device=x.device)
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
-        orow, oth, prow, ein, eout, trow, tslot = pairing.owner_csr
+        # (owner_rowptr, pair_other, pair_row, pair_edge_in, pair_edge_out, other_rowptr, other_slot)
+        owner = pairing.owner_csr
         es = x.element_size()
         # algorithmic bytes: SURVEY.md 8(d)'s boundary figure of the backward, per DIRECTED edge as the reference's
         # interface defines it (the same formulas as bwd_fused / bwd_edge) -- this kernel moves less than that because it
         # reads the shared weight row and writes its gradient once per pair
-        if need_gx:
-            nbytes = E * (es * (2 * self.weight_numel + 2 * self.dim_in2) + 16) + N * es * (2 * self.dim_in1 + self.dim_out)
-        else:
-            nbytes = E * (es * (2 * self.weight_numel + 2 * self.dim_in2) + 16) + N * es * (self.dim_in1 + self.dim_out)
+        nbytes = E * (es * (2 * self.weight_numel + 2 * self.dim_in2) + 16) + N * es * (
+            (2 if need_gx else 1) * self.dim_in1 + self.dim_out)
         with torch.cuda.device(x.device), ktimer.region("tp_bwd_fused" if need_gx else "tp_bwd_edge", nbytes, 0.0,
                                                         E * es * 2 * self.weight_numel, self.weight_numel):
-            rc = lib.nqa_tp_scatter_bwd_pairs(
-                self.plan.handle, _ptr(self.image), _nqa_dtype(x.dtype), _ptr(x), _ptr(y), _ptr(w), _ptr(g),
-                _ptr(orow), _ptr(oth), _ptr(prow), _ptr(ein), _ptr(eout), _ptr(trow), _ptr(tslot),
-                _ptr(gw), _ptr(gy), _ptr(gx), _ptr(ws), ws_bytes, N, E, current_stream_ptr(x.device),
-            )  # fmt: skip
-        _lib.check(rc, "nqa_tp_scatter_bwd_pairs")
+            self._call("bwd_pairs", None, None, x, x, y, w, g, *owner, gw, gy, gx, ws, ws_bytes, N, E)
         return gx, gw, gy
-
-    def has_fwd_jvp(self, dtype: torch.dtype) -> bool:
-        cache = self.__dict__.setdefault("_has_jvp", {})
-        if dtype not in cache:
-            cache[dtype] = bool(_lib.load().nqa_tp_fwd_jvp_supported(self.plan.handle, _nqa_dtype(dtype)))
-        return cache[dtype]
 
     def fwd_jvp(self, x, y, w, c_x, c_y, c_w, topo: EdgeTopology, pairing=None) -> torch.Tensor:
         """``F(c_x, y, w) + F(x, c_y, w) + F(x, y, c_w)`` in one pass (``nqa_tp_scatter_fwd_jvp``); a cotangent that is
         None drops its term."""
         self._check(x, y, w, topo, pairing)
-        lib = _lib.load()
         out = torch.empty((topo.num_nodes, self.dim_out), dtype=x.dtype, device=x.device)
-        rowptr, eid, nbr = topo.by_dst
+        csr = topo.by_dst
         es = x.element_size()
         nterms = sum(t is not None for t in (c_x, c_y, c_w))
         nbytes = topo.num_edges * (es * (self.weight_numel * (2 if c_w is not None else 1) + 2 * self.dim_in2) + 16) + \
             topo.num_nodes * es * (2 * self.dim_in1 + self.dim_out)
         with torch.cuda.device(x.device), ktimer.region("tp_fwd", nbytes):
-            rc = lib.nqa_tp_scatter_fwd_jvp(
-                self.plan.handle, _ptr(self.image), _nqa_dtype(x.dtype), _ptr(x), _ptr(y), _ptr(w), _ptr(c_x), _ptr(c_y),
-                _ptr(c_w), _ptr(rowptr), _ptr(eid), _ptr(nbr), _ptr(out), topo.num_nodes, topo.num_edges,
-                _ptr(pairing.slots_dst) if pairing is not None else ctypes.c_void_p(),
-                pairing.num_pairs if pairing is not None else 0, current_stream_ptr(x.device),
-            )  # fmt: skip
-        _lib.check(rc, "nqa_tp_scatter_fwd_jvp")
+            # (one entry point: the weight rows are optional)
+            self._call("fwd_jvp", None, None, x, x, y, w, c_x, c_y, c_w, *csr, out, topo.num_nodes, topo.num_edges,
+                       *((pairing.slots_dst, pairing.num_pairs) if pairing is not None else (None, 0)))
         assert nterms > 0
         return out
 
     def bwd_x_dual(self, y, w, c_y, c_w, g, topo: EdgeTopology, pairing=None) -> torch.Tensor:
         """``Bx(c_y, w, g) + Bx(y, c_w, g)`` in one pass (``nqa_tp_scatter_bwd_x_dual``)."""
         self._check(None, y, w, topo, pairing)
-        lib = _lib.load()
         gx = torch.empty((topo.num_nodes, self.dim_in1), dtype=g.dtype, device=g.device)
-        rowptr, eid, nbr = topo.by_src
+        csr = topo.by_src
         es = g.element_size()
         nbytes = topo.num_edges * (es * 2 * (self.weight_numel + self.dim_in2) + 16) + topo.num_nodes * es * (
             self.dim_in1 + self.dim_out)
         with torch.cuda.device(g.device), ktimer.region("tp_bwd_x", nbytes):
-            rc = lib.nqa_tp_scatter_bwd_x_dual(
-                self.plan.handle, _ptr(self.image), _nqa_dtype(g.dtype), _ptr(y), _ptr(w), _ptr(c_y), _ptr(c_w), _ptr(g),
-                _ptr(rowptr), _ptr(eid), _ptr(nbr), _ptr(gx), topo.num_nodes, topo.num_edges,
-                _ptr(pairing.slots_src) if pairing is not None else ctypes.c_void_p(),
-                pairing.num_pairs if pairing is not None else 0, current_stream_ptr(g.device),
-            )  # fmt: skip
-        _lib.check(rc, "nqa_tp_scatter_bwd_x_dual")
+            self._call("bwd_x_dual", None, None, g, y, w, c_y, c_w, g, *csr, gx, topo.num_nodes, topo.num_edges,
+                       *((pairing.slots_src, pairing.num_pairs) if pairing is not None else (None, 0)))
         return gx
-
-    def has_dual_pairs_kernel(self, dtype: torch.dtype) -> bool:
-        cache = self.__dict__.setdefault("_has_dual", {})
-        if dtype not in cache:
-            cache[dtype] = bool(_lib.load().nqa_tp_bwd_pairs_dual_supported(self.plan.handle, _nqa_dtype(dtype)))
-        return cache[dtype]
 
     def edge_grads_dual(self, x, x_cot, y, y_cot, w, g, topo: EdgeTopology, pairing, w_cot=None):
         """``(Bw(x_cot, y, g) + Bw(x, y_cot, g), By(x_cot, w, g) [+ By(x, w_cot, g)])`` in one pair-centric pass
@@ -292,22 +258,17 @@ class _Kernels:
         gw = torch.empty((pairing.num_pairs, self.weight_numel), dtype=x.dtype, device=x.device)
         gy = torch.empty((E, self.dim_in2), dtype=x.dtype, device=x.device)
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
-        orow, oth, prow, ein, eout, _, _ = pairing.owner_csr
+        owner = pairing.owner_csr[:5]
         es = x.element_size()
         nbytes = E * (es * (2 * self.weight_numel + 3 * self.dim_in2) + 16) + N * es * (2 * self.dim_in1 + self.dim_out)
         with torch.cuda.device(x.device), ktimer.region("tp_bwd_edge", nbytes):
-            rc = lib.nqa_tp_scatter_bwd_pairs_dual(
-                self.plan.handle, _ptr(self.image), _nqa_dtype(x.dtype), _ptr(x), _ptr(x_cot), _ptr(y), _ptr(y_cot),
-                _ptr(w), _ptr(w_cot), _ptr(g), _ptr(orow), _ptr(oth), _ptr(prow), _ptr(ein), _ptr(eout), _ptr(gw), _ptr(gy),
-                _ptr(ws), ws_bytes, N, E, current_stream_ptr(x.device),
-            )  # fmt: skip
-        _lib.check(rc, "nqa_tp_scatter_bwd_pairs_dual")
+            self._call("bwd_pairs_dual", None, None, x, x, x_cot, y, y_cot, w, w_cot, g, *owner, gw, gy,
+                       ws, ws_bytes, N, E)
         return gw, gy
 
     def use_pairs(self, dtype: torch.dtype, pairing) -> bool:
         """Pair-centric backward applicable (paired weights, kernel generated for this structure, not switched off)?"""
-        return (pairing is not None and os.environ.get("NQA_NO_PAIR_BWD", "") in ("", "0")
-                and self.has_pairs_kernel(dtype))
+        return pairing is not None and not _switched_off("NQA_NO_PAIR_BWD") and self.has_pairs_kernel(dtype)
 
     def edge_grads_folded(self, x, y, w, g, topo: EdgeTopology, pairing, need_gw: bool, need_gy: bool):
         """(gw, gy) of the edge operands with ``gw`` per weight ROW (per pair when ``pairing`` is given, summed over its
@@ -322,28 +283,16 @@ class _Kernels:
 
     def bwd_x(self, y, w, g, topo: EdgeTopology, pairing=None) -> torch.Tensor:
         self._check(None, y, w, topo, pairing)
-        lib = _lib.load()
         gx = torch.empty((topo.num_nodes, self.dim_in1), dtype=g.dtype, device=g.device)
-        rowptr, eid, nbr = topo.by_src
+        csr = topo.by_src
         es = g.element_size()
         nbytes = topo.num_edges * (es * (self.weight_numel + self.dim_in2) + 16) + topo.num_nodes * es * (
             self.dim_in1 + self.dim_out
         )
         with torch.cuda.device(g.device), ktimer.region("tp_bwd_x", nbytes, 0.0, topo.num_edges * es * self.weight_numel,
                                                         self.weight_numel):
-            if pairing is None:
-                rc = lib.nqa_tp_scatter_bwd_x(
-                    self.plan.handle, _ptr(self.image), _nqa_dtype(g.dtype), _ptr(y), _ptr(w), _ptr(g),
-                    _ptr(rowptr), _ptr(eid), _ptr(nbr), _ptr(gx), topo.num_nodes, topo.num_edges,
-                    current_stream_ptr(g.device),
-                )  # fmt: skip
-            else:
-                rc = lib.nqa_tp_scatter_bwd_x_paired(
-                    self.plan.handle, _ptr(self.image), _nqa_dtype(g.dtype), _ptr(y), _ptr(w), _ptr(g),
-                    _ptr(rowptr), _ptr(eid), _ptr(nbr), _ptr(gx), topo.num_nodes, topo.num_edges,
-                    _ptr(pairing.slots_src), pairing.num_pairs, current_stream_ptr(g.device),
-                )  # fmt: skip
-        _lib.check(rc, "nqa_tp_scatter_bwd_x")
+            self._call("bwd_x", pairing, "slots_src", g, y, w, g, *csr, gx,
+                       topo.num_nodes, topo.num_edges)
         return gx
 
 
@@ -382,7 +331,7 @@ class _TPScatterBwdFn(torch.autograd.Function):
         g = g.contiguous()
         fused = None
         folded = False
-        if need[0] and need[1] and need[2] and k.prefer_fused_bwd and os.environ.get("NQA_NO_FUSED_BWD", "") in ("", "0"):
+        if need[0] and need[1] and need[2] and k.prefer_fused_bwd and not _switched_off("NQA_NO_FUSED_BWD"):
             if k.use_pairs(x.dtype, pairing):
                 fused = k.bwd_pairs(x, y, w, g, topo, pairing)
                 folded = fused is not None
@@ -415,7 +364,7 @@ class _TPScatterBwdFn(torch.autograd.Function):
 
         gg = gxx = gyy = gww = None
         if need_g and sum(t is not None for t in (c_x, c_y, c_w)) > 1 and k.has_fwd_jvp(x.dtype) and \
-                os.environ.get("NQA_NO_FWD_JVP", "") in ("", "0"):
+                not _switched_off("NQA_NO_FWD_JVP"):
             gg = k.fwd_jvp(x, y, w, c_x, c_y, c_w, topo, pr)  # the three terms in one pass
         elif need_g:
             if c_x is not None:
@@ -425,7 +374,7 @@ class _TPScatterBwdFn(torch.autograd.Function):
             if c_w is not None:
                 gg = add(gg, k.fwd(x, y, c_w, topo, pr))
         if need_x and c_y is not None and c_w is not None and k.has_fwd_jvp(x.dtype) and \
-                os.environ.get("NQA_NO_FWD_JVP", "") in ("", "0"):
+                not _switched_off("NQA_NO_FWD_JVP"):
             gxx = k.bwd_x_dual(y, w, c_y, c_w, g, topo, pr)  # both terms in one pass
         elif need_x:
             if c_y is not None:
@@ -433,7 +382,7 @@ class _TPScatterBwdFn(torch.autograd.Function):
             if c_w is not None:
                 gxx = add(gxx, k.bwd_x(y, c_w, g, topo, pr))
         if (need_w and c_x is not None and c_y is not None and k.use_pairs(x.dtype, pr)
-                and k.has_dual_pairs_kernel(x.dtype) and os.environ.get("NQA_NO_DUAL_PAIR_BWD", "") in ("", "0")):
+                and k.has_dual_pairs_kernel(x.dtype) and not _switched_off("NQA_NO_DUAL_PAIR_BWD")):
             # both weight-gradient terms (and By(c_x, w, g)) in one pair-centric pass over the shared intermediate
             gww, a_y = k.edge_grads_dual(x, c_x, y, c_y, w, g, topo, pr, w_cot=c_w if need_y else None)
             gyy = add(gyy, a_y if need_y else None)
