@@ -476,6 +476,34 @@ int nqa_energy_head(int32_t backward, const void* h, const void* readout_weight,
                     const void* shifts, int32_t n_shifts, const int64_t* atom_types, const void* grad_e, void* out,
                     int32_t dim, int32_t act, double cst, int64_t num_nodes, nqa_stream stream);
 
+/* Training form of the energy head: trainable PerTypeScaleShift tables (nequip/nn/atomwise.py:190-234).  The forward is
+ *   nqa_energy_head(0, ...).  With a(x) = cst act(x), s_n = sum_c W[c] a(h[n, c]) (float32), t = type n,
+ *   gf_n = float(grad_e[n] * scale[t]):
+ *   nqa_energy_head_train_bwd:      grad_h[n, c] = gf_n W[c] a'(h[n, c])                       (may be NULL)
+ *                                   grad_w[c] = sum_n gf_n a(h[n, c])                          (may be NULL)
+ *                                   grad_scales[t] = sum_{n in t} grad_e[n] double(s_n)        (may be NULL; [n_scales])
+ *                                   grad_shifts[t] = sum_{n in t} grad_e[n]                    (may be NULL; [n_shifts])
+ *   nqa_energy_head_train_bwd_bwd:  the backward of (grad_e, h, W, scale) -> grad_h for a cotangent cot_grad_h [N, dim],
+ *                                   u_n = sum_c cot[n, c] W[c] a'(h[n, c]) (float32):
+ *                                   grad_grad_e[n] = scale[t] double(u_n)                      (may be NULL)
+ *                                   grad_h[n, c] = gf_n W[c] a''(h[n, c]) cot[n, c]            (may be NULL)
+ *                                   grad_w[c] = sum_n gf_n a'(h[n, c]) cot[n, c]               (may be NULL)
+ *                                   grad_scales[t] = sum_{n in t} grad_e[n] double(u_n)        (may be NULL)
+ *   Tables of one entry collect every atom.  The sums over atoms are taken in two launches: one row of partial sums per
+ *   workgroup into `workspace` (device memory of nqa_energy_head_train_workspace_bytes(num_nodes, dim or 0, n_scales or 0,
+ *   n_shifts or 0) bytes, 0 for a gradient that is not requested; 8-byte aligned, owned by the caller), then the rows added
+ *   in a fixed order.  No atomics: the results are bit-reproducible.  No allocation, no host synchronisation.  dim a multiple
+ *   of 4 up to 512; a table whose gradient is requested has at most 128 entries. */
+int64_t nqa_energy_head_train_workspace_bytes(int64_t num_nodes, int32_t dim, int32_t n_scales, int32_t n_shifts);
+int nqa_energy_head_train_bwd(const void* h, const void* readout_weight, const void* scales, int32_t n_scales,
+                              int32_t n_shifts, const int64_t* atom_types, const void* grad_e, void* grad_h, void* grad_w,
+                              void* grad_scales, void* grad_shifts, void* workspace, int64_t workspace_bytes, int32_t dim,
+                              int32_t act, double cst, int64_t num_nodes, nqa_stream stream);
+int nqa_energy_head_train_bwd_bwd(const void* h, const void* readout_weight, const void* scales, int32_t n_scales,
+                                  const int64_t* atom_types, const void* grad_e, const void* cot_grad_h, void* grad_grad_e,
+                                  void* grad_h, void* grad_w, void* grad_scales, void* workspace, int64_t workspace_bytes,
+                                  int32_t dim, int32_t act, double cst, int64_t num_nodes, nqa_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * ZBL core-repulsion pair term (nequip/nn/pair_potential.py:230-389, _ZBL / ZBL; LAMMPS pair_style zbl).  Per edge
  *   e = (i <- j), r = |edge_vec_e|, u = r * rmax_recip(e):

@@ -228,6 +228,17 @@ SIGNATURES = {
         [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
          c_double, c_int64, c_void_p],
     ),
+    "nqa_energy_head_train_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    "nqa_energy_head_train_bwd": (
+        c_int32,
+        [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_int64, c_int32, c_int32, c_double, c_int64, c_void_p],
+    ),
+    "nqa_energy_head_train_bwd_bwd": (
+        c_int32,
+        [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_int64, c_int32, c_int32, c_double, c_int64, c_void_p],
+    ),
     "nqa_zbl_fwd": (
         c_int32,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int32, c_void_p, c_int64,

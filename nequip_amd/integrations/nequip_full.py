@@ -21,7 +21,8 @@ Reference class (attributes read)                                        -> mirr
     ``ConvNetLayer`` (``irreps_in``, ``feature_irreps_hidden``, ``resnet``, ``equivariant_nonlin``,
         ``conv.{use_sc, is_first_layer, edge_mlp.dims, avg_num_neighbors_norm.norm_const}``)        ``ConvNetLayer`` (+ ``InteractionBlock``)
     ``ScalarMLP`` (``field``, ``out_field``, ``mlp_module.{dims, bias/has_bias, mlp}``)             ``ScalarMLP``
-    ``PerTypeScaleShift`` (``type_names``, ``field``, ``out_field``, ``scales``, ``shifts``)        ``PerTypeScaleShift``
+    ``PerTypeScaleShift`` (``type_names``, ``field``, ``out_field``, ``scales``, ``shifts`` and
+        whether each is an ``nn.Parameter``)                                                    ``PerTypeScaleShift`` (trainable tables stay Parameters)
     ``ZBL`` (``atomic_numbers``, ``_qqr2exesquare``, ``cutoff.p``, ``per_atom_energy_field``)          ``nn.pair_potential.ZBL``
     ``AtomwiseReduce`` (``field``, ``out_field``, ``reduce``, ``constant``)                         ``AtomwiseReduce``
     ``ForceStressOutput`` (``func``, ``do_derivatives``)                                           ``ForceStressOutput``
@@ -316,8 +317,12 @@ def _factories(model) -> Dict[str, Callable]:
             t = t.detach().double().reshape(-1)
             return float(t[0]) if t.numel() == 1 else {n: float(v) for n, v in zip(old.type_names, t.tolist())}
 
+        # a table the reference holds as an nn.Parameter (scales_trainable / shifts_trainable, atomwise.py:205-231) stays one:
+        # same name, same [T, 1] values, still seen by the optimiser
         return ann.PerTypeScaleShift(type_names=list(old.type_names), field=old.field, out_field=old.out_field,
                                      scales=val(old.scales, old.has_scales), shifts=val(old.shifts, old.has_shifts),
+                                     scales_trainable=old.has_scales and isinstance(old.scales, torch.nn.Parameter),
+                                     shifts_trainable=old.has_shifts and isinstance(old.shifts, torch.nn.Parameter),
                                      irreps_in=_irreps_dict(old.irreps_in))
 
     def zbl(old):
@@ -403,6 +408,7 @@ def _plan(model: torch.nn.Module) -> None:
                 if isinstance(nxt, ann.PerTypeScaleShift):
                     b.__dict__["_scale_shift"] = [nxt]
                     a.defer_gate = True
+                    a.__dict__["_gate_consumer"] = [b]
         norms = [m for m in kids if isinstance(m, aemb.EdgeLengthNormalizer)]
         if norms and not norms[0].symmetric:
             for layer in convs:

@@ -152,14 +152,21 @@ def _full_nequip_energy_model(
     avg_num_neighbors: Optional[Union[float, Dict[str, float]]] = None,
     per_type_energy_scales: Optional[Union[float, Dict[str, float]]] = None,
     per_type_energy_shifts: Optional[Union[float, Dict[str, float]]] = None,
+    per_type_energy_scales_trainable: Optional[bool] = False,
+    per_type_energy_shifts_trainable: Optional[bool] = False,
     do_derivatives: bool = True,
     convnet_sc: bool = True,
     convnet_resnet: bool = False,
+    learnable_shift: bool = False,
     convnet_nonlinearity_type: str = "gate",
     convnet_nonlinearity_scalars: Dict[str, str] = {"e": "silu", "o": "tanh"},
     convnet_nonlinearity_gates: Dict[str, str] = {"e": "silu", "o": "tanh"},
     pair_potential: Optional[Dict] = None,
 ):
+    # (without `learnable_shift` the first layer has no self-connection / resnet update: an isolated atom then has exactly its
+    # per-type shift as energy.  With it the first layer is built like the others, which needs one of the two switched on.)
+    assert not learnable_shift or (convnet_sc or convnet_resnet), (
+        "`learnable_shift=True` needs at least one of `convnet_sc` and `convnet_resnet`")
     if not all(name.isalnum() for name in type_names):
         raise AssertionError("type names must be alphanumeric")
     depths, widths, hidden = list(radial_mlp_depth), list(radial_mlp_width), list(feature_irreps_hidden)
@@ -186,11 +193,12 @@ def _full_nequip_energy_model(
     convnets = []
     for k, (irreps_k, depth_k, width_k) in enumerate(zip(hidden, depths, widths)):
         first = k == 0
-        conv_kwargs = dict(radial_mlp_depth=depth_k, radial_mlp_width=width_k, use_sc=convnet_sc and not first,
+        skip_ok = learnable_shift or not first
+        conv_kwargs = dict(radial_mlp_depth=depth_k, radial_mlp_width=width_k, use_sc=convnet_sc and skip_ok,
                            is_first_layer=first, avg_num_neighbors=avg_num_neighbors, type_names=type_names)
         convnets.append(chain.add(f"layer{k}_convnet", lambda prev: ConvNetLayer(
             irreps_in=prev, feature_irreps_hidden=irreps_k, convolution_kwargs=conv_kwargs,
-            resnet=convnet_resnet and not first, nonlinearity_type=convnet_nonlinearity_type,
+            resnet=convnet_resnet and skip_ok, nonlinearity_type=convnet_nonlinearity_type,
             nonlinearity_scalars=convnet_nonlinearity_scalars, nonlinearity_gates=convnet_nonlinearity_gates)))
 
     # ---- energy head: readout -> per-type scale / shift (float64) -> per-frame sum ----
@@ -202,7 +210,8 @@ def _full_nequip_energy_model(
         field=AtomicDataDict.NODE_FEATURES_KEY, out_field=energy, irreps_in=prev))
     scale_shift = chain.add("per_type_energy_scale_shift", lambda prev: PerTypeScaleShift(
         type_names=type_names, field=energy, out_field=energy, scales=per_type_energy_scales,
-        shifts=per_type_energy_shifts, irreps_in=prev))
+        shifts=per_type_energy_shifts, scales_trainable=bool(per_type_energy_scales_trainable),
+        shifts_trainable=bool(per_type_energy_shifts_trainable), irreps_in=prev))
     if pair_potential is not None:  # (nequip/model/energy_modules.py:10-35)
         chain.add("pair_potential", lambda prev: _instantiate_pair_potential(pair_potential, type_names, prev))
     chain.add("total_energy_sum", lambda prev: AtomwiseReduce(irreps_in=prev, reduce="sum", field=energy,
@@ -285,6 +294,7 @@ def _plan_fusions(convnets, edge_norm, readout, scale_shift, readout_depth: int)
     if readout_depth == 0:
         readout.__dict__["_scale_shift"] = [scale_shift]
         convnets[-1].defer_gate = True
+        convnets[-1].__dict__["_gate_consumer"] = [readout]  # (training: deferred only for the training energy head)
     if not edge_norm.symmetric:
         for layer in convnets:
             layer.conv.paired_radial_ok = False

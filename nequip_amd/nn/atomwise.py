@@ -1,5 +1,5 @@
-"""Per-atom readout helpers (mirror of ``nequip/nn/atomwise.py:62-284``): ``AtomwiseReduce`` (per-frame energy sum)
-and ``PerTypeScaleShift`` (float64 scale/shift).  O(N) elementwise work, outside the hot kernels."""
+"""Per-atom readout helpers (mirror of ``nequip/nn/atomwise.py:62-378``): ``AtomwiseReduce`` (per-frame energy sum)
+and ``PerTypeScaleShift`` (float64 scale/shift, constant or trainable tables, ``modify_PerTypeScaleShift``).  O(N) elementwise work, outside the hot kernels."""
 
 from typing import Dict, List, Optional, Union
 
@@ -7,6 +7,7 @@ import torch
 
 from ..data import AtomicDataDict
 from ._graph_mixin import GraphModuleMixin
+from .model_modifier_utils import model_modifier, replace_submodules
 from .utils import scatter
 
 _GLOBAL_DTYPE = torch.float64
@@ -35,9 +36,14 @@ class AtomwiseReduce(GraphModuleMixin, torch.nn.Module):
 
 
 class PerTypeScaleShift(GraphModuleMixin, torch.nn.Module):
+    """``E_atom = shift[type] + scale[type] * E_atom`` in float64.  A single value takes a shortcut (no per-atom lookup); a
+    trainable table (``scales_trainable`` / ``shifts_trainable``) is an ``nn.Parameter`` with one entry per type, a single
+    initial value repeated for every type (``nequip/nn/atomwise.py:116-234``)."""
+
     def __init__(self, type_names: List[str], field: str, out_field: Optional[str] = None,
                  scales: Optional[Union[float, Dict[str, float]]] = None,
-                 shifts: Optional[Union[float, Dict[str, float]]] = None, irreps_in={}):
+                 shifts: Optional[Union[float, Dict[str, float]]] = None, scales_trainable: bool = False,
+                 shifts_trainable: bool = False, irreps_in={}):
         super().__init__()
         self.type_names = type_names
         self.num_types = len(type_names)
@@ -46,8 +52,11 @@ class PerTypeScaleShift(GraphModuleMixin, torch.nn.Module):
         self._init_irreps(irreps_in=irreps_in, my_irreps_in={self.field: "0e"},
                           irreps_out={self.out_field: irreps_in[self.field]})
         self.out_dtype = _GLOBAL_DTYPE
+        if isinstance(scales, list) or isinstance(shifts, list):
+            raise ValueError("per-type scales / shifts as lists are not supported: give one number, or a dict keyed by the "
+                             "model's type names, e.g. per_type_energy_shifts: {C: 1.0, H: 2.0, O: 3.0}")
 
-        def prep(v):
+        def prep(v, trainable: bool):
             if v is None:
                 return None
             if isinstance(v, (float, int)):
@@ -57,13 +66,23 @@ class PerTypeScaleShift(GraphModuleMixin, torch.nn.Module):
                 v = [v[name] for name in self.type_names]
             else:
                 raise ValueError("per-type scales/shifts must be a float or a dict keyed by type name")
-            return torch.as_tensor(v, dtype=self.out_dtype).reshape(-1, 1)
+            t = torch.as_tensor(v, dtype=self.out_dtype)
+            if trainable and t.numel() == 1:
+                t = torch.ones(self.num_types, dtype=t.dtype) * t  # one trainable entry per type
+            assert t.shape == (self.num_types,) or t.numel() == 1
+            return t.reshape(-1, 1)
 
-        scales, shifts = prep(scales), prep(shifts)
+        self.scales_trainable, self.shifts_trainable = scales_trainable, shifts_trainable
+        for name, table, trainable in (("scales", prep(scales, scales_trainable), scales_trainable),
+                                       ("shifts", prep(shifts, shifts_trainable), shifts_trainable)):
+            if table is None:
+                self.register_buffer(name, torch.Tensor())
+            elif trainable:
+                setattr(self, name, torch.nn.Parameter(table))
+            else:
+                self.register_buffer(name, table)
         self.has_scales = scales is not None
         self.has_shifts = shifts is not None
-        self.register_buffer("scales", scales if self.has_scales else torch.Tensor())
-        self.register_buffer("shifts", shifts if self.has_shifts else torch.Tensor())
         self.scales_shortcut = self.scales.numel() == 1
         self.shifts_shortcut = self.shifts.numel() == 1
 
@@ -99,3 +118,59 @@ class PerTypeScaleShift(GraphModuleMixin, torch.nn.Module):
                 in_field = shifts + in_field
         data[self.out_field] = in_field
         return data
+
+    @model_modifier(persistent=True, private=False)
+    @classmethod
+    def modify_PerTypeScaleShift(cls, model, scales: Optional[Union[float, Dict[str, float]]] = None,
+                                 shifts: Optional[Union[float, Dict[str, float]]] = None, scales_trainable: bool = False,
+                                 shifts_trainable: bool = False):
+        """New per-type scales / shifts for a built model, e.g. the isolated-atom energies of a fine-tuning dataset
+        (``nequip/nn/atomwise.py:286-353``).  A dict may name some of the model's types only: the other types keep their
+        values; one number applies to every type; ``None`` keeps the table.  ``*_trainable`` says whether the new tables
+        are parameters."""
+
+        def merged(new, vname, old):
+            cur = getattr(old, vname).detach().cpu().reshape(-1).tolist()
+            if len(cur) != len(old.type_names):
+                assert len(cur) == 1
+                cur = cur * len(old.type_names)
+            table = dict(zip(old.type_names, cur))
+            if new is not None:
+                if isinstance(new, (float, int)):
+                    new = {name: new for name in old.type_names}
+                assert isinstance(new, dict)
+                assert all(k in old.type_names for k in new), (
+                    f"`{vname}` names {list(new)}, the model's types are {list(old.type_names)}")
+                table.update(new)
+            return table
+
+        def factory(old):
+            return cls(type_names=old.type_names, field=old.field, out_field=old.out_field,
+                       scales=merged(scales, "scales", old), shifts=merged(shifts, "shifts", old),
+                       scales_trainable=scales_trainable, shifts_trainable=shifts_trainable, irreps_in=old.irreps_in)
+
+        model = replace_submodules(model, cls, factory)
+        # a readout planned to run the fused energy head holds its scale / shift module in a plain list
+        # (model/nequip_models.py::_plan_fusions): point it at the module that is in the chain now
+        for parent in model.modules():
+            kids = list(parent._modules.values())
+            for a, b in zip(kids, kids[1:]):
+                if isinstance(b, cls) and "_scale_shift" in getattr(a, "__dict__", {}):
+                    a.__dict__["_scale_shift"] = [b]
+        return model
+
+    def __repr__(self) -> str:
+        return (f"{self.__class__.__name__} \n  scales: {_format_type_vals(self.scales.reshape(-1).tolist(), self.type_names)}"
+                f"\n  shifts: {_format_type_vals(self.shifts.reshape(-1).tolist(), self.type_names)}")
+
+
+def _format_type_vals(vals: List[float], type_names: List[str], element_formatter: str = ".6f") -> str:
+    """``[A: 1.000000, B: 2.000000]``; one value for all types: ``[A, B: 1.000000]``; no table: ``[A, B: None]``."""
+    names = ", ".join(type_names)
+    if not vals:
+        return f"[{names}: None]"
+    if len(vals) == 1:
+        return f"[{names}: {format(vals[0], element_formatter)}]"
+    if len(vals) != len(type_names):
+        raise ValueError(f"{len(vals)} values for the types {type_names}")
+    return "[" + ", ".join(f"{n}: {format(v, element_formatter)}" for n, v in zip(type_names, vals)) + "]"

@@ -87,8 +87,14 @@ class ConvNetLayer(GraphModuleMixin, torch.nn.Module):
         if not self.defer_gate or self.resnet or not isinstance(self.equivariant_nonlin, Gate):
             return False
         meta = self.equivariant_nonlin._kernel_meta
-        if meta is None or not h.is_cuda or h.dtype != torch.float32 or self.training:
+        if meta is None or not h.is_cuda or h.dtype != torch.float32:
             return False
+        if self.training:
+            # training keeps the gate here, except in front of a readout that runs the training energy head (trainable
+            # scale / shift tables: nn/mlp.py::ScalarMLP.wants_training_head; a plain list entry set by the model builder)
+            consumer = self.__dict__.get("_gate_consumer")
+            if consumer is None or not consumer[0].training or not consumer[0].wants_training_head():
+                return False
         if traceable() and os.environ.get("NQA_TRACE_NO_NODE_FUSION", "") not in ("", "0"):
             return False
         return _node_kernels.fusion_enabled() and meta.fusable()

@@ -503,35 +503,68 @@ class ScalarMLP(_WeightCacheMixin, GraphModuleMixin, torch.nn.Module):
         )
         self.irreps_out[self.out_field] = Irreps([(self.mlp_module.dims[-1], (0, 1))])
 
-    def _energy_head(self, data, h: torch.Tensor, gate_meta):
-        """Gate (scalars only) + this depth-0 readout + the following PerTypeScaleShift as one launch (nn/_energy_head.py);
-        None when the shapes / modes do not fit (the caller then applies the gate and the modules run one by one)."""
+    def _head_tables(self):
+        """``(module, [its scale / shift tables])`` of the PerTypeScaleShift the fused energy head would apply, or None."""
         tail = self.__dict__.get("_scale_shift")
-        fn = self.mlp_module
-        if (tail is None or fn.num_layers != 1 or fn.has_bias or fn.dims[-1] != 1 or not h.is_cuda or h.dtype != torch.float32
-                or self.training or h.shape[1] % 4 != 0 or len(gate_meta.blocks) != 1
-                or gate_meta.blocks[0][4] >= 0 or os.environ.get("NQA_NO_ENERGY_HEAD", "") not in ("", "0")
-                or differentiable_parameters(self.training, fn.mlp[0].weight)):
+        if tail is None:
             return None
         ss = tail[0]
+        return ss, [t for t, has in ((ss.scales, ss.has_scales), (ss.shifts, ss.has_shifts)) if has]
+
+    def wants_training_head(self) -> bool:
+        """Would this readout run the TRAINING form of the energy head (nn/_energy_head.py::energy_head_train) on float32 GPU
+        rows?  Only with a trainable scale / shift table.  (The last ``ConvNetLayer`` asks before it leaves its gate to this
+        module in training mode; with constant tables the training step keeps the module chain.)"""
+        found = self._head_tables()
+        fn = self.mlp_module
+        return (found is not None and fn.num_layers == 1 and not fn.has_bias and fn.dims[-1] == 1 and not traceable()
+                and os.environ.get("NQA_NO_ENERGY_HEAD", "") in ("", "0") and any(t.requires_grad for t in found[1]))
+
+    def _energy_head(self, data, h: torch.Tensor, gate_meta):
+        """Gate (scalars only) + this depth-0 readout + the following PerTypeScaleShift as one launch (nn/_energy_head.py);
+        None when the shapes / modes do not fit (the caller then applies the gate and the modules run one by one).
+
+        Eval mode: weight and tables are constants.  Training mode, or eval mode with ``eval_parameter_gradients()``: the
+        parameters need gradients, which the constant-weight head would drop -- with a trainable table the training head
+        runs (its backward returns the gradients of the weight and the tables), otherwise the module chain."""
+        found = self._head_tables()
+        fn = self.mlp_module
+        if (found is None or fn.num_layers != 1 or fn.has_bias or fn.dims[-1] != 1 or not h.is_cuda or h.dtype != torch.float32
+                or h.shape[1] % 4 != 0 or len(gate_meta.blocks) != 1
+                or gate_meta.blocks[0][4] >= 0 or os.environ.get("NQA_NO_ENERGY_HEAD", "") not in ("", "0")):
+            return None
+        ss, tables = found
+        lin = fn.mlp[0]
+        training_head = False
+        if differentiable_parameters(self.training, lin.weight, *tables):
+            if not self.wants_training_head() or h.shape[1] > 512 or any(t.numel() > 128 for t in tables):
+                return None
+            training_head = True
         if ss.field != self.out_field or ss.out_field != self.out_field:
             return None
         # the head reads scales / shifts as float64 and the types as int64 (a `model.float()` must not be reinterpreted)
         if ((ss.has_scales and ss.scales.dtype != torch.float64) or (ss.has_shifts and ss.shifts.dtype != torch.float64)
                 or data[AtomicDataDict.ATOM_TYPE_KEY].dtype != torch.int64):
             return None
-        lin = fn.mlp[0]
         types = data[AtomicDataDict.ATOM_TYPE_KEY].view(-1)[: h.shape[0]].contiguous()
         _, _, _, _, _, act, cst = gate_meta.blocks[0]
+        if training_head:
+            from ._energy_head import energy_head_train
+
+            if lin.weight.dtype != torch.float32:
+                return None
+            return energy_head_train(h, lin.weight.view(-1) * lin.alpha_value, ss.scales.view(-1) if ss.has_scales else None,
+                                     ss.shifts.view(-1) if ss.has_shifts else None, types, act, cst)
         if traceable():  # the same launch as a dispatcher-op pair (nn/_energy_head.py)
             from ._energy_head import energy_head_op
 
             w = (lin.weight.detach().view(-1) * lin.alpha_value).to(torch.float32)
             return energy_head_op(h, w, ss.scales.view(-1) if ss.has_scales else None,
                                   ss.shifts.view(-1) if ss.has_shifts else None, types, act, cst)
-        if torch.is_grad_enabled() and lin.weight.requires_grad and not h.requires_grad:
-            # nothing upstream asks for a gradient but the readout weight does (an energy-only backward in eval mode): the
-            # module chain, whose `mm` gives that gradient -- the fused head treats the weight as a constant
+        if (torch.is_grad_enabled() and not h.requires_grad
+                and (lin.weight.requires_grad or any(t.requires_grad for t in tables))):
+            # nothing upstream asks for a gradient but the readout weight or a table does (an energy-only backward in eval
+            # mode): the module chain, which gives those gradients -- the fused head treats them as constants
             return None
         key = (lin.weight._version, lin.weight.data_ptr(), h.device)
         cached = self.__dict__.get("_head_w")
