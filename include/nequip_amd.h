@@ -796,6 +796,80 @@ int nqa_neighbor_list_batched_fill_typed(const void* workspace, const int32_t* r
                                          int64_t num_atoms, int64_t num_frames, int64_t num_types, int64_t num_edges,
                                          int64_t* edge_index, double* edge_cell_shift, nqa_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Losses and error metrics on one fused reduction: what nequip.train.MetricsManager.forward evaluates entry by entry
+ *   (nequip/train/metrics_manager.py:283-373; the metric classes of nequip/train/metrics.py on nequip/data/stats.py::_MeanX;
+ *   nequip/data/modifier.py::PerAtomModifier), without boolean indexing, masked_select or a host read.
+ *   A STREAM is one distinct (prediction, target) pair: [rows, cols] row-major, float32 or float64 each (either
+ *   combination); optional row_scale [rows] float64 applied to BOTH sides (PerAtomModifier: factor / num_atoms); optional
+ *   group [rows] int64 (the atom types, for per-type terms).  With p, t promoted to float64 FIRST (the reference subtracts in
+ *   the tensors' own dtype and promotes afterwards): d = p scale - t scale.
+ *   A TERM is one metric on a stream; it owns n_groups slots (1, or T: slot g collects the rows with group == g).  Per slot:
+ *   sum of m(d) (float64), count of contributing elements (int64), max |d| (float64), where m is d^2 (MSE, RMSE), |d|
+ *   (MAE), Huber (|d| < delta ? d^2 / 2 : delta (|d| - delta / 2), strict <) or stratified Huber (the delta of the stratum
+ *   i with |t row| >= bound[i] and not |t row| >= bound[i + 1]; strata in the given order, the last match wins, a row in no
+ *   stratum adds 0).  ignore_nan: an element whose TARGET is NaN contributes to nothing of that term.
+ *   Slot value: sum / count (MSE, MAE, Huber kinds with reduce_sum == 0), sqrt(sum / count) (RMSE), sum (reduce_sum != 0),
+ *   max (-inf without elements); no element: 0 / 0 = NaN.  Term value: the slot value, or over the groups whose value is not
+ *   NaN the equal mean / sum(c_g v_g) / sum(c_g) with has_group_coeffs.  weighted_sum = sum over the terms with has_coeff of
+ *   coeff * term value, in term order.
+ *   The term table: ordered by stream, slot0 contiguous in term order; out0 is the index of the term's first returned value
+ *   (n_groups > 1: out0 + g per group, out0 + n_groups the aggregate).  It is read on the device (terms_device: a device
+ *   copy of the host table `terms`, which the entry points use for checking and sizing); streams are passed by value.
+ * nqa_metrics_fwd: two launches.  NQA_METRICS_GROUPS workgroups (nqa_metrics_groups) walk every stream once and leave one
+ *   row of per-slot partials each in `workspace` (nqa_metrics_workspace_bytes(total slots), 8-byte aligned); one workgroup
+ *   adds the rows in row order (no floating-point atomics: bit-reproducible) and writes values [n_values] (float64),
+ *   saved [2, slots] (batch sums float64, counts int64: for the backward) and, if state != NULL, adds the batch to the running
+ *   state [3, slots] (sum float64, count int64, max float64; the caller initialises 0, 0, -inf).  rows == 0 is valid.
+ *   The first launch keeps 256 float64 values per term of one stream in LDS: from about 30 terms on ONE stream it asks the
+ *   device for more than 64 KiB (at most 102 KiB at the limits) and returns NQA_ERR_LAUNCH if that is not granted.
+ * nqa_metrics_bwd: one launch.  grad_values [n_values] is the upstream gradient over ALL returned values; every stream with
+ *   grad_pred != NULL gets [rows, cols] in the prediction's dtype, every element written, the contributions of all its terms
+ *   summed, with m'(d), the row scale, 1 / count, 1 / (2 rmse) and the group weights folded in; masked elements exactly 0.
+ *   Max-abs terms are metrics, computed detached: no gradient.  Targets get no gradient.  Once differentiable.
+ *   No allocation, no host synchronisation: forward, state update and backward capture into a hipGraph.
+ * ------------------------------------------------------------------------------------------- */
+#define NQA_METRICS_MAX_STREAMS 8
+#define NQA_METRICS_MAX_TERMS 32
+#define NQA_METRICS_MAX_TYPES 16
+#define NQA_METRICS_MAX_STRATA 8
+#define NQA_METRICS_GROUPS 64
+
+enum nqa_metric_kind {
+  NQA_METRIC_MSE = 0,
+  NQA_METRIC_MAE = 1,
+  NQA_METRIC_RMSE = 2,
+  NQA_METRIC_MAXABS = 3,
+  NQA_METRIC_HUBER = 4,
+  NQA_METRIC_STRATIFIED_HUBER = 5
+};
+
+typedef struct nqa_metric_stream {
+  const void* pred;        /* [rows, cols] */
+  const void* target;      /* [rows, cols] */
+  const double* row_scale; /* optional [rows] */
+  const int64_t* group;    /* optional [rows] */
+  void* grad_pred;         /* backward: optional [rows, cols], dtype of pred */
+  int64_t rows;
+  int32_t cols, pred_dtype, target_dtype, pad;
+} nqa_metric_stream;
+
+typedef struct nqa_metric_term {
+  int32_t stream, kind, n_groups, ignore_nan, reduce_sum, n_strata, has_coeff, has_group_coeffs, slot0, out0;
+  double coeff, delta;
+  double bound[NQA_METRICS_MAX_STRATA], stratum_delta[NQA_METRICS_MAX_STRATA];
+  double group_coeff[NQA_METRICS_MAX_TYPES];
+} nqa_metric_term;
+
+int32_t nqa_metrics_groups(void);
+int64_t nqa_metrics_workspace_bytes(int32_t n_slots);
+int nqa_metrics_fwd(const nqa_metric_stream* streams, int32_t n_streams, const nqa_metric_term* terms,
+                    const nqa_metric_term* terms_device, int32_t n_terms, int32_t n_values, int32_t weighted_sum_index,
+                    void* workspace, int64_t workspace_bytes, void* state, void* saved, double* values, nqa_stream stream);
+int nqa_metrics_bwd(const nqa_metric_stream* streams, int32_t n_streams, const nqa_metric_term* terms,
+                    const nqa_metric_term* terms_device, int32_t n_terms, int32_t n_values, int32_t weighted_sum_index,
+                    const void* saved, const double* grad_values, nqa_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,32 @@ class NodePart(ctypes.Structure):
                 ("scale", c_double), ("in_gate", c_void_p), ("n_in_gate", c_int32), ("pad", c_int32)]
 
 
+NQA_METRICS_MAX_STREAMS = 8
+NQA_METRICS_MAX_TERMS = 32
+NQA_METRICS_MAX_TYPES = 16
+NQA_METRICS_MAX_STRATA = 8
+NQA_METRICS_GROUPS = 64  # workgroups (= rows of partials) of the first forward launch; nqa_metrics_groups()
+NQA_METRIC_MSE, NQA_METRIC_MAE, NQA_METRIC_RMSE, NQA_METRIC_MAXABS, NQA_METRIC_HUBER, NQA_METRIC_STRATIFIED_HUBER = range(6)
+
+
+class MetricStream(ctypes.Structure):
+    """``nqa_metric_stream`` (include/nequip_amd.h): one distinct (prediction, target) pair of ``nqa_metrics_*``."""
+
+    _fields_ = [("pred", c_void_p), ("target", c_void_p), ("row_scale", c_void_p), ("group", c_void_p),
+                ("grad_pred", c_void_p), ("rows", c_int64), ("cols", c_int32), ("pred_dtype", c_int32),
+                ("target_dtype", c_int32), ("pad", c_int32)]
+
+
+class MetricTerm(ctypes.Structure):
+    """``nqa_metric_term`` (include/nequip_amd.h): one metric attached to a stream."""
+
+    _fields_ = [("stream", c_int32), ("kind", c_int32), ("n_groups", c_int32), ("ignore_nan", c_int32),
+                ("reduce_sum", c_int32), ("n_strata", c_int32), ("has_coeff", c_int32), ("has_group_coeffs", c_int32),
+                ("slot0", c_int32), ("out0", c_int32), ("coeff", c_double), ("delta", c_double),
+                ("bound", c_double * NQA_METRICS_MAX_STRATA), ("stratum_delta", c_double * NQA_METRICS_MAX_STRATA),
+                ("group_coeff", c_double * NQA_METRICS_MAX_TYPES)]
+
+
 # name -> (restype, argtypes); must list every symbol include/nequip_amd.h declares
 SIGNATURES = {
     "nqa_abi_version": (c_int32, []),
@@ -313,6 +339,15 @@ SIGNATURES = {
         [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_int32, c_int64, c_int32,
          c_void_p, c_void_p],
     ),
+    "nqa_metrics_groups": (c_int32, []),
+    "nqa_metrics_workspace_bytes": (c_int64, [c_int32]),
+    "nqa_metrics_fwd": (
+        c_int32,
+        [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+         c_void_p],
+    ),
+    "nqa_metrics_bwd": (
+        c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
 }
 
 # nqa_tp_scatter_<family>_paired: the family's arguments with (weight_rows, num_pairs) before the stream

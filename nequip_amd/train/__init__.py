@@ -1,1 +1,18 @@
 from .simple_ddp import SimpleDDPStrategy, all_reduce_gradients, broadcast_parameters  # noqa: F401
+from .metrics import (  # noqa: F401
+    HuberLoss,
+    MaximumAbsoluteError,
+    MeanAbsoluteError,
+    MeanSquaredError,
+    RootMeanSquaredError,
+    StratifiedHuberForceLoss,
+)
+from .metrics_manager import (  # noqa: F401
+    EnergyForceLoss,
+    EnergyForceMetrics,
+    EnergyForceStressLoss,
+    EnergyForceStressMetrics,
+    EnergyOnlyLoss,
+    EnergyOnlyMetrics,
+    MetricsManager,
+)
