@@ -870,6 +870,42 @@ int nqa_metrics_bwd(const nqa_metric_stream* streams, int32_t n_streams, const n
                     const nqa_metric_term* terms_device, int32_t n_terms, int32_t n_values, int32_t weighted_sum_index,
                     const void* saved, const double* grad_values, nqa_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exponential moving average of the model weights (nequip/train/ema.py::EMAWeights) as multi-tensor launches over
+ *   device-resident tables: `tensors` [n] (one entry per EMA buffer / parameter pair, float32 or float64, dense) and `chunks`
+ *   [chunk_capacity] (the tensor a chunk belongs to and the element offset at which it starts; a chunk is NQA_EMA_CHUNK
+ *   elements, nqa_ema_chunk_elems, the last one of a tensor shorter; a tensor without elements has an entry and no chunk).
+ *   One workgroup takes one chunk.  The grid is chunk_capacity; *n_chunks (device memory) says how many entries of the map
+ *   are in use, so the tables can be rewritten in place under a captured launch.  Pointers need only be element-aligned
+ *   (16-byte accesses where both pointers of a chunk allow them).
+ * nqa_ema_update: with n = *counter (device memory, int64): n == 0 copies param into ema (ema may hold anything); otherwise
+ *   w = 1 - min(decay, (1 + n) / (10 + n)) in double, rounded to float for float32 tensors, and
+ *   ema = w < 0.5 ? ema + w (param - ema) : param - (param - ema) (1 - w)  (ATen's lerp).  Then *counter += 1, by a second
+ *   one-thread launch on the same stream (no workgroup of the first sees the advanced value).  chunk_capacity == 0: only
+ *   the counter moves.
+ * nqa_ema_swap: exchanges ema and param element by element in registers: bit-exact, no temporary, one launch.
+ *   No allocation, no host synchronisation: both capture into a hipGraph, and each replay of an update advances the warm-up.
+ * ------------------------------------------------------------------------------------------- */
+#define NQA_EMA_CHUNK 1024
+
+typedef struct nqa_ema_tensor {
+  void* ema;
+  void* param;
+  int64_t numel;
+  int32_t dtype, pad; /* nqa_dtype */
+} nqa_ema_tensor;
+
+typedef struct nqa_ema_chunk {
+  int64_t offset; /* first element of the chunk within its tensor */
+  int32_t tensor, pad;
+} nqa_ema_chunk;
+
+int32_t nqa_ema_chunk_elems(void);
+int nqa_ema_update(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+                   double decay, int64_t* counter, nqa_stream stream);
+int nqa_ema_swap(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+                 nqa_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -348,6 +348,9 @@ SIGNATURES = {
     ),
     "nqa_metrics_bwd": (
         c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "nqa_ema_chunk_elems": (c_int32, []),
+    "nqa_ema_update": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_double, c_void_p, c_void_p]),
+    "nqa_ema_swap": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 # nqa_tp_scatter_<family>_paired: the family's arguments with (weight_rows, num_pairs) before the stream
