@@ -906,6 +906,64 @@ int nqa_ema_update(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, i
 int nqa_ema_swap(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                  nqa_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dataset statistics on one fused reduction: what nequip.data.DataStatisticsManager.forward accumulates entry by entry
+ *   (nequip/data/stats_manager.py:121-165 on the metric classes of nequip/data/stats.py; nequip/data/modifier.py::NumNeighbors),
+ *   without boolean indexing, masked_select, unique or a host read.
+ *   A STREAM is one distinct field tensor: [rows, cols] row-major, float32, float64, int32 or int64, promoted to float64;
+ *   optional row_scale [rows] float64 (PerAtomModifier: factor / num_atoms).  Its group index, formed in the kernel:
+ *   NQA_STATS_GROUP_NODE  atom_types[row];  NQA_STATS_GROUP_EDGE  atom_types[edge_index[0, row]] * T + atom_types[edge_index[1,
+ *   row]] with edge_index [2, rows] int64, T = num_types; a type or an atom index out of range belongs to no group (the element
+ *   still enters the terms with one slot).
+ *   A TERM is one entry on a stream; it owns 1 slot, or T (node stream) / T * T (edge stream) slots: slot g collects the
+ *   elements of group g.  ignore_nan: a NaN element contributes to nothing of that term; otherwise NaN propagates (through min
+ *   and max as well).  The table is ordered by stream, slot0 contiguous in term order; both tables are HOST pointers, passed to
+ *   the kernels by value.
+ *   Running state [6, slots], 8 bytes each: count (int64), mean, mean_lo, M2 = sum (y - mean)^2, min, max (float64) of y = m(x)
+ *   with m the term's modifier; the caller initialises 0, 0, 0, 0, +inf, -inf.  The mean is mean + mean_lo: mean the rounded
+ *   value, mean_lo what the rounding lost, so that the difference of two means in Chan's merge keeps its digits when the data
+ *   are large against their spread.  Every metric kind follows from the state: mean, sqrt(mean of squares), M2 / (count - 1),
+ *   min, max, count.
+ * nqa_stats_update: two launches for any number of terms and types.  NQA_STATS_GROUPS workgroups (nqa_stats_groups) walk every
+ *   stream once and leave one row of per-slot partial states each in `workspace` (nqa_stats_workspace_bytes(total slots), 8-byte
+ *   aligned): Welford updates in element order, Chan merges in a fixed order.  One wavefront per slot then merges the rows in a
+ *   fixed order and the batch into the running state; a slot that received no element stays bit for bit.  No floating-point
+ *   atomics: bit-reproducible.  No sum of squares is differenced.  All rows == 0: nothing is launched.
+ * nqa_stats_neighbor_counts: counts [num_atoms] int32 = number of edges with edge_center[e] == atom (zeroed here, then integer
+ *   atomics: exact, any edge order); an index outside [0, num_atoms) is skipped.  num_atoms == 0: nothing is launched.
+ *   No allocation, no host synchronisation: both capture into a hipGraph.
+ * ------------------------------------------------------------------------------------------- */
+#define NQA_STATS_MAX_STREAMS 8
+#define NQA_STATS_MAX_TERMS 32
+#define NQA_STATS_MAX_NODE_TYPES 128
+#define NQA_STATS_MAX_EDGE_TYPES 16
+#define NQA_STATS_MAX_SLOTS 1024
+#define NQA_STATS_GROUPS 256
+
+enum nqa_stats_dtype { NQA_STATS_F32 = 0, NQA_STATS_F64 = 1, NQA_STATS_I32 = 2, NQA_STATS_I64 = 3 }; /* 0, 1: nqa_dtype */
+enum nqa_stats_mod { NQA_STATS_MOD_IDENTITY = 0, NQA_STATS_MOD_ABS = 1, NQA_STATS_MOD_SQUARE = 2 };
+enum nqa_stats_group { NQA_STATS_GROUP_NONE = 0, NQA_STATS_GROUP_NODE = 1, NQA_STATS_GROUP_EDGE = 2 };
+
+typedef struct nqa_stats_stream {
+  const void* data;          /* [rows, cols] */
+  const double* row_scale;   /* optional [rows] */
+  const int64_t* atom_types; /* grouped streams: [rows] (node) / [num_atoms] (edge) */
+  const int64_t* edge_index; /* edge streams: [2, rows] */
+  int64_t rows, num_atoms;
+  int32_t cols, dtype, group_kind, num_types;
+} nqa_stats_stream;
+
+typedef struct nqa_stats_term {
+  int32_t stream, mod, n_groups, ignore_nan, slot0, pad[3];
+} nqa_stats_term;
+
+int32_t nqa_stats_groups(void);
+int64_t nqa_stats_workspace_bytes(int32_t n_slots);
+int nqa_stats_update(const nqa_stats_stream* streams, int32_t n_streams, const nqa_stats_term* terms, int32_t n_terms,
+                     void* workspace, int64_t workspace_bytes, void* state, nqa_stream stream);
+int nqa_stats_neighbor_counts(const int64_t* edge_center, int64_t num_edges, int64_t num_atoms, int32_t* counts,
+                              nqa_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

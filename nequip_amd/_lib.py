@@ -80,6 +80,32 @@ class MetricTerm(ctypes.Structure):
                 ("group_coeff", c_double * NQA_METRICS_MAX_TYPES)]
 
 
+NQA_STATS_MAX_STREAMS = 8
+NQA_STATS_MAX_TERMS = 32
+NQA_STATS_MAX_NODE_TYPES = 128
+NQA_STATS_MAX_EDGE_TYPES = 16
+NQA_STATS_MAX_SLOTS = 1024  # all slots of one manager
+NQA_STATS_GROUPS = 256  # workgroups (= rows of partial states) of the first launch; nqa_stats_groups()
+NQA_STATS_F32, NQA_STATS_F64, NQA_STATS_I32, NQA_STATS_I64 = range(4)
+NQA_STATS_MOD_IDENTITY, NQA_STATS_MOD_ABS, NQA_STATS_MOD_SQUARE = range(3)
+NQA_STATS_GROUP_NONE, NQA_STATS_GROUP_NODE, NQA_STATS_GROUP_EDGE = range(3)
+
+
+class StatsStream(ctypes.Structure):
+    """``nqa_stats_stream`` (include/nequip_amd.h): one distinct field tensor of ``nqa_stats_update``."""
+
+    _fields_ = [("data", c_void_p), ("row_scale", c_void_p), ("atom_types", c_void_p), ("edge_index", c_void_p),
+                ("rows", c_int64), ("num_atoms", c_int64), ("cols", c_int32), ("dtype", c_int32), ("group_kind", c_int32),
+                ("num_types", c_int32)]
+
+
+class StatsTerm(ctypes.Structure):
+    """``nqa_stats_term`` (include/nequip_amd.h): one statistics entry attached to a stream."""
+
+    _fields_ = [("stream", c_int32), ("mod", c_int32), ("n_groups", c_int32), ("ignore_nan", c_int32), ("slot0", c_int32),
+                ("pad", c_int32 * 3)]
+
+
 # name -> (restype, argtypes); must list every symbol include/nequip_amd.h declares
 SIGNATURES = {
     "nqa_abi_version": (c_int32, []),
@@ -351,6 +377,10 @@ SIGNATURES = {
     "nqa_ema_chunk_elems": (c_int32, []),
     "nqa_ema_update": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_double, c_void_p, c_void_p]),
     "nqa_ema_swap": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "nqa_stats_groups": (c_int32, []),
+    "nqa_stats_workspace_bytes": (c_int64, [c_int32]),
+    "nqa_stats_update": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "nqa_stats_neighbor_counts": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
 }
 
 # nqa_tp_scatter_<family>_paired: the family's arguments with (weight_rows, num_pairs) before the stream

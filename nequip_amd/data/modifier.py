@@ -5,6 +5,11 @@ names (``str(modifier)``) and says whether its field is per-frame, per-atom or p
 ``MetricsManager`` recognises the three classes below and hands their tensors to the fused reduction directly --
 ``PerAtomModifier`` as the raw field plus a per-row scale ``factor / num_atoms``, so the normalised copies are never
 materialised.  A subclass that overrides ``_func`` or ``__call__`` is called as it is.
+
+``NumNeighbors`` and ``EdgeLengths`` are for ``DataStatisticsManager`` (one dict).  ``NumNeighbors`` differs from the reference
+on purpose: there the counts come compacted out of ``torch.unique`` and zeros are padded at the END, so an isolated atom in the
+middle of the index range shifts every later count to the wrong atom (and the wrong type); here atom ``i`` gets its own count.
+The mean over all atoms is the same either way.
 """
 
 from typing import Optional
@@ -85,3 +90,53 @@ class MappedFieldModifier(BaseModifier):
     @property
     def type(self) -> str:
         return self._type
+
+
+class EdgeLengths(BaseModifier):
+    """``[E, 1]`` edge lengths, from positions, cell and shifts through ``with_edge_vectors_`` (which also leaves the vectors
+    and lengths in ``data``)."""
+
+    def __init__(self) -> None:
+        super().__init__(AtomicDataDict.EDGE_INDEX_KEY)
+
+    def _func(self, data: AtomicDataDict.Type) -> torch.Tensor:
+        from ..nn.utils import with_edge_vectors_
+
+        return with_edge_vectors_(data, with_lengths=True)[AtomicDataDict.EDGE_LENGTH_KEY]
+
+    def __str__(self) -> str:
+        return "edge_lengths"
+
+    @property
+    def type(self) -> str:
+        return "edge"
+
+
+class NumNeighbors(BaseModifier):
+    """``[N]`` number of edges that each atom is the centre of, for an edge list in any order; an atom without edges has 0 at
+    its own index.  GPU tensors: ``nqa_stats_neighbor_counts`` (int32; the statistics manager makes the same call into a
+    workspace of its own); CPU tensors: ATen (int64)."""
+
+    def __init__(self) -> None:
+        super().__init__(AtomicDataDict.EDGE_INDEX_KEY)
+
+    def _func(self, data: AtomicDataDict.Type) -> torch.Tensor:
+        center = data[AtomicDataDict.EDGE_INDEX_KEY][0].to(torch.int64).contiguous()
+        n = data[AtomicDataDict.POSITIONS_KEY].shape[0]
+        if not center.is_cuda:
+            return torch.zeros(n, dtype=torch.int64).index_add_(0, center, torch.ones_like(center))
+        from .. import _lib
+
+        counts = torch.empty(n, dtype=torch.int32, device=center.device)
+        with torch.cuda.device(center.device):
+            rc = _lib.load().nqa_stats_neighbor_counts(_lib.ptr(center), center.numel(), n, _lib.ptr(counts),
+                                                       _lib.stream_ptr(center.device))
+        _lib.check(rc, "nqa_stats_neighbor_counts")
+        return counts
+
+    def __str__(self) -> str:
+        return "num_neighbors"
+
+    @property
+    def type(self) -> str:
+        return "node"
