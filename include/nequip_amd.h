@@ -907,6 +907,48 @@ int nqa_ema_swap(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int
                  nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Conflict-free inverse gradients, ConFIG (nequip/train/config.py::ConFIGLightningModule._ConFIG_backwards) as multi-tensor
+ *   launches over the device tables of the weight averaging above: in an nqa_ema_tensor `ema` is the .grad of a parameter
+ *   (float32 or float64, dense), `param` its slice of ROW 0 of the buffer of collected gradients [n_terms, row_stride]
+ *   (`buf_dtype`: float64 if any .grad is, else float32; row_stride a multiple of 4 elements, the elements past the last slice
+ *   zero).  One workgroup per chunk, the grid is chunk_capacity, *n_chunks (device) the entries in use.
+ *   The tables live in device memory and are not validated by these calls: an entry with a float64 .grad under a float32
+ *   buffer is outside the contract (the buffer dtype rule above excludes it) and such a chunk is skipped, neither read nor written.
+ * nqa_config_collect: row `row` of the buffer = .grad (widened exactly), then .grad = 0, in one pass.  row < 0: only the zeros.
+ * nqa_config_gram: two launches.  (1) One workgroup per NQA_CONFIG_GRAM_CHUNK elements of the rows (grid gram_capacity, the row
+ *   length *numel read from device memory) forms the n_terms (n_terms + 1) / 2 products g_k . g_l in double and writes them to
+ *   partials[chunk][pair] (gram_capacity * 36 doubles at most).  (2) One workgroup adds the partials in a fixed order and solves
+ *       n_k = max(sqrt(G_kk), eps), Gh_kl = G_kl / (n_k n_l), bh = b / max(|b|, eps), c = pinv(Gh) bh (cyclic Jacobi, eigenvalues
+ *       <= 1e-12 lambda_max dropped), xi = sqrt(max(c' Gh c, 0)), d = max(xi, eps), s = (sum_kl G_kl c_l / n_l) / d,
+ *       w_l = s c_l / (n_l d), |new_grad| = |s| xi / d
+ *   and writes out[NQA_CONFIG_OUT] = [w_0 .. w_7 (0 past n_terms), |new_grad|, factor]; with NQA_CONFIG_CLIP_NORM factor =
+ *   min(1, clip / (|new_grad| + 1e-6)) and w is multiplied by it, otherwise factor = 1.  `b`: n_terms doubles on the device.
+ *   No floating-point atomics: the same rows give the same bits.
+ * nqa_config_apply: .grad[i] = (dtype of the .grad) clamp(sum_l weights[l] row_l[i]), the sum in double; the clamp to +-clip
+ *   only with NQA_CONFIG_CLIP_VALUE (NaN passes).  `weights`: n_terms doubles on the device (the head of `out`).
+ *   No allocation, no host synchronisation: all capture into a hipGraph.
+ * nqa_config_solve_host: the solve of launch (2) on the host, all pointers host memory, `gram` the upper triangle row by row
+ *   (for tests without a GPU; it runs the very function the kernel runs).
+ * ------------------------------------------------------------------------------------------- */
+#define NQA_CONFIG_GRAM_CHUNK 2048
+#define NQA_CONFIG_MAX_TERMS 8
+#define NQA_CONFIG_OUT 10
+
+enum nqa_config_clip { NQA_CONFIG_CLIP_NONE = 0, NQA_CONFIG_CLIP_NORM = 1, NQA_CONFIG_CLIP_VALUE = 2 };
+
+int32_t nqa_config_gram_chunk_elems(void);
+int nqa_config_collect(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+                       int32_t row, int64_t row_stride, int32_t buf_dtype, nqa_stream stream);
+int nqa_config_gram(const void* buf, int32_t buf_dtype, int32_t n_terms, int64_t row_stride, const int64_t* numel,
+                    int64_t gram_capacity, double* partials, const double* b, double norm_eps, int32_t clip_mode, double clip,
+                    double* out, nqa_stream stream);
+int nqa_config_apply(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+                     int32_t n_terms, int64_t row_stride, int32_t buf_dtype, const double* weights, int32_t clip_mode, double clip,
+                     nqa_stream stream);
+int nqa_config_solve_host(const double* gram, int32_t n_terms, const double* b, double norm_eps, int32_t clip_mode, double clip,
+                          double* out);
+
+/* ---------------------------------------------------------------------------------------------
  * Dataset statistics on one fused reduction: what nequip.data.DataStatisticsManager.forward accumulates entry by entry
  *   (nequip/data/stats_manager.py:121-165 on the metric classes of nequip/data/stats.py; nequip/data/modifier.py::NumNeighbors),
  *   without boolean indexing, masked_select, unique or a host read.

@@ -377,6 +377,14 @@ SIGNATURES = {
     "nqa_ema_chunk_elems": (c_int32, []),
     "nqa_ema_update": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_double, c_void_p, c_void_p]),
     "nqa_ema_swap": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "nqa_config_gram_chunk_elems": (c_int32, []),
+    "nqa_config_collect": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int64, c_int32, c_void_p]),
+    "nqa_config_gram": (
+        c_int32, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_double, c_int32, c_double,
+                  c_void_p, c_void_p]),
+    "nqa_config_apply": (
+        c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int32, c_double, c_void_p]),
+    "nqa_config_solve_host": (c_int32, [c_void_p, c_int32, c_void_p, c_double, c_int32, c_double, c_void_p]),
     "nqa_stats_groups": (c_int32, []),
     "nqa_stats_workspace_bytes": (c_int64, [c_int32]),
     "nqa_stats_update": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),

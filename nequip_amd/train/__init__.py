@@ -1,5 +1,6 @@
 from .simple_ddp import SimpleDDPStrategy, all_reduce_gradients, broadcast_parameters  # noqa: F401
 from .ema import EMAWeights  # noqa: F401
+from .config import ConFIGGradients  # noqa: F401
 from .metrics import (  # noqa: F401
     HuberLoss,
     MaximumAbsoluteError,
