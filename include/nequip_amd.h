@@ -1006,6 +1006,45 @@ int nqa_stats_update(const nqa_stats_stream* streams, int32_t n_streams, const n
 int nqa_stats_neighbor_counts(const int64_t* edge_center, int64_t num_edges, int64_t num_atoms, int32_t* counts,
                               nqa_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-tensor statistics of weights, gradients and Adam moments (nequip/train/callbacks/training_stats.py::
+ *   TrainingStatsMonitor) as one multi-tensor reduction over device-resident tables: `tensors` [tensor_capacity] (float32 or
+ *   float64, dense; transform f = identity or sqrt, applied element by element after the promotion to double; chunk0 the index
+ *   of the tensor's first chunk in the map, its chunks are contiguous and ascending) and `chunks` [chunk_capacity] (an
+ *   nqa_ema_chunk: the tensor a chunk belongs to and the element offset at which it starts; a chunk is NQA_TSTATS_CHUNK
+ *   elements, nqa_tstats_chunk_elems, the last one of a tensor shorter).  counts = [chunks in use, tensors in use] (device
+ *   memory, int64): the grids are the capacities and the workgroups past the counts return, so the tables can be rewritten in
+ *   place under a captured launch.  Pointers need only be element-aligned (16-byte accesses where a chunk's start allows them).
+ * nqa_tstats_reduce: two launches.  With n = *counter (device memory, int64), every workgroup returns without touching a
+ *   tensor, the workspace or the table unless n % log_freq == 0.  (1) One workgroup per chunk forms count, mean, M2, sum of
+ *   squares, min, max, absmin, absmax of f(x) in double (Welford per lane, Chan merges in a fixed lane and wavefront order)
+ *   and writes workspace[chunk] (chunk_capacity * 8 doubles).  (2) One wavefront per tensor merges its chunk rows in ascending
+ *   order and writes table[tensor] = [min, max, mean, std (unbiased, NaN for one element), absmin, absmax, rms, count]
+ *   (tensor_capacity * 8 doubles); *stamp = n.  One NaN makes all seven statistics NaN; with +-inf and no NaN, min, max,
+ *   absmin, absmax and rms are exact and mean and std non-finite (Welford forms inf - inf).  No floating-point atomics: the same
+ *   inputs give the same bits.  A capacity of 0: nothing is launched.
+ * nqa_tstats_advance: *counter += 1 by a one-thread launch (a launch of its own, after every reduce launch of the step on the
+ *   same stream: no workgroup of a reduce sees the advanced value).
+ *   No allocation, no host synchronisation: both capture into a hipGraph; every replay advances the count and every
+ *   log_freq-th replay rewrites the table.
+ * ------------------------------------------------------------------------------------------- */
+#define NQA_TSTATS_CHUNK 4096
+
+enum nqa_tstats_transform { NQA_TSTATS_IDENTITY = 0, NQA_TSTATS_SQRT = 1 };
+
+typedef struct nqa_tstats_tensor {
+  const void* data;
+  int64_t numel;
+  int32_t dtype, transform; /* nqa_dtype, nqa_tstats_transform */
+  int32_t chunk0, pad;
+} nqa_tstats_tensor;
+
+int32_t nqa_tstats_chunk_elems(void);
+int nqa_tstats_reduce(const nqa_tstats_tensor* tensors, int64_t tensor_capacity, const nqa_ema_chunk* chunks,
+                      int64_t chunk_capacity, const int64_t* counts, const int64_t* counter, int64_t log_freq, double* workspace,
+                      double* table, int64_t* stamp, nqa_stream stream);
+int nqa_tstats_advance(int64_t* counter, nqa_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -389,6 +389,10 @@ SIGNATURES = {
     "nqa_stats_workspace_bytes": (c_int64, [c_int32]),
     "nqa_stats_update": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "nqa_stats_neighbor_counts": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "nqa_tstats_chunk_elems": (c_int32, []),
+    "nqa_tstats_reduce": (
+        c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nqa_tstats_advance": (c_int32, [c_void_p, c_void_p]),
 }
 
 # nqa_tp_scatter_<family>_paired: the family's arguments with (weight_rows, num_pairs) before the stream
