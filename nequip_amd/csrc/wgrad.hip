@@ -454,8 +454,19 @@ int nqa_wgrad(int32_t dtype, const void* a_rows, const void* b_rows, const int64
     set_error("nqa_wgrad: float32 only");
     return NQA_ERR_UNSUPPORTED;
   }
-  if (!instr_table || n_instr <= 0 || n_instr > kMaxWgradInstr || n_types < 1 || (n_types > 1 && !row_types) ||
-      num_rows < 0 || splits < 1 || out_stride <= 0 || lda <= 0 || ldb <= 0 || lda > (1 << 24) || ldb > (1 << 24) || !partials || (num_rows > 0 && (!a_rows || !b_rows))) {
+  if (!instr_table || n_instr <= 0 || n_instr > kMaxWgradInstr) {
+    set_error("nqa_wgrad: instruction table missing or not 1..64 records");
+    return NQA_ERR_INVALID;
+  }
+  if (n_types < 1 || (n_types > 1 && !row_types)) {
+    set_error("nqa_wgrad: n_types < 1, or n_types > 1 without row_types");
+    return NQA_ERR_INVALID;
+  }
+  if (lda <= 0 || ldb <= 0 || lda > (1 << 24) || ldb > (1 << 24)) {
+    set_error("nqa_wgrad: lda / ldb outside 1..2^24 (32-bit byte offsets inside a pipeline step)");
+    return NQA_ERR_INVALID;
+  }
+  if (num_rows < 0 || splits < 1 || out_stride <= 0 || !partials || (num_rows > 0 && (!a_rows || !b_rows))) {
     set_error("nqa_wgrad: invalid argument");
     return NQA_ERR_INVALID;
   }
@@ -502,10 +513,14 @@ int nqa_wgrad(int32_t dtype, const void* a_rows, const void* b_rows, const int64
     q.N = tab[6 * i + 3];
     q.d = tab[6 * i + 4];
     q.out_off = tab[6 * i + 5];
-    if (q.M <= 0 || q.N <= 0 || q.d <= 0 || q.a_off < 0 || q.b_off < 0 || q.out_off < 0 ||
-        (int64_t)q.out_off + (int64_t)q.M * q.N > out_stride || (int64_t)q.a_off + (int64_t)q.M * q.d > lda ||
-        (int64_t)q.b_off + (int64_t)q.N * q.d > ldb) {
-      set_error("nqa_wgrad: instruction outside its operand rows / the weight vector");
+    const char* why = nullptr;
+    if (q.M <= 0 || q.N <= 0 || q.d <= 0) why = "M, N or d < 1";
+    else if (q.a_off < 0 || q.b_off < 0 || q.out_off < 0) why = "negative offset";
+    else if ((int64_t)q.a_off + (int64_t)q.M * q.d > lda) why = "runs past lda";
+    else if ((int64_t)q.b_off + (int64_t)q.N * q.d > ldb) why = "runs past ldb";
+    else if ((int64_t)q.out_off + (int64_t)q.M * q.N > out_stride) why = "runs past out_stride";
+    if (why) {
+      set_error("nqa_wgrad: instruction " + std::to_string(i) + " " + why);
       return NQA_ERR_INVALID;
     }
     q.mt = (q.M + 32 * RB - 1) / (32 * RB);

@@ -295,14 +295,23 @@ class _WeightCacheMixin:
 
 
 class WgradTable:
-    """Records ``(a_off, b_off, M, N, d, out_off)`` of one launch, kept as a host buffer (kernel arguments)."""
+    """Records ``(a_off, b_off, M, N, d, out_off)`` of one launch, kept as a host buffer (kernel arguments).
+
+    ``covered``: the records' output ranges ``[out_off, out_off + M*N)`` tile ``[0, out_stride)`` exactly -- no gap, no
+    overlap -- so the launch writes every element and the partial tiles need no zero fill."""
 
     def __init__(self, records: Sequence[Tuple[int, int, int, int, int, int]], out_stride: int):
         self.records = [tuple(int(v) for v in r) for r in records]
         self.out_stride = int(out_stride)
         raw = b"".join(struct.pack("<6i", *r) for r in self.records)
         self.buf = ctypes.create_string_buffer(raw, max(len(raw), 1))
-        self.covered = sum(r[2] * r[3] for r in self.records) == self.out_stride
+        end = 0
+        for off, size in sorted((r[5], r[2] * r[3]) for r in self.records):
+            if off != end or size <= 0:
+                end = -1
+                break
+            end = off + size
+        self.covered = end == self.out_stride
         self.flops_per_row = 2.0 * sum(r[2] * r[3] * r[4] for r in self.records)
 
     def __len__(self):
@@ -316,12 +325,24 @@ def supported(a: torch.Tensor, b: torch.Tensor) -> bool:
 def wgrad(a: torch.Tensor, b: torch.Tensor, table: WgradTable, types: Optional[torch.Tensor] = None,
           n_types: int = 1) -> torch.Tensor:
     """``out[t, out_off + i*N + j] = sum_{z: type z = t} sum_m a[z, a_off + i*d + m] b[z, b_off + j*d + m]`` ->
-    ``[n_types, out_stride]`` (float32, CUDA)."""
+    ``[n_types, out_stride]`` (float32, CUDA).
+
+    ``types`` (read when ``n_types > 1``): one integer per row.  The kernel reads contiguous int64 on the operands'
+    device, so any other integer dtype, a strided view or a tensor elsewhere is converted here (a copy); a tensor that is
+    not one-dimensional with ``a.shape[0]`` elements, or not of an integer dtype, raises ``ValueError``."""
     if not supported(a, b):
         raise RuntimeError("nqa_wgrad needs float32 CUDA operands (there is no CPU path)")
     assert a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0]
     a, b = a.contiguous(), b.contiguous()
     Z = a.shape[0]
+    if n_types > 1:
+        if types is None:
+            raise ValueError("nqa_wgrad: n_types > 1 needs the rows' types")
+        if types.dim() != 1 or types.shape[0] != Z:
+            raise ValueError(f"nqa_wgrad: types must have shape ({Z},), got {tuple(types.shape)}")
+        if types.dtype.is_floating_point or types.dtype.is_complex or types.dtype == torch.bool:
+            raise ValueError(f"nqa_wgrad: types must be integers, got {types.dtype}")
+        types = types.to(device=a.device, dtype=torch.int64).contiguous()
     lib = _lib.load()
     tab = ctypes.cast(table.buf, ctypes.c_void_p)
     S = lib.nqa_wgrad_splits(tab, len(table), n_types, Z)
