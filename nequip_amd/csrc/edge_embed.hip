@@ -72,6 +72,7 @@ namespace nqa {
 
 constexpr int kMaxBessel = 32;
 constexpr double kPi = 3.14159265358979323846;
+constexpr double kBesselSeriesBelow = 0.0078125;  // 2^-7, see BesselBasis
 
 struct EdgeEmbedParams {
   const double* __restrict__ vec;
@@ -161,13 +162,16 @@ __device__ __forceinline__ Geom<S> geom(const S& vx, const S& vy, const S& vz) {
 //   b_n'(x) = (w_n cos(pi x w_n) - b_n(x)) / x                                           b_n'(0) = 0
 // and, when the weights are the untrained Bessel roots w_n = n + 1 (checked on the device, wave-uniform), sin/cos of
 // (n + 1) pi x follow from ONE sin/cos pair by angle addition (error grows ~ n ulp in f64; the outputs are cast to T).
+// Below a = pi x w_n = 2^-7 the closed forms cancel (b_n' adds two terms of size w_n / x, its derivative two of size
+// w_n / x^2: rounding noise of 1e12 on an edge of 1e-14) and the series take over, exact to 1 ulp there and at x = 0:
+//   b_n(x)  = w_n (1 - a^2/6 + a^4/120 - a^6/5040),   b_n'(x) = -pi w_n^2 a (1/3 - a^2/30 + a^4/840 - a^6/45360)
 template <typename S>
 struct BesselBasis {
-  S inv_x, inv_pix, s1, c1, s, c;
-  bool zero, harmonic;
+  S x0, inv_x, inv_pix, s1, c1, s, c;
+  bool harmonic;
   __device__ __forceinline__ BesselBasis(const EdgeEmbedParams& prm, const S& x) {
-    zero = val(x) == 0.0;
-    inv_x = zero ? S(0.0) : 1.0 / x;
+    x0 = x;
+    inv_x = val(x) == 0.0 ? S(0.0) : 1.0 / x;  // (x = 0 is served by the series)
     inv_pix = inv_x * (1.0 / kPi);
     harmonic = true;
     for (int n = 0; n < prm.nb; ++n) harmonic = harmonic && (prm.bw[n] == (double)(n + 1));
@@ -190,8 +194,23 @@ struct BesselBasis {
       c = dcos(a);
     }
   }
-  __device__ __forceinline__ S value(double w) const { return zero ? S(w) : s * inv_pix; }
-  __device__ __forceinline__ S grad(double w) const { return zero ? S(0.0) : (w * c - s * inv_pix) * inv_x; }
+  __device__ __forceinline__ bool series(double w) const { return fabs(val(x0) * w) < kBesselSeriesBelow / kPi; }
+  __device__ __forceinline__ S value(double w) const {
+    if (series(w)) {
+      const S a = (kPi * w) * x0;
+      const S a2 = a * a;
+      return w * (1.0 - a2 * (1.0 / 6.0 - a2 * (1.0 / 120.0 - a2 * (1.0 / 5040.0))));
+    }
+    return s * inv_pix;
+  }
+  __device__ __forceinline__ S grad(double w) const {
+    if (series(w)) {
+      const S a = (kPi * w) * x0;
+      const S a2 = a * a;
+      return (-kPi * w * w) * (a * (1.0 / 3.0 - a2 * (1.0 / 30.0 - a2 * (1.0 / 840.0 - a2 * (1.0 / 45360.0)))));
+    }
+    return (w * c - s * inv_pix) * inv_x;
+  }
 };
 
 // VJP of (sh, emb) w.r.t. the edge vector for cotangents (g_sh, g_emb); returns the three components in S.
@@ -238,10 +257,17 @@ __device__ __forceinline__ void embed_vjp(const EdgeEmbedParams& prm, int64_t e,
       const double gn = (gi != nullptr ? (double)gi[n] : 0.0) + (gp != nullptr ? (double)gp[n] : 0.0);
       acc += gn * (bb.grad(w) * c + bb.value(w) * dc);
     }
-    const S gr = acc * (prm.factor * rr);  // dE/dr ; d|v|/dv = u
-    gx += gr * gm.ux;
-    gy += gr * gm.uy;
-    gz += gr * gm.uz;
+    const S gr = acc * (prm.factor * rr);  // dE/dr ; d|v|/dv = v / |v|: u, except on the clamped branch (u = 1e12 v there)
+    S tx = gm.ux, ty = gm.uy, tz = gm.uz;
+    if (gm.clamped) {
+      const S ri = val(gm.r) > 0.0 ? 1.0 / gm.r : S(0.0);
+      tx = vx * ri;
+      ty = vy * ri;
+      tz = vz * ri;
+    }
+    gx += gr * tx;
+    gy += gr * ty;
+    gz += gr * tz;
   }
   out3[0] = gx;
   out3[1] = gy;
@@ -539,7 +565,7 @@ int nqa_edge_embed_bwd_bwd(int32_t dtype, int32_t lmax, const double* edge_vec, 
     set_error("nqa_edge_embed_bwd_bwd: unsupported dtype");
     return NQA_ERR_UNSUPPORTED;
   }
-  if (lmax < 0 || (num_edges > 0 && cot_g_edge_vec == nullptr) || (gg_sh != nullptr && g_sh == nullptr && false)) {
+  if (lmax < 0 || (num_edges > 0 && cot_g_edge_vec == nullptr)) {
     set_error("nqa_edge_embed_bwd_bwd: invalid argument");
     return NQA_ERR_INVALID;
   }

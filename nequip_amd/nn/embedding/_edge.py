@@ -41,13 +41,51 @@ def _dt(dtype):
     return _lib.NQA_F32 if dtype == torch.float32 else _lib.NQA_F64
 
 
+class EdgeEmbedOperandError(ValueError):
+    """An operand that the edge-embedding kernels read through a raw pointer is not what they expect."""
+
+
+_GPU_ONLY = "nequip_amd edge embedding runs on the GPU only (HIP kernel); no CPU fallback exists"
+
+
+def _check_operands(fn, vec, bessel_weights, cfg):
+    """The kernels take ``bessel_weights`` and ``cfg["rmax_edge"]`` by pointer: refuse, before any launch, what they would
+    misread."""
+    nb, E = int(cfg["nb"]), vec.shape[0]
+    bw = bessel_weights
+    if not (torch.is_tensor(bw) and bw.dtype == torch.float64 and bw.is_contiguous() and bw.device == vec.device
+            and bw.numel() >= nb):
+        what = f"{bw.dtype} {tuple(bw.shape)} on {bw.device}, contiguous = {bw.is_contiguous()}" if torch.is_tensor(bw) else repr(bw)
+        raise EdgeEmbedOperandError(f"{fn}: bessel_weights must be a contiguous float64 tensor on {vec.device} with at least "
+                                    f"nb = {nb} elements, got {what}")
+    re = cfg.get("rmax_edge")
+    if re is not None and not (torch.is_tensor(re) and re.dtype == torch.float64 and re.is_contiguous()
+                               and re.device == vec.device and tuple(re.shape) == (E,)):
+        what = f"{re.dtype} {tuple(re.shape)} on {re.device}, contiguous = {re.is_contiguous()}" if torch.is_tensor(re) else repr(re)
+        raise EdgeEmbedOperandError(f"{fn}: rmax_edge must be a contiguous float64 tensor of shape ({E},) on {vec.device}, "
+                                    f"got {what}")
+
+
+def _check_cotangent(fn, name, t, shape, dtype, device):
+    if t is not None and not (t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.device == device):
+        raise EdgeEmbedOperandError(f"{fn}: cotangent {name} must be {dtype} of shape {tuple(shape)} on {device}, got "
+                                    f"{t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _check_first_order_cotangents(fn, vec, g_sh, g_emb, cfg):
+    E = vec.shape[0]
+    _check_cotangent(fn, "g_sh", g_sh, (E, (max(cfg["lmax"], 0) + 1) ** 2), cfg["dtype"], vec.device)
+    _check_cotangent(fn, "g_emb", g_emb, (E, cfg["nb"]), cfg["dtype"], vec.device)
+
+
 class _EdgeEmbedFn(torch.autograd.Function):
     """edge_vec [E,3] f64 -> (sh [E,S] | None, emb [E,nb] | None) in model dtype."""
 
     @staticmethod
     def forward(ctx, edge_vec, bessel_weights, cfg):
+        _check_operands("edge_embed_fwd", edge_vec, bessel_weights, cfg)
         if not edge_vec.is_cuda:
-            raise RuntimeError("nequip_amd edge embedding runs on the GPU only (HIP kernel); no CPU fallback exists")
+            raise RuntimeError(_GPU_ONLY)
         assert edge_vec.dtype == torch.float64, "edge vectors must be float64 (nequip _GLOBAL_DTYPE)"
         lib = _lib.load()
         vec = edge_vec.contiguous()
@@ -84,6 +122,10 @@ class _EdgeEmbedBwdFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vec, bw, g_sh, g_emb, cfg):
+        _check_operands("edge_embed_bwd", vec, bw, cfg)
+        _check_first_order_cotangents("edge_embed_bwd", vec, g_sh, g_emb, cfg)
+        if not vec.is_cuda:
+            raise RuntimeError(_GPU_ONLY)
         lib = _lib.load()
         g_sh = g_sh.contiguous() if g_sh is not None else None
         g_emb = g_emb.contiguous() if g_emb is not None else None
@@ -112,6 +154,11 @@ class _EdgeEmbedBwdFn(torch.autograd.Function):
 
 def _edge_embed_second_order(vec, bw, g_sh, g_emb, c, cfg, need_vec: bool, need_gsh: bool, need_gemb: bool):
     """``nqa_edge_embed_bwd_bwd``: gradients of ``g_vec = J(v)^T g`` w.r.t. (v, g_sh, g_emb) for the cotangent ``c``."""
+    _check_operands("edge_embed_bwd_bwd", vec, bw, cfg)
+    _check_first_order_cotangents("edge_embed_bwd_bwd", vec, g_sh, g_emb, cfg)
+    _check_cotangent("edge_embed_bwd_bwd", "c", c, (vec.shape[0], 3), torch.float64, vec.device)
+    if not vec.is_cuda:
+        raise RuntimeError(_GPU_ONLY)
     lib = _lib.load()
     c = c.contiguous()
     g_sh = g_sh.contiguous() if g_sh is not None else None
@@ -171,8 +218,9 @@ class _EdgeEmbedPairedFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, edge_vec, bessel_weights, cfg, pairing):
+        _check_operands("edge_embed_fwd_paired", edge_vec, bessel_weights, cfg)
         if not edge_vec.is_cuda:
-            raise RuntimeError("nequip_amd edge embedding runs on the GPU only (HIP kernel); no CPU fallback exists")
+            raise RuntimeError(_GPU_ONLY)
         assert edge_vec.dtype == torch.float64, "edge vectors must be float64 (nequip _GLOBAL_DTYPE)"
         lib = _lib.load()
         vec = edge_vec.contiguous()
@@ -197,6 +245,8 @@ class _EdgeEmbedPairedFn(torch.autograd.Function):
     def backward(ctx, g_sh, g_emb, g_pairs):
         vec, bw = ctx.saved_tensors
         cfg, pairing = ctx.cfg, ctx.pairing
+        _check_first_order_cotangents("edge_embed_bwd_paired", vec, g_sh, g_emb, cfg)
+        _check_cotangent("edge_embed_bwd_paired", "g_pairs", g_pairs, (pairing.num_pairs, cfg["nb"]), cfg["dtype"], vec.device)
         lib = _lib.load()
         g_sh = g_sh.contiguous() if g_sh is not None else None
         g_emb = g_emb.contiguous() if g_emb is not None else None
