@@ -907,6 +907,47 @@ int nqa_ema_swap(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int
                  nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Schedule-free AdamW (the optimizer nequip/train/schedulefree.py::ScheduleFreeLightningModule is driven with) as multi-tensor
+ *   launches over device-resident tables: `tensors` [n] (parameter, .grad, z, exp_avg_sq: float32 or float64, dense, the four
+ *   of one dtype; `group` indexes `groups`), the chunk map of the weight averaging above (nqa_ema_chunk, NQA_EMA_CHUNK elements,
+ *   one workgroup per chunk, the grid is chunk_capacity, *n_chunks the entries in use) and `groups` [n_groups]: the
+ *   hyper-parameters AND the state of every parameter group, in device memory, so that a captured step advances.
+ * nqa_sfree_step: per group, from the OLD state, in double (each rounded once to float for float32 tensors):
+ *       sched = k < warmup_steps ? (k + 1) / warmup_steps : 1,  bc2 = 1 - beta2^(k+1),  lr_k = lr sched,
+ *       lr_max' = max(lr_k, lr_max),  weight = (k + 1)^r lr_max'^weight_lr_power,  weight_sum' = weight_sum + weight,
+ *       c = weight_sum' == 0 ? 0 : weight / weight_sum'
+ *   and per element of every tensor whose `grad` is not null (the others are skipped, their state untouched)
+ *       v = beta2 v + (1 - beta2) g g,  gn = g / (sqrt(v / bc2) + eps) + weight_decay y,
+ *       y = lerp(y, z, c) + lr_k (beta1 (1 - c) - 1) gn,  z = z - lr_k gn
+ *   with ATen's lerp (nqa_ema_update) and y the parameter; for k == 0, z is read as y (z may hold anything).  `grad` is only
+ *   read.  Then k += 1, weight_sum = weight_sum', lr_max = lr_max', scheduled_lr = lr_k, by a second launch with one thread per
+ *   group on the same stream (no workgroup of the first sees the advanced state).  chunk_capacity == 0: only the state moves.
+ * nqa_sfree_swap: param = lerp(param, z, w) for every tensor of the table, w = 1 - 1 / beta1 with `to_eval` (the parameter
+ *   then holds the averaged weights x), w = 1 - beta1 without (it holds y again).  beta1 == 0 has no way to x.
+ *   No allocation, no host synchronisation: both capture into a hipGraph.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct nqa_sfree_tensor {
+  void* param;
+  void* grad; /* null: skipped by nqa_sfree_step */
+  void* z;
+  void* exp_avg_sq;
+  int64_t numel;
+  int32_t dtype, group; /* nqa_dtype, index into the group records */
+} nqa_sfree_tensor;
+
+typedef struct nqa_sfree_group {
+  double lr, beta1, beta2, eps, weight_decay, r, weight_lr_power;
+  int64_t warmup_steps;
+  int64_t k; /* steps done */
+  double weight_sum, lr_max, scheduled_lr;
+} nqa_sfree_group;
+
+int nqa_sfree_step(const nqa_sfree_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+                   nqa_sfree_group* groups, int32_t n_groups, nqa_stream stream);
+int nqa_sfree_swap(const nqa_sfree_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+                   const nqa_sfree_group* groups, int32_t n_groups, int32_t to_eval, nqa_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Conflict-free inverse gradients, ConFIG (nequip/train/config.py::ConFIGLightningModule._ConFIG_backwards) as multi-tensor
  *   launches over the device tables of the weight averaging above: in an nqa_ema_tensor `ema` is the .grad of a parameter
  *   (float32 or float64, dense), `param` its slice of ROW 0 of the buffer of collected gradients [n_terms, row_stride]

@@ -2,6 +2,7 @@ from .simple_ddp import SimpleDDPStrategy, all_reduce_gradients, broadcast_param
 from .ema import EMAWeights  # noqa: F401
 from .config import ConFIGGradients  # noqa: F401
 from .training_stats import TrainingStatsMonitor  # noqa: F401
+from .schedulefree import AdamWScheduleFree, ScheduleFreeHooks  # noqa: F401
 from .metrics import (  # noqa: F401
     HuberLoss,
     MaximumAbsoluteError,
