@@ -871,13 +871,25 @@ int nqa_metrics_bwd(const nqa_metric_stream* streams, int32_t n_streams, const n
                     const void* saved, const double* grad_values, nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Exponential moving average of the model weights (nequip/train/ema.py::EMAWeights) as multi-tensor launches over
- *   device-resident tables: `tensors` [n] (one entry per EMA buffer / parameter pair, float32 or float64, dense) and `chunks`
- *   [chunk_capacity] (the tensor a chunk belongs to and the element offset at which it starts; a chunk is NQA_EMA_CHUNK
- *   elements, nqa_ema_chunk_elems, the last one of a tensor shorter; a tensor without elements has an entry and no chunk).
- *   One workgroup takes one chunk.  The grid is chunk_capacity; *n_chunks (device memory) says how many entries of the map
- *   are in use, so the tables can be rewritten in place under a captured launch.  Pointers need only be element-aligned
- *   (16-byte accesses where both pointers of a chunk allow them).
+ * The multi-tensor chunk layout of the four sections that follow (weight averaging, schedule-free AdamW, ConFIG, per-tensor
+ *   statistics): launches over device-resident tables.  `tensors` [n] is the tensor table, one record per tensor (or per set of
+ *   tensors of one shape that are walked together), float32 or float64, dense.  `chunks` [chunk_capacity] is the chunk map: the
+ *   tensor a chunk belongs to and the element offset at which it starts.  A chunk is NQA_EMA_CHUNK elements (nqa_ema_chunk_elems;
+ *   NQA_TSTATS_CHUNK, nqa_tstats_chunk_elems, for the statistics), the last one of a tensor shorter; a tensor without elements
+ *   has an entry and no chunk.  One workgroup takes one chunk.  The grid is chunk_capacity; *n_chunks (device memory, int64) says
+ *   how many entries of the map are in use and the workgroups past it return, so the tables can be rewritten in place under a
+ *   captured launch.  An entry that does not lie inside its tensor is skipped, nothing is read or written through it.  Pointers
+ *   need only be element-aligned: accesses are 16 bytes per lane where all pointers of a chunk are 16-byte aligned, element by
+ *   element otherwise.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct nqa_mt_chunk {
+  int64_t offset; /* first element of the chunk within its tensor */
+  int32_t tensor, pad;
+} nqa_mt_chunk;
+
+/* ---------------------------------------------------------------------------------------------
+ * Exponential moving average of the model weights (nequip/train/ema.py::EMAWeights) as multi-tensor launches over the chunk
+ *   layout above: one table entry per EMA buffer / parameter pair.
  * nqa_ema_update: with n = *counter (device memory, int64): n == 0 copies param into ema (ema may hold anything); otherwise
  *   w = 1 - min(decay, (1 + n) / (10 + n)) in double, rounded to float for float32 tensors, and
  *   ema = w < 0.5 ? ema + w (param - ema) : param - (param - ema) (1 - w)  (ATen's lerp).  Then *counter += 1, by a second
@@ -895,23 +907,17 @@ typedef struct nqa_ema_tensor {
   int32_t dtype, pad; /* nqa_dtype */
 } nqa_ema_tensor;
 
-typedef struct nqa_ema_chunk {
-  int64_t offset; /* first element of the chunk within its tensor */
-  int32_t tensor, pad;
-} nqa_ema_chunk;
-
 int32_t nqa_ema_chunk_elems(void);
-int nqa_ema_update(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+int nqa_ema_update(const nqa_ema_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                    double decay, int64_t* counter, nqa_stream stream);
-int nqa_ema_swap(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+int nqa_ema_swap(const nqa_ema_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                  nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Schedule-free AdamW (the optimizer nequip/train/schedulefree.py::ScheduleFreeLightningModule is driven with) as multi-tensor
- *   launches over device-resident tables: `tensors` [n] (parameter, .grad, z, exp_avg_sq: float32 or float64, dense, the four
- *   of one dtype; `group` indexes `groups`), the chunk map of the weight averaging above (nqa_ema_chunk, NQA_EMA_CHUNK elements,
- *   one workgroup per chunk, the grid is chunk_capacity, *n_chunks the entries in use) and `groups` [n_groups]: the
- *   hyper-parameters AND the state of every parameter group, in device memory, so that a captured step advances.
+ *   launches over the chunk layout above: a table entry is (parameter, .grad, z, exp_avg_sq), the four of one dtype, and `group`
+ *   indexes `groups` [n_groups]: the hyper-parameters AND the state of every parameter group, in device memory, so that a
+ *   captured step advances.  A chunk whose `group` is outside [0, n_groups) is skipped.
  * nqa_sfree_step: per group, from the OLD state, in double (each rounded once to float for float32 tensors):
  *       sched = k < warmup_steps ? (k + 1) / warmup_steps : 1,  bc2 = 1 - beta2^(k+1),  lr_k = lr sched,
  *       lr_max' = max(lr_k, lr_max),  weight = (k + 1)^r lr_max'^weight_lr_power,  weight_sum' = weight_sum + weight,
@@ -942,17 +948,16 @@ typedef struct nqa_sfree_group {
   double weight_sum, lr_max, scheduled_lr;
 } nqa_sfree_group;
 
-int nqa_sfree_step(const nqa_sfree_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+int nqa_sfree_step(const nqa_sfree_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                    nqa_sfree_group* groups, int32_t n_groups, nqa_stream stream);
-int nqa_sfree_swap(const nqa_sfree_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+int nqa_sfree_swap(const nqa_sfree_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                    const nqa_sfree_group* groups, int32_t n_groups, int32_t to_eval, nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Conflict-free inverse gradients, ConFIG (nequip/train/config.py::ConFIGLightningModule._ConFIG_backwards) as multi-tensor
- *   launches over the device tables of the weight averaging above: in an nqa_ema_tensor `ema` is the .grad of a parameter
- *   (float32 or float64, dense), `param` its slice of ROW 0 of the buffer of collected gradients [n_terms, row_stride]
- *   (`buf_dtype`: float64 if any .grad is, else float32; row_stride a multiple of 4 elements, the elements past the last slice
- *   zero).  One workgroup per chunk, the grid is chunk_capacity, *n_chunks (device) the entries in use.
+ *   launches over the chunk layout above, with the records of the weight averaging: in an nqa_ema_tensor `ema` is the .grad of a
+ *   parameter, `param` its slice of ROW 0 of the buffer of collected gradients [n_terms, row_stride] (`buf_dtype`: float64 if any
+ *   .grad is, else float32; row_stride a multiple of 4 elements, the elements past the last slice zero).
  *   The tables live in device memory and are not validated by these calls: an entry with a float64 .grad under a float32
  *   buffer is outside the contract (the buffer dtype rule above excludes it) and such a chunk is skipped, neither read nor written.
  * nqa_config_collect: row `row` of the buffer = .grad (widened exactly), then .grad = 0, in one pass.  row < 0: only the zeros.
@@ -978,12 +983,12 @@ int nqa_sfree_swap(const nqa_sfree_tensor* tensors, const nqa_ema_chunk* chunks,
 enum nqa_config_clip { NQA_CONFIG_CLIP_NONE = 0, NQA_CONFIG_CLIP_NORM = 1, NQA_CONFIG_CLIP_VALUE = 2 };
 
 int32_t nqa_config_gram_chunk_elems(void);
-int nqa_config_collect(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+int nqa_config_collect(const nqa_ema_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                        int32_t row, int64_t row_stride, int32_t buf_dtype, nqa_stream stream);
 int nqa_config_gram(const void* buf, int32_t buf_dtype, int32_t n_terms, int64_t row_stride, const int64_t* numel,
                     int64_t gram_capacity, double* partials, const double* b, double norm_eps, int32_t clip_mode, double clip,
                     double* out, nqa_stream stream);
-int nqa_config_apply(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+int nqa_config_apply(const nqa_ema_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                      int32_t n_terms, int64_t row_stride, int32_t buf_dtype, const double* weights, int32_t clip_mode, double clip,
                      nqa_stream stream);
 int nqa_config_solve_host(const double* gram, int32_t n_terms, const double* b, double norm_eps, int32_t clip_mode, double clip,
@@ -1049,13 +1054,10 @@ int nqa_stats_neighbor_counts(const int64_t* edge_center, int64_t num_edges, int
 
 /* ---------------------------------------------------------------------------------------------
  * Per-tensor statistics of weights, gradients and Adam moments (nequip/train/callbacks/training_stats.py::
- *   TrainingStatsMonitor) as one multi-tensor reduction over device-resident tables: `tensors` [tensor_capacity] (float32 or
- *   float64, dense; transform f = identity or sqrt, applied element by element after the promotion to double; chunk0 the index
- *   of the tensor's first chunk in the map, its chunks are contiguous and ascending) and `chunks` [chunk_capacity] (an
- *   nqa_ema_chunk: the tensor a chunk belongs to and the element offset at which it starts; a chunk is NQA_TSTATS_CHUNK
- *   elements, nqa_tstats_chunk_elems, the last one of a tensor shorter).  counts = [chunks in use, tensors in use] (device
- *   memory, int64): the grids are the capacities and the workgroups past the counts return, so the tables can be rewritten in
- *   place under a captured launch.  Pointers need only be element-aligned (16-byte accesses where a chunk's start allows them).
+ *   TrainingStatsMonitor) as one multi-tensor reduction over the chunk layout above, with NQA_TSTATS_CHUNK elements per chunk:
+ *   `tensors` [tensor_capacity] (transform f = identity or sqrt, applied element by element after the promotion to double;
+ *   chunk0 the index of the tensor's first chunk in the map, its chunks are contiguous and ascending).  counts = [chunks in use,
+ *   tensors in use] (device memory, int64): the grids are the two capacities and the workgroups past the counts return.
  * nqa_tstats_reduce: two launches.  With n = *counter (device memory, int64), every workgroup returns without touching a
  *   tensor, the workspace or the table unless n % log_freq == 0.  (1) One workgroup per chunk forms count, mean, M2, sum of
  *   squares, min, max, absmin, absmax of f(x) in double (Welford per lane, Chan merges in a fixed lane and wavefront order)
@@ -1081,7 +1083,7 @@ typedef struct nqa_tstats_tensor {
 } nqa_tstats_tensor;
 
 int32_t nqa_tstats_chunk_elems(void);
-int nqa_tstats_reduce(const nqa_tstats_tensor* tensors, int64_t tensor_capacity, const nqa_ema_chunk* chunks,
+int nqa_tstats_reduce(const nqa_tstats_tensor* tensors, int64_t tensor_capacity, const nqa_mt_chunk* chunks,
                       int64_t chunk_capacity, const int64_t* counts, const int64_t* counter, int64_t log_freq, double* workspace,
                       double* table, int64_t* stamp, nqa_stream stream);
 int nqa_tstats_advance(int64_t* counter, nqa_stream stream);

@@ -8,10 +8,9 @@
 //   c   = pinv(Gh) bh   (cyclic Jacobi; eigenvalues <= CONFIG_TAU * lambda_max are dropped)
 //   xi  = sqrt(max(c' Gh c, 0))     d = max(xi, eps)     s = (sum_k sum_l G_kl c_l / n_l) / d
 //   w_l = s c_l / (n_l d)           new_grad = sum_l w_l g_l          |new_grad| = |s| xi / d
-// Layout: the tensor table and chunk map of ema.hip (nqa_ema_tensor / nqa_ema_chunk, NQA_EMA_CHUNK elements per chunk, one
-// workgroup per chunk, the count read from device memory, the grid the capacity of the map).  In a table entry `ema` is the
-// .grad of a parameter and `param` its slice of ROW 0 of the [K, row_stride] buffer of collected gradients; row k lies
-// k * row_stride elements further.  row_stride is a multiple of 4 elements, so every row is 16-byte aligned when row 0 is.
+// Layout: the tensor table and chunk map of multi_tensor.h, with the records of ema.hip (nqa_ema_tensor).  In a table entry
+// `ema` is the .grad of a parameter and `param` its slice of ROW 0 of the [K, row_stride] buffer of collected gradients; row k
+// lies k * row_stride elements further.  row_stride is a multiple of 4 elements, so every row is 16-byte aligned when row 0 is.
 //   config_collect_kernel   row k of the buffer = .grad (widened exactly where the buffer is float64), .grad = 0, one pass; with
 //                           row < 0 only the zeros.
 //   config_gram_kernel      one workgroup per CONFIG_GRAM_CHUNK elements of the rows: the K (K + 1) / 2 products in double, lanes
@@ -28,7 +27,7 @@
 #include <cstdint>
 #include <string>
 
-#include "plan.h"
+#include "multi_tensor.h"
 
 namespace nqa {
 
@@ -42,101 +41,36 @@ constexpr double CONFIG_TAU = 1e-12;
 constexpr int CONFIG_SWEEPS = 30;
 static_assert(CONFIG_MAX_K == 8 && NQA_CONFIG_OUT == CONFIG_MAX_K + 2, "out = [w_0 .. w_7, |new_grad|, clip factor]");
 
-#define NQA_GLOBAL __attribute__((address_space(1)))
-
-template <typename T>
-struct ConfigVec;
-template <>
-struct ConfigVec<float> {
-  typedef float type __attribute__((ext_vector_type(4)));
-};
-template <>
-struct ConfigVec<double> {
-  typedef double type __attribute__((ext_vector_type(2)));
-};
-
-// N consecutive elements at a 16-byte aligned address, as 16-byte accesses (one for four floats, two for four doubles)
-template <typename T, int N>
-__device__ __forceinline__ void config_load(NQA_GLOBAL const T* p, T (&v)[N]) {
-  using V = typename ConfigVec<T>::type;
-  constexpr int PER = 16 / sizeof(T);
-  static_assert(N % PER == 0, "whole 16-byte accesses");
-#pragma unroll
-  for (int a = 0; a < N / PER; ++a) {
-    const V x = ((NQA_GLOBAL const V*)p)[a];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) v[a * PER + j] = x[j];
-  }
-}
-
-template <typename T, int N>
-__device__ __forceinline__ void config_store(NQA_GLOBAL T* p, const T (&v)[N]) {
-  using V = typename ConfigVec<T>::type;
-  constexpr int PER = 16 / sizeof(T);
-  static_assert(N % PER == 0, "whole 16-byte accesses");
-#pragma unroll
-  for (int a = 0; a < N / PER; ++a) {
-    V x;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) x[j] = v[a * PER + j];
-    ((NQA_GLOBAL V*)p)[a] = x;
-  }
-}
-
-// the chunk of this workgroup (ema.hip's rule): false past the count, or for an entry that does not lie inside its tensor
-__device__ __forceinline__ bool config_chunk_of(const nqa_ema_tensor* __restrict__ tensors, const nqa_ema_chunk* __restrict__ chunks,
-                                                const int64_t* __restrict__ n_chunks, nqa_ema_tensor& t, int64_t& offset, int& len) {
-  if ((int64_t)blockIdx.x >= *n_chunks) return false;
-  const nqa_ema_chunk c = chunks[blockIdx.x];
-  t = tensors[c.tensor];
-  offset = c.offset;
-  const int64_t left = t.numel - offset;
-  if (offset < 0 || left <= 0) return false;
-  len = left < CONFIG_CHUNK ? (int)left : CONFIG_CHUNK;
-  return true;
-}
-
 // ---- collect --------------------------------------------------------------------------------------------------------------------
 // S: dtype of the .grad, D: dtype of the buffer (float -> float, float -> double, double -> double)
 template <typename S, typename D>
 __device__ __forceinline__ void config_collect_chunk(void* grad, void* row, int64_t offset, int len) {
-  constexpr int N = 16 / sizeof(S);
   NQA_GLOBAL S* g = (NQA_GLOBAL S*)grad + offset;
   NQA_GLOBAL D* r = row ? (NQA_GLOBAL D*)row + offset : nullptr;
-  const bool aligned = (((uintptr_t)g | (uintptr_t)r) & 15u) == 0;  // (the same for the whole workgroup; a null row is aligned)
-  int done = 0;
-  if (aligned) {
-    const int n_vec = len / N;
-    S zero[N];
+  chunk_walk<S, CONFIG_THREADS>(len, aligned16(g, r), [&](int i, auto width) {
+    constexpr int N = decltype(width)::value;
+    S x[N];
+    if (r) {
+      D y[N];
+      pack_load<S, N>(g + i, x);
 #pragma unroll
-    for (int j = 0; j < N; ++j) zero[j] = S(0);
-    for (int i = threadIdx.x; i < n_vec; i += CONFIG_THREADS) {
-      if (r) {
-        S x[N];
-        D y[N];
-        config_load<S, N>(g + (int64_t)i * N, x);
-#pragma unroll
-        for (int j = 0; j < N; ++j) y[j] = (D)x[j];
-        config_store<D, N>(r + (int64_t)i * N, y);
-      }
-      config_store<S, N>(g + (int64_t)i * N, zero);
+      for (int j = 0; j < N; ++j) y[j] = (D)x[j];
+      pack_store<D, N>(r + i, y);
     }
-    done = n_vec * N;
-  }
-  for (int i = done + threadIdx.x; i < len; i += CONFIG_THREADS) {
-    if (r) r[i] = (D)g[i];
-    g[i] = S(0);
-  }
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j] = S(0);
+    pack_store<S, N>(g + i, x);
+  });
 }
 
 __global__ __launch_bounds__(CONFIG_THREADS) void config_collect_kernel(const nqa_ema_tensor* __restrict__ tensors,
-                                                                         const nqa_ema_chunk* __restrict__ chunks,
+                                                                         const nqa_mt_chunk* __restrict__ chunks,
                                                                          const int64_t* __restrict__ n_chunks, int row,
                                                                          int64_t row_stride, int buf_dtype) {
   nqa_ema_tensor t;
   int64_t offset;
   int len;
-  if (!config_chunk_of(tensors, chunks, n_chunks, t, offset, len)) return;
+  if (!chunk_of<CONFIG_CHUNK>(tensors, chunks, n_chunks, t, offset, len)) return;
   const int64_t esz = buf_dtype == NQA_F64 ? 8 : 4;
   void* dst = row < 0 ? nullptr : (void*)((char*)t.param + (int64_t)row * row_stride * esz);
   // (a float64 .grad under a float32 buffer is outside the contract of nequip_amd.h: the chunk is skipped)
@@ -339,47 +273,37 @@ __device__ __forceinline__ double config_clamp(double v, bool clamp, double clip
 template <typename S, typename D>
 __device__ __forceinline__ void config_apply_chunk(void* grad, const void* row0, int64_t offset, int len, int K, int64_t row_stride,
                                                    const double* __restrict__ w, bool clamp, double clip) {
-  constexpr int N = 16 / sizeof(S);
   NQA_GLOBAL S* g = (NQA_GLOBAL S*)grad + offset;
   NQA_GLOBAL const D* r = (NQA_GLOBAL const D*)row0 + offset;
-  const bool aligned = (((uintptr_t)g | (uintptr_t)r) & 15u) == 0;  // (rows are row_stride apart, a multiple of 16 bytes)
-  int done = 0;
-  if (aligned) {
-    const int n_vec = len / N;
-    for (int i = threadIdx.x; i < n_vec; i += CONFIG_THREADS) {
-      double acc[N];
+  // (rows are row_stride apart, a multiple of 16 bytes)
+  chunk_walk<S, CONFIG_THREADS>(len, aligned16(g, r), [&](int i, auto width) {
+    constexpr int N = decltype(width)::value;
+    double acc[N];
 #pragma unroll
-      for (int j = 0; j < N; ++j) acc[j] = 0.0;
-      for (int l = 0; l < K; ++l) {
-        D x[N];
-        config_load<D, N>(r + (int64_t)l * row_stride + (int64_t)i * N, x);
-        const double wl = w[l];
+    for (int j = 0; j < N; ++j) acc[j] = 0.0;
+    for (int l = 0; l < K; ++l) {
+      D x[N];
+      pack_load<D, N>(r + (int64_t)l * row_stride + i, x);
+      const double wl = w[l];
 #pragma unroll
-        for (int j = 0; j < N; ++j) acc[j] += wl * (double)x[j];
-      }
-      S y[N];
-#pragma unroll
-      for (int j = 0; j < N; ++j) y[j] = (S)config_clamp(acc[j], clamp, clip);
-      config_store<S, N>(g + (int64_t)i * N, y);
+      for (int j = 0; j < N; ++j) acc[j] += wl * (double)x[j];
     }
-    done = n_vec * N;
-  }
-  for (int i = done + threadIdx.x; i < len; i += CONFIG_THREADS) {
-    double acc = 0.0;
-    for (int l = 0; l < K; ++l) acc += w[l] * (double)r[(int64_t)l * row_stride + i];
-    g[i] = (S)config_clamp(acc, clamp, clip);
-  }
+    S y[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) y[j] = (S)config_clamp(acc[j], clamp, clip);
+    pack_store<S, N>(g + i, y);
+  });
 }
 
 __global__ __launch_bounds__(CONFIG_THREADS) void config_apply_kernel(const nqa_ema_tensor* __restrict__ tensors,
-                                                                       const nqa_ema_chunk* __restrict__ chunks,
+                                                                       const nqa_mt_chunk* __restrict__ chunks,
                                                                        const int64_t* __restrict__ n_chunks, int K, int64_t row_stride,
                                                                        int buf_dtype, const double* __restrict__ w, int clip_mode,
                                                                        double clip) {
   nqa_ema_tensor t;
   int64_t offset;
   int len;
-  if (!config_chunk_of(tensors, chunks, n_chunks, t, offset, len)) return;
+  if (!chunk_of<CONFIG_CHUNK>(tensors, chunks, n_chunks, t, offset, len)) return;
   const bool clamp = clip_mode == NQA_CONFIG_CLIP_VALUE;
   if (t.dtype == NQA_F64) {
     if (buf_dtype == NQA_F64) config_apply_chunk<double, double>(t.ema, t.param, offset, len, K, row_stride, w, clamp, clip);
@@ -398,8 +322,8 @@ static int config_invalid(const char* name, const char* what) {
 
 static int config_check_tables(const char* name, const void* tensors, const void* chunks, int64_t chunk_capacity,
                                const void* n_chunks, int64_t row_stride, int buf_dtype) {
-  if (chunk_capacity < 0 || chunk_capacity > INT32_MAX || (chunk_capacity > 0 && (!tensors || !chunks || !n_chunks)))
-    return config_invalid(name, "device tables (tensors, chunks, chunk count) are required, 0 <= chunk_capacity < 2^31");
+  const int rc = check_tables(name, tensors, chunks, chunk_capacity, n_chunks);
+  if (rc != NQA_OK) return rc;
   if (row_stride < 0 || row_stride % 4 != 0) return config_invalid(name, "row_stride must be a multiple of 4 elements");
   if (buf_dtype != NQA_F32 && buf_dtype != NQA_F64) return config_invalid(name, "the buffer is float32 or float64");
   return NQA_OK;
@@ -410,22 +334,13 @@ static bool config_clip_ok(int clip_mode, double clip) {
   return (clip_mode == NQA_CONFIG_CLIP_NORM || clip_mode == NQA_CONFIG_CLIP_VALUE) && clip >= 0.0;
 }
 
-static int config_launch_status(const char* name) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string(name) + ": " + hipGetErrorString(e));
-    return NQA_ERR_LAUNCH;
-  }
-  return NQA_OK;
-}
-
 }  // namespace nqa
 
 extern "C" {
 
 int32_t nqa_config_gram_chunk_elems(void) { return nqa::CONFIG_GRAM_CHUNK; }
 
-int nqa_config_collect(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+int nqa_config_collect(const nqa_ema_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                        int32_t row, int64_t row_stride, int32_t buf_dtype, nqa_stream stream) {
   using namespace nqa;
   const char* name = "nqa_config_collect";
@@ -435,7 +350,7 @@ int nqa_config_collect(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunk
   if (chunk_capacity == 0) return NQA_OK;
   hipLaunchKernelGGL(config_collect_kernel, dim3((unsigned)chunk_capacity), dim3(CONFIG_THREADS), 0,
                      static_cast<hipStream_t>(stream), tensors, chunks, n_chunks, (int)row, row_stride, (int)buf_dtype);
-  return config_launch_status(name);
+  return launch_status(name);
 }
 
 int nqa_config_gram(const void* buf, int32_t buf_dtype, int32_t n_terms, int64_t row_stride, const int64_t* numel,
@@ -461,10 +376,10 @@ int nqa_config_gram(const void* buf, int32_t buf_dtype, int32_t n_terms, int64_t
   }
   hipLaunchKernelGGL(config_solve_kernel, dim3(1), dim3(CONFIG_THREADS), 0, s, (const double*)partials, (int)n_terms, numel,
                      gram_capacity, b, norm_eps, (int)clip_mode, clip, out);
-  return config_launch_status(name);
+  return launch_status(name);
 }
 
-int nqa_config_apply(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+int nqa_config_apply(const nqa_ema_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                      int32_t n_terms, int64_t row_stride, int32_t buf_dtype, const double* weights, int32_t clip_mode, double clip,
                      nqa_stream stream) {
   using namespace nqa;
@@ -476,7 +391,7 @@ int nqa_config_apply(const nqa_ema_tensor* tensors, const nqa_ema_chunk* chunks,
   if (chunk_capacity == 0) return NQA_OK;
   hipLaunchKernelGGL(config_apply_kernel, dim3((unsigned)chunk_capacity), dim3(CONFIG_THREADS), 0, static_cast<hipStream_t>(stream),
                      tensors, chunks, n_chunks, (int)n_terms, row_stride, (int)buf_dtype, weights, (int)clip_mode, clip);
-  return config_launch_status(name);
+  return launch_status(name);
 }
 
 int nqa_config_solve_host(const double* gram, int32_t n_terms, const double* b, double norm_eps, int32_t clip_mode, double clip,

@@ -21,7 +21,7 @@
 #include <cstdint>
 #include <string>
 
-#include "plan.h"
+#include "launch_status.h"
 
 namespace nqa {
 
@@ -490,15 +490,6 @@ static int mt_prepare(const char* name, const nqa_metric_stream* streams, int32_
   return NQA_OK;
 }
 
-static int mt_launch_status(const char* name) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string(name) + ": " + hipGetErrorString(e));
-    return NQA_ERR_LAUNCH;
-  }
-  return NQA_OK;
-}
-
 }  // namespace nqa
 
 extern "C" {
@@ -557,7 +548,7 @@ int nqa_metrics_fwd(const nqa_metric_stream* streams, int32_t n_streams, const n
   f.groups = MT_GROUPS;
   f.ws_index = weighted_sum_index;
   hipLaunchKernelGGL(metrics_final_kernel, dim3(1), dim3(256), 0, s, f);
-  return mt_launch_status(name);
+  return launch_status(name);
 }
 
 int nqa_metrics_bwd(const nqa_metric_stream* streams, int32_t n_streams, const nqa_metric_term* terms,
@@ -578,7 +569,7 @@ int nqa_metrics_bwd(const nqa_metric_stream* streams, int32_t n_streams, const n
   const int64_t* saved_cnt = reinterpret_cast<const int64_t*>(saved_sum + a.n_slots);
   hipLaunchKernelGGL(metrics_bwd_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256),
                      (size_t)a.n_slots * 8, static_cast<hipStream_t>(stream), a, saved_sum, saved_cnt, grad_values);
-  return mt_launch_status(name);
+  return launch_status(name);
 }
 
 }  // extern "C"

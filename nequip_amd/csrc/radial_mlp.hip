@@ -28,8 +28,8 @@
 #include <string>
 #include <type_traits>
 
+#include "launch_status.h"
 #include "mfma_split.h"
-#include "plan.h"
 
 namespace nqa {
 
@@ -1461,10 +1461,6 @@ MlpWorkspace mlp_view(void* workspace, const MlpLayout& lay) {
 int fail(int rc, const std::string& text) {
   set_error(text);
   return rc;
-}
-int launch_status(const char* fn) {
-  hipError_t err = hipGetLastError();
-  return err == hipSuccess ? NQA_OK : fail(NQA_ERR_LAUNCH, std::string(fn) + ": " + hipGetErrorString(err));
 }
 
 // Operands of the two drivers.  `fn` names the entry point in the error texts.  `xin`: `in` holds the pre-activations

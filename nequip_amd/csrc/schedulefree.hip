@@ -6,10 +6,8 @@
 // replays step k for ever (the defect ema.hip describes for the EMA warm-up).  Here hyper-parameters AND state of every
 // parameter group are a record in device memory and the kernel forms the scalars itself.
 //
-// Layout: a device table of TENSORS (parameter, .grad, z, exp_avg_sq, element count, dtype, group), the CHUNK map of ema.hip
-// (nqa_ema_chunk: the tensor a chunk belongs to and the element offset at which it starts; NQA_EMA_CHUNK elements, the last
-// one of a tensor shorter; one workgroup per chunk; the grid is the CAPACITY of the map and the workgroups past the device-side
-// count return) and one nqa_sfree_group RECORD per parameter group.
+// Layout: the tensor table and chunk map of multi_tensor.h; a table entry is (parameter, .grad, z, exp_avg_sq, element count,
+// dtype, group), and there is one nqa_sfree_group RECORD per parameter group.
 //   sfree_step_kernel     every workgroup reads the record of its tensor's group and derives sched, bc2, lr_k, lr_max', weight
 //                         and c from the OLD state (pure functions of it: no workgroup depends on another), in double, rounded
 //                         once to the tensor's arithmetic type as ATen rounds a Python scalar; then per element
@@ -18,11 +16,10 @@
 //                         with z read as y in the first step of a group (k == 0: z may hold anything, NaN included).  A tensor
 //                         whose .grad is null is skipped, its state untouched.  .grad is only read.
 //   sfree_advance_kernel  one thread per group commits k + 1, weight_sum, lr_max, scheduled_lr.  A SECOND launch on the same
-//                         stream, the rule of ema_advance_kernel: every workgroup of the step has read the old state before
+//                         stream, the rule of ema.hip's advance: every workgroup of the step has read the old state before
 //                         the single writer of a record starts.  No ticket, no atomics, no fence.
 //   sfree_swap_kernel     the mode switch p = lerp(p, z, w): w = 1 - 1 / b1 to the averaged weights x, w = 1 - b1 back to y.
-// Accesses are 16 bytes per lane where ALL pointers of a chunk are 16-byte aligned; a tensor that is a view at an odd element
-// offset takes the element-wise path.  Plain vector loads and stores, no LDS.  Nothing is read by the host.
+// Plain vector loads and stores, no LDS.  Nothing is read by the host.
 //
 // The three pow() of a step are formed by every wavefront (a chunk is 4 elements per lane): the exponents that occur by
 // default (r == 0, weight_lr_power == 1 or 2) are products, which are what a correctly rounded pow returns for them.
@@ -31,38 +28,15 @@
 #include <cstdint>
 #include <string>
 
-#include "plan.h"
+#include "multi_tensor.h"
 
 namespace nqa {
 
 constexpr int SFREE_CHUNK = NQA_EMA_CHUNK;
 constexpr int SFREE_THREADS = 256;
-static_assert(sizeof(nqa_sfree_tensor) == 48 && sizeof(nqa_sfree_group) == 96 && sizeof(nqa_ema_chunk) == 16,
+static_assert(sizeof(nqa_sfree_tensor) == 48 && sizeof(nqa_sfree_group) == 96 && sizeof(nqa_mt_chunk) == 16,
               "the host writes these tables as int64 words");
 static_assert((SFREE_CHUNK * sizeof(float)) % 16 == 0, "a chunk must keep the 16-byte alignment of its tensor");
-
-// The pointers come out of a device table, so the compiler cannot know that they are global memory: said here, the accesses
-// are global_load / global_store and not the flat forms.
-#define NQA_GLOBAL __attribute__((address_space(1)))
-
-template <typename T>
-struct SfreeVec;
-template <>
-struct SfreeVec<float> {
-  typedef float type __attribute__((ext_vector_type(4)));
-  static constexpr int N = 4;
-};
-template <>
-struct SfreeVec<double> {
-  typedef double type __attribute__((ext_vector_type(2)));
-  static constexpr int N = 2;
-};
-
-template <typename T>
-__device__ __forceinline__ T sfree_lerp(T a, T b, T w) {
-  const T diff = b - a;
-  return w < T(0.5) ? a + w * diff : b - diff * (T(1) - w);
-}
 
 __device__ __forceinline__ double sfree_pow(double x, double e) {
   if (e == 0.0) return 1.0;
@@ -100,7 +74,7 @@ struct SfreeStepOp {
     const T z_old = first ? y : z;
     const T v_new = b2 * v + one_minus_b2 * g * g;
     const T gn = g / (sqrt(v_new / bc2) + eps) + wd * y;
-    y = sfree_lerp(y, z_old, c) + a * gn;
+    y = lerp(y, z_old, c) + a * gn;
     z = z_old - lr_k * gn;
     v = v_new;
   }
@@ -109,87 +83,51 @@ struct SfreeStepOp {
 // `len` elements at `offset` of the four tensors of one table entry
 template <typename T>
 __device__ __forceinline__ void sfree_step_chunk(const nqa_sfree_tensor& t, int64_t offset, int len, const SfreeStepOp<T> op) {
-  using V = typename SfreeVec<T>::type;
-  constexpr int N = SfreeVec<T>::N;
   NQA_GLOBAL T* y = (NQA_GLOBAL T*)t.param + offset;
   const NQA_GLOBAL T* g = (const NQA_GLOBAL T*)t.grad + offset;
   NQA_GLOBAL T* z = (NQA_GLOBAL T*)t.z + offset;
   NQA_GLOBAL T* v = (NQA_GLOBAL T*)t.exp_avg_sq + offset;
-  const bool aligned = (((uintptr_t)y | (uintptr_t)g | (uintptr_t)z | (uintptr_t)v) & 15u) == 0;  // (the same for the whole workgroup)
-  int done = 0;
-  if (aligned) {
-    const int n_vec = len / N;
-    NQA_GLOBAL V* yv = (NQA_GLOBAL V*)y;
-    const NQA_GLOBAL V* gv = (const NQA_GLOBAL V*)g;
-    NQA_GLOBAL V* zv = (NQA_GLOBAL V*)z;
-    NQA_GLOBAL V* vv = (NQA_GLOBAL V*)v;
-    for (int i = threadIdx.x; i < n_vec; i += SFREE_THREADS) {
-      V ye = yv[i], ge = gv[i], ze = zv[i], ve = vv[i];
+  chunk_walk<T, SFREE_THREADS>(len, aligned16(y, g, z, v), [&](int i, auto width) {
+    constexpr int N = decltype(width)::value;
+    T ye[N], ge[N], ze[N], ve[N];
+    pack_load<T, N>(y + i, ye);
+    pack_load<T, N>(g + i, ge);
+    pack_load<T, N>(z + i, ze);
+    pack_load<T, N>(v + i, ve);
 #pragma unroll
-      for (int j = 0; j < N; ++j) {
-        T a = ye[j], b = ze[j], c = ve[j];
-        op(a, ge[j], b, c);
-        ye[j] = a;
-        ze[j] = b;
-        ve[j] = c;
-      }
-      yv[i] = ye;
-      zv[i] = ze;
-      vv[i] = ve;
-    }
-    done = n_vec * N;
-  }
-  for (int i = done + threadIdx.x; i < len; i += SFREE_THREADS) {
-    T a = y[i], b = z[i], c = v[i];
-    op(a, g[i], b, c);
-    y[i] = a;
-    z[i] = b;
-    v[i] = c;
-  }
+    for (int j = 0; j < N; ++j) op(ye[j], ge[j], ze[j], ve[j]);
+    pack_store<T, N>(y + i, ye);
+    pack_store<T, N>(z + i, ze);
+    pack_store<T, N>(v + i, ve);
+  });
 }
 
 // p = lerp(p, z, w) over `len` elements
 template <typename T>
 __device__ __forceinline__ void sfree_swap_chunk(const nqa_sfree_tensor& t, int64_t offset, int len, T w) {
-  using V = typename SfreeVec<T>::type;
-  constexpr int N = SfreeVec<T>::N;
   NQA_GLOBAL T* p = (NQA_GLOBAL T*)t.param + offset;
   const NQA_GLOBAL T* z = (const NQA_GLOBAL T*)t.z + offset;
-  const bool aligned = (((uintptr_t)p | (uintptr_t)z) & 15u) == 0;
-  int done = 0;
-  if (aligned) {
-    const int n_vec = len / N;
-    NQA_GLOBAL V* pv = (NQA_GLOBAL V*)p;
-    const NQA_GLOBAL V* zv = (const NQA_GLOBAL V*)z;
-    for (int i = threadIdx.x; i < n_vec; i += SFREE_THREADS) {
-      V pe = pv[i];
-      const V ze = zv[i];
+  chunk_walk<T, SFREE_THREADS>(len, aligned16(p, z), [&](int i, auto width) {
+    constexpr int N = decltype(width)::value;
+    T pe[N], ze[N];
+    pack_load<T, N>(p + i, pe);
+    pack_load<T, N>(z + i, ze);
 #pragma unroll
-      for (int j = 0; j < N; ++j) pe[j] = sfree_lerp<T>(pe[j], ze[j], w);
-      pv[i] = pe;
-    }
-    done = n_vec * N;
-  }
-  for (int i = done + threadIdx.x; i < len; i += SFREE_THREADS) p[i] = sfree_lerp<T>(p[i], z[i], w);
+    for (int j = 0; j < N; ++j) pe[j] = lerp<T>(pe[j], ze[j], w);
+    pack_store<T, N>(p + i, pe);
+  });
 }
 
 // the chunk of this workgroup: false past the count, for an entry that does not lie inside its tensor, or for a group that is
 // not in the table of records
-__device__ __forceinline__ bool sfree_chunk_of(const nqa_sfree_tensor* __restrict__ tensors, const nqa_ema_chunk* __restrict__ chunks,
+__device__ __forceinline__ bool sfree_chunk_of(const nqa_sfree_tensor* __restrict__ tensors, const nqa_mt_chunk* __restrict__ chunks,
                                                const int64_t* __restrict__ n_chunks, int32_t n_groups, nqa_sfree_tensor& t,
                                                int64_t& offset, int& len) {
-  if ((int64_t)blockIdx.x >= *n_chunks) return false;
-  const nqa_ema_chunk c = chunks[blockIdx.x];
-  t = tensors[c.tensor];
-  offset = c.offset;
-  const int64_t left = t.numel - offset;
-  if (offset < 0 || left <= 0 || t.group < 0 || t.group >= n_groups) return false;
-  len = left < SFREE_CHUNK ? (int)left : SFREE_CHUNK;
-  return true;
+  return chunk_of<SFREE_CHUNK>(tensors, chunks, n_chunks, t, offset, len) && t.group >= 0 && t.group < n_groups;
 }
 
 __global__ __launch_bounds__(SFREE_THREADS) void sfree_step_kernel(const nqa_sfree_tensor* __restrict__ tensors,
-                                                                    const nqa_ema_chunk* __restrict__ chunks,
+                                                                    const nqa_mt_chunk* __restrict__ chunks,
                                                                     const int64_t* __restrict__ n_chunks,
                                                                     const nqa_sfree_group* __restrict__ groups, int32_t n_groups) {
   nqa_sfree_tensor t;
@@ -217,7 +155,7 @@ __global__ void sfree_advance_kernel(nqa_sfree_group* __restrict__ groups, int32
 }
 
 __global__ __launch_bounds__(SFREE_THREADS) void sfree_swap_kernel(const nqa_sfree_tensor* __restrict__ tensors,
-                                                                    const nqa_ema_chunk* __restrict__ chunks,
+                                                                    const nqa_mt_chunk* __restrict__ chunks,
                                                                     const int64_t* __restrict__ n_chunks,
                                                                     const nqa_sfree_group* __restrict__ groups, int32_t n_groups,
                                                                     int32_t to_eval) {
@@ -236,22 +174,11 @@ __global__ __launch_bounds__(SFREE_THREADS) void sfree_swap_kernel(const nqa_sfr
 
 static int sfree_check(const char* name, const void* tensors, const void* chunks, int64_t chunk_capacity, const void* n_chunks,
                        const void* groups, int32_t n_groups) {
-  if (chunk_capacity < 0 || chunk_capacity > INT32_MAX || (chunk_capacity > 0 && (!tensors || !chunks || !n_chunks))) {
-    set_error(std::string(name) + ": device tables (tensors, chunks, chunk count) are required, 0 <= chunk_capacity < 2^31");
-    return NQA_ERR_INVALID;
-  }
+  const int rc = check_tables(name, tensors, chunks, chunk_capacity, n_chunks);
+  if (rc != NQA_OK) return rc;
   if (n_groups < 1 || !groups) {
     set_error(std::string(name) + ": the device records of the parameter groups are required, n_groups >= 1");
     return NQA_ERR_INVALID;
-  }
-  return NQA_OK;
-}
-
-static int sfree_launch_status(const char* name) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string(name) + ": " + hipGetErrorString(e));
-    return NQA_ERR_LAUNCH;
   }
   return NQA_OK;
 }
@@ -260,7 +187,7 @@ static int sfree_launch_status(const char* name) {
 
 extern "C" {
 
-int nqa_sfree_step(const nqa_sfree_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+int nqa_sfree_step(const nqa_sfree_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                    nqa_sfree_group* groups, int32_t n_groups, nqa_stream stream) {
   using namespace nqa;
   const char* name = "nqa_sfree_step";
@@ -271,10 +198,10 @@ int nqa_sfree_step(const nqa_sfree_tensor* tensors, const nqa_ema_chunk* chunks,
     hipLaunchKernelGGL(sfree_step_kernel, dim3((unsigned)chunk_capacity), dim3(SFREE_THREADS), 0, s, tensors, chunks, n_chunks,
                        groups, n_groups);
   hipLaunchKernelGGL(sfree_advance_kernel, dim3((unsigned)((n_groups + 63) / 64)), dim3(64), 0, s, groups, n_groups);
-  return sfree_launch_status(name);
+  return launch_status(name);
 }
 
-int nqa_sfree_swap(const nqa_sfree_tensor* tensors, const nqa_ema_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
+int nqa_sfree_swap(const nqa_sfree_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                    const nqa_sfree_group* groups, int32_t n_groups, int32_t to_eval, nqa_stream stream) {
   using namespace nqa;
   const char* name = "nqa_sfree_swap";
@@ -283,7 +210,7 @@ int nqa_sfree_swap(const nqa_sfree_tensor* tensors, const nqa_ema_chunk* chunks,
   if (chunk_capacity == 0) return NQA_OK;
   hipLaunchKernelGGL(sfree_swap_kernel, dim3((unsigned)chunk_capacity), dim3(SFREE_THREADS), 0, static_cast<hipStream_t>(stream),
                      tensors, chunks, n_chunks, groups, n_groups, to_eval);
-  return sfree_launch_status(name);
+  return launch_status(name);
 }
 
 }  // extern "C"

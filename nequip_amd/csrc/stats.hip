@@ -30,7 +30,7 @@
 #include <cstdint>
 #include <string>
 
-#include "plan.h"
+#include "launch_status.h"
 
 namespace nqa {
 
@@ -296,14 +296,6 @@ static int st_fail(const char* name, const std::string& what) {
   set_error(std::string(name) + ": " + what);
   return NQA_ERR_INVALID;
 }
-static int st_launch_status(const char* name) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string(name) + ": " + hipGetErrorString(e));
-    return NQA_ERR_LAUNCH;
-  }
-  return NQA_OK;
-}
 
 static int st_prepare(const char* name, const nqa_stats_stream* streams, int32_t n_streams, const nqa_stats_term* terms,
                       int32_t n_terms, StatsArgs& a) {
@@ -407,7 +399,7 @@ int nqa_stats_update(const nqa_stats_stream* streams, int32_t n_streams, const n
                      part_f + 2 * gs, part_f + 3 * gs, part_f + 4 * gs);
   hipLaunchKernelGGL(stats_final_kernel, dim3((unsigned)((a.n_slots + 3) / 4)), dim3(256), 0, s, part_n, part_f, state_n,
                      state_f, a.n_slots);
-  return st_launch_status(name);
+  return launch_status(name);
 }
 
 int nqa_stats_neighbor_counts(const int64_t* edge_center, int64_t num_edges, int64_t num_atoms, int32_t* counts,
@@ -418,12 +410,12 @@ int nqa_stats_neighbor_counts(const int64_t* edge_center, int64_t num_edges, int
   if (num_atoms == 0) return NQA_OK;
   if (!counts || (num_edges > 0 && !edge_center)) return st_fail(name, "null pointer");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(counts, 0, (size_t)num_atoms * sizeof(int32_t), s) != hipSuccess) return st_launch_status(name);
-  if (num_edges == 0) return st_launch_status(name);
+  if (hipMemsetAsync(counts, 0, (size_t)num_atoms * sizeof(int32_t), s) != hipSuccess) return launch_status(name);
+  if (num_edges == 0) return launch_status(name);
   const int64_t blocks = (num_edges + 255) / 256;
   hipLaunchKernelGGL(neighbor_count_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, edge_center,
                      num_edges, num_atoms, counts);
-  return st_launch_status(name);
+  return launch_status(name);
 }
 
 }  // extern "C"

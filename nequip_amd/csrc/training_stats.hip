@@ -5,11 +5,10 @@
 // host (`step_count % log_freq`) whether a step logs: captured into the hipGraph of a training step that decision is frozen.
 // Here the step count lives in device memory, every workgroup reads it and returns when the step does not log.
 //
-// Layout (as in ema.hip): a device table of TENSORS (pointer, element count, dtype, transform f = identity | sqrt, the first
-// chunk of the tensor) and a device map of CHUNKS (the tensor a chunk belongs to, the element offset at which it starts); a chunk
-// is NQA_TSTATS_CHUNK elements of one tensor, the last one shorter.  counts = [chunks in use, tensors in use] is read from device
-// memory: the grids are the CAPACITIES of the map and of the table, the workgroups past the counts return without reading
-// anything else, so a captured launch stays right when the tables are rewritten in place.
+// Layout: the tensor table and chunk map of multi_tensor.h, with NQA_TSTATS_CHUNK elements per chunk; a table entry is (pointer,
+// element count, dtype, transform f = identity | sqrt, the first chunk of the tensor).  counts = [chunks in use, tensors in use]
+// is read from device memory: the grids are the CAPACITIES of the map and of the table, the workgroups past the counts return
+// without reading anything else.
 //   tstats_partial_kernel  one workgroup per chunk.  Every lane folds its elements y = f(x), promoted to double, by Welford
 //                          updates into (count, mean, M2, sum of squares, min, max, absmin, absmax); the lanes of a wavefront are
 //                          merged by a fixed shuffle tree, the four wavefronts in wavefront order (Chan's formula); one workspace
@@ -18,33 +17,29 @@
 //                          order, the lanes are merged by the same tree (lane l takes lane l + off BEHIND itself, so the chunks
 //                          stay in ascending order), lane 0 writes [min, max, mean, std, absmin, absmax, rms, count] and, for
 //                          tensor 0, the step at which this table was written.
-//   tstats_advance_kernel  count += 1, one thread.
+//   advance_kernel         count += 1, one thread (multi_tensor.h).
 // The counter hazard is the one ema.hip describes: no workgroup of a reduce launch may see the advanced count, so the count is
 // advanced by a launch of its own on the same stream.
 // NaN: minimum and maximum keep a NaN (fmin / fmax would drop it), Welford and the sum of squares carry it: one NaN makes all
 // seven statistics of the row NaN, as ATen does.  +-inf without NaN: min, max, absmin, absmax, rms are ATen's; Welford forms
 // inf - inf, so mean and std are NaN where ATen's sum may give inf (std is NaN there as well): non-finite either way.
 // No floating-point atomics, no allocation, nothing read by the host, a fixed merge order: the same inputs give the same bits.
-// Accesses are 16 bytes per lane where the chunk's first element is 16-byte aligned (chunks are a multiple of 16 bytes long:
-// that is the alignment of the tensor); a view at an odd element offset takes the element-wise path.  LDS: the four wavefront
-// states of the first stage only.
+// LDS: the four wavefront states of the first stage only.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <string>
 
-#include "plan.h"
+#include "multi_tensor.h"
 
 namespace nqa {
 
 constexpr int TS_CHUNK = NQA_TSTATS_CHUNK;
 constexpr int TS_THREADS = 256;
 constexpr int TS_ROW = 8;  // doubles per workspace row and per table row
-static_assert(sizeof(nqa_tstats_tensor) == 32 && sizeof(nqa_ema_chunk) == 16, "the host writes these tables as int64 words");
+static_assert(sizeof(nqa_tstats_tensor) == 32 && sizeof(nqa_mt_chunk) == 16, "the host writes these tables as int64 words");
 static_assert((TS_CHUNK * sizeof(float)) % 16 == 0, "a chunk must keep the 16-byte alignment of its tensor");
-
-#define NQA_GLOBAL __attribute__((address_space(1)))
 
 struct TsAcc {
   double n, mean, m2, ss, mn, mx, amn, amx;  // (n as a double: exact below 2^53)
@@ -120,45 +115,31 @@ __device__ __forceinline__ TsAcc ts_load(const double* __restrict__ row) {
   return TsAcc{row[0], row[1], row[2], row[3], row[4], row[5], row[6], row[7]};
 }
 
-template <typename T>
-struct TsVec;
-template <>
-struct TsVec<float> {
-  typedef float type __attribute__((ext_vector_type(4)));
-  static constexpr int N = 4;
-};
-template <>
-struct TsVec<double> {
-  typedef double type __attribute__((ext_vector_type(2)));
-  static constexpr int N = 2;
-};
-
-// the elements of one chunk that this lane owns, folded in index order
+// the elements of one chunk that this lane owns, folded in index order.  The loops of chunk_walk (multi_tensor.h) are written in
+// place here: through the walker the same instructions come out with another register allocation (62 VGPRs for 61), and the
+// captured logging step measured 0.4 us of 46 slower.
 template <typename T, bool SQRT>
 __device__ __forceinline__ TsAcc ts_chunk_fold(const void* data, int64_t offset, int len) {
-  using V = typename TsVec<T>::type;
-  constexpr int N = TsVec<T>::N;
+  constexpr int N = 16 / sizeof(T);
   const NQA_GLOBAL T* x = (const NQA_GLOBAL T*)data + offset;
-  const bool aligned = ((uintptr_t)x & 15u) == 0;  // (the same for the whole workgroup)
   TsAcc acc = ts_empty();
-  int done = 0;
-  if (aligned) {
-    const int n_vec = len / N;
-    const NQA_GLOBAL V* xv = (const NQA_GLOBAL V*)x;
-    for (int i = threadIdx.x; i < n_vec; i += TS_THREADS) {
-      const V v = xv[i];
+  auto fold = [&](int i, auto width) {
+    constexpr int W = decltype(width)::value;
+    T v[W];
+    pack_load<T, W>(x + i, v);
 #pragma unroll
-      for (int j = 0; j < N; ++j) {
-        const double y = (double)v[j];
-        ts_push(acc, SQRT ? sqrt(y) : y);
-      }
+    for (int j = 0; j < W; ++j) {
+      const double y = (double)v[j];
+      ts_push(acc, SQRT ? sqrt(y) : y);
     }
+  };
+  int done = 0;
+  if (aligned16(x)) {
+    const int n_vec = len / N;
+    for (int i = threadIdx.x; i < n_vec; i += TS_THREADS) fold(i * N, std::integral_constant<int, N>{});
     done = n_vec * N;
   }
-  for (int i = done + threadIdx.x; i < len; i += TS_THREADS) {
-    const double y = (double)x[i];
-    ts_push(acc, SQRT ? sqrt(y) : y);
-  }
+  for (int i = done + threadIdx.x; i < len; i += TS_THREADS) fold(i, std::integral_constant<int, 1>{});
   return acc;
 }
 
@@ -168,7 +149,7 @@ __device__ __forceinline__ bool ts_logs(const int64_t* __restrict__ counter, int
 }
 
 __global__ __launch_bounds__(TS_THREADS) void tstats_partial_kernel(const nqa_tstats_tensor* __restrict__ tensors,
-                                                                     const nqa_ema_chunk* __restrict__ chunks,
+                                                                     const nqa_mt_chunk* __restrict__ chunks,
                                                                      const int64_t* __restrict__ counts,
                                                                      const int64_t* __restrict__ counter, int64_t log_freq,
                                                                      double* __restrict__ workspace) {
@@ -177,19 +158,19 @@ __global__ __launch_bounds__(TS_THREADS) void tstats_partial_kernel(const nqa_ts
   if (!ts_logs(counter, log_freq, count)) return;  // (uniform: the whole workgroup leaves before any barrier)
   if ((int64_t)blockIdx.x >= counts[0]) return;
   double* __restrict__ row = workspace + (int64_t)blockIdx.x * TS_ROW;
-  const nqa_ema_chunk c = chunks[blockIdx.x];
+  const nqa_mt_chunk c = chunks[blockIdx.x];
   TsAcc acc = ts_empty();
   // an entry that does not lie inside a tensor in use leaves an empty row
   if (c.tensor >= 0 && (int64_t)c.tensor < counts[1]) {
     const nqa_tstats_tensor t = tensors[c.tensor];
-    const int64_t left = t.numel - c.offset;
-    if (c.offset >= 0 && left > 0) {
-      const int len = left < TS_CHUNK ? (int)left : TS_CHUNK;
+    int64_t offset;
+    int len;
+    if (chunk_span<TS_CHUNK>(c, t.numel, offset, len)) {
       const bool root = t.transform == NQA_TSTATS_SQRT;
       if (t.dtype == NQA_F64)
-        acc = root ? ts_chunk_fold<double, true>(t.data, c.offset, len) : ts_chunk_fold<double, false>(t.data, c.offset, len);
+        acc = root ? ts_chunk_fold<double, true>(t.data, offset, len) : ts_chunk_fold<double, false>(t.data, offset, len);
       else
-        acc = root ? ts_chunk_fold<float, true>(t.data, c.offset, len) : ts_chunk_fold<float, false>(t.data, c.offset, len);
+        acc = root ? ts_chunk_fold<float, true>(t.data, offset, len) : ts_chunk_fold<float, false>(t.data, offset, len);
     }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -235,26 +216,13 @@ __global__ __launch_bounds__(64) void tstats_final_kernel(const nqa_tstats_tenso
   out[7] = v.n;
 }
 
-__global__ void tstats_advance_kernel(int64_t* __restrict__ counter) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) *counter += 1;
-}
-
-static int ts_launch_status(const char* name) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string(name) + ": " + hipGetErrorString(e));
-    return NQA_ERR_LAUNCH;
-  }
-  return NQA_OK;
-}
-
 }  // namespace nqa
 
 extern "C" {
 
 int32_t nqa_tstats_chunk_elems(void) { return nqa::TS_CHUNK; }
 
-int nqa_tstats_reduce(const nqa_tstats_tensor* tensors, int64_t tensor_capacity, const nqa_ema_chunk* chunks,
+int nqa_tstats_reduce(const nqa_tstats_tensor* tensors, int64_t tensor_capacity, const nqa_mt_chunk* chunks,
                       int64_t chunk_capacity, const int64_t* counts, const int64_t* counter, int64_t log_freq, double* workspace,
                       double* table, int64_t* stamp, nqa_stream stream) {
   using namespace nqa;
@@ -273,7 +241,7 @@ int nqa_tstats_reduce(const nqa_tstats_tensor* tensors, int64_t tensor_capacity,
                      counter, log_freq, workspace);
   hipLaunchKernelGGL(tstats_final_kernel, dim3((unsigned)tensor_capacity), dim3(64), 0, s, tensors, counts, counter, log_freq,
                      workspace, table, stamp);
-  return ts_launch_status(name);
+  return launch_status(name);
 }
 
 int nqa_tstats_advance(int64_t* counter, nqa_stream stream) {
@@ -283,8 +251,8 @@ int nqa_tstats_advance(int64_t* counter, nqa_stream stream) {
     set_error(std::string(name) + ": the device counter is required");
     return NQA_ERR_INVALID;
   }
-  hipLaunchKernelGGL(tstats_advance_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), counter);
-  return ts_launch_status(name);
+  hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), counter);
+  return launch_status(name);
 }
 
 }  // extern "C"

@@ -55,8 +55,8 @@ import torch.distributed as dist
 
 from .. import _lib
 from ..utils import ktimer
+from ._multi_tensor import _DT, ChunkTables, n_chunks, require_eager
 
-_DT = {torch.float32: _lib.NQA_F32, torch.float64: _lib.NQA_F64}
 _CLIP = {None: 0, "norm": 1, "value": 2}
 MAX_TERMS = 8
 TAU = 1e-12
@@ -124,51 +124,39 @@ def solve_host(gram: torch.Tensor, b: torch.Tensor, eps: float, clip_algorithm: 
     return out
 
 
-class _DeviceTables:
-    """What the kernels read on one device: the tensor table and chunk map (``nqa_ema_tensor`` / ``nqa_ema_chunk``), ``state =
-    [chunks in use, P]``, the ``[K, row_stride]`` buffer of collected gradients (``row_stride``: P rounded up to 4 elements, the
-    pad zero), the partial Gram products, ``b`` and ``out = [w_0 .. w_7, |new_grad|, clip factor]``.  Rewritten IN PLACE when only
-    the addresses of the gradients change: a captured launch keeps reading the same buffers."""
+class _DeviceTables(ChunkTables):
+    """The chunk tables of the gradients (``nqa_ema_tensor``: 4 words each), ``numel_dev = [P]``, the ``[K, row_stride]`` buffer of
+    collected gradients (``row_stride``: P rounded up to 4 elements, the pad zero), the partial Gram products, ``b`` and ``out =
+    [w_0 .. w_7, |new_grad|, clip factor]``.  Rewritten in place when only the addresses of the gradients change."""
 
     def __init__(self, device: torch.device, grads: List[torch.Tensor], n_terms: int, buf_dtype: torch.dtype):
         lib = _lib.load()
-        self.chunk, self.gram_chunk = int(lib.nqa_ema_chunk_elems()), int(lib.nqa_config_gram_chunk_elems())
-        self.device, self.n_terms, self.buf_dtype = device, n_terms, buf_dtype
+        chunk, self.gram_chunk = int(lib.nqa_ema_chunk_elems()), int(lib.nqa_config_gram_chunk_elems())
+        super().__init__(device, chunk, len(grads), n_chunks([g.numel() for g in grads], chunk), words=4)
+        self.n_terms, self.buf_dtype = n_terms, buf_dtype
         self.shapes = [(g.numel(), g.dtype) for g in grads]
         self.numel = sum(g.numel() for g in grads)
         self.row_stride = -(-self.numel // 4) * 4
-        self.capacity = sum(-(-g.numel() // self.chunk) for g in grads)
         self.gram_capacity = -(-self.numel // self.gram_chunk)
-        self.tensors = torch.zeros(max(len(grads), 1), 4, dtype=torch.int64, device=device)
-        self.chunks = torch.zeros(max(self.capacity, 1), 2, dtype=torch.int64, device=device)
-        self.state = torch.zeros(2, dtype=torch.int64, device=device)
+        self.numel_dev = torch.tensor([self.numel], dtype=torch.int64, device=device)
         self.buf = torch.zeros(n_terms, max(self.row_stride, 4), dtype=buf_dtype, device=device)
         self.partials = torch.zeros(max(self.gram_capacity, 1) * (MAX_TERMS * (MAX_TERMS + 1) // 2), dtype=torch.float64,
                                     device=device)
         self.b = torch.zeros(MAX_TERMS, dtype=torch.float64, device=device)
         self.out = torch.zeros(MAX_TERMS + 2, dtype=torch.float64, device=device)
-        self.key = None
 
     def fits(self, device: torch.device, grads: List[torch.Tensor], n_terms: int, buf_dtype: torch.dtype) -> bool:
         return (device == self.device and n_terms == self.n_terms and buf_dtype == self.buf_dtype
                 and [(g.numel(), g.dtype) for g in grads] == self.shapes)
 
     def write(self, key, grads: List[torch.Tensor]) -> None:
-        """(little-endian words: the int32 ``dtype`` / ``tensor`` fields are the low halves of their words, the pads 0)"""
+        """(little-endian words: the int32 ``dtype`` is the low half of its word, the pad 0)"""
         esz, rows, start = self.buf.element_size(), [], 0
         for g in grads:
             rows.append([g.data_ptr(), self.buf.data_ptr() + start * esz, g.numel(), _DT[g.dtype]])
             start += g.numel()
-        offsets = [torch.arange(0, g.numel(), self.chunk, dtype=torch.int64) for g in grads]
-        chunk_rows = [torch.stack([o, torch.full_like(o, i)], dim=1) for i, o in enumerate(offsets)]
-        n_chunks = sum(len(o) for o in offsets)
-        assert len(rows) <= self.tensors.shape[0] and n_chunks <= self.capacity and start == self.numel
-        if rows:
-            self.tensors[:len(rows)].copy_(torch.tensor(rows, dtype=torch.int64))
-        if n_chunks:
-            self.chunks[:n_chunks].copy_(torch.cat(chunk_rows))
-        self.state.copy_(torch.tensor([n_chunks, self.numel], dtype=torch.int64))
-        self.key = key
+        assert start == self.numel
+        super().write(key, [g.numel() for g in grads], rows)
 
 
 class ConFIGGradients:
@@ -275,12 +263,10 @@ class ConFIGGradients:
             self._aten_backward(params, terms, [c for _, c in active])
 
     def _device_tables(self, device, params, n_terms: int) -> _DeviceTables:
-        capturing = torch.cuda.is_current_stream_capturing()
         hint = ("ConFIGGradients.backward: call backward once eagerly before capturing it (the gradients of the parameters are "
                 "allocated and the device tables built, and rebuilt after the gradients moved, eagerly)")
         if any(p.grad is None for p in params):
-            if capturing:
-                raise RuntimeError(hint)
+            require_eager(hint)
             for p in params:
                 if p.grad is None:
                     p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
@@ -289,8 +275,7 @@ class ConFIGGradients:
         tables = self._tables
         if tables is not None and tables.key == key and tables.device == device:
             return tables
-        if capturing:
-            raise RuntimeError(hint)
+        require_eager(hint)
         buf_dtype = torch.float64 if any(g.dtype == torch.float64 for g in grads) else torch.float32
         with torch.cuda.device(device):
             if tables is None or not tables.fits(device, grads, n_terms, buf_dtype):
@@ -304,7 +289,7 @@ class ConFIGGradients:
         the zeros)."""
         nbytes = t.numel * t.buf.element_size()
         with torch.cuda.device(t.device), ktimer.region("config_collect", 3.0 * nbytes):
-            rc = _lib.load().nqa_config_collect(_lib.ptr(t.tensors), _lib.ptr(t.chunks), t.capacity, _lib.ptr(t.state), row,
+            rc = _lib.load().nqa_config_collect(_lib.ptr(t.tensors), _lib.ptr(t.chunks), t.capacity, _lib.ptr(t.counts), row,
                                                 t.row_stride, _DT[t.buf_dtype], _lib.stream_ptr(t.device))
         _lib.check(rc, "nqa_config_collect")
 
@@ -315,12 +300,12 @@ class ConFIGGradients:
         nbytes = t.numel * t.buf.element_size()
         with torch.cuda.device(t.device):
             with ktimer.region("config_gram", float(k * nbytes)):
-                rc = lib.nqa_config_gram(_lib.ptr(t.buf), _DT[t.buf_dtype], k, t.row_stride, _lib.ptr(t.state[1:]),
+                rc = lib.nqa_config_gram(_lib.ptr(t.buf), _DT[t.buf_dtype], k, t.row_stride, _lib.ptr(t.numel_dev),
                                          t.gram_capacity, _lib.ptr(t.partials), _lib.ptr(t.b), self.norm_eps, clip_mode, clip,
                                          _lib.ptr(t.out), _lib.stream_ptr(t.device))
             _lib.check(rc, "nqa_config_gram")
             with ktimer.region("config_apply", float((k + 1) * nbytes)):
-                rc = lib.nqa_config_apply(_lib.ptr(t.tensors), _lib.ptr(t.chunks), t.capacity, _lib.ptr(t.state), k, t.row_stride,
+                rc = lib.nqa_config_apply(_lib.ptr(t.tensors), _lib.ptr(t.chunks), t.capacity, _lib.ptr(t.counts), k, t.row_stride,
                                           _DT[t.buf_dtype], _lib.ptr(t.out), clip_mode, clip, _lib.stream_ptr(t.device))
             _lib.check(rc, "nqa_config_apply")
 

@@ -25,8 +25,7 @@ import torch
 
 from .. import _lib
 from ..utils import ktimer
-
-_DT = {torch.float32: _lib.NQA_F32, torch.float64: _lib.NQA_F64}
+from ._multi_tensor import _DT, ChunkTables, n_chunks, require_eager
 
 
 def _decay_at(decay: float, n: int) -> float:
@@ -59,39 +58,19 @@ def _aten_swap(emas: List[torch.Tensor], params: List[torch.Tensor]) -> None:
         p.copy_(tmp)
 
 
-class _DeviceTables:
-    """What the kernels read on one device: the tensor table, the chunk map and ``state = [num_updates, chunks in use]``.
-    Allocated once for the most the EMA buffers can need and rewritten IN PLACE when the tensors change: a captured launch
-    keeps reading the same buffers."""
+class _DeviceTables(ChunkTables):
+    """The chunk tables of the EMA buffers (``nqa_ema_tensor``: 4 words each) and ``state = [num_updates]``.  Allocated once for
+    the most the EMA buffers can need."""
 
     def __init__(self, device: torch.device, emas: List[torch.Tensor], num_updates: int):
-        self.chunk = int(_lib.load().nqa_ema_chunk_elems())
-        self.device = device
-        self.n_tensors = max(len(emas), 1)
-        self.capacity = sum(-(-e.numel() // self.chunk) for e in emas)
-        self.tensors = torch.zeros(self.n_tensors, 4, dtype=torch.int64, device=device)  # nqa_ema_tensor: 4 words each
-        self.chunks = torch.zeros(max(self.capacity, 1), 2, dtype=torch.int64, device=device)  # nqa_ema_chunk: 2 words each
-        self.state = torch.tensor([num_updates, 0], dtype=torch.int64, device=device)
-        self.key = None
+        chunk = int(_lib.load().nqa_ema_chunk_elems())
+        super().__init__(device, chunk, len(emas), n_chunks([e.numel() for e in emas], chunk), words=4)
+        self.state = torch.tensor([num_updates], dtype=torch.int64, device=device)
         self.nbytes = 0
 
-    def fits(self, device: torch.device, emas: List[torch.Tensor]) -> bool:
-        return (device == self.device and len(emas) <= self.n_tensors
-                and sum(-(-e.numel() // self.chunk) for e in emas) <= self.capacity)
-
     def write(self, key, pairs: List[Tuple[torch.Tensor, torch.Tensor]]) -> None:
-        """(little-endian words: the int32 ``dtype`` / ``tensor`` fields are the low halves of their words, the pads 0)"""
-        rows = [[e.data_ptr(), p.data_ptr(), e.numel(), _DT[e.dtype]] for e, p in pairs]
-        offsets = [torch.arange(0, e.numel(), self.chunk, dtype=torch.int64) for e, _ in pairs]
-        chunk_rows = [torch.stack([o, torch.full_like(o, i)], dim=1) for i, o in enumerate(offsets)]
-        n_chunks = sum(len(o) for o in offsets)
-        assert len(rows) <= self.n_tensors and n_chunks <= self.capacity
-        if rows:
-            self.tensors[:len(rows)].copy_(torch.tensor(rows, dtype=torch.int64))
-        if n_chunks:
-            self.chunks[:n_chunks].copy_(torch.cat(chunk_rows))
-        self.state[1:].copy_(torch.tensor([n_chunks], dtype=torch.int64))
-        self.key = key
+        """(little-endian words: the int32 ``dtype`` is the low half of its word, the pad 0)"""
+        super().write(key, [e.numel() for e, _ in pairs], [[e.data_ptr(), p.data_ptr(), e.numel(), _DT[e.dtype]] for e, p in pairs])
         self.nbytes = sum(e.numel() * e.element_size() for e, _ in pairs)
 
 
@@ -169,13 +148,11 @@ class EMAWeights(torch.nn.Module):
         tables = self._tables
         if tables is not None and tables.key == key and tables.device == device:
             return tables
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"EMAWeights.{what}: call update_parameters once eagerly before capturing it (the device "
-                               "tables of the parameters are built, and rebuilt after the parameters moved, eagerly)")
+        require_eager(f"EMAWeights.{what}: call update_parameters once eagerly before capturing it (the device tables of the "
+                      "parameters are built, and rebuilt after the parameters moved, eagerly)")
         with torch.cuda.device(device):
-            emas = self.ema_weights
-            if tables is None or not tables.fits(device, emas):
-                tables = _DeviceTables(device, emas, self.num_updates)
+            if tables is None or not tables.fits(device, [e.numel() for e in self.ema_weights]):
+                tables = _DeviceTables(device, self.ema_weights, self.num_updates)
             tables.write(key, native)
         self._tables = tables
         return tables
@@ -198,7 +175,7 @@ class EMAWeights(torch.nn.Module):
             _aten_update([e for e, _ in rest], [p for _, p in rest], self.num_updates, self.decay)
         with torch.cuda.device(device), ktimer.region("ema_update", 3.0 * tables.nbytes):
             rc = _lib.load().nqa_ema_update(_lib.ptr(tables.tensors), _lib.ptr(tables.chunks), tables.capacity,
-                                            _lib.ptr(tables.state[1:]), float(self.decay), _lib.ptr(tables.state),
+                                            _lib.ptr(tables.counts), float(self.decay), _lib.ptr(tables.state),
                                             _lib.stream_ptr(device))
         _lib.check(rc, "nqa_ema_update")
         torch.autograd.graph.increment_version([e for e, _ in native])
@@ -214,7 +191,7 @@ class EMAWeights(torch.nn.Module):
             tables = self._device_tables(device, native, "swap_parameters")
             with torch.cuda.device(device), ktimer.region("ema_swap", 4.0 * tables.nbytes):
                 rc = _lib.load().nqa_ema_swap(_lib.ptr(tables.tensors), _lib.ptr(tables.chunks), tables.capacity,
-                                              _lib.ptr(tables.state[1:]), _lib.stream_ptr(device))
+                                              _lib.ptr(tables.counts), _lib.stream_ptr(device))
             _lib.check(rc, "nqa_ema_swap")
             torch.autograd.graph.increment_version([t for pair in native for t in pair])
         _aten_swap([e for e, _ in rest], [p for _, p in rest])

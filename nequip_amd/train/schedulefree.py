@@ -62,8 +62,8 @@ import torch
 
 from .. import _lib
 from ..utils import ktimer
+from ._multi_tensor import _DT, ChunkTables, n_chunks, require_eager
 
-_DT = {torch.float32: _lib.NQA_F32, torch.float64: _lib.NQA_F64}
 _GROUP_WORDS = 12  # nqa_sfree_group: lr, beta1, beta2, eps, weight_decay, r, weight_lr_power, warmup_steps | k, weight_sum, lr_max, scheduled_lr
 _N_HYPER_WORDS = 8
 CHECKPOINT_KEY = "schedulefree_optimizer_state_dict"
@@ -113,41 +113,26 @@ def _strip_grads(key):
     return None if key is None else tuple(row[:1] + row[2:] for row in key)
 
 
-class _DeviceTables:
-    """What the kernels read on one device: the tensor table, the chunk map, the number of chunks in use and one record per
-    parameter group.  Allocated once and rewritten IN PLACE when the tensors or the hyper-parameters change: a captured launch
-    keeps reading the same buffers."""
+class _DeviceTables(ChunkTables):
+    """The chunk tables of the parameters (``nqa_sfree_tensor``: 6 words each) and one record per parameter group
+    (``nqa_sfree_group``), rewritten in place when the hyper-parameters change."""
 
     def __init__(self, device: torch.device, n_tensors: int, capacity: int, n_groups: int, chunk: int):
-        self.device, self.chunk = device, chunk
-        self.n_tensors, self.capacity, self.n_groups = max(n_tensors, 1), capacity, n_groups
-        self.tensors = torch.zeros(self.n_tensors, 6, dtype=torch.int64, device=device)  # nqa_sfree_tensor: 6 words each
-        self.chunks = torch.zeros(max(capacity, 1), 2, dtype=torch.int64, device=device)  # nqa_ema_chunk: 2 words each
-        self.count = torch.zeros(1, dtype=torch.int64, device=device)
-        self.groups = torch.zeros(n_groups, _GROUP_WORDS, dtype=torch.float64, device=device)  # nqa_sfree_group
-        self.key = None
+        super().__init__(device, chunk, n_tensors, capacity, words=6)
+        self.n_groups = n_groups
+        self.groups = torch.zeros(n_groups, _GROUP_WORDS, dtype=torch.float64, device=device)
         self.hypers = None
         self.step_bytes = 0.0
         self.swap_bytes = 0.0
 
     def fits(self, device: torch.device, rows: List[_Row], n_groups: int) -> bool:
-        return (device == self.device and n_groups == self.n_groups and len(rows) <= self.n_tensors
-                and sum(-(-r[0].numel() // self.chunk) for r in rows) <= self.capacity)
+        return n_groups == self.n_groups and super().fits(device, [r[0].numel() for r in rows])
 
     def write(self, key, rows: List[_Row]) -> None:
         """(little-endian words: ``dtype`` is the low half of its word, ``group`` the high half)"""
-        table = [[p.data_ptr(), 0 if g is None else g.data_ptr(), z.data_ptr(), v.data_ptr(), p.numel(),
-                  _DT[p.dtype] | (gi << 32)] for p, g, z, v, gi in rows]
-        offsets = [torch.arange(0, r[0].numel(), self.chunk, dtype=torch.int64) for r in rows]
-        chunk_rows = [torch.stack([o, torch.full_like(o, i)], dim=1) for i, o in enumerate(offsets)]
-        n_chunks = sum(len(o) for o in offsets)
-        assert len(table) <= self.n_tensors and n_chunks <= self.capacity
-        if table:
-            self.tensors[:len(table)].copy_(torch.tensor(table, dtype=torch.int64))
-        if n_chunks:
-            self.chunks[:n_chunks].copy_(torch.cat(chunk_rows))
-        self.count.copy_(torch.tensor([n_chunks], dtype=torch.int64))
-        self.key = key
+        super().write(key, [r[0].numel() for r in rows], [
+            [p.data_ptr(), 0 if g is None else g.data_ptr(), z.data_ptr(), v.data_ptr(), p.numel(), _DT[p.dtype] | (gi << 32)]
+            for p, g, z, v, gi in rows])
         self.step_bytes = 7.0 * sum(p.numel() * p.element_size() for p, g, _, _, _ in rows if g is not None)
         self.swap_bytes = 3.0 * sum(p.numel() * p.element_size() for p, _, _, _, _ in rows)
 
@@ -271,16 +256,15 @@ class AdamWScheduleFree(torch.optim.Optimizer):
             tables.key == key or (what != "step" and _strip_grads(tables.key) == _strip_grads(key)))
         if same and tables.hypers == hypers:
             return tables
-        if self._capturing():
-            raise RuntimeError(f"AdamWScheduleFree.{what}: call step() once eagerly before capturing it (the device tables are "
-                               "built, and rewritten after a parameter, its .grad or a hyper-parameter changed, eagerly; keep "
-                               "the gradient buffers with zero_grad(set_to_none=False))")
+        require_eager(f"AdamWScheduleFree.{what}: call step() once eagerly before capturing it (the device tables are built, and "
+                      "rewritten after a parameter, its .grad or a hyper-parameter changed, eagerly; keep the gradient buffers "
+                      "with zero_grad(set_to_none=False))")
         with torch.cuda.device(device):
             if not same:
                 if tables is None or not tables.fits(device, native, len(self.param_groups)):
                     self._drop_tables()
                     chunk = int(_lib.load().nqa_ema_chunk_elems())
-                    tables = _DeviceTables(device, len(native), sum(-(-r[0].numel() // chunk) for r in native),
+                    tables = _DeviceTables(device, len(native), n_chunks([r[0].numel() for r in native], chunk),
                                            len(self.param_groups), chunk)
                     tables.write_state(self.param_groups)
                 tables.write(key, native)
@@ -324,7 +308,7 @@ class AdamWScheduleFree(torch.optim.Optimizer):
         if native:
             with torch.cuda.device(device), ktimer.region("sfree_step", tables.step_bytes):
                 rc = _lib.load().nqa_sfree_step(_lib.ptr(tables.tensors), _lib.ptr(tables.chunks), tables.capacity,
-                                                _lib.ptr(tables.count), _lib.ptr(tables.groups), tables.n_groups,
+                                                _lib.ptr(tables.counts), _lib.ptr(tables.groups), tables.n_groups,
                                                 _lib.stream_ptr(device))
             _lib.check(rc, "nqa_sfree_step")
             torch.autograd.graph.increment_version([t for p, g, z, v, _ in native if g is not None for t in (p, z, v)])
@@ -350,7 +334,7 @@ class AdamWScheduleFree(torch.optim.Optimizer):
             tables = self._device_tables(device, native, what)
             with torch.cuda.device(device), ktimer.region("sfree_swap", tables.swap_bytes):
                 rc = _lib.load().nqa_sfree_swap(_lib.ptr(tables.tensors), _lib.ptr(tables.chunks), tables.capacity,
-                                                _lib.ptr(tables.count), _lib.ptr(tables.groups), tables.n_groups, int(to_eval),
+                                                _lib.ptr(tables.counts), _lib.ptr(tables.groups), tables.n_groups, int(to_eval),
                                                 _lib.stream_ptr(device))
             _lib.check(rc, "nqa_sfree_swap")
             torch.autograd.graph.increment_version([r[0] for r in native])

@@ -44,8 +44,8 @@ import torch
 
 from .. import _lib
 from ..utils import ktimer
+from ._multi_tensor import _DT, ChunkTables, n_chunks, require_eager
 
-_DT = {torch.float32: _lib.NQA_F32, torch.float64: _lib.NQA_F64}
 _PREFIX = "training_stats"
 COLUMNS = {"min": 0, "max": 1, "mean": 2, "std": 3, "absmin": 4, "absmax": 5, "rms": 6, "count": 7}
 _IDENTITY, _SQRT = 0, 1  # nqa_tstats_transform
@@ -102,43 +102,25 @@ def _aten_row(t: torch.Tensor, stats: Sequence[str], transform: int) -> torch.Te
     return torch.stack(row)
 
 
-class _DeviceTables:
-    """What the kernels read and write for one hook on one device: the tensor table, the chunk map, ``counts = [chunks,
-    tensors]`` in use, the workspace of chunk rows and ``out``: one row per tensor and a last row whose first word is the step
-    (int64) at which the rows were written.  Allocated once and rewritten IN PLACE: a captured launch keeps its buffers."""
+class _DeviceTables(ChunkTables):
+    """What the kernels read and write for one hook on one device: the chunk tables of the tensors (``nqa_tstats_tensor``: 4 words
+    each), the workspace of chunk rows and ``out``: one row per tensor and a last row whose first word is the step (int64) at
+    which the rows were written."""
 
-    def __init__(self, device: torch.device, n_tensors: int, n_chunks: int, chunk: int):
-        self.device, self.chunk = device, chunk
-        self.n_tensors, self.capacity = max(n_tensors, 1), max(n_chunks, 1)
-        self.tensors = torch.zeros(self.n_tensors, 4, dtype=torch.int64, device=device)  # nqa_tstats_tensor: 4 words each
-        self.chunks = torch.zeros(self.capacity, 2, dtype=torch.int64, device=device)  # nqa_ema_chunk: 2 words each
-        self.counts = torch.zeros(2, dtype=torch.int64, device=device)
+    def __init__(self, device: torch.device, n_tensors: int, capacity: int, chunk: int):
+        super().__init__(device, chunk, n_tensors, max(capacity, 1), words=4)
         self.workspace = torch.zeros(self.capacity, 8, dtype=torch.float64, device=device)
         self.out = torch.zeros(self.n_tensors + 1, 8, dtype=torch.float64, device=device)
         self.stamp = self.out[self.n_tensors].view(torch.int64)[:1]
         self.stamp.fill_(-1)
-        self.key = None
         self.names: Optional[tuple] = None
         self.nbytes = 0
 
-    def fits(self, device: torch.device, entries: List[_Entry]) -> bool:
-        return (device == self.device and len(entries) <= self.n_tensors
-                and sum(-(-e.tensor.numel() // self.chunk) for e in entries) <= self.capacity)
-
     def write(self, key, entries: List[_Entry]) -> None:
         """(little-endian words: ``dtype`` and ``chunk0`` are the low halves of their words, ``transform`` a high half)"""
-        rows, chunk_rows, chunk0 = [], [], 0
-        for i, e in enumerate(entries):
-            t = e.tensor
-            rows.append([t.data_ptr(), t.numel(), _DT[t.dtype] | (e.transform << 32), chunk0])
-            o = torch.arange(0, t.numel(), self.chunk, dtype=torch.int64)
-            chunk_rows.append(torch.stack([o, torch.full_like(o, i)], dim=1))
-            chunk0 += len(o)
-        assert len(rows) <= self.n_tensors and chunk0 <= self.capacity
-        if rows:
-            self.tensors[:len(rows)].copy_(torch.tensor(rows, dtype=torch.int64))
-            self.chunks[:chunk0].copy_(torch.cat(chunk_rows))
-        self.counts.copy_(torch.tensor([chunk0, len(rows)], dtype=torch.int64))
+        tensors = [e.tensor for e in entries]
+        super().write(key, [t.numel() for t in tensors], with_chunk0=True, rows=[
+            [t.data_ptr(), t.numel(), _DT[t.dtype] | (e.transform << 32)] for t, e in zip(tensors, entries)])
         names = tuple((e.head, e.name) for e in entries)
         if names != self.names:  # the rows move with their tensors; those of new tensors hold nothing (count 0) until a step logs
             old = {name: i for i, name in enumerate(self.names or ())}
@@ -147,8 +129,8 @@ class _DeviceTables:
             if kept:
                 moved[[i for i, _ in kept]] = self.out[[j for _, j in kept]]
             self.out[:self.n_tensors].copy_(moved)
-        self.key, self.names = key, names
-        self.nbytes = sum(e.tensor.numel() * e.tensor.element_size() for e in entries)
+        self.names = names
+        self.nbytes = sum(t.numel() * t.element_size() for t in tensors)
 
 
 class _Section:
@@ -205,9 +187,8 @@ class TrainingStatsMonitor:
 
     def _device_counter(self, device: torch.device, what: str) -> torch.Tensor:
         if self._counter is None or self._counter.device != device:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError(f"TrainingStatsMonitor.{what}: run the hooks once eagerly before capturing them (the device "
-                                   "tables and the step counter are built eagerly)")
+            require_eager(f"TrainingStatsMonitor.{what}: run the hooks once eagerly before capturing them (the device tables and "
+                          "the step counter are built eagerly)")
             self._counter = torch.tensor([self.step_count], dtype=torch.int64, device=device)
         return self._counter
 
@@ -246,7 +227,7 @@ class TrainingStatsMonitor:
         """(tensors, chunks): the most a hook can need for this model and these optimizers."""
         def size(ps):
             ps = [p for p in ps if p.numel() > 0]
-            return len(ps), sum(-(-p.numel() // chunk) for p in ps)
+            return len(ps), n_chunks([p.numel() for p in ps], chunk)
 
         trainable = size(p for p in model.parameters() if p.requires_grad)
         if section is self._gradients:
@@ -265,15 +246,14 @@ class TrainingStatsMonitor:
         tables = section.tables
         if tables is not None and tables.key == key and tables.device == device:
             return tables
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"TrainingStatsMonitor.{section.what}: run the hooks once eagerly before capturing them (the "
-                               "device tables are built, and rebuilt after a tensor moved or appeared, eagerly)")
+        require_eager(f"TrainingStatsMonitor.{section.what}: run the hooks once eagerly before capturing them (the device tables "
+                      "are built, and rebuilt after a tensor moved or appeared, eagerly)")
         with torch.cuda.device(device):
-            if tables is None or not tables.fits(device, native):
+            numels = [e.tensor.numel() for e in native]
+            if tables is None or not tables.fits(device, numels):
                 chunk = int(_lib.load().nqa_tstats_chunk_elems())
                 n, c = self._most(section, model, optimizers, chunk)
-                tables = _DeviceTables(device, max(n, len(native)),
-                                       max(c, sum(-(-e.tensor.numel() // chunk) for e in native)), chunk)
+                tables = _DeviceTables(device, max(n, len(native)), max(c, n_chunks(numels, chunk)), chunk)
             tables.write(key, native)
         section.tables = tables
         return tables

@@ -149,6 +149,59 @@ def test_misaligned_views_and_odd_lengths_stay_inside_their_bounds(device, fx, m
     assert calls == {"nqa_ema_update": 2, "nqa_ema_swap": 1}
 
 
+def test_float64_views_take_the_two_element_packs_inside_their_bounds(device, fx, monkeypatch):
+    """The float64 form of the shared chunk walker (packs of two elements): float64 EMA and parameter views of 1, C - 1, C and
+    C + 1 elements at byte offsets 0 and 8 (mod 16) into guarded flat buffers, every combination of the two sides (only 0 / 0
+    takes the 16-byte accesses, with a one-element tail for the odd lengths).  One copying update, one averaging update and one
+    swap; the guards are compared bit for bit."""
+    from nequip_amd.train import EMAWeights
+
+    calls = _native_launches(monkeypatch)
+    chunk = fx.chunk
+    p_spans, e_spans, cursor = [], [], 0
+    for n in (1, chunk - 1, chunk, chunk + 1):
+        for p_off in (0, 1):
+            for e_off in (0, 1):
+                start = (cursor + 3 + 1) // 2 * 2  # an even element (16 bytes) behind three guard elements or more
+                p_spans.append((start + p_off, n))
+                e_spans.append((start + e_off, n))
+                cursor = start + 1 + n
+    g = torch.Generator().manual_seed(5)
+    p_flat = torch.randn(cursor + 4, generator=g, dtype=torch.float64).to(device)
+    e_flat = torch.randn(cursor + 4, generator=g, dtype=torch.float64).to(device)
+    assert p_flat.data_ptr() % 16 == 0 and e_flat.data_ptr() % 16 == 0
+    model = torch.nn.Module()
+    model.p = torch.nn.ParameterList([torch.nn.Parameter(p_flat[s:s + n]) for s, n in p_spans])
+    ema = EMAWeights(model, 0.5).to(device)
+    for i, (s, n) in enumerate(e_spans):
+        setattr(ema, f"ema_weight_{i}", e_flat[s:s + n])
+    assert {(p.data_ptr() % 16, b.data_ptr() % 16) for p, b in zip(model.parameters(), ema.ema_weights)} == \
+        {(0, 0), (0, 8), (8, 0), (8, 8)}
+    p_inside, e_inside = torch.zeros_like(p_flat, dtype=torch.bool), torch.zeros_like(e_flat, dtype=torch.bool)
+    for (ps, n), (es, _) in zip(p_spans, e_spans):
+        p_inside[ps:ps + n] = True
+        e_inside[es:es + n] = True
+
+    e_flat[e_inside] = NAN
+    for n_before in (0, 1):
+        p0, e0 = p_flat.clone(), e_flat.clone()
+        ema.update_parameters(model)
+        assert torch.equal(er.bits(p_flat), er.bits(p0)), "an update must not write the parameters"
+        assert torch.equal(er.bits(e_flat)[~e_inside], er.bits(e0)[~e_inside]), "written outside the EMA views"
+        for (ps, n), (es, _) in zip(p_spans, e_spans):
+            er.assert_update(e_flat[es:es + n], e0[es:es + n], p0[ps:ps + n], n_before, 0.5, f"view at {ps} / {es}, {n} elements")
+        p_flat.add_(torch.randn(p_flat.shape, generator=g, dtype=torch.float64).to(device))
+
+    p0, e0 = p_flat.clone(), e_flat.clone()
+    ema.swap_parameters(model)
+    for (ps, n), (es, _) in zip(p_spans, e_spans):
+        assert torch.equal(er.bits(p_flat[ps:ps + n]), er.bits(e0[es:es + n]))
+        assert torch.equal(er.bits(e_flat[es:es + n]), er.bits(p0[ps:ps + n]))
+    assert torch.equal(er.bits(p_flat)[~p_inside], er.bits(p0)[~p_inside]), "swap wrote outside the parameter views"
+    assert torch.equal(er.bits(e_flat)[~e_inside], er.bits(e0)[~e_inside]), "swap wrote outside the EMA views"
+    assert calls == {"nqa_ema_update": 2, "nqa_ema_swap": 1}
+
+
 # ---- 3 ----------------------------------------------------------------------------------------------------------------------
 def test_swap_is_exact_in_place_and_bumps_versions(device, fx, monkeypatch):
     from nequip_amd.train import EMAWeights
