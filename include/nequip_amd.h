@@ -255,9 +255,10 @@ int nqa_edge_embed_bwd_bwd(int32_t dtype, int32_t lmax, const double* edge_vec, 
  *   v_mfma_f32_32x32x16_bf16 (dropped terms < 2^-24 relative: fp32 accuracy, 2.7x the fp32-MFMA ceiling).  The
  *   small first layer (K = nb) and all element-wise maths are fp32 in both modes.
  * nqa_radial_mlp_bwd is its vector-Jacobian product w.r.t. the edge embedding (inference forces:
- *   nequip/nn/grad_output.py:217-221); pre-activations are recomputed, not stored.  Parameter gradients
- *   (training) are not produced by these entry points -- the host side keeps the reference's mm/SiLU
- *   formulation in training mode.
+ *   nequip/nn/grad_output.py:217-221); pre-activations are recomputed, not stored.  These two entry points give
+ *   no parameter gradients: training runs the variants below (nqa_radial_mlp_bwd_train, nqa_radial_mlp_fwd_tangent),
+ *   which hand out the on-chip pieces of dW0 and dW1.  num_basis 1..8: rows of edge_embedding and of
+ *   grad_edge_embedding have stride num_basis.
  * nqa_radial_mlp_supported returns 1 when (dtype, nb, H, W) can run on the fused kernels
  *   (float32, nb <= 8, H in {64, 128}, W % 4 == 0).  `workspace` (>= nqa_radial_mlp_workspace_bytes(mode,
  *   backward, H, W); 0 for the fp32 forward) receives the re-laid-out / split second-layer weights (a function of
@@ -291,12 +292,16 @@ int nqa_radial_mlp_bwd(int32_t dtype, int32_t mode, const void* edge_embedding, 
 
 /* Training variants of the fused radial MLP (force-matching training differentiates the force pass once more,
  *   nequip/nn/grad_output.py:216-221 `create_graph=self.training`; in the reference all of this is autograd through
- *   ScalarMLPFunction.forward, nequip/nn/mlp.py:194-196).  NQA_MLP_BF16X6 only.  With W_i = w_i alpha_i, P = emb W0,
- *   G_h = grad_edge_weight W1^T:
+ *   ScalarMLPFunction.forward, nequip/nn/mlp.py:194-196).  nqa_radial_mlp_bwd_train: NQA_MLP_BF16X6 or
+ *   NQA_MLP_F16X3 (the host's default, nn/mlp.py::backward_mode); nqa_radial_mlp_fwd_tangent: NQA_MLP_BF16X6 only.
+ *   NQA_MLP_FP32 has no training form and no second gradient stream: NQA_ERR_UNSUPPORTED, outputs untouched.  Every
+ *   output below is tested element by element against float64 (tests/test_radial_mlp_launches.py).  With
+ *   W_i = w_i alpha_i, P = emb W0, G_h = grad_edge_weight W1^T:
  * nqa_radial_mlp_bwd_train, cotangent == NULL (first order, with the pieces of the parameter gradients):
  *     grad_edge_embedding = (G_h silu'(P)) W0^T                       [E, num_basis]
  *     hidden_out          = silu(P)                                   [E, hidden]   (dW1 = alpha1 hidden_out^T grad_edge_weight)
  *     w0_partials[tile]   = emb_tile^T (G_h silu'(P))_tile            [tiles][num_basis][hidden], dW0 = alpha0 sum_tiles
+ *                           (tile t = rows 128 t .. 128 t + 127; every element of every tile is written)
  *   cotangent != NULL ([E, num_basis], a cotangent c of grad_edge_embedding; second order), Q = c W0:
  *     grad_edge_embedding = (Q G_h silu''(P)) W0^T                    = d<c, g_emb>/d emb
  *     hidden_out          = Q silu'(P)                                (d<c,g_emb>/dW1 = alpha1 hidden_out^T grad_edge_weight)
@@ -331,6 +336,8 @@ int nqa_radial_mlp_fwd_tangent(int32_t dtype, int32_t mode, const void* edge_emb
  *   first two weight matrices (out_features = hidden width), whose gradient nqa_radial_mlp_bwd then takes on to the edge
  *   embedding; deeper stacks chain nqa_radial_mlp_last_fwd.  hidden 64 or 128, out_features % 4 == 0, float32, mode
  *   NQA_MLP_F16X3 (fp32-accurate two-plane fp16 split; workspaces as for nqa_radial_mlp_fwd / _bwd in that mode).
+ *   Any other mode, or another hidden width: NQA_ERR_UNSUPPORTED.  `pre` is taken as exact data: silu and silu' are
+ *   evaluated to fp32 accuracy for |pre| up to 30 and beyond (compensated exponent, radial_mlp.hip).
  *   Inference (first order) only: training-mode deep MLPs stay on the ATen formulation. */
 int nqa_radial_mlp_last_fwd(int32_t dtype, int32_t mode, const void* pre, const void* w, double alpha, int32_t hidden,
                             int32_t out_features, int64_t num_edges, void* out, void* workspace, int64_t workspace_bytes,

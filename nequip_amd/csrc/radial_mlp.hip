@@ -61,6 +61,22 @@ __device__ __forceinline__ float silu_grad_f(float x) {
   const float s = 1.0f / (1.0f + __expf(-x));
   return s * (1.0f + x * (1.0f - s));
 }
+// The last-layer entry points (XIN) get their pre-activations as DATA, exact as given.  __expf rounds x log2(e) to fp32
+// before the hardware exponential: an error of |x| 2^-24 relative to the result, 1.8e-6 of silu'(-30), which an fp32
+// evaluation of the same formula does not have (tests/test_radial_mlp_launches.py, the rows of -30).  Here the rounding
+// error of that product -- recovered with one fma -- and the low part of log2(e) enter as a first-order correction.  The
+// two-layer kernels keep __expf: their x = emb W0 is a rounded sum whose own error is of the same size.
+__device__ __forceinline__ float exp_neg_given_f(float x) {
+  constexpr float c_hi = -1.44269502162933349609375f, c_lo = -1.92596299112661746e-8f;  // -log2(e) = c_hi + c_lo
+  const float t = x * c_hi;
+  const float r = __builtin_fmaf(x, c_hi, -t) + x * c_lo;  // -x log2(e) = t + r
+  return __builtin_amdgcn_exp2f(t) * (1.0f + r * 0.693147182f);
+}
+__device__ __forceinline__ float silu_given_f(float x) { return x / (1.0f + exp_neg_given_f(x)); }
+__device__ __forceinline__ float silu_grad_given_f(float x) {
+  const float s = 1.0f / (1.0f + exp_neg_given_f(x));
+  return s * (1.0f + x * (1.0f - s));
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // forward: out[E, W] = silu(emb[E, NB] @ W0s[NB, H]) @ W1s[H, W]
@@ -842,8 +858,8 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_fwd_split_bal_kernel(const 
       }
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
-        const float h0 = row_ok ? silu_f(hacc[r]) : 0.f;
-        const float h1 = row_ok ? silu_f(hacc[r + 1]) : 0.f;
+        const float h0 = row_ok ? (XIN ? silu_given_f(hacc[r]) : silu_f(hacc[r])) : 0.f;
+        const float h1 = row_ok ? (XIN ? silu_given_f(hacc[r + 1]) : silu_f(hacc[r + 1])) : 0.f;
         if constexpr (F16) {
           hv[kb * 16 + r] = h0;
           hv[kb * 16 + r + 1] = h1;
@@ -1277,7 +1293,7 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_bwd_split_kernel(const floa
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int64_t row = blk0 + wv * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (row < E) g_emb[row * H + col] = acc[t][r] * silu_grad_f(pv[r]);
+        if (row < E) g_emb[row * H + col] = acc[t][r] * silu_grad_given_f(pv[r]);
       }
     }
     return;
@@ -1631,7 +1647,8 @@ int mlp_bwd(MlpCall c, int tm, const void* cotangent, void* hidden_out, void* w0
   if (c.workspace == nullptr || c.workspace_bytes < lay.total)
     return fail(NQA_ERR_WORKSPACE, fn + ": workspace missing or too small");
   if (c.mode == NQA_MLP_FP32 && (tm != 0 || gw2 != nullptr))
-    return fail(NQA_ERR_UNSUPPORTED, "nqa_radial_mlp_bwd_train / _paired: only NQA_MLP_BF16X6 is implemented");
+    return fail(NQA_ERR_UNSUPPORTED,
+                "nqa_radial_mlp_bwd_train / _paired: NQA_MLP_BF16X6 or NQA_MLP_F16X3 (no exact-fp32 form)");
   if (gw2 != nullptr && tm != 0) return fail(NQA_ERR_UNSUPPORTED, "nqa_radial_mlp_bwd_paired: inference backward only");
   const MlpWorkspace ws = mlp_view(c.workspace, lay);
   hipStream_t s = static_cast<hipStream_t>(c.stream);

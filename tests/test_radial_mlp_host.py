@@ -296,7 +296,7 @@ REFUSED = {'bwd: E = -1': (-1, 'nqa_radial_mlp_bwd: invalid argument'),
  'bwd_paired: W = 0': (-1, 'nqa_radial_mlp_bwd: invalid argument'),
  'bwd_paired: W = 6': (-1, 'nqa_radial_mlp_bwd: invalid argument (needs out_features % 4 == 0)'),
  'bwd_paired: f16x3 mode, one-byte workspace': (-4, 'nqa_radial_mlp_bwd: workspace missing or too small'),
- 'bwd_paired: fp32 mode': (-2, 'nqa_radial_mlp_bwd_train / _paired: only NQA_MLP_BF16X6 is implemented'),
+ 'bwd_paired: fp32 mode': (-2, 'nqa_radial_mlp_bwd_train / _paired: NQA_MLP_BF16X6 or NQA_MLP_F16X3 (no exact-fp32 form)'),
  'bwd_paired: fp32 mode, one-byte workspace': (-4, 'nqa_radial_mlp_bwd: workspace missing or too small'),
  'bwd_paired: idle hint alone': (-4, 'nqa_radial_mlp_bwd: workspace missing or too small'),
  'bwd_paired: idle hint, one-byte workspace': (-4, 'nqa_radial_mlp_bwd: workspace missing or too small'),
@@ -319,10 +319,10 @@ REFUSED = {'bwd: E = -1': (-1, 'nqa_radial_mlp_bwd: invalid argument'),
  'bwd_train: W = 0': (-1, 'nqa_radial_mlp_bwd: invalid argument'),
  'bwd_train: W = 6': (-1, 'nqa_radial_mlp_bwd: invalid argument (needs out_features % 4 == 0)'),
  'bwd_train: f16x3 mode, one-byte workspace': (-4, 'nqa_radial_mlp_bwd: workspace missing or too small'),
- 'bwd_train: fp32 mode': (-2, 'nqa_radial_mlp_bwd_train / _paired: only NQA_MLP_BF16X6 is implemented'),
+ 'bwd_train: fp32 mode': (-2, 'nqa_radial_mlp_bwd_train / _paired: NQA_MLP_BF16X6 or NQA_MLP_F16X3 (no exact-fp32 form)'),
  'bwd_train: fp32 mode, one-byte workspace': (-4, 'nqa_radial_mlp_bwd: workspace missing or too small'),
  'bwd_train: fp32 mode, second order off': (-2,
-                                            'nqa_radial_mlp_bwd_train / _paired: only NQA_MLP_BF16X6 is implemented'),
+                                            'nqa_radial_mlp_bwd_train / _paired: NQA_MLP_BF16X6 or NQA_MLP_F16X3 (no exact-fp32 form)'),
  'bwd_train: idle hint alone': (-4, 'nqa_radial_mlp_bwd: workspace missing or too small'),
  'bwd_train: idle hint, one-byte workspace': (-4, 'nqa_radial_mlp_bwd: workspace missing or too small'),
  'bwd_train: nb = 0': (-1, 'nqa_radial_mlp_bwd: invalid argument'),
