@@ -1095,6 +1095,43 @@ int nqa_tstats_reduce(const nqa_tstats_tensor* tensors, int64_t tensor_capacity,
                       double* table, int64_t* stamp, nqa_stream stream);
 int nqa_tstats_advance(int64_t* counter, nqa_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Nose-Hoover / velocity-Verlet molecular dynamics (the scheme of nequip/ase/nosehoover.py) with the state in device memory:
+ *   positions, velocities, masses (float64, [N, 3] / [N]) and the record below.  One MD step is nqa_md_step followed by
+ *   nqa_md_bath on the same stream, then one force evaluation at the new positions by the caller.
+ *   With F the force at the current positions (float32 or float64, promoted on load), m the masses, hdt = dt / 2:
+ * nqa_md_step: flat over the 3N components (component i belongs to atom i / 3), one launch.
+ *   (1) unless state->fresh: v = (v + hdt F/m) / (1 + hdt xi), which completes the PREVIOUS step (its last line needs this
+ *       step's force; between two steps `velocities` holds the half-step velocities);
+ *   (2) a = F/m - xi v;  x += dt v + dt^2/2 a;  v_half = v + hdt a, written to `velocities`.
+ *   Workgroup b (NQA_MD_THREADS components) writes partials[2b] = sum m v^2 over the completed velocities of (1) and
+ *   partials[2b + 1] = sum m v_half^2, both summed in a fixed order; `partials` holds 2 * nqa_md_num_partials(N) doubles.
+ *   NQA_MD_FINISH_ONLY: only (1), written to `vel_out` ([N, 3], required in this mode); positions, velocities and the record are
+ *   not written, partials[2b + 1] = 0.  Give this mode a partials table of its own if the sums of the last step are still needed.
+ * nqa_md_bath: one wavefront; adds the rows of `partials` in a fixed order to S = sum m v^2 and S_half = sum m v_half^2, then
+ *   with NQA_MD_THERMOSTAT: xi_half = xi + hdt (S - g) / (2 Q);  xi = xi_half + hdt (S_half - g) / (2 Q)   (without: xi untouched)
+ *   kinetic_energy = S / 2 (of the completed velocities, i.e. at the START of this step);  nsteps += 1;  fresh = 0.
+ *   NQA_MD_FINISH_ONLY: observed_kinetic_energy = S / 2 and nothing else.
+ *   The record is rewritten by this second launch so that no workgroup of nqa_md_step sees the new xi (launches of one stream
+ *   run in order).  g = (3N + 1) kB T, as in the reference.  The host may rewrite dt, g and q in place between steps.
+ *   No floating-point atomics, no fused multiply-adds: the same inputs give the same bits, and (1) gives the same bits in both
+ *   modes.  No allocation, no host synchronisation: both capture into a hipGraph.
+ * ------------------------------------------------------------------------------------------- */
+#define NQA_MD_THREADS 256
+
+enum nqa_md_mode { NQA_MD_FINISH_ONLY = 1, NQA_MD_THERMOSTAT = 2 };
+
+typedef struct nqa_md_state {
+  double dt, g, q, xi, kinetic_energy;
+  int64_t nsteps, fresh; /* fresh != 0: `velocities` holds completed velocities, (1) is skipped */
+  double observed_kinetic_energy;
+} nqa_md_state;
+
+int64_t nqa_md_num_partials(int64_t num_atoms);
+int nqa_md_step(int32_t force_dtype, const void* forces, const double* masses, double* positions, double* velocities,
+                double* vel_out, int64_t num_atoms, const nqa_md_state* state, double* partials, int32_t mode, nqa_stream stream);
+int nqa_md_bath(const double* partials, int64_t num_partials, nqa_md_state* state, int32_t mode, nqa_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -395,6 +395,10 @@ SIGNATURES = {
     "nqa_tstats_reduce": (
         c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nqa_tstats_advance": (c_int32, [c_void_p, c_void_p]),
+    "nqa_md_num_partials": (c_int64, [c_int64]),
+    "nqa_md_step": (
+        c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
+    "nqa_md_bath": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
 }
 
 # nqa_tp_scatter_<family>_paired: the family's arguments with (weight_rows, num_pairs) before the stream
