@@ -75,6 +75,7 @@ struct NodeFusedArgs {
   int32_t grp_n[kNFMaxChunks];
 };
 static_assert(sizeof(NodeFusedArgs) <= 3900, "kernel arguments must stay below 4 KiB");
+static_assert(kNFMaxChunks <= kMaxNodeChunks, "the unit plan's group tables hold kMaxNodeChunks chunks");
 
 // Activations of the fused stage: one v_exp_f32 + one v_rcp_f32 per value (1 ulp each) instead of expf() and an IEEE
 // division -- a unit re-activates the gate scalars of every slab it stages (8 per lane and stage), which at ~20
@@ -107,10 +108,7 @@ struct NFStage {  // one (instruction, atom type, 32-channel K slab) step of a c
   bool valid;
 };
 
-// PIPE: the stage loop of node_linear_wave_bf16_unit<D, true, PIPE = true> (node_ops.hip): one wait per stage, at its top, for
-// loads requested a full stage earlier -- the x slab, the gate scalars and BOTH K blocks' weight fragments of stage s + 1 go
-// out right after the slab of stage s is in LDS (second fragment buffer, loop unrolled by two); two wavefronts per SIMD.
-template <int D, bool PIPE>
+template <int D>
 __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NFChunk& ch, int64_t g,
                                                 float* __restrict__ xs, float* __restrict__ gs) {
   constexpr int NZT = 32 / D;
@@ -395,59 +393,6 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
   float4 gr0[XG4];
   NFStage cur = first_stage();
   NFStage ld = cur;
-  if constexpr (PIPE) {
-    u32x4 Ap[2][2][2][2];  // [buffer][K block][tile][plane]
-    int wep[2][2];
-    auto load_a2 = [&](int b, const NFStage& st) __attribute__((always_inline)) {
-      const NFSet& s = a.sets[__builtin_amdgcn_readfirstlane(st.set)];
-      const int k16a = st.k0 >> 4;
-      const bool second = st.k0 + 16 < st.mul_in;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        const int k16 = (kb == 1 && second) ? k16a + 1 : k16a;
-        const u32x4* __restrict__ p = s.wf + (int64_t)st.t * s.frag_stride + st.frag_off + lane +
-                                         ((int64_t)(k16 * nct + ct0) * 2) * 64;
-        Ap[b][kb][0][0] = p[0]; Ap[b][kb][0][1] = p[64];
-        if (two_tiles) { Ap[b][kb][1][0] = p[128]; Ap[b][kb][1][1] = p[192]; }
-        wep[b][kb] = s.wexp[__builtin_amdgcn_readfirstlane(st.t * s.exp_stride + st.exp_off + k16)];
-      }
-    };
-    auto blocks = [&](int b, const NFStage& st) __attribute__((always_inline)) {
-      const bool bsel = col_ok && (st.n_types == 1 || tzj == st.t);
-      const bool gated = st.gate_off >= 0;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-        for (int tl2 = 0; tl2 < 2; ++tl2) {
-          Af[tl2][0] = Ap[b][kb][tl2][0];
-          Af[tl2][1] = Ap[b][kb][tl2][1];
-        }
-        we_blk = wep[b][kb];
-        block(kb, bsel, gated, st.n_types > 1);
-      }
-    };
-    if (ld.valid) { load_x(xr0, ld); load_g(gr0, ld); load_a2(0, ld); ld = next_stage(ld); }
-    asm volatile("" ::"v"(tzj));  // (consume the atom-type load once, outside the loop: see node_linear_wave_bf16_unit)
-    while (cur.valid) {
-      store_x(xr0, cur);
-      store_g(gr0, cur);
-      __builtin_amdgcn_sched_barrier(0);
-      if (ld.valid) { load_x(xr0, ld); load_g(gr0, ld); load_a2(1, ld); }
-      __builtin_amdgcn_sched_barrier(0);
-      blocks(0, cur);
-      cur = ld;
-      ld = next_stage(ld);
-      if (!cur.valid) break;
-      store_x(xr0, cur);
-      store_g(gr0, cur);
-      __builtin_amdgcn_sched_barrier(0);
-      if (ld.valid) { load_x(xr0, ld); load_g(gr0, ld); load_a2(0, ld); }
-      __builtin_amdgcn_sched_barrier(0);
-      blocks(1, cur);
-      cur = ld;
-      ld = next_stage(ld);
-    }
-  } else {
   if (ld.valid) { load_x(xr0, ld); load_g(gr0, ld); ld = next_stage(ld); }
   while (cur.valid) {
     store_x(xr0, cur);
@@ -472,7 +417,6 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
       }
     }
     cur = next_stage(cur);
-  }
   }
 
   // ---- epilogue: accumulators -> the wavefront's slab -> contiguous runs per atom, through the chunk's epilogue
@@ -616,8 +560,7 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
   }
 }
 
-template <bool PIPE>
-__global__ __launch_bounds__(64 * kNLWavesPerWG, PIPE ? 2 : 3) void node_fused_kernel(const NodeFusedArgs a_kernarg) {
+__global__ __launch_bounds__(64 * kNLWavesPerWG, 3) void node_fused_kernel(const NodeFusedArgs a_kernarg) {
   __shared__ __align__(16) float xs_all[kNLWavesPerWG * (kNLXS + kNFGS)];
   // The tables are read where the dispatch packet put them (the kernel-argument segment; this kernel's only argument sits at
   // its start): with the by-value parameter the compiler kept a 3 KiB private copy of the struct per lane -- scratch stores
@@ -635,11 +578,11 @@ __global__ __launch_bounds__(64 * kNLWavesPerWG, PIPE ? 2 : 3) void node_fused_k
   const NFChunk ch = a.chunks[a.grp_chunk0[gi] + local % n];
   const int64_t g = (int64_t)(local / n);
   switch (ch.d) {
-    case 1: node_fused_unit<1, PIPE>(a, ch, g, xs, gs); break;
-    case 3: node_fused_unit<3, PIPE>(a, ch, g, xs, gs); break;
-    case 5: node_fused_unit<5, PIPE>(a, ch, g, xs, gs); break;
-    case 7: node_fused_unit<7, PIPE>(a, ch, g, xs, gs); break;
-    case 9: node_fused_unit<9, PIPE>(a, ch, g, xs, gs); break;
+    case 1: node_fused_unit<1>(a, ch, g, xs, gs); break;
+    case 3: node_fused_unit<3>(a, ch, g, xs, gs); break;
+    case 5: node_fused_unit<5>(a, ch, g, xs, gs); break;
+    case 7: node_fused_unit<7>(a, ch, g, xs, gs); break;
+    case 9: node_fused_unit<9>(a, ch, g, xs, gs); break;
     default: break;
   }
 }
@@ -652,7 +595,7 @@ namespace {
 struct NFPlanned {
   std::vector<nqa::NFChunk> chunks;
   std::vector<nqa::NFInstr> instr;
-  std::vector<int> stages;  // per chunk
+  std::vector<NodeUnitChunk> units;  // d and stage count of every chunk
 };
 
 const nqa_gate_block* nf_find_block(const nqa_gate_block* blocks, int32_t n, int32_t off, int32_t d, int32_t mul) {
@@ -743,7 +686,7 @@ std::string nf_plan(const nqa_node_part* parts, int32_t n_parts, const nqa_gate_
     const NodeChunk* chunks = static_cast<const NodeChunk*>(pt.chunk_table);
     for (int c = 0; c < pt.n_chunks; ++c) {
       const NodeChunk& cc = chunks[c];
-      if (cc.d != 1 && cc.d != 3 && cc.d != 5 && cc.d != 7 && cc.d != 9) return "irrep dimension above 9 (l > 4)";
+      if (!node_d_ok(cc.d)) return "irrep dimension above 9 (l > 4)";
       if (cc.c0 % 64 != 0) return "chunks must start at multiples of 64 channels";
       NFChunk r{};
       r.o_off = cc.o_off;
@@ -788,7 +731,7 @@ std::string nf_plan(const nqa_node_part* parts, int32_t n_parts, const nqa_gate_
       for (int q = r.instr_begin; q < r.instr_end; ++q)
         st += parts[P.instr[q].set].n_types * ((P.instr[q].mul_in + nqa::kNLK3 - 1) / nqa::kNLK3);
       P.chunks.push_back(r);
-      P.stages.push_back(st);
+      P.units.push_back({r.d, st});
     }
   }
   if ((int)P.instr.size() > kNFMaxInstr) return "more than 48 instructions in one fused launch";
@@ -863,54 +806,29 @@ int nqa_node_fused(const nqa_node_part* parts, int32_t n_parts, const int64_t* a
   a.perm = atom_order;
   a.N = num_nodes;
   std::memcpy(a.instr, P.instr.data(), sizeof(NFInstr) * P.instr.size());
-  const int n_chunks = (int)P.chunks.size();
-  std::vector<int> order(n_chunks);
-  for (int c = 0; c < n_chunks; ++c) order[c] = c;
-  std::stable_sort(order.begin(), order.end(), [&](int l, int r) { return P.stages[l] > P.stages[r]; });
   hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int c0 = 0; c0 < n_chunks; c0 += kNFMaxChunks) {
-    const int nc = std::min(n_chunks - c0, kNFMaxChunks);
-    int64_t nblk = 0;
-    int ng = 0;
-    for (int c = 0; c < nc; ++c) {
-      a.chunks[c] = P.chunks[order[c0 + c]];
-      const NFChunk& cc = a.chunks[c];
-      const bool same = c > 0 && cc.instr_begin == a.chunks[c - 1].instr_begin && cc.instr_end == a.chunks[c - 1].instr_end &&
-                        cc.d == a.chunks[c - 1].d && cc.o_off == a.chunks[c - 1].o_off && cc.dst == a.chunks[c - 1].dst;
-      const int per_unit = 32 / cc.d;
-      if (!same) {
-        a.grp_begin[ng] = (int32_t)nblk;
-        a.grp_chunk0[ng] = c;
-        a.grp_n[ng] = 0;
-        ++ng;
-      }
-      ++a.grp_n[ng - 1];
-      nblk += (num_nodes + per_unit - 1) / per_unit;
-    }
-    a.grp_begin[ng] = (int32_t)nblk;
-    a.n_groups = ng;
-    a.n_chunks = nc;
-    if (nblk > 2147483647LL) {
-      set_error("nqa_node_fused: too many work units for one launch");
-      return NQA_ERR_UNSUPPORTED;
-    }
-    // NQA_NODE_PIPE=1: the one-wait-per-stage loop at two wavefronts per SIMD.  Measured (cfg-3 and cu20k, same box): no
-    // faster -- these kernels are bound by how many vector instructions a stage issues with three wavefronts sharing a
-    // SIMD, not by the waits of one wavefront, and the second fragment buffer costs the third wavefront.
-    const char* pe = std::getenv("NQA_NODE_PIPE");
-    if (pe != nullptr && pe[0] == '1')
-      hipLaunchKernelGGL(node_fused_kernel<true>, dim3((unsigned)((nblk + kNLWavesPerWG - 1) / kNLWavesPerWG)),
-                         dim3(64 * kNLWavesPerWG), 0, s, a);
-    else
-      hipLaunchKernelGGL(node_fused_kernel<false>, dim3((unsigned)((nblk + kNLWavesPerWG - 1) / kNLWavesPerWG)),
-                         dim3(64 * kNLWavesPerWG), 0, s, a);
+  const char* perr = node_plan_units(
+      P.units, num_nodes, kNFMaxChunks, true,
+      [&](int l, int r) {
+        const NFChunk &cl = P.chunks[l], &cr = P.chunks[r];
+        return cl.instr_begin == cr.instr_begin && cl.instr_end == cr.instr_end && cl.d == cr.d && cl.o_off == cr.o_off &&
+               cl.dst == cr.dst;
+      },
+      [&](const NodeUnitSlice& sl) {
+        for (int c = 0; c < sl.n; ++c) a.chunks[c] = P.chunks[sl.order[c]];
+        a.n_chunks = sl.n;
+        a.n_groups = sl.n_groups;
+        std::memcpy(a.grp_begin, sl.grp_begin, sizeof(a.grp_begin));
+        std::memcpy(a.grp_chunk0, sl.grp_chunk0, sizeof(a.grp_chunk0));
+        std::memcpy(a.grp_n, sl.grp_n, sizeof(a.grp_n));
+        hipLaunchKernelGGL(node_fused_kernel, dim3((unsigned)((sl.units + kNLWavesPerWG - 1) / kNLWavesPerWG)),
+                           dim3(64 * kNLWavesPerWG), 0, s, a);
+      });
+  if (perr != nullptr) {
+    set_error(std::string("nqa_node_fused: ") + perr);
+    return NQA_ERR_UNSUPPORTED;
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string("nqa_node_fused: ") + hipGetErrorString(e));
-    return NQA_ERR_LAUNCH;
-  }
-  return NQA_OK;
+  return launch_status("nqa_node_fused");
 }
 
 // The merged tables of a launch, for host-side tests (no GPU): chunk records of 12 int32 (cst as float bits), instruction

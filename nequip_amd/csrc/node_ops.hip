@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "launch_status.h"
 #include "mfma_split.h"
 #include "plan.h"
 
@@ -53,7 +54,7 @@ struct NodeLinearArgs {
   // the types it does not hold (node_fused.h)
   const int32_t* __restrict__ perm;
   int32_t n_chunks, n_types, din, dout;
-  int32_t dbg;  // ablation switches (NQA_NODE_DBG), 0 in production
+  int32_t pad0;  // always 0, read by nothing (keeps the offsets of the members below)
   int64_t wstride;
   int64_t N;
   T scale;
@@ -606,17 +607,9 @@ struct NodeStage {  // one (instruction, atom type, 32-channel K slab) step of a
   bool valid;
 };
 
-// PIPE (F16 only; round 4): the stage loop restructured around how the memory counter retires.  vmcnt retires IN ORDER, and
-// across the branches of this loop the compiler waits with vmcnt(0): in the loop above the weight fragments of a stage's
-// second K block are requested AFTER the next stage's x slab, so waiting for them drains the slab prefetch as well -- every
-// stage pays the full HBM latency twice (ISA: `s_waitcnt vmcnt(0)` in front of both MFMA groups; per-unit timeline 8-10 k
-// cycles per stage for ~1.5 k cycles of issue).  Here a stage has ONE wait, at its top, for loads that were all requested a
-// full stage earlier: x slab AND both K blocks' fragments of stage s+1 go out right after the slab of stage s has been
-// written to LDS, into a second fragment buffer (the stage loop is unrolled by two so that both buffers are addressed
-// statically); inside a stage nothing waits on memory.  64 fragment registers instead of 16: two wavefronts per SIMD.
-template <int D, bool F16, bool PIPE = false>
+template <int D, bool F16>
 __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPackedArgs& pa, const NodeChunk& ch, int64_t g,
-                                                           float* __restrict__ xs, int unit) {
+                                                           float* __restrict__ xs) {
   constexpr int NPL = F16 ? 2 : 3;  // operand planes
   const NodeLinearArgs<float>& a = pa.base;
   constexpr int NZT = 32 / D;
@@ -873,80 +866,13 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
     }
   };
 
-  int nst = 0;
-  const bool tl = (a.dbg & 64) != 0;
-  unsigned* tl_dst = reinterpret_cast<unsigned*>(a.out) + (int64_t)unit * 16;
-  unsigned long long tl_t0 = 0;
-  auto stamp = [&]() {
-    if (nst < 13) {
-      const unsigned long long tt = __builtin_readcyclecounter();
-      if (nst == 0) tl_t0 = tt;
-      if (lane == 0) tl_dst[1 + nst] = nst == 0 ? (unsigned)(tt & 0xffffffffu) : (unsigned)(tt - tl_t0);
-      ++nst;
-    }
-  };
-  if (tl) stamp();
-
   // one stage: slab registers -> LDS, request the next slab into the same registers, then the K blocks of the slab
   float4 xr0[XV4];
   NodeStage cur = first_stage();
   NodeStage ld = cur;  // the stage whose slab is requested next
-  if constexpr (PIPE && F16) {
-    u32x4 Ap[2][2][2][2];  // [buffer][K block][tile][plane]
-    int wep[2][2];
-    auto load_a2 = [&](int b, const NodeStage& st) {
-      const int k16a = st.k0 >> 4;
-      const bool second = st.k0 + 16 < st.mul_in;  // (a slab of <= 16 channels repeats its block with B = 0)
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        const int k16 = (kb == 1 && second) ? k16a + 1 : k16a;
-        const u32x4* __restrict__ p = pa.wf + (int64_t)st.t * pa.frag_stride + pa.frag_off[st.q] + lane +
-                                         ((int64_t)(k16 * nct + ct0) * 2) * 64;
-        Ap[b][kb][0][0] = p[0]; Ap[b][kb][0][1] = p[64];
-        if (two_tiles) { Ap[b][kb][1][0] = p[128]; Ap[b][kb][1][1] = p[192]; }
-        // (scalar load: a vector load here would sit in the in-order vmcnt queue behind the slab prefetch)
-        wep[b][kb] = pa.wexp[__builtin_amdgcn_readfirstlane(st.t * pa.exp_stride + a.instr[st.q].pad + k16)];
-      }
-    };
-    auto blocks = [&](int b, const NodeStage& st) {
-      const bool bsel = col_ok && (a.n_types == 1 || tzj == st.t);
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-        for (int tl2 = 0; tl2 < 2; ++tl2) {
-          Af[0][tl2][0] = Ap[b][kb][tl2][0];
-          Af[0][tl2][1] = Ap[b][kb][tl2][1];
-        }
-        we_blk = wep[b][kb];
-        block(0, kb, bsel && (st.k0 + 16 * kb < st.mul_in));
-      }
-    };
-    if (ld.valid) { load_x(xr0, ld); load_a2(0, ld); ld = next_stage(ld); }
-    // the atom type of this lane's column was requested at the top of the unit: consume the load HERE, once -- its first use
-    // inside the loop would otherwise carry a vmcnt(0) into every stage
-    asm volatile("" ::"v"(tzj));
-    while (cur.valid) {
-      store_x(xr0, cur);
-      __builtin_amdgcn_sched_barrier(0);
-      if (ld.valid) { load_x(xr0, ld); load_a2(1, ld); }
-      __builtin_amdgcn_sched_barrier(0);
-      blocks(0, cur);
-      cur = ld;
-      ld = next_stage(ld);
-      if (!cur.valid) break;
-      store_x(xr0, cur);
-      __builtin_amdgcn_sched_barrier(0);
-      if (ld.valid) { load_x(xr0, ld); load_a2(0, ld); }
-      __builtin_amdgcn_sched_barrier(0);
-      blocks(1, cur);
-      cur = ld;
-      ld = next_stage(ld);
-    }
-  } else {
   if (ld.valid) { load_x(xr0, ld); ld = next_stage(ld); }
   while (cur.valid) {
     store_x(xr0, cur);
-    if (tl) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); stamp(); }
     const int k16a = cur.k0 >> 4;
     load_a(0, cur, k16a);
     __builtin_amdgcn_sched_barrier(0);
@@ -965,12 +891,6 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
       }
     }
     cur = next_stage(cur);
-  }
-  }
-  if (tl) {
-    stamp();
-    if (lane == 0) tl_dst[0] = (unsigned)nst;
-    return;
   }
   // ---- epilogue (as in node_linear_wave_unit)
   constexpr int SE = kNLW * D + P;
@@ -1055,34 +975,11 @@ __global__ __launch_bounds__(64 * kNLWavesPerWG, 3) void node_linear_wave_bf16_k
   const NodeChunk ch = a.chunks[pa.grp_chunk0[gi] + local % n];
   const int64_t g = (int64_t)(local / n);
   switch (ch.d) {
-    case 1: node_linear_wave_bf16_unit<1, F16>(pa, ch, g, xs, unit); break;
-    case 3: node_linear_wave_bf16_unit<3, F16>(pa, ch, g, xs, unit); break;
-    case 5: node_linear_wave_bf16_unit<5, F16>(pa, ch, g, xs, unit); break;
-    case 7: node_linear_wave_bf16_unit<7, F16>(pa, ch, g, xs, unit); break;
-    case 9: node_linear_wave_bf16_unit<9, F16>(pa, ch, g, xs, unit); break;
-    default: break;
-  }
-}
-
-__global__ __launch_bounds__(64 * kNLWavesPerWG, 2) void node_linear_pipe_kernel(const NodeLinearPackedArgs pa) {
-  __shared__ __align__(16) float xs_all[kNLWavesPerWG * kNLXS];
-  const NodeLinearArgs<float>& a = pa.base;
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int unit = (int)blockIdx.x * kNLWavesPerWG + wv;
-  if (unit >= pa.grp_begin[pa.n_groups]) return;
-  float* xs = xs_all + wv * kNLXS;
-  int gi = 0;
-  while (gi + 1 < pa.n_groups && unit >= pa.grp_begin[gi + 1]) ++gi;
-  const int local = unit - pa.grp_begin[gi];
-  const int n = pa.grp_n[gi];
-  const NodeChunk ch = a.chunks[pa.grp_chunk0[gi] + local % n];
-  const int64_t g = (int64_t)(local / n);
-  switch (ch.d) {
-    case 1: node_linear_wave_bf16_unit<1, true, true>(pa, ch, g, xs, unit); break;
-    case 3: node_linear_wave_bf16_unit<3, true, true>(pa, ch, g, xs, unit); break;
-    case 5: node_linear_wave_bf16_unit<5, true, true>(pa, ch, g, xs, unit); break;
-    case 7: node_linear_wave_bf16_unit<7, true, true>(pa, ch, g, xs, unit); break;
-    case 9: node_linear_wave_bf16_unit<9, true, true>(pa, ch, g, xs, unit); break;
+    case 1: node_linear_wave_bf16_unit<1, F16>(pa, ch, g, xs); break;
+    case 3: node_linear_wave_bf16_unit<3, F16>(pa, ch, g, xs); break;
+    case 5: node_linear_wave_bf16_unit<5, F16>(pa, ch, g, xs); break;
+    case 7: node_linear_wave_bf16_unit<7, F16>(pa, ch, g, xs); break;
+    case 9: node_linear_wave_bf16_unit<9, F16>(pa, ch, g, xs); break;
     default: break;
   }
 }
@@ -1272,6 +1169,140 @@ __global__ __launch_bounds__(256) void gate_bwd_bwd_x_kernel(const GateArgs<T> a
 
 using namespace nqa;
 
+// ---- host side ------------------------------------------------------------------------------------------------------
+namespace {
+
+// two-plane fp16 split with running column scales (default) or the three-plane bf16 split (NQA_NODE_F16=0).  Read once per
+// entry point and passed down: a packed buffer must be used in the mode it was packed in (the Python host and the torch ops
+// key their caches on the same rule: unset, or any value that does not start with '0', means fp16).
+bool node_f16() { return env_flag("NQA_NODE_F16", true); }
+
+bool node_d_ok(int d) { return d == 1 || d == 3 || d == 5 || d == 7 || d == 9; }
+
+// ---- unit plan of the per-wavefront kernels ----------------------------------------------------------------------------
+// A work unit is (64-channel chunk, floor(32/d) atoms).  The chunks of a map are sorted ONCE, most stages first (stable: the
+// long units are dispatched first), and cut into launches of at most `capacity` chunks.  Within a launch the units are
+// enumerated group by group: with `merge`, consecutive chunks of one output block (same instructions, same x columns) form a
+// group whose unit u is (atom group u / n, chunk u % n) -- the chunks that read the same x slab run next to each other;
+// without, every chunk is a group of its own (grp_begin is then the first unit of every chunk).
+struct NodeUnitChunk {
+  int d, stages;
+};
+struct NodeUnitSlice {  // one launch
+  const int* order;     // its n chunks, as indices into the caller's table
+  int n, n_groups;
+  int64_t units;
+  int32_t grp_begin[kMaxNodeChunks + 1], grp_chunk0[kMaxNodeChunks], grp_n[kMaxNodeChunks];
+};
+
+// same(l, r): chunks l and r of the caller's table belong to one output block.  launch(slice) is called once per launch.
+// Returns nullptr, or the text of an NQA_ERR_UNSUPPORTED error (nothing more is launched after one).
+template <class Same, class Launch>
+const char* node_plan_units(const std::vector<NodeUnitChunk>& chunks, int64_t num_nodes, int capacity, bool merge, Same same,
+                            Launch launch) {
+  const int n_chunks = (int)chunks.size();
+  std::vector<int> order(n_chunks);
+  for (int c = 0; c < n_chunks; ++c) {
+    if (!node_d_ok(chunks[c].d)) return "irrep dimension above 9 (l > 4)";
+    order[c] = c;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int l, int r) { return chunks[l].stages > chunks[r].stages; });
+  for (int c0 = 0; c0 < n_chunks; c0 += capacity) {
+    NodeUnitSlice sl{};
+    sl.order = order.data() + c0;
+    sl.n = std::min(n_chunks - c0, capacity);
+    for (int c = 0; c < sl.n; ++c) {
+      if (!(merge && c > 0 && same(sl.order[c - 1], sl.order[c]))) {
+        sl.grp_begin[sl.n_groups] = (int32_t)sl.units;
+        sl.grp_chunk0[sl.n_groups] = c;
+        ++sl.n_groups;
+      }
+      ++sl.grp_n[sl.n_groups - 1];
+      const int per_unit = 32 / chunks[sl.order[c]].d;
+      sl.units += (num_nodes + per_unit - 1) / per_unit;
+      if (sl.units > 2147483647LL) return "too many work units for one launch";
+    }
+    sl.grp_begin[sl.n_groups] = (int32_t)sl.units;
+    launch(sl);
+  }
+  return nullptr;
+}
+
+int node_stages(const NodeInstr* instr, int begin, int end, int n_types) {  // (instruction, atom type, 32-channel K slab)
+  int st = 0;
+  for (int q = begin; q < end; ++q) st += n_types * ((instr[q].mul_in + kNLK3 - 1) / kNLK3);
+  return st;
+}
+static_assert(kNLK2 == kNLK3, "one stage count serves the exact and the split kernels");
+
+// everything of NodeLinearArgs<T> but the chunk tables (those are filled per launch)
+template <typename T>
+void node_fill_args(NodeLinearArgs<T>& a, const void* x, const void* w, const void* addend, void* out, const int64_t* types,
+                    const int32_t* perm, const void* instr_table, int32_t n_instr, int32_t n_types, int64_t wstride,
+                    int32_t dim_in, int32_t dim_out, int64_t num_nodes, double scale) {
+  a.x = static_cast<const T*>(x);
+  a.w = static_cast<const T*>(w);
+  a.addend = static_cast<const T*>(addend);
+  a.out = static_cast<T*>(out);
+  a.types = n_types > 1 ? types : nullptr;
+  a.perm = perm;
+  if (n_instr > 0) std::memcpy(a.instr, instr_table, sizeof(NodeInstr) * (size_t)n_instr);
+  a.n_types = n_types;
+  a.din = dim_in;
+  a.dout = dim_out;
+  a.wstride = wstride;
+  a.N = num_nodes;
+  a.scale = (T)scale;
+}
+
+// VALU kernel (float64, and float32 on request): a workgroup stages the rows of kNZ atoms; the caller's chunk order, at most
+// kMaxNodeChunks chunks per launch -- chunk records are self-contained (absolute offsets / instruction ranges)
+template <typename T>
+void node_launch_valu(NodeLinearArgs<T>& a, const NodeChunk* chunks, int32_t n_chunks, size_t smem, hipStream_t s) {
+  if (smem > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(node_linear_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)smem);
+  for (int32_t c0 = 0; c0 < n_chunks; c0 += kMaxNodeChunks) {
+    a.n_chunks = std::min(n_chunks - c0, kMaxNodeChunks);
+    std::memcpy(a.chunks, chunks + c0, sizeof(NodeChunk) * (size_t)a.n_chunks);
+    const dim3 grid((unsigned)((a.N + kNZ - 1) / kNZ), (unsigned)((a.n_chunks + 3) / 4));
+    hipLaunchKernelGGL(node_linear_kernel<T>, grid, dim3(256), smem, s, a);
+  }
+}
+
+// fragment layout of one atom type: per instruction ceil(mul_in / 16) x ceil(mul_out / 32) fragments of `planes` x 64 lanes
+// (uint4 each); mul_out is that of the output block the instruction feeds.  Returns the uint4 count per type, -1 on error.
+int64_t node_frag_layout(const nqa::NodeChunk* chunks, int32_t n_chunks, const nqa::NodeInstr* instr, int32_t n_instr,
+                         int32_t* frag_off, int32_t* mul_out, int planes) {
+  for (int q = 0; q < n_instr; ++q) mul_out[q] = 0;
+  for (int c = 0; c < n_chunks; ++c)
+    for (int q = chunks[c].instr_begin; q < chunks[c].instr_end; ++q) {
+      if (q < 0 || q >= n_instr) return -1;
+      mul_out[q] = chunks[c].mul_out;
+    }
+  int64_t off = 0;
+  for (int q = 0; q < n_instr; ++q) {
+    frag_off[q] = (int32_t)off;
+    off += (int64_t)((instr[q].mul_in + 15) / 16) * ((mul_out[q] + 31) / 32) * planes * 64;
+    if (off > 2147483647LL) return -1;
+  }
+  frag_off[n_instr] = (int32_t)off;
+  return off;
+}
+
+// exponent table of the F16 layout: one int per (instruction, 16-row K block); returns the count per type
+int32_t node_exp_layout(const nqa::NodeInstr* instr, int32_t n_instr, int32_t* exp_off) {
+  int32_t off = 0;
+  for (int q = 0; q < n_instr; ++q) {
+    exp_off[q] = off;
+    off += (instr[q].mul_in + 15) / 16;
+  }
+  exp_off[n_instr] = off;
+  return off;
+}
+
+}  // namespace
+
 extern "C" {
 
 int nqa_node_linear(int32_t dtype, const void* x, const void* weights, const void* addend, void* out,
@@ -1302,18 +1333,6 @@ int nqa_node_linear_ordered(int32_t dtype, const void* x, const void* weights, c
     set_error("nqa_node_linear: more than 64 instructions in one call");
     return NQA_ERR_UNSUPPORTED;
   }
-  if (n_chunks > kMaxNodeChunks && chunk_table != nullptr) {
-    // wide layers (e.g. l_max = 3 with 128 features: > 40 output chunks): one launch per group of chunks -- chunk
-    // records are self-contained (absolute offsets / instruction ranges)
-    for (int32_t c0 = 0; c0 < n_chunks; c0 += kMaxNodeChunks) {
-      const int32_t nc = n_chunks - c0 < kMaxNodeChunks ? n_chunks - c0 : kMaxNodeChunks;
-      const int rc = nqa_node_linear_ordered(dtype, x, weights, addend, out, atom_types, atom_order,
-                                             static_cast<const NodeChunk*>(chunk_table) + c0, nc, instr_table, n_instr,
-                                             n_types, weight_stride, dim_in, dim_out, num_nodes, scale, chunk_width, stream);
-      if (rc != NQA_OK) return rc;
-    }
-    return NQA_OK;
-  }
   if (num_nodes < 0 || n_chunks < 0 || n_instr < 0 || n_types < 1 || dim_in <= 0 || dim_out <= 0 ||
       (num_nodes > 0 && (!x || !weights || !out || !chunk_table || (n_instr > 0 && !instr_table))) ||
       (n_types > 1 && atom_types == nullptr)) {
@@ -1321,160 +1340,59 @@ int nqa_node_linear_ordered(int32_t dtype, const void* x, const void* weights, c
     return NQA_ERR_INVALID;
   }
   if (num_nodes == 0) return NQA_OK;
-  const size_t es = dtype == NQA_F32 ? 4 : 8;
-  const size_t smem = (size_t)kNZ * dim_in * es;
-  if (!use_mfma && smem > 160 * 1024 - 1024) {  // (the MFMA kernel stages 64-channel slabs, not whole rows)
+  const size_t smem = (size_t)kNZ * dim_in * (dtype == NQA_F32 ? 4 : 8);
+  if (!use_mfma && smem > 160 * 1024 - 1024) {  // (the MFMA kernel stages 32-channel slabs, not whole rows)
     set_error("nqa_node_linear: feature rows too wide for the LDS tile of the VALU kernel");
     return NQA_ERR_UNSUPPORTED;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)((num_nodes + kNZ - 1) / kNZ), (unsigned)((n_chunks + 3) / 4));
-  hipError_t err;
-  if (dtype == NQA_F32) {
+  const NodeChunk* chunks = static_cast<const NodeChunk*>(chunk_table);
+  if (use_mfma) {
+    // per-wavefront kernel: one 64-thread workgroup per unit; a group of one chunk is the kernel's blk_begin
     NodeLinearArgs<float> a{};
-    a.x = static_cast<const float*>(x);
-    a.w = static_cast<const float*>(weights);
-    a.addend = static_cast<const float*>(addend);
-    a.out = static_cast<float*>(out);
-    a.types = n_types > 1 ? atom_types : nullptr;
-    a.perm = use_mfma ? atom_order : nullptr;  // (the VALU kernel keeps the natural order)
-    std::memcpy(a.chunks, chunk_table, sizeof(NodeChunk) * (size_t)n_chunks);
-    if (n_instr > 0) std::memcpy(a.instr, instr_table, sizeof(NodeInstr) * (size_t)n_instr);
-    a.n_chunks = n_chunks;
-    a.n_types = n_types;
-    a.din = dim_in;
-    a.dout = dim_out;
-    a.wstride = weight_stride;
-    a.N = num_nodes;
-    a.scale = (float)scale;
-    {
-      static const int dbg = [] {
-        const char* e = std::getenv("NQA_NODE_DBG");
-        return e ? std::atoi(e) : 0;
-      }();
-      a.dbg = dbg;
+    node_fill_args(a, x, weights, addend, out, atom_types, atom_order, instr_table, n_instr, n_types, weight_stride, dim_in,
+                   dim_out, num_nodes, scale);
+    std::vector<NodeUnitChunk> uc(n_chunks);
+    for (int c = 0; c < n_chunks; ++c) uc[c] = {chunks[c].d, node_stages(a.instr, chunks[c].instr_begin, chunks[c].instr_end, n_types)};
+    const char* perr = node_plan_units(uc, num_nodes, kMaxNodeChunks, false, [](int, int) { return false; },
+                                       [&](const NodeUnitSlice& sl) {
+                                         for (int c = 0; c < sl.n; ++c) a.chunks[c] = chunks[sl.order[c]];
+                                         std::memcpy(a.blk_begin, sl.grp_begin, sizeof(int32_t) * (size_t)(sl.n + 1));
+                                         a.n_chunks = sl.n;
+                                         hipLaunchKernelGGL(node_linear_wave_kernel, dim3((unsigned)sl.units), dim3(64), 0, s, a);
+                                       });
+    if (perr != nullptr) {
+      set_error(std::string("nqa_node_linear: ") + perr);
+      return NQA_ERR_UNSUPPORTED;
     }
-    if (use_mfma) {
-      // per-wavefront kernel: one 64-thread workgroup per (chunk, floor(32/d) atoms) unit; chunks with the most stages
-      // (instruction x type x 32-channel K slab) first, so that the long units are dispatched first
-      int order[kMaxNodeChunks];
-      int stages[kMaxNodeChunks];
-      for (int c = 0; c < n_chunks; ++c) {
-        const int d = a.chunks[c].d;
-        if (d != 1 && d != 3 && d != 5 && d != 7 && d != 9) {
-          set_error("nqa_node_linear: irrep dimension above 9 (l > 4)");
-          return NQA_ERR_UNSUPPORTED;
-        }
-        int st = 0;
-        for (int q = a.chunks[c].instr_begin; q < a.chunks[c].instr_end; ++q)
-          st += n_types * ((a.instr[q].mul_in + kNLK2 - 1) / kNLK2);
-        stages[c] = st;
-        order[c] = c;
-      }
-      std::stable_sort(order, order + n_chunks, [&](int l, int r) { return stages[l] > stages[r]; });
-      NodeChunk sorted[kMaxNodeChunks];
-      for (int c = 0; c < n_chunks; ++c) sorted[c] = a.chunks[order[c]];
-      int64_t nblk = 0;
-      for (int c = 0; c < n_chunks; ++c) {
-        a.chunks[c] = sorted[c];
-        a.blk_begin[c] = (int32_t)nblk;
-        const int per_unit = 32 / a.chunks[c].d;
-        nblk += (num_nodes + per_unit - 1) / per_unit;
-      }
-      a.blk_begin[n_chunks] = (int32_t)nblk;
-      if (nblk > 2147483647LL) {
-        set_error("nqa_node_linear: too many work units for one launch");
-        return NQA_ERR_UNSUPPORTED;
-      }
-      if (nblk == 0) return NQA_OK;
-      hipLaunchKernelGGL(node_linear_wave_kernel, dim3((unsigned)nblk), dim3(64), 0, s, a);
-    } else {
-      if (smem > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(node_linear_kernel<float>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      hipLaunchKernelGGL(node_linear_kernel<float>, grid, dim3(256), smem, s, a);
-    }
+  } else if (dtype == NQA_F32) {
+    NodeLinearArgs<float> a{};
+    node_fill_args(a, x, weights, addend, out, atom_types, nullptr, instr_table, n_instr, n_types, weight_stride, dim_in,
+                   dim_out, num_nodes, scale);  // (the VALU kernel keeps the natural atom order)
+    node_launch_valu(a, chunks, n_chunks, smem, s);
   } else {
     NodeLinearArgs<double> a{};
-    a.x = static_cast<const double*>(x);
-    a.w = static_cast<const double*>(weights);
-    a.addend = static_cast<const double*>(addend);
-    a.out = static_cast<double*>(out);
-    a.types = n_types > 1 ? atom_types : nullptr;
-    std::memcpy(a.chunks, chunk_table, sizeof(NodeChunk) * (size_t)n_chunks);
-    if (n_instr > 0) std::memcpy(a.instr, instr_table, sizeof(NodeInstr) * (size_t)n_instr);
-    a.n_chunks = n_chunks;
-    a.n_types = n_types;
-    a.din = dim_in;
-    a.dout = dim_out;
-    a.wstride = weight_stride;
-    a.N = num_nodes;
-    a.scale = scale;
-    if (smem > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(node_linear_kernel<double>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(node_linear_kernel<double>, grid, dim3(256), smem, s, a);
+    node_fill_args(a, x, weights, addend, out, atom_types, nullptr, instr_table, n_instr, n_types, weight_stride, dim_in,
+                   dim_out, num_nodes, scale);
+    node_launch_valu(a, chunks, n_chunks, smem, s);
   }
-  err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_error(std::string("nqa_node_linear: ") + hipGetErrorString(err));
-    return NQA_ERR_LAUNCH;
-  }
-  return NQA_OK;
+  return launch_status("nqa_node_linear");
 }
 
-// ---- packed (split-bf16) weights ------------------------------------------------------------------------------------
-namespace {
-// fragment layout of one atom type: per instruction ceil(mul_in / 16) x ceil(mul_out / 32) fragments of 3 planes x 64 lanes
-// (uint4 each); mul_out is that of the output block the instruction feeds.  Returns the uint4 count per type, -1 on error.
-// two-plane fp16 split with running column scales (default) or the three-plane bf16 split (NQA_NODE_F16=0).  Read at every
-// call: a packed buffer must be used in the mode it was packed in (the Python host keys its cache on the variable).
-bool node_f16() {
-  const char* e = std::getenv("NQA_NODE_F16");
-  return e == nullptr || e[0] != '0';
-}
-
-// exponent table of the F16 layout: one int per (instruction, 16-row K block); returns the count per type
-int32_t node_exp_layout(const nqa::NodeInstr* instr, int32_t n_instr, int32_t* exp_off) {
-  int32_t off = 0;
-  for (int q = 0; q < n_instr; ++q) {
-    exp_off[q] = off;
-    off += (instr[q].mul_in + 15) / 16;
-  }
-  exp_off[n_instr] = off;
-  return off;
-}
-
-int64_t node_frag_layout(const nqa::NodeChunk* chunks, int32_t n_chunks, const nqa::NodeInstr* instr, int32_t n_instr,
-                         int32_t* frag_off, int32_t* mul_out, int planes = node_f16() ? 2 : 3) {
-  for (int q = 0; q < n_instr; ++q) mul_out[q] = 0;
-  for (int c = 0; c < n_chunks; ++c)
-    for (int q = chunks[c].instr_begin; q < chunks[c].instr_end; ++q) {
-      if (q < 0 || q >= n_instr) return -1;
-      mul_out[q] = chunks[c].mul_out;
-    }
-  int64_t off = 0;
-  for (int q = 0; q < n_instr; ++q) {
-    frag_off[q] = (int32_t)off;
-    off += (int64_t)((instr[q].mul_in + 15) / 16) * ((mul_out[q] + 31) / 32) * planes * 64;
-    if (off > 2147483647LL) return -1;
-  }
-  frag_off[n_instr] = (int32_t)off;
-  return off;
-}
-}  // namespace
-
+// ---- packed (split-bf16 / split-fp16) weights ---------------------------------------------------------------------------
 int64_t nqa_node_weights_pack_bytes(const void* chunk_table, int32_t n_chunks, const void* instr_table, int32_t n_instr,
                                     int32_t n_types) {
   if (n_instr < 0 || n_instr > nqa::kMaxNodeInstr || n_chunks < 0 || n_types < 1 || (n_chunks > 0 && !chunk_table) ||
       (n_instr > 0 && !instr_table))
     return -1;
+  const bool f16 = node_f16();
   int32_t frag_off[nqa::kMaxNodeInstr + 1], mul_out[nqa::kMaxNodeInstr];
   const int64_t per_type = node_frag_layout(static_cast<const nqa::NodeChunk*>(chunk_table), n_chunks,
-                                            static_cast<const nqa::NodeInstr*>(instr_table), n_instr, frag_off, mul_out);
+                                            static_cast<const nqa::NodeInstr*>(instr_table), n_instr, frag_off, mul_out,
+                                            f16 ? 2 : 3);
   if (per_type < 0) return -1;
   int32_t exp_off[nqa::kMaxNodeInstr + 1];
-  const int64_t nexp = node_f16() ? node_exp_layout(static_cast<const nqa::NodeInstr*>(instr_table), n_instr, exp_off) : 0;
+  const int64_t nexp = f16 ? node_exp_layout(static_cast<const nqa::NodeInstr*>(instr_table), n_instr, exp_off) : 0;
   return per_type * 16 * n_types + ((nexp * n_types * 4 + 255) & ~(int64_t)255);
 }
 
@@ -1486,10 +1404,11 @@ int nqa_node_weights_pack(const void* weights, const void* chunk_table, int32_t 
     set_error("nqa_node_weights_pack: invalid argument");
     return NQA_ERR_INVALID;
   }
+  const bool f16 = node_f16();
   NodePackArgs a{};
   const NodeInstr* instr = static_cast<const NodeInstr*>(instr_table);
   const int64_t per_type = node_frag_layout(static_cast<const NodeChunk*>(chunk_table), n_chunks, instr, n_instr,
-                                            a.frag_off, a.mul_out);
+                                            a.frag_off, a.mul_out, f16 ? 2 : 3);
   if (per_type < 0) {
     set_error("nqa_node_weights_pack: inconsistent tables");
     return NQA_ERR_INVALID;
@@ -1505,7 +1424,7 @@ int nqa_node_weights_pack(const void* weights, const void* chunk_table, int32_t 
   a.frag_stride = per_type;
   a.n_instr = n_instr;
   a.n_types = n_types;
-  if (node_f16()) {
+  if (f16) {
     a.exp_stride = node_exp_layout(instr, n_instr, a.exp_off);
     a.wexp = reinterpret_cast<int32_t*>(static_cast<char*>(packed) + per_type * 16 * n_types);
     const int64_t nexp = (int64_t)a.exp_stride * n_types;
@@ -1518,12 +1437,7 @@ int nqa_node_weights_pack(const void* weights, const void* chunk_table, int32_t 
     hipLaunchKernelGGL(node_weights_pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), a);
   }
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_error(std::string("nqa_node_weights_pack: ") + hipGetErrorString(err));
-    return NQA_ERR_LAUNCH;
-  }
-  return NQA_OK;
+  return launch_status("nqa_node_weights_pack");
 }
 
 int nqa_node_linear_packed(const void* x, const void* packed, const void* addend, void* out, const int64_t* atom_types,
@@ -1546,11 +1460,12 @@ int nqa_node_linear_packed_ordered(const void* x, const void* packed, const void
     return NQA_ERR_INVALID;
   }
   if (num_nodes == 0 || n_chunks == 0) return NQA_OK;
+  const bool f16 = node_f16();
   const NodeChunk* chunks = static_cast<const NodeChunk*>(chunk_table);
   const NodeInstr* instr = static_cast<const NodeInstr*>(instr_table);
   NodeLinearPackedArgs pa{};
   int32_t frag_off[kMaxNodeInstr + 1], mul_out[kMaxNodeInstr];
-  const int64_t per_type = node_frag_layout(chunks, n_chunks, instr, n_instr, frag_off, mul_out);
+  const int64_t per_type = node_frag_layout(chunks, n_chunks, instr, n_instr, frag_off, mul_out, f16 ? 2 : 3);
   if (per_type < 0) {
     set_error("nqa_node_linear_packed: inconsistent tables");
     return NQA_ERR_INVALID;
@@ -1562,91 +1477,40 @@ int nqa_node_linear_packed_ordered(const void* x, const void* packed, const void
   pa.exp_stride = node_exp_layout(instr, n_instr, exp_off);
   pa.wexp = reinterpret_cast<const int32_t*>(static_cast<const char*>(packed) + per_type * 16 * n_types);
   NodeLinearArgs<float>& a = pa.base;
-  a.x = static_cast<const float*>(x);
-  a.addend = static_cast<const float*>(addend);
-  a.out = static_cast<float*>(out);
-  a.types = n_types > 1 ? atom_types : nullptr;
-  a.perm = atom_order;
-  if (n_instr > 0) std::memcpy(a.instr, instr, sizeof(NodeInstr) * (size_t)n_instr);
+  node_fill_args(a, x, nullptr, addend, out, atom_types, atom_order, instr_table, n_instr, n_types, 0, dim_in, dim_out,
+                 num_nodes, scale);
   for (int q = 0; q < n_instr; ++q) a.instr[q].pad = exp_off[q];  // (F16: first exponent of the instruction)
-  a.n_types = n_types;
-  a.din = dim_in;
-  a.dout = dim_out;
-  a.N = num_nodes;
-  a.scale = (float)scale;
-  {
-    static const int dbg = [] {
-      const char* e = std::getenv("NQA_NODE_DBG");
-      return e ? std::atoi(e) : 0;
-    }();
-    a.dbg = dbg;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // chunks with the most stages first; more than kMaxNodeChunks chunks (wide l_max = 3 layers) in several launches
-  std::vector<int> order(n_chunks), stages(n_chunks);
+  std::vector<NodeUnitChunk> uc(n_chunks);
   for (int c = 0; c < n_chunks; ++c) {
-    const int d = chunks[c].d;
-    if (d != 1 && d != 3 && d != 5 && d != 7 && d != 9) {
-      set_error("nqa_node_linear_packed: irrep dimension above 9 (l > 4)");
-      return NQA_ERR_UNSUPPORTED;
-    }
     if (chunks[c].c0 % 64 != 0) {
       set_error("nqa_node_linear_packed: chunks must start at multiples of 64 channels");
       return NQA_ERR_INVALID;
     }
-    int st = 0;
-    for (int q = chunks[c].instr_begin; q < chunks[c].instr_end; ++q) st += n_types * ((instr[q].mul_in + kNLK3 - 1) / kNLK3);
-    stages[c] = st;
-    order[c] = c;
+    uc[c] = {chunks[c].d, node_stages(instr, chunks[c].instr_begin, chunks[c].instr_end, n_types)};
   }
-  std::stable_sort(order.begin(), order.end(), [&](int l, int r) { return stages[l] > stages[r]; });
-  for (int c0 = 0; c0 < n_chunks; c0 += kMaxNodeChunks) {
-    const int nc = std::min(n_chunks - c0, kMaxNodeChunks);
-    int64_t nblk = 0;
-    int ng = 0;
-    for (int c = 0; c < nc; ++c) {
-      a.chunks[c] = chunks[order[c0 + c]];
-      const NodeChunk& cc = a.chunks[c];
-      const bool same = c > 0 && cc.instr_begin == a.chunks[c - 1].instr_begin &&
-                        cc.instr_end == a.chunks[c - 1].instr_end && cc.d == a.chunks[c - 1].d &&
-                        cc.o_off == a.chunks[c - 1].o_off;
-      const int per_unit = 32 / cc.d;
-      if (!same) {
-        pa.grp_begin[ng] = (int32_t)nblk;
-        pa.grp_chunk0[ng] = c;
-        pa.grp_n[ng] = 0;
-        ++ng;
-      }
-      ++pa.grp_n[ng - 1];
-      nblk += (num_nodes + per_unit - 1) / per_unit;
-    }
-    pa.grp_begin[ng] = (int32_t)nblk;
-    pa.n_groups = ng;
-    a.n_chunks = nc;
-    if (nblk > 2147483647LL) {
-      set_error("nqa_node_linear_packed: too many work units for one launch");
-      return NQA_ERR_UNSUPPORTED;
-    }
-    // NQA_NODE_PIPE=1: the one-wait-per-stage loop (two wavefronts per SIMD); measured no faster than the default, see
-    // node_fused.h
-    const char* pe = std::getenv("NQA_NODE_PIPE");
-    const bool pipe = pe != nullptr && pe[0] == '1';
-    if (node_f16() && pipe && (a.dbg & 64) == 0)
-      hipLaunchKernelGGL(node_linear_pipe_kernel, dim3((unsigned)((nblk + kNLWavesPerWG - 1) / kNLWavesPerWG)),
-                         dim3(64 * kNLWavesPerWG), 0, s, pa);
-    else if (node_f16())
-      hipLaunchKernelGGL(node_linear_wave_bf16_kernel<true>, dim3((unsigned)((nblk + kNLWavesPerWG - 1) / kNLWavesPerWG)),
-                         dim3(64 * kNLWavesPerWG), 0, s, pa);
-    else
-      hipLaunchKernelGGL(node_linear_wave_bf16_kernel<false>, dim3((unsigned)((nblk + kNLWavesPerWG - 1) / kNLWavesPerWG)),
-                         dim3(64 * kNLWavesPerWG), 0, s, pa);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const char* perr = node_plan_units(
+      uc, num_nodes, kMaxNodeChunks, true,
+      [&](int l, int r) {
+        return chunks[l].instr_begin == chunks[r].instr_begin && chunks[l].instr_end == chunks[r].instr_end &&
+               chunks[l].d == chunks[r].d && chunks[l].o_off == chunks[r].o_off;
+      },
+      [&](const NodeUnitSlice& sl) {
+        for (int c = 0; c < sl.n; ++c) a.chunks[c] = chunks[sl.order[c]];
+        a.n_chunks = sl.n;
+        pa.n_groups = sl.n_groups;
+        std::memcpy(pa.grp_begin, sl.grp_begin, sizeof(sl.grp_begin));
+        std::memcpy(pa.grp_chunk0, sl.grp_chunk0, sizeof(sl.grp_chunk0));
+        std::memcpy(pa.grp_n, sl.grp_n, sizeof(sl.grp_n));
+        const dim3 grid((unsigned)((sl.units + kNLWavesPerWG - 1) / kNLWavesPerWG)), block(64 * kNLWavesPerWG);
+        if (f16) hipLaunchKernelGGL(node_linear_wave_bf16_kernel<true>, grid, block, 0, s, pa);
+        else hipLaunchKernelGGL(node_linear_wave_bf16_kernel<false>, grid, block, 0, s, pa);
+      });
+  if (perr != nullptr) {
+    set_error(std::string("nqa_node_linear_packed: ") + perr);
+    return NQA_ERR_UNSUPPORTED;
   }
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_error(std::string("nqa_node_linear_packed: ") + hipGetErrorString(err));
-    return NQA_ERR_LAUNCH;
-  }
-  return NQA_OK;
+  return launch_status("nqa_node_linear_packed");
 }
 
 int nqa_gate(int32_t dtype, int32_t backward, const void* input, const void* grad_out, const void* cotangent,

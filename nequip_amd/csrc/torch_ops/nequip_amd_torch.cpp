@@ -1085,9 +1085,15 @@ Tensor transposed_weights(const Tensor& wp, const std::string& key) {
          }).first;
 }
 
-// fp16-split fragment image of packed weights [T, wstride] for the tables of M (nqa_node_weights_pack), once per constant
+// NQA_NODE_F16 as the C library reads it: unset, or any value that does not start with '0', means the two-plane fp16 split
+bool node_split_f16() {
+  const char* v = std::getenv("NQA_NODE_F16");
+  return v == nullptr || v[0] != '0';
+}
+
+// split fragment image of packed weights [T, wstride] for the tables of M (nqa_node_weights_pack), once per constant
 Tensor packed_weights(const Tensor& wp, LinearMeta& M, const std::string& full_key) {
-  const bool f16 = !(std::getenv("NQA_NODE_F16") && std::getenv("NQA_NODE_F16")[0] == '0');
+  const bool f16 = node_split_f16();
   return const_cached(wp, std::string("node_packed:") + (f16 ? "h:" : "b:") + full_key, [&] {
            const int32_t T = (int32_t)wp.size(0);
            const int64_t nbytes = nqa_node_weights_pack_bytes(M.chunks.data(), M.n_chunks, M.instr.data(), M.n_instr, T);
@@ -1363,7 +1369,7 @@ StageOperands stage_operands(const Tensor& h_, const Tensor& types_, const Tenso
   TORCH_CHECK(o.wp1.dim() == 2 && o.wp1.size(0) == 1 && o.wp1.size(1) == M1.wstride, "nequip_amd::", op, ": wp1 must be [1, ",
               M1.wstride, "]");
   TORCH_CHECK(o.wps.dim() == 2 && o.wps.size(1) == MS.wstride, "nequip_amd::", op, ": wps must be [T, ", MS.wstride, "]");
-  TORCH_CHECK(!env_on("NQA_NODE_EXACT_FP32") && !(std::getenv("NQA_NODE_F16") && std::getenv("NQA_NODE_F16")[0] == '0'),
+  TORCH_CHECK(!env_on("NQA_NODE_EXACT_FP32") && node_split_f16(),
               "nequip_amd::", op, ": the fused node stage needs the default fp16-split packing");
   o.types = (types_.scalar_type() == at::kLong ? types_ : types_.to(at::kLong)).contiguous();
   TORCH_CHECK(o.types.numel() == o.h.size(0), "nequip_amd::", op, ": one atom type per row");

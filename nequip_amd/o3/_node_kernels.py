@@ -82,6 +82,13 @@ class NodeLinearMeta:
                                  ctypes.create_string_buffer(ib, max(len(ib), 1)), len(instr))
         return self._host[which]
 
+    def flops(self, which: str, n_atoms: int) -> float:
+        """FLOPs of the map over ``n_atoms`` rows as the work units run it: per 64-channel chunk, 2 x (2l + 1) x the chunk's
+        live channels x the input channels of the instructions that feed it."""
+        chunks, instr = getattr(self, which)
+        return 2.0 * n_atoms * sum(d * min(64, mul_out - c0) * sum(i[1] for i in instr[begin:end])
+                                   for _, d, mul_out, c0, begin, end, _, _ in chunks)
+
     def wgrad_table(self) -> "_wgrad.WgradTable":
         """Records of ``nqa_wgrad`` for the packed forward weights: A = input rows, B = output-gradient rows."""
         if getattr(self, "_wgrad_table", None) is None:
@@ -116,12 +123,18 @@ def exact_fp32() -> bool:
     return os.environ.get("NQA_NODE_EXACT_FP32", "") not in ("", "0")
 
 
+def split_f16() -> bool:
+    """The split of constant weights, by the rule the C library reads ``NQA_NODE_F16`` with: unset, or any value that does not
+    start with ``0``, means two fp16 planes; otherwise three bf16 planes."""
+    return not os.environ.get("NQA_NODE_F16", "1").startswith("0")
+
+
 def packed_weights(wp: torch.Tensor, meta: NodeLinearMeta, which: str) -> torch.Tensor:
     """``wp [T, wstride]`` split into 16-bit planes in MFMA-fragment order (``nqa_node_weights_pack``: two fp16 planes of
     power-of-two scaled K blocks by default, three bf16 planes with ``NQA_NODE_F16=0``).  Constant
     weights (eval mode: the modules keep ``wp`` alive across steps) are packed once per version of the tensor; a ``wp``
     that is part of an autograd graph (training: rebuilt from the parameter every step) is packed per call."""
-    key = ("node_packed", id(meta), which, os.environ.get("NQA_NODE_F16", ""))  # (the layout depends on the split in use)
+    key = ("node_packed", id(meta), which, split_f16())  # (the layout depends on the split in use)
     # constants (eval mode: the module keeps `wp`; a compiled graph: a constant buffer) are packed once per version of the
     # tensor -- the cache is keyed on the storage (utils/constcache.py); a graph tensor of a training step lives for that
     # step only and is packed per call when NQA_NODE_TRAIN_PACKED=1 asks for it at all
@@ -161,15 +174,12 @@ def _launch_linear(x, wp, addend, types, meta: NodeLinearMeta, which: str, scale
     din, dout = (meta.din, meta.dout) if which == "fwd" else (meta.dout, meta.din)
     N = x.shape[0]
     out = torch.empty((N, dout), dtype=x.dtype, device=x.device)
-    flops = 2.0 * N * sum(c[1] * min(64, c[2] - c[3]) * sum(meta_i[1] for meta_i in (meta.fwd if which == "fwd" else meta.bwd)[1][c[4]:c[5]]) for c in (meta.fwd if which == "fwd" else meta.bwd)[0])
+    flops = meta.flops(which, N)
     # (weights that are part of an autograd graph -- training -- change every step: the exact-fp32 kernel reads them as
     # they are; see train_packed())
     # a typed map (one weight set per atom type) walks the atoms grouped by type: a work unit then runs the stages of the
     # one or two types it holds instead of one masked pass per type (float32 MFMA kernels; any order gives the same result)
-    order = None
-    if (wp.shape[0] > 1 and types is not None and x.dtype == torch.float32
-            and os.environ.get("NQA_NODE_TYPE_ORDER", "") != "0"):
-        order = type_order(types)
+    order = type_order_or_none(types) if (wp.shape[0] > 1 and types is not None and x.dtype == torch.float32) else None
     if (x.dtype == torch.float32 and not exact_fp32() and ninstr > 0
             and (train_packed() or not (wp.requires_grad or getattr(wp, "_nqa_volatile", False)))):
         wf = packed_weights(wp, meta, which)
@@ -467,8 +477,7 @@ def apply_deferred_gate(pregate):
 # ---- fused node stage (nqa_node_fused): Gate folded into its consumers / into the producers of its gradient -------------
 def fusion_enabled() -> bool:
     """The fused node stage needs the default fp16-split packing; ``NQA_NO_NODE_FUSION=1`` keeps the separate launches."""
-    return (os.environ.get("NQA_NO_NODE_FUSION", "") in ("", "0") and os.environ.get("NQA_NODE_F16", "") != "0"
-            and not exact_fp32())
+    return os.environ.get("NQA_NO_NODE_FUSION", "") in ("", "0") and split_f16() and not exact_fp32()
 
 
 class FusedPart:
@@ -521,6 +530,11 @@ def type_order(types: torch.Tensor) -> torch.Tensor:
     return hit
 
 
+def type_order_or_none(types: torch.Tensor) -> Optional[torch.Tensor]:
+    """``type_order(types)`` for a typed launch, or None (the caller's own atom order) with ``NQA_NODE_TYPE_ORDER=0``."""
+    return type_order(types) if os.environ.get("NQA_NODE_TYPE_ORDER", "") != "0" else None
+
+
 def launch_fused(parts: Sequence[FusedPart], types, out_gate: Optional[GateMeta] = None, gate_h=None,
                  order: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
     """``nqa_node_fused``: returns the destination tensors (one per non-accumulating part).  With ``out_gate`` the single
@@ -544,8 +558,7 @@ def launch_fused(parts: Sequence[FusedPart], types, out_gate: Optional[GateMeta]
             nbytes += 4 * N * dout
         if k == 0 or part.x.data_ptr() != parts[0].x.data_ptr():
             nbytes += 4 * N * part.x.shape[1]
-        chunks, instr = part.meta.fwd
-        flops += 2.0 * N * sum(c[1] * min(64, c[2] - c[3]) * sum(i[1] for i in instr[c[4]:c[5]]) for c in chunks)
+        flops += part.meta.flops("fwd", N)
         _fill_part(cparts[k], part, out, keep)
     if out_gate is not None:
         arr, n = out_gate.blocks_c()
@@ -582,7 +595,7 @@ class _FusedNodeStageFn(torch.autograd.Function):
             parts.append(FusedPart(h, wps, metas, 1.0, in_gate=gate_meta))
         typed = wps is not None and wps.shape[0] > 1
         # typed self-connection: the units walk the atoms grouped by type, so a unit stages one type's weights, not all
-        ctx.order = type_order(types) if (typed and os.environ.get("NQA_NODE_TYPE_ORDER", "") != "0") else None
+        ctx.order = type_order_or_none(types) if typed else None
         outs = launch_fused(parts, types if typed else None, order=ctx.order)
         ctx.save_for_backward(h, types, wp1, wps)
         ctx.gate_meta, ctx.meta1, ctx.metas, ctx.scale1 = gate_meta, meta1, metas, scale1

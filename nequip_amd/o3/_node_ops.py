@@ -119,12 +119,10 @@ def _gate_bwd_bwd_cuda(x, g, c, key, need_x, need_g):
 
 
 def _stage_order(types, wps):
-    import os
-
-    from ._node_kernels import type_order
+    from ._node_kernels import type_order_or_none
 
     typed = wps.shape[0] > 1
-    return typed, (type_order(types) if (typed and os.environ.get("NQA_NODE_TYPE_ORDER", "") != "0") else None)
+    return typed, (type_order_or_none(types) if typed else None)
 
 
 def _node_stage_fwd_cuda(h, types, wp1, wps, gate_key, lin_key, sc_key, scale):

@@ -71,5 +71,5 @@ if __name__ == "__main__":
         print(f"== {os.path.basename(obj)} ({len(ks)} kernels)")
         for n, r in sorted(ks.items()):
             short = re.sub(r"\(.*$", "", n.replace("(anonymous namespace)::", "")).replace("void ", "").replace("nqa::", "")
-            print(f"  {short[:78]:78s} vgpr {r['vgpr']:3d} ({waves_per_simd(r['vgpr'])} w/SIMD) spill {r['vgpr_spill']:3d} "
-                  f"lds {r['lds']:6d} scratch {r['scratch']}")
+            print(f"  {short[:78]:78s} vgpr {r['vgpr']:3d} ({waves_per_simd(r['vgpr'])} w/SIMD) sgpr {r['sgpr']:3d} "
+                  f"spill {r['vgpr_spill']:3d} lds {r['lds']:6d} scratch {r['scratch']}")

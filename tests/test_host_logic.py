@@ -334,6 +334,23 @@ def test_split_mode_workspace_sizes():
             os.environ.pop("NQA_NODE_F16", None)
     assert sizes["0"] == frags * 3 * 1024 * 2
     assert sizes["1"] == frags * 2 * 1024 * 2 + ((nexp * 2 * 4 + 255) // 256) * 256
+    # one reading of NQA_NODE_F16 on both sides of the C ABI: unset, or any value that does not start with "0", is fp16
+    from nequip_amd.o3._node_kernels import split_f16
+
+    saved = os.environ.get("NQA_NODE_F16")
+    try:
+        for value, f16 in ((None, True), ("", True), ("1", True), ("0", False), ("00", False)):
+            os.environ.pop("NQA_NODE_F16", None)
+            if value is not None:
+                os.environ["NQA_NODE_F16"] = value
+            assert split_f16() is f16, value
+            nbytes = lib.nqa_node_weights_pack_bytes(ctypes.cast(cb, ctypes.c_void_p), len(chunks),
+                                                     ctypes.cast(ib, ctypes.c_void_p), len(instr), 2)
+            assert nbytes == sizes["1" if split_f16() else "0"], value
+    finally:
+        os.environ.pop("NQA_NODE_F16", None)
+        if saved is not None:
+            os.environ["NQA_NODE_F16"] = saved
 
 
 def test_mode_switches_and_volatile_weight_copies(monkeypatch):

@@ -66,7 +66,7 @@ def test_node_kernels_keep_three_or_four_wavefronts_per_simd():
     assert 4 * f16["lds"] <= 160 * 1024  # LDS does not cap the occupancy below the register limit
     for name in ("gate_fwd_kernel<float>", "gate_bwd_kernel<float>"):
         assert _find(ks, name)["vgpr_spill"] == 0
-    fused = _find(ks, "node_fused_kernel<false>")  # 160 VGPRs, 4 x (8320 + 1536) B: the fused layer-boundary stage
+    fused = _find(ks, "node_fused_kernel(")  # 160 VGPRs, 4 x (8320 + 1536) B: the fused layer-boundary stage
     assert fused["vgpr_spill"] == 0 and fused["scratch"] == 0 and kr.waves_per_simd(fused["vgpr"]) >= 3
     assert 3 * fused["lds"] <= 160 * 1024
 

@@ -167,20 +167,36 @@ CASES = [
     ("32x0e+32x0o+32x1e+32x1o", 4, 105),                  # tutorial shape (parity=True: tanh on odd scalars), 4 species
     ("128x0e+128x1o+128x2e+128x3o", 1, 257),              # cfg-5 (two 64-channel chunks per block, d = 7)
     ("64x0e+64x1o+64x2e+64x3o+64x4e", 5, 70),             # d = 9, five species
+    # the smallest uniform layer whose merged forward table (10 chunks of linear_1 + 18 of the self-connection) does not
+    # fit one launch of NF_MAX_CHUNKS chunks: the host cuts it into two; three species
+    ("128x0e+128x1o+128x2e+128x3o+128x4e", 3, 70),
 ]
+WIDE = CASES[-1]
+NF_MAX_CHUNKS = 24  # kNFMaxChunks of csrc/node_fused.h
+
+
+def _forward_plan_chunks(gate, lin1, sc, n_types):
+    gm = gate._kernel_meta
+    parts = [_part(lin1._meta, 1, gm.din, gm.dout, in_gate=gm, scale=0.16), _part(sc._meta, n_types, gm.din, gm.din, in_gate=gm)]
+    return len(_plan(parts)[0])
+
+
+def test_forward_plan_of_the_wide_case_exceeds_one_launch():
+    hidden, n_types, _ = WIDE
+    assert _forward_plan_chunks(*_layer(hidden), n_types) == 28 > NF_MAX_CHUNKS
+    # one multiplicity step down (the fourth of CASES at 128 channels up to l = 3) still fits
+    assert _forward_plan_chunks(*_layer("128x0e+128x1o+128x2e+128x3o"), n_types) == 22 <= NF_MAX_CHUNKS
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("stage_loop", ["default", "one_wait_per_stage"])
 @pytest.mark.parametrize("hidden,n_types,n_atoms", CASES)
-def test_fused_stage_matches_separate_launches_and_float64(device, hidden, n_types, n_atoms, stage_loop, monkeypatch):
-    # `one_wait_per_stage`: the opt-in stage loop of node_fused_kernel<true> / node_linear_pipe_kernel (NQA_NODE_PIPE=1, read
-    # at every launch; measured no faster) has to give the default's results
-    monkeypatch.setenv("NQA_NODE_PIPE", "1" if stage_loop == "one_wait_per_stage" else "0")
+def test_fused_stage_matches_separate_launches_and_float64(device, hidden, n_types, n_atoms):
     torch.manual_seed(1)
     gate, lin1, sc = _layer(hidden)
     gate, lin1, sc = gate.eval(), lin1.eval(), sc.eval()
     gm = gate._kernel_meta
+    if (hidden, n_types, n_atoms) == WIDE:  # the forward launch is cut: more merged chunks than one launch holds
+        assert _forward_plan_chunks(gate, lin1, sc, n_types) == 28 > NF_MAX_CHUNKS
     table = torch.randn(n_types, 8, dtype=torch.float64)
     types = torch.randint(0, n_types, (n_atoms,))
     h = torch.randn(n_atoms, gm.din, dtype=torch.float64)

@@ -147,6 +147,23 @@ def test_gate_kernel_double_backward(device, dtype):
             torch.testing.assert_close(r, o.cpu(), atol=tol * max(1.0, float(r.abs().max())), rtol=tol)
 
 
+def _magnitude_reference(xx, w, m, types):
+    """The map of ``m`` in float64 and, per output element, its magnitude sum  sum |x| |W|  (types None: untyped weights)."""
+    out = torch.zeros(xx.shape[0], m.dout, dtype=torch.float64)
+    mag = torch.zeros_like(out)
+    io, oo = m.irreps_in.offsets(), m.irreps_out.offsets()
+    for k, (i, o) in enumerate(m.instructions):
+        mi, ir = m.irreps_in[i]
+        mo = m.irreps_out[o].mul
+        d = ir.dim
+        W = w[:, m.w_off[k]:m.w_off[k] + mi * mo].view(-1, mi, mo).double()
+        Wz = W[types] if types is not None else W[0].expand(xx.shape[0], mi, mo)
+        xb = xx[:, io[i]:io[i] + mi * d].view(-1, mi, d).double()
+        out[:, oo[o]:oo[o] + mo * d] += torch.einsum("zum,zuw->zwm", xb, Wz).reshape(-1, mo * d)
+        mag[:, oo[o]:oo[o] + mo * d] += torch.einsum("zum,zuw->zwm", xb.abs(), Wz.abs()).reshape(-1, mo * d)
+    return out, mag.clamp_min(1e-300)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("typed", [False, True])
 def test_node_linear_constant_weight_modes_over_a_wide_dynamic_range(device, monkeypatch, typed):
@@ -185,27 +202,12 @@ def test_node_linear_constant_weight_modes_over_a_wide_dynamic_range(device, mon
             wp[:, meta.w_off[k]:meta.w_off[k] + n] *= 1e4
     types = torch.randint(0, T, (N,)) if typed else None
 
-    def reference(xx, w, m):
-        out = torch.zeros(xx.shape[0], m.dout, dtype=torch.float64)
-        mag = torch.zeros_like(out)
-        io, oo = m.irreps_in.offsets(), m.irreps_out.offsets()
-        for k, (i, o) in enumerate(m.instructions):
-            mi, ir = m.irreps_in[i]
-            mo = m.irreps_out[o].mul
-            d = ir.dim
-            W = w[:, m.w_off[k]:m.w_off[k] + mi * mo].view(-1, mi, mo).double()
-            Wz = W[types] if typed else W[0].expand(xx.shape[0], mi, mo)
-            xb = xx[:, io[i]:io[i] + mi * d].view(-1, mi, d).double()
-            out[:, oo[o]:oo[o] + mo * d] += torch.einsum("zum,zuw->zwm", xb, Wz).reshape(-1, mo * d)
-            mag[:, oo[o]:oo[o] + mo * d] += torch.einsum("zum,zuw->zwm", xb.abs(), Wz.abs()).reshape(-1, mo * d)
-        return out, mag.clamp_min(1e-300)
-
     cases = [("fwd", x, wp, meta)]
     xt = torch.randn(N, i_out.dim) * atom[:, None]
     xt[7] = 0.0
     cases.append(("transposed", xt, meta_transposed_weights(meta, wp), _transposed(meta)))
     for label, xx, w, m in cases:
-        ref, mag = reference(xx, w, m)
+        ref, mag = _magnitude_reference(xx, w, m, types)
         errs = {}
         for mode, env in (("f16", {"NQA_NODE_F16": "1", "NQA_NODE_EXACT_FP32": "0"}),
                           ("bf16", {"NQA_NODE_F16": "0", "NQA_NODE_EXACT_FP32": "0"}),
@@ -268,3 +270,87 @@ def test_typed_node_linear_atom_order_is_a_pure_schedule(device, monkeypatch, mo
     assert rc == 0
     torch.cuda.synchronize()
     assert torch.equal(natural, out)
+
+
+_MODE_ENV = {"f16": {"NQA_NODE_F16": "1", "NQA_NODE_EXACT_FP32": "0"},
+             "bf16": {"NQA_NODE_F16": "0", "NQA_NODE_EXACT_FP32": "0"},
+             "fp32": {"NQA_NODE_F16": "1", "NQA_NODE_EXACT_FP32": "1"},
+             "f64": {"NQA_NODE_F16": "1", "NQA_NODE_EXACT_FP32": "0"}}
+
+
+def _linear_call(mode, x, wp, types, meta, out, c0, nc):
+    """Chunks [c0, c0 + nc) of ``meta``'s forward tables with the FULL instruction table, straight through the C ABI, into
+    the columns of ``out`` that those chunks own (packed modes: the weights packed for exactly this chunk table)."""
+    import ctypes
+
+    from nequip_amd import _lib
+    from nequip_amd.o3._node_kernels import _ptr, _stream
+
+    lib = _lib.load()
+    ct, nchunks, it, ninstr = meta.host_tables("fwd")
+    assert 0 <= c0 and c0 + nc <= nchunks
+    cptr, iptr = ctypes.c_void_p(ctypes.addressof(ct) + 32 * c0), ctypes.cast(it, ctypes.c_void_p)
+    T, N = wp.shape[0], x.shape[0]
+    if mode in ("f16", "bf16"):
+        nbytes = lib.nqa_node_weights_pack_bytes(cptr, nc, iptr, ninstr, T)
+        assert nbytes > 0
+        wf = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
+        assert lib.nqa_node_weights_pack(_ptr(wp), cptr, nc, iptr, ninstr, T, wp.shape[1], _ptr(wf), _stream(x.device)) == 0
+        rc = lib.nqa_node_linear_packed_ordered(_ptr(x), _ptr(wf), None, _ptr(out), _ptr(types), None, cptr, nc, iptr, ninstr,
+                                                T, meta.din, meta.dout, N, 1.0, _stream(x.device))
+    else:
+        rc = lib.nqa_node_linear_ordered(_lib.NQA_F64 if mode == "f64" else _lib.NQA_F32, _ptr(x), _ptr(wp), None, _ptr(out),
+                                         _ptr(types), None, cptr, nc, iptr, ninstr, T, wp.shape[1], meta.din, meta.dout, N,
+                                         1.0, 64, _stream(x.device))
+    assert rc == 0, lib.nqa_last_error().decode()
+    torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_types", [1, 3])
+def test_node_linear_with_more_chunks_than_one_launch_holds(device, monkeypatch, n_types):
+    """43 output chunks (one launch holds 40): forty-one ``64x0e`` blocks and ``70x1o`` (its second chunk has 6 live
+    channels).  Input block 0 feeds every 0e block and block 1 the first ten as well, so the stage counts differ and the
+    host's sort (most stages first) really permutes the chunks before it cuts them into two launches; 52 instructions.
+    (a) every element within 1e-6 of its float64 magnitude sum (float64: 1e-11 relative); (b) bitwise the result of the same
+    map issued as two calls on the chunk table cut at chunk 20 -- chunk records are self-contained, so this holds whatever
+    the order and the cut of the host; (c) the transposed map (3 chunks, 52 instructions).  Typed: type 2 of 3 is absent."""
+    from nequip_amd.o3._node_kernels import NodeLinearMeta, _launch_linear, _transposed, meta_transposed_weights
+    from nequip_amd.o3.irreps import Irreps
+
+    torch.manual_seed(7)
+    i_in, i_out = Irreps("16x0e+8x0e+8x1o"), Irreps("+".join(["64x0e"] * 41 + ["70x1o"]))
+    ins = [(0, b) for b in range(41)] + [(1, b) for b in range(10)] + [(2, 41)]
+    meta = NodeLinearMeta(i_in, i_out, ins)
+    assert (len(meta.fwd[0]), len(meta.fwd[1])) == (43, 52) and (len(meta.bwd[0]), len(meta.bwd[1])) == (3, 52)
+    assert meta.fwd[0][-1][2] - meta.fwd[0][-1][3] == 6
+    N = 37
+    types = torch.randint(0, 2, (N,)) if n_types > 1 else None
+    x, xt = torch.randn(N, i_in.dim), torch.randn(N, i_out.dim)
+    x[5] = 0.0
+    wp = torch.randn(n_types, meta.wstride)
+    mt, wt = _transposed(meta), meta_transposed_weights(meta, wp)
+    ref, mag = _magnitude_reference(x, wp, meta, types)
+    ref_t, mag_t = _magnitude_reference(xt, wt, mt, types)
+    td = None if types is None else types.to(device)
+
+    for mode, env in _MODE_ENV.items():
+        for k_, v_ in env.items():
+            monkeypatch.setenv(k_, v_)
+        dt = torch.float64 if mode == "f64" else torch.float32
+        xd, wd = x.to(device, dt), wp.to(device, dt).contiguous()
+        out = _launch_linear(xd, wd, None, td, meta, "fwd", 1.0)
+        out_t = _launch_linear(xt.to(device, dt), wt.to(device, dt).contiguous(), None, td, mt, "fwd", 1.0)
+        for label, o, r, m in (("fwd", out, ref, mag), ("transposed", out_t, ref_t, mag_t)):
+            o = o.cpu().double()
+            assert torch.isfinite(o).all(), (mode, label)
+            if mode == "f64":
+                torch.testing.assert_close(o, r, atol=1e-11 * float(r.abs().max()), rtol=1e-11)
+            else:
+                err = float(((o - r).abs() / m).max())
+                print(mode, label, "max error / magnitude sum:", err)
+                assert err < 1e-6, (mode, label, err)
+        two = torch.full_like(out, float("nan"))
+        _linear_call(mode, xd, wd, td, meta, two, 0, 20)
+        _linear_call(mode, xd, wd, td, meta, two, 20, 23)
+        assert torch.equal(out, two), mode
