@@ -18,7 +18,7 @@ import torch
 
 from .irreps import Irrep, Irreps
 from ._node_kernels import GateMeta, NodeLinearMeta, gate as _gate_kernel, node_linear as _node_linear
-from ..utils.wgrad import _WeightCacheMixin, differentiable_parameters, parameter_side, publish
+from ..utils.wgrad import _WeightCacheMixin, differentiable_parameters
 
 
 from ..utils.tracing import traceable
@@ -66,9 +66,7 @@ class Linear(_WeightCacheMixin, torch.nn.Module):
             # eval mode: parameter gradients are not produced (inference fast path, as for the radial MLP) unless
             # nequip_amd.utils.wgrad.eval_parameter_gradients(True) asks for the reference's behaviour
             if differentiable_parameters(self.training, self.weight):
-                with parameter_side(x.device):  # (utils/wgrad.py: parameter-side work has its own stream in training)
-                    wp = (self.weight * self._scale_vec).unsqueeze(0)
-                publish(x.device, wp)
+                wp = (self.weight * self._scale_vec).unsqueeze(0)
                 # (what grad(wp) means for the parameter: lets the backward deliver it outside autograd, utils/wgrad.py)
                 wp._nqa_param = (self.weight, self._scale_vec, False)
             else:
@@ -308,9 +306,7 @@ class FullyConnectedTensorProduct(_WeightCacheMixin, torch.nn.Module):
         out = None
         for idx, tb, v0 in [(types, table, 0)] + list(classes):
             if differentiable_parameters(self.training, self.weight):
-                with parameter_side(x.device, tb):
-                    wp = self._contract_cols(self.weight, tb, v0)
-                publish(x.device, wp)
+                wp = self._contract_cols(self.weight, tb, v0)
             else:
                 wp = self._eval_weights_cols(tb, v0, x.dtype)
             out = _node_linear(x, wp, idx.view(-1)[:n].contiguous(), self._meta, addend=out)
@@ -326,9 +322,7 @@ class FullyConnectedTensorProduct(_WeightCacheMixin, torch.nn.Module):
                 return _skinny_mm(table, weight.index_select(0, perm).view(table.shape[1], -1) * scale)
 
             if differentiable_parameters(self.training, self.weight):
-                with parameter_side(x.device, table):
-                    wp = contract(self.weight, table)
-                publish(x.device, wp)
+                wp = contract(self.weight, table)
             else:  # constants in eval mode: contracted once per (weight, table) version
                 wp = self.eval_weights_typed(table, x.dtype)
             return _node_linear(x, wp, types.view(-1).contiguous(), self._meta)

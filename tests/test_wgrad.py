@@ -2,38 +2,38 @@
 backward of ScalarLinearLayer (nequip/nn/mlp.py:262-268), e3nn o3.Linear (interaction_block.py:82-87,129-138) and the
 per-type pre-contracted self-connection (:142-146), as restated in oracle/ (the oracle's autograd produces exactly these
 einsums)."""
-# Measured on an MI355X (rho = max |X - ref64| / (|A|^T |B|); bound: rho(kernel) <= 3 rho(fp32 CPU); the four settings are
-# (NQA_WGRAD_EXACT_FP32, NQA_WGRAD_WG_REDUCE), each entry rho(kernel) and its ratio to rho(fp32 CPU)).  The largest ratio
-# is 1.21; the CPU emulation without one 2^-16 product gives >= 4.6 (tests/test_wgrad_host.py).
+# Measured on an MI355X (rho = max |X - ref64| / (|A|^T |B|); bound: rho(kernel) <= 3 rho(fp32 CPU); the two settings are
+# NQA_WGRAD_EXACT_FP32 = 0 and 1, each entry rho(kernel) and its ratio to rho(fp32 CPU)).  The largest ratio is 0.92; the
+# CPU emulation without one 2^-16 product gives >= 4.6 (tests/test_wgrad_host.py).
 #
-# case                   fp32 CPU   (0, 1) default    (0, 0)            (1, 1)            (1, 0)
-# dense128-Z67-randn     2.200e-07  1.029e-07 0.47    1.109e-07 0.50    1.692e-07 0.77    1.593e-07 0.72
-# dense128-Z67-rows      2.089e-07  1.069e-07 0.51    1.147e-07 0.55    1.308e-07 0.63    1.463e-07 0.70
-# dense128-Z67-cols      2.084e-07  1.062e-07 0.51    1.361e-07 0.65    1.426e-07 0.68    1.562e-07 0.75
-# dense128-Z1000-randn   7.343e-08  2.792e-08 0.38    3.394e-08 0.46    3.107e-08 0.42    3.446e-08 0.47
-# dense128-Z1000-rows    7.225e-08  3.253e-08 0.45    3.065e-08 0.42    3.362e-08 0.47    3.171e-08 0.44
-# dense128-Z1000-cols    6.172e-08  2.686e-08 0.44    2.651e-08 0.43    3.287e-08 0.53    3.051e-08 0.49
-# dense128-Z4099-randn   2.977e-08  1.579e-08 0.53    1.500e-08 0.50    1.547e-08 0.52    1.515e-08 0.51
-# dense128-Z4099-rows    2.969e-08  1.343e-08 0.45    1.375e-08 0.46    1.641e-08 0.55    1.641e-08 0.55
-# dense128-Z4099-cols    2.901e-08  1.605e-08 0.55    1.453e-08 0.50    1.514e-08 0.52    1.548e-08 0.53
-# typed128-Z67-randn     3.592e-07  2.833e-07 0.79    3.244e-07 0.90    2.242e-07 0.62    2.811e-07 0.78
-# typed128-Z67-rows      2.185e-07  2.008e-07 0.92    2.636e-07 1.21    1.811e-07 0.83    1.797e-07 0.82
-# typed128-Z67-cols      2.941e-07  2.564e-07 0.87    3.250e-07 1.10    2.263e-07 0.77    2.416e-07 0.82
-# typed128-Z1000-randn   1.097e-07  6.546e-08 0.60    5.714e-08 0.52    4.421e-08 0.40    4.588e-08 0.42
-# typed128-Z1000-rows    1.455e-07  5.666e-08 0.39    5.556e-08 0.38    4.390e-08 0.30    4.061e-08 0.28
-# typed128-Z1000-cols    1.436e-07  7.038e-08 0.49    7.559e-08 0.53    6.567e-08 0.46    7.870e-08 0.55
-# typed128-Z4099-randn   4.208e-08  2.793e-08 0.66    2.840e-08 0.67    2.016e-08 0.48    2.017e-08 0.48
-# typed128-Z4099-rows    3.858e-08  2.966e-08 0.77    3.085e-08 0.80    1.964e-08 0.51    2.016e-08 0.52
-# typed128-Z4099-cols    6.223e-08  4.334e-08 0.70    4.068e-08 0.65    3.177e-08 0.51    3.019e-08 0.49
-# dense64-Z67-randn      2.054e-07  1.326e-07 0.65    1.546e-07 0.75    1.326e-07 0.65    1.546e-07 0.75
-# dense64-Z67-rows       1.983e-07  1.052e-07 0.53    1.744e-07 0.88    1.052e-07 0.53    1.744e-07 0.88
-# dense64-Z67-cols       2.646e-07  1.043e-07 0.39    1.668e-07 0.63    1.043e-07 0.39    1.668e-07 0.63
-# dense64-Z1000-randn    7.202e-08  3.512e-08 0.49    3.804e-08 0.53    3.512e-08 0.49    3.804e-08 0.53
-# dense64-Z1000-rows     5.894e-08  3.605e-08 0.61    2.957e-08 0.50    3.605e-08 0.61    2.957e-08 0.50
-# dense64-Z1000-cols     5.874e-08  3.622e-08 0.62    3.321e-08 0.57    3.622e-08 0.62    3.321e-08 0.57
-# dense64-Z4099-randn    2.837e-08  1.440e-08 0.51    1.440e-08 0.51    1.440e-08 0.51    1.440e-08 0.51
-# dense64-Z4099-rows     2.338e-08  1.940e-08 0.83    1.648e-08 0.70    1.940e-08 0.83    1.648e-08 0.70
-# dense64-Z4099-cols     2.630e-08  1.678e-08 0.64    1.697e-08 0.65    1.678e-08 0.64    1.697e-08 0.65
+# case                   fp32 CPU   0 (default)       1
+# dense128-Z67-randn     2.200e-07  1.029e-07 0.47    1.692e-07 0.77
+# dense128-Z67-rows      2.089e-07  1.069e-07 0.51    1.308e-07 0.63
+# dense128-Z67-cols      2.084e-07  1.062e-07 0.51    1.426e-07 0.68
+# dense128-Z1000-randn   7.343e-08  2.792e-08 0.38    3.107e-08 0.42
+# dense128-Z1000-rows    7.225e-08  3.253e-08 0.45    3.362e-08 0.47
+# dense128-Z1000-cols    6.172e-08  2.686e-08 0.44    3.287e-08 0.53
+# dense128-Z4099-randn   2.977e-08  1.579e-08 0.53    1.547e-08 0.52
+# dense128-Z4099-rows    2.969e-08  1.343e-08 0.45    1.641e-08 0.55
+# dense128-Z4099-cols    2.901e-08  1.605e-08 0.55    1.514e-08 0.52
+# typed128-Z67-randn     3.592e-07  2.833e-07 0.79    2.242e-07 0.62
+# typed128-Z67-rows      2.185e-07  2.008e-07 0.92    1.811e-07 0.83
+# typed128-Z67-cols      2.941e-07  2.564e-07 0.87    2.263e-07 0.77
+# typed128-Z1000-randn   1.097e-07  6.546e-08 0.60    4.421e-08 0.40
+# typed128-Z1000-rows    1.455e-07  5.666e-08 0.39    4.390e-08 0.30
+# typed128-Z1000-cols    1.436e-07  7.038e-08 0.49    6.567e-08 0.46
+# typed128-Z4099-randn   4.208e-08  2.793e-08 0.66    2.016e-08 0.48
+# typed128-Z4099-rows    3.858e-08  2.966e-08 0.77    1.964e-08 0.51
+# typed128-Z4099-cols    6.223e-08  4.334e-08 0.70    3.177e-08 0.51
+# dense64-Z67-randn      2.054e-07  1.326e-07 0.65    1.326e-07 0.65
+# dense64-Z67-rows       1.983e-07  1.052e-07 0.53    1.052e-07 0.53
+# dense64-Z67-cols       2.646e-07  1.043e-07 0.39    1.043e-07 0.39
+# dense64-Z1000-randn    7.202e-08  3.512e-08 0.49    3.512e-08 0.49
+# dense64-Z1000-rows     5.894e-08  3.605e-08 0.61    3.605e-08 0.61
+# dense64-Z1000-cols     5.874e-08  3.622e-08 0.62    3.622e-08 0.62
+# dense64-Z4099-randn    2.837e-08  1.440e-08 0.51    1.440e-08 0.51
+# dense64-Z4099-rows     2.338e-08  1.940e-08 0.83    1.940e-08 0.83
+# dense64-Z4099-cols     2.630e-08  1.678e-08 0.64    1.678e-08 0.64
 import subprocess
 
 import pytest
@@ -105,7 +105,7 @@ def test_wgrad_partial_coverage_and_empty(device):
 @pytest.mark.parametrize("name", [c.name for c in wc.EXACT_CASES])
 def test_wgrad_exact(device, name):
     """Integer data: bit-for-bit equal to the float64 reference, output gaps zero, partial elements outside every record
-    untouched (forced-S cases).  Default switches: wgrad_kernel<1 | 2, TYPED, true> and wgrad_split_kernel<TYPED, true>."""
+    untouched (forced-S cases).  Default switch: wgrad_kernel<1 | 2, TYPED, false> and wgrad_kernel<2, TYPED, true>."""
     fails = wc.check_exact(wc.EXACT_BY_NAME[name], device)
     assert not fails, "\n".join(fails)
 
@@ -180,12 +180,12 @@ def test_wgrad_accuracy_and_determinism(device, name):
 
 @pytest.mark.gpu
 def test_wgrad_switch_settings_in_child_processes(device):
-    """NQA_WGRAD_EXACT_FP32 x NQA_WGRAD_WG_REDUCE (function-local statics: a fresh process each), one child after another:
-    each proves from nqa_wgrad_splits that its setting took effect, then runs the exact-data list and the accuracy cases.
-    (0, 0): WGRED = false of wgrad_kernel<1 | 2> and the split kernel; (1, *): wgrad_kernel<4, *, *>.  The first child that
-    fails, is killed by a signal or runs out of time ends the test: no further child is started."""
-    for exact_fp32, wg_reduce in wc.SWITCH_SETTINGS:
-        done = subprocess.run(wc.child_command("child_gpu_main"), timeout=300, env=wc.child_env(exact_fp32, wg_reduce),
+    """NQA_WGRAD_EXACT_FP32 = 0 and 1 (a function-local static: a fresh process each), one child after another: each
+    proves from nqa_wgrad_splits that its setting took effect, then runs the exact-data list and the accuracy cases.
+    1: wgrad_kernel<4, *, false> instead of wgrad_kernel<2, *, true>.  The first child that fails, is killed by a signal or
+    runs out of time ends the test: no further child is started."""
+    for exact_fp32 in wc.SWITCH_SETTINGS:
+        done = subprocess.run(wc.child_command("child_gpu_main"), timeout=300, env=wc.child_env(exact_fp32),
                               capture_output=True, text=True)
         print(done.stdout)
-        assert done.returncode == 0, (exact_fp32, wg_reduce, done.returncode, done.stdout[-4000:], done.stderr[-4000:])
+        assert done.returncode == 0, (exact_fp32, done.returncode, done.stdout[-4000:], done.stderr[-4000:])

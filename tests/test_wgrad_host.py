@@ -1,5 +1,5 @@
 """Host side of ``nqa_wgrad`` (``nequip_amd/csrc/wgrad.hip``, ``nequip_amd/utils/wgrad.py``) without a GPU: the split count
-``nqa_wgrad_splits`` suggests, the calls that ``nqa_wgrad`` refuses before any launch, the two environment switches of the
+``nqa_wgrad_splits`` suggests, the calls that ``nqa_wgrad`` refuses before any launch, the environment switch of the
 kernel choice (read once per process, so probed in child processes), ``WgradTable.covered``, and the CPU emulation of the
 six-product bf16 split that shows the accuracy bound of ``tests/test_wgrad.py`` can fail."""
 
@@ -38,10 +38,10 @@ TABLES = [((0, 0, 8, 8, 1, 0),), ((0, 0, 32, 64, 1, 0),), ((0, 0, 64, 65, 3, 0),
 
 
 def test_splits_bounds_and_formula():
-    """1 <= S <= ceil(Z / (64 wpu)) for Z > 0, S = 1 for Z = 0, and the documented formula -- for the switches of this
-    process, whatever they are."""
-    exact_fp32, wg_reduce = wc.switches_from_env()
-    wpu = 4 if wg_reduce else 1
+    """1 <= S <= ceil(Z / (64 wpu)) for Z > 0, S = 1 for Z = 0, and the documented formula -- for the switch of this
+    process, whatever it is."""
+    exact_fp32 = wc.switches_from_env()
+    wpu = 4
     for records in TABLES:
         for T in (1, 5):
             for Z in (0, 1, 63, 64, 65, 255, 256, 257, 1000, 4099, 10 ** 5, 10 ** 6, 10 ** 9):
@@ -49,7 +49,7 @@ def test_splits_bounds_and_formula():
                 assert S >= 1, (records, T, Z, S)
                 if Z > 0:
                     assert S <= -(-Z // (64 * wpu)), (records, T, Z, S)
-                assert S == wc.expected_splits(records, T, Z, exact_fp32, wg_reduce), (records, T, Z, S)
+                assert S == wc.expected_splits(records, T, Z, exact_fp32), (records, T, Z, S)
 
 
 def test_splits_do_not_grow_with_the_tile_count():
@@ -119,22 +119,33 @@ def test_invalid_arguments_are_refused_before_any_launch():
 def test_expected_splits_literals():
     """The formula restated in ``wgrad_cases.expected_splits`` against the split counts named in the kernel's design notes:
     M = 128, N = 64 at Z = 10^6 and one tile at Z = 10^5 (there ``ceil(Z / (64 wpu))`` is the limit)."""
-    for (exact_fp32, wg_reduce), (wide, one_tile) in wc.PROBE_LITERALS.items():
-        assert wc.expected_splits(wc.PROBE_WIDE, 1, 10 ** 6, exact_fp32, wg_reduce) == wide
-        assert wc.expected_splits(wc.PROBE_ONE_TILE, 1, 10 ** 5, exact_fp32, wg_reduce) == one_tile
-    assert wc.switches_from_env({}) == (False, True)
-    assert wc.switches_from_env({"NQA_WGRAD_EXACT_FP32": "", "NQA_WGRAD_WG_REDUCE": ""}) == (False, True)
-    assert wc.switches_from_env({"NQA_WGRAD_EXACT_FP32": "0", "NQA_WGRAD_WG_REDUCE": "0"}) == (False, False)
-    assert wc.switches_from_env({"NQA_WGRAD_EXACT_FP32": "1", "NQA_WGRAD_WG_REDUCE": "1"}) == (True, True)
+    assert set(wc.PROBE_LITERALS) == {False, True}
+    for exact_fp32, (wide, one_tile) in wc.PROBE_LITERALS.items():
+        assert wc.expected_splits(wc.PROBE_WIDE, 1, 10 ** 6, exact_fp32) == wide
+        assert wc.expected_splits(wc.PROBE_ONE_TILE, 1, 10 ** 5, exact_fp32) == one_tile
+    assert wc.switches_from_env({}) is False
+    assert wc.switches_from_env({"NQA_WGRAD_EXACT_FP32": ""}) is False
+    assert wc.switches_from_env({"NQA_WGRAD_EXACT_FP32": "0"}) is False
+    assert wc.switches_from_env({"NQA_WGRAD_EXACT_FP32": "1"}) is True
 
 
 def test_switches_reach_the_library_in_a_fresh_process():
-    """The four settings of (NQA_WGRAD_EXACT_FP32, NQA_WGRAD_WG_REDUCE), one child process after another: each asserts the
-    split counts its setting implies.  Stops at the first child that fails."""
-    for exact_fp32, wg_reduce in wc.SWITCH_SETTINGS:
-        done = subprocess.run(wc.child_command("child_host_main"), timeout=120, env=wc.child_env(exact_fp32, wg_reduce),
+    """The two settings of NQA_WGRAD_EXACT_FP32, one child process after another: each asserts the split counts its setting
+    implies.  Stops at the first child that fails."""
+    for exact_fp32 in wc.SWITCH_SETTINGS:
+        done = subprocess.run(wc.child_command("child_host_main"), timeout=120, env=wc.child_env(exact_fp32),
                               capture_output=True, text=True)
-        assert done.returncode == 0, (exact_fp32, wg_reduce, done.returncode, done.stdout[-2000:], done.stderr[-2000:])
+        assert done.returncode == 0, (exact_fp32, done.returncode, done.stdout[-2000:], done.stderr[-2000:])
+
+
+def test_the_removed_wg_reduce_switch_is_no_longer_honoured():
+    """NQA_WGRAD_WG_REDUCE=0 once selected one partial tile per wavefront (split counts 1024 / 1563 and 2048 / 1563 at the
+    probes).  The switch is gone: a fresh process with it in the environment still gives the counts of four wavefronts per
+    partial, under both settings of the switch that stays."""
+    for exact_fp32 in wc.SWITCH_SETTINGS:
+        env = dict(wc.child_env(exact_fp32), NQA_WGRAD_WG_REDUCE="0")
+        done = subprocess.run(wc.child_command("child_host_main"), timeout=120, env=env, capture_output=True, text=True)
+        assert done.returncode == 0, (exact_fp32, done.returncode, done.stdout[-2000:], done.stderr[-2000:])
 
 
 def test_covered_means_an_exact_tiling():

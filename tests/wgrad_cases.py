@@ -1,5 +1,5 @@
 """Cases and checkers of ``nqa_wgrad`` (``nequip_amd/csrc/wgrad.hip``), shared by ``tests/test_wgrad.py``,
-``tests/test_wgrad_host.py`` and the child processes these start (the two environment switches of the kernel choice are read
+``tests/test_wgrad_host.py`` and the child processes these start (the environment switch of the kernel choice is read
 once per process).  A plain module: no fixtures, no pytest import.
 
 The reference is float64 and built by index: ``ref[t] = A[types == t]^T B[types == t]`` per record, the ``d`` components of
@@ -61,8 +61,8 @@ def _case(name, Z, blocks, **kw):
 
 
 # ---- the case lists --------------------------------------------------------------------------------------------------------
-# kernel choice (wgrad_rb): widest M <= 32 -> wgrad_kernel<1>, <= 64 -> wgrad_kernel<2>, wider -> wgrad_split_kernel (or
-# wgrad_kernel<4> under NQA_WGRAD_EXACT_FP32=1); T > 1 with types -> TYPED; NQA_WGRAD_WG_REDUCE=0 -> WGRED = false.
+# kernel choice (wgrad_rb): widest M <= 32 -> wgrad_kernel<1>, <= 64 -> wgrad_kernel<2>, wider -> the split form
+# wgrad_kernel<2, *, true> (or wgrad_kernel<4> under NQA_WGRAD_EXACT_FP32=1); T > 1 with types -> TYPED.
 SPLIT_M, SPLIT_N, SPLIT_D = (65, 100, 128, 130), (1, 63, 64, 65, 129), (1, 3, 5, 7)
 MIXED = ((8, 40, 3), (33, 65, 1), (64, 64, 5), (100, 63, 7))  # an 8-row record in the wide kernel, one launch
 NARROW = ((8, 40, 3), (33, 65, 1), (64, 64, 5))
@@ -328,7 +328,7 @@ def check_accuracy(case: Case, device):
 
 
 # ---- CPU emulation of the six-product scheme (mfma_split.h: x = hi + mid + lo in bf16, fp32 products) ------------------------
-PRODUCTS = ("mid.mid", "hi.lo", "lo.hi", "hi.mid", "mid.hi", "hi.hi")  # the order of wgrad_split_kernel's mfma_bf16 lines
+PRODUCTS = ("mid.mid", "hi.lo", "lo.hi", "hi.mid", "mid.hi", "hi.hi")  # the order of the split form's mfma_bf16 lines
 
 
 def bf16_planes(x: torch.Tensor):
@@ -354,30 +354,28 @@ def emulation_case(Z: int, kind: str) -> Case:
     return _case(f"emulation-Z{Z}-{kind}", Z, ((96, 80, 1),), data=kind)
 
 
-# ---- the two switches ------------------------------------------------------------------------------------------------------------
-SWITCH_SETTINGS = (("0", "1"), ("0", "0"), ("1", "1"), ("1", "0"))  # (NQA_WGRAD_EXACT_FP32, NQA_WGRAD_WG_REDUCE)
+# ---- the switch -----------------------------------------------------------------------------------------------------------------
+SWITCH_SETTINGS = ("0", "1")  # NQA_WGRAD_EXACT_FP32
 PROBE_WIDE = ((0, 0, 128, 64, 1, 0),)  # two 64-row tiles in the wide kernel, one 128-row tile on the fp32 path
 PROBE_ONE_TILE = ((0, 0, 64, 64, 1, 0),)
-# nqa_wgrad_splits(PROBE_WIDE, T = 1, Z = 10^6) and (PROBE_ONE_TILE, 1, 10^5) per (exact_fp32, wg_reduce)
-PROBE_LITERALS = {(False, True): (256, 391), (False, False): (1024, 1563), (True, True): (512, 391),
-                  (True, False): (2048, 1563)}
+# nqa_wgrad_splits(PROBE_WIDE, T = 1, Z = 10^6) and (PROBE_ONE_TILE, 1, 10^5) per exact_fp32
+PROBE_LITERALS = {False: (256, 391), True: (512, 391)}
 
 
 def switches_from_env(env=None):
-    """(exact_fp32, wg_reduce) as ``wgrad.hip`` parses the environment."""
+    """exact_fp32 as ``wgrad.hip`` parses the environment."""
     env = os.environ if env is None else env
     e = env.get("NQA_WGRAD_EXACT_FP32", "")
-    r = env.get("NQA_WGRAD_WG_REDUCE", "")
-    return (e != "" and e[0] != "0"), not (r != "" and r[0] == "0")
+    return e != "" and e[0] != "0"
 
 
-def expected_splits(records, T: int, Z: int, exact_fp32: bool, wg_reduce: bool) -> int:
+def expected_splits(records, T: int, Z: int, exact_fp32: bool) -> int:
     """The formula of ``nqa_wgrad_splits``."""
     max_m = max(r[2] for r in records)
     split = max_m > 64 and not exact_fp32
     rb = 1 if max_m <= 32 else (2 if (max_m <= 64 or split) else 4)
     tiles = T * sum(-(-r[2] // (32 * rb)) * -(-r[3] // 64) for r in records)
-    wpu = 4 if wg_reduce else 1
+    wpu = 4  # wavefronts per partial: the four of a workgroup share one
     S = -(-(2048 // wpu) // tiles)
     return max(1, min(S, -(-Z // (64 * wpu))))
 
@@ -389,25 +387,24 @@ def library_splits(records, T: int, Z: int) -> int:
 
 
 def check_switches():
-    """Failure strings: did this process's environment switches reach the library?  Host-visible only (the split counts)."""
-    exact_fp32, wg_reduce = switches_from_env()
+    """Failure strings: did this process's environment switch reach the library?  Host-visible only (the split counts)."""
+    exact_fp32 = switches_from_env()
     fails = []
-    lit = PROBE_LITERALS[exact_fp32, wg_reduce]
+    lit = PROBE_LITERALS[exact_fp32]
     probes = [(PROBE_WIDE, 1, 10 ** 6, lit[0]), (PROBE_ONE_TILE, 1, 10 ** 5, lit[1]),
               (PROBE_WIDE, 1, 10 ** 5, None), (PROBE_WIDE, 5, 10 ** 6, None), (PROBE_ONE_TILE, 1, 10 ** 6, None)]
     for records, T, Z, literal in probes:
-        want = expected_splits(records, T, Z, exact_fp32, wg_reduce)
+        want = expected_splits(records, T, Z, exact_fp32)
         got = library_splits(records, T, Z)
         if literal is not None and want != literal:
             fails.append(f"expected_splits({records}, {T}, {Z}) = {want}, the literal says {literal}")
         if got != want:
-            fails.append(f"nqa_wgrad_splits({records}, {T}, {Z}) = {got}, expected {want} for exact_fp32={exact_fp32} "
-                         f"wg_reduce={wg_reduce}")
+            fails.append(f"nqa_wgrad_splits({records}, {T}, {Z}) = {got}, expected {want} for exact_fp32={exact_fp32}")
     return fails
 
 
-def child_env(exact_fp32: str, wg_reduce: str):
-    return dict(os.environ, NQA_WGRAD_EXACT_FP32=exact_fp32, NQA_WGRAD_WG_REDUCE=wg_reduce)
+def child_env(exact_fp32: str):
+    return dict(os.environ, NQA_WGRAD_EXACT_FP32=exact_fp32)
 
 
 def child_command(entry: str):
@@ -425,14 +422,14 @@ def child_host_main() -> int:
 
 
 def child_gpu_main() -> int:
-    """Child process on the GPU: prove the switches took effect, then the exact-data list and the accuracy cases."""
+    """Child process on the GPU: prove the switch took effect, then the exact-data list and the accuracy cases."""
     fails = check_switches()
     if fails:  # the wrong kernels would run: nothing below would mean what it claims
         for f in fails:
             print("FAIL", f)
         return 1
     device = torch.device("cuda:0")
-    setting = "exact_fp32=%d wg_reduce=%d" % switches_from_env()
+    setting = "exact_fp32=%d" % switches_from_env()
     for case in EXACT_CASES:
         fails += check_exact(case, device)
     for case in ACCURACY_CASES:
