@@ -804,6 +804,21 @@ int nqa_neighbor_list_batched_fill_typed(const void* workspace, const int32_t* r
                                          int64_t* edge_index, double* edge_cell_shift, nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * STREAM / TERM / SLOT reductions: the form nqa_metrics_* and nqa_stats_* below share.
+ *   A STREAM is one [rows, cols] row-major tensor (or pair of tensors) that is read once; a TERM is one quantity reduced over a
+ *   stream; a term owns n_groups SLOTS, slot g collecting the elements of group g.  The term table is ordered by stream
+ *   ("terms must be ordered by stream") and slot0 counts the slots of the terms before it ("slots must be contiguous in term
+ *   order"); every stream carries at least one term ("a stream without terms").  A table that breaks one of these is refused
+ *   with NQA_ERR_INVALID and that text under the entry point's name, before anything is launched.
+ *   Two stages.  A fixed number of workgroups (NQA_*_GROUPS) walk every stream once and leave ONE row of per-slot partial
+ *   accumulators each in `workspace`: [groups, slots] per 8-byte plane, nqa_*_workspace_bytes(total slots), 8-byte aligned.
+ *   Inside a workgroup the elements of a slot are folded in element order by a fixed number of owner threads, whose parts are
+ *   merged in part order.  The second stage merges the rows in row order, and where lanes of a wavefront hold partial results
+ *   lane l takes lane l + off behind itself, off = 32 .. 1.  No floating-point atomics and a fixed merge order everywhere: the
+ *   same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+
+/* ---------------------------------------------------------------------------------------------
  * Losses and error metrics on one fused reduction: what nequip.train.MetricsManager.forward evaluates entry by entry
  *   (nequip/train/metrics_manager.py:283-373; the metric classes of nequip/train/metrics.py on nequip/data/stats.py::_MeanX;
  *   nequip/data/modifier.py::PerAtomModifier), without boolean indexing, masked_select or a host read.
@@ -820,12 +835,12 @@ int nqa_neighbor_list_batched_fill_typed(const void* workspace, const int32_t* r
  *   max (-inf without elements); no element: 0 / 0 = NaN.  Term value: the slot value, or over the groups whose value is not
  *   NaN the equal mean / sum(c_g v_g) / sum(c_g) with has_group_coeffs.  weighted_sum = sum over the terms with has_coeff of
  *   coeff * term value, in term order.
- *   The term table: ordered by stream, slot0 contiguous in term order; out0 is the index of the term's first returned value
+ *   The term table (ordered as described above): out0 is the index of the term's first returned value
  *   (n_groups > 1: out0 + g per group, out0 + n_groups the aggregate).  It is read on the device (terms_device: a device
  *   copy of the host table `terms`, which the entry points use for checking and sizing); streams are passed by value.
- * nqa_metrics_fwd: two launches.  NQA_METRICS_GROUPS workgroups (nqa_metrics_groups) walk every stream once and leave one
- *   row of per-slot partials each in `workspace` (nqa_metrics_workspace_bytes(total slots), 8-byte aligned); one workgroup
- *   adds the rows in row order (no floating-point atomics: bit-reproducible) and writes values [n_values] (float64),
+ * nqa_metrics_fwd: two launches, the two stages described above.  NQA_METRICS_GROUPS workgroups (nqa_metrics_groups) leave
+ *   their rows of partials (sum, count, max) in `workspace` (nqa_metrics_workspace_bytes(total slots)); one workgroup
+ *   adds the rows in row order and writes values [n_values] (float64),
  *   saved [2, slots] (batch sums float64, counts int64: for the backward) and, if state != NULL, adds the batch to the running
  *   state [3, slots] (sum float64, count int64, max float64; the caller initialises 0, 0, -inf).  rows == 0 is valid.
  *   The first launch keeps 256 float64 values per term of one stream in LDS: from about 30 terms on ONE stream it asks the
@@ -1012,18 +1027,17 @@ int nqa_config_solve_host(const double* gram, int32_t n_terms, const double* b, 
  *   still enters the terms with one slot).
  *   A TERM is one entry on a stream; it owns 1 slot, or T (node stream) / T * T (edge stream) slots: slot g collects the
  *   elements of group g.  ignore_nan: a NaN element contributes to nothing of that term; otherwise NaN propagates (through min
- *   and max as well).  The table is ordered by stream, slot0 contiguous in term order; both tables are HOST pointers, passed to
- *   the kernels by value.
+ *   and max as well).  The table is ordered as described above; both tables are HOST pointers, passed to the kernels by value.
  *   Running state [6, slots], 8 bytes each: count (int64), mean, mean_lo, M2 = sum (y - mean)^2, min, max (float64) of y = m(x)
  *   with m the term's modifier; the caller initialises 0, 0, 0, 0, +inf, -inf.  The mean is mean + mean_lo: mean the rounded
  *   value, mean_lo what the rounding lost, so that the difference of two means in Chan's merge keeps its digits when the data
  *   are large against their spread.  Every metric kind follows from the state: mean, sqrt(mean of squares), M2 / (count - 1),
  *   min, max, count.
- * nqa_stats_update: two launches for any number of terms and types.  NQA_STATS_GROUPS workgroups (nqa_stats_groups) walk every
- *   stream once and leave one row of per-slot partial states each in `workspace` (nqa_stats_workspace_bytes(total slots), 8-byte
- *   aligned): Welford updates in element order, Chan merges in a fixed order.  One wavefront per slot then merges the rows in a
- *   fixed order and the batch into the running state; a slot that received no element stays bit for bit.  No floating-point
- *   atomics: bit-reproducible.  No sum of squares is differenced.  All rows == 0: nothing is launched.
+ * nqa_stats_update: two launches for any number of terms and types, the two stages described above.  NQA_STATS_GROUPS
+ *   workgroups (nqa_stats_groups) leave their rows of partial states in `workspace` (nqa_stats_workspace_bytes(total slots)):
+ *   Welford updates in element order, Chan merges in the fixed order.  One wavefront per slot then merges the rows and the batch
+ *   into the running state; a slot that received no element stays bit for bit.  No sum of squares is differenced.  All
+ *   rows == 0: nothing is launched.
  * nqa_stats_neighbor_counts: counts [num_atoms] int32 = number of edges with edge_center[e] == atom (zeroed here, then integer
  *   atomics: exact, any edge order); an index outside [0, num_atoms) is skipped.  num_atoms == 0: nothing is launched.
  *   No allocation, no host synchronisation: both capture into a hipGraph.

@@ -5,10 +5,9 @@
 // and `masked_select` for `ignore_nan` (data-dependent shapes: a host synchronisation each) and one `.item()` per entry.  Here
 // a STREAM is one distinct (prediction, target) pair and a TERM one metric attached to a stream; a term owns one SLOT per
 // group (1, or one per atom type).  Forward, two launches for any number of terms:
-//   metrics_partial_kernel  NQA_METRICS_GROUPS workgroups walk every stream once (grid stride over the elements, both sides
-//                           promoted to float64 before the subtraction) and leave ONE row of per-slot partials each:
-//                           sum of the modifier of the difference (float64), count of contributing elements (int64),
-//                           maximum of |d| (float64);
+//   metrics_partial_kernel  the first stage of slot_reduce.h on NQA_METRICS_GROUPS workgroups (both sides promoted to float64
+//                           before the subtraction); a row of partials holds per slot the sum of the modifier of the difference
+//                           (float64), the count of contributing elements (int64) and the maximum of |d| (float64);
 //   metrics_final_kernel    one workgroup adds the rows in row order (no floating-point atomics anywhere: bit-reproducible),
 //                           forms every slot's batch value, the aggregate over types, weighted_sum, adds the batch to the
 //                           running epoch state and writes every returned value into one float64 vector.
@@ -17,11 +16,7 @@
 // Nothing here depends on data read by the host: forward, state update and backward capture into a hipGraph.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdint>
-#include <string>
-
-#include "launch_status.h"
+#include "slot_reduce.h"
 
 namespace nqa {
 
@@ -35,21 +30,16 @@ constexpr int MT_PARTS = 4;  // owners per slot in the first stage: each adds 64
 
 struct MetricsArgs {
   nqa_metric_stream st[MT_MAX_STREAMS];
-  int32_t term_begin[MT_MAX_STREAMS], term_count[MT_MAX_STREAMS];  // the terms of a stream are contiguous in the table
-  int32_t slot_begin[MT_MAX_STREAMS], slot_count[MT_MAX_STREAMS];  // ... and so are their slots
-  int32_t need_norm[MT_MAX_STREAMS];                               // a stratified term: the target's row norm is needed
-  const nqa_metric_term* __restrict__ terms;                       // device table
-  int32_t n_streams, n_terms, n_slots, n_values;
-  int32_t kmax, lmax;  // most terms / slots of one stream: the LDS layout of the first stage
+  SlotLayout<MT_MAX_STREAMS> lay;
+  int32_t need_norm[MT_MAX_STREAMS];          // a stratified term: the target's row norm is needed
+  const nqa_metric_term* __restrict__ terms;  // device table
+  int32_t n_values, kmax;  // kmax: the most terms of one stream (with lay.lmax: the LDS layout of the first stage)
   int32_t ws_index, pad;
 };
 
 __device__ __forceinline__ double mt_load(const void* __restrict__ p, int dtype, int64_t i) {
   return dtype == NQA_F64 ? static_cast<const double*>(p)[i] : (double)static_cast<const float*>(p)[i];
 }
-
-// maximum that keeps a NaN (torch.maximum / Tensor.max do)
-__device__ __forceinline__ double mt_nanmax(double a, double b) { return (a != a || b != b) ? (a + b) : fmax(a, b); }
 
 // the stratum of a row: `norm >= bound[i]` and not `norm >= bound[i + 1]`, in the order the strata were given (the last
 // match wins, a NaN norm matches none: that row's loss is 0)
@@ -165,99 +155,96 @@ __device__ __forceinline__ MtElement mt_element(const nqa_metric_stream& st, boo
   return e;
 }
 
-// ---- forward, first stage -------------------------------------------------------------------------------------------------
-// LDS: vals [kmax, 256] float64 (one value per term of the stream and element of the sweep), acc_val / acc_cnt
-// [MT_PARTS, lmax] (one writing thread per entry: plain read-modify-write), slot_term / slot_group [lmax], grp / msk [256].
+// ---- forward, first stage: the policy of slot_sweep --------------------------------------------------------------------------
+// LDS behind the slot map: vals [kmax, 256] float64 (one value per term of the stream and element of the sweep), acc_val /
+// acc_cnt [MT_PARTS, lmax], grp / msk [256] (the group of an element and the terms it contributes to).
+struct MtAcc {
+  double v;  // the sum, or the maximum of a max-abs term
+  int64_t c;
+};
+
+struct MtSweep {
+  const MetricsArgs& a;
+  double *__restrict__ part_sum, *__restrict__ part_max, *__restrict__ vals, *__restrict__ acc_val;
+  int64_t *__restrict__ part_cnt, *__restrict__ acc_cnt;
+  int32_t* __restrict__ grp;
+  uint32_t* __restrict__ msk;
+  const nqa_metric_term* __restrict__ terms;  // of the open stream
+  int s, tc;
+  static constexpr bool INIT_READS_SLOT_MAP = true;  // (a max-abs term starts from -inf)
+
+  __device__ __forceinline__ MtSweep(const MetricsArgs& a_, char* lds, double* ps, int64_t* pc, double* pm) : a(a_) {
+    part_sum = ps, part_cnt = pc, part_max = pm;
+    vals = reinterpret_cast<double*>(lds);
+    acc_val = vals + (size_t)a.kmax * 256;
+    acc_cnt = reinterpret_cast<int64_t*>(acc_val + (size_t)MT_PARTS * a.lay.lmax);
+    grp = reinterpret_cast<int32_t*>(acc_cnt + (size_t)MT_PARTS * a.lay.lmax);
+    msk = reinterpret_cast<uint32_t*>(grp + 256);
+  }
+  __device__ __forceinline__ int64_t open(int stream) {
+    s = stream, terms = a.terms + a.lay.term_begin[s], tc = a.lay.term_count[s];
+    return a.st[s].rows * a.st[s].cols;
+  }
+  __device__ __forceinline__ int parts() const { return MT_PARTS; }
+  __device__ __forceinline__ const nqa_metric_term& term(int k) const { return terms[k]; }
+  __device__ __forceinline__ bool is_max(int k) const { return terms[k].kind == NQA_METRIC_MAXABS; }
+  __device__ __forceinline__ void init(int part, int sl, int k) {
+    acc_val[part * a.lay.lmax + sl] = is_max(k) ? -INFINITY : 0.0;
+    acc_cnt[part * a.lay.lmax + sl] = 0;
+  }
+  __device__ __forceinline__ void stage(int64_t idx, bool in_range) {
+    const int tid = threadIdx.x;
+    uint32_t m = 0;
+    int g = 0;
+    if (in_range) {
+      const MtElement e = mt_element(a.st[s], a.need_norm[s] != 0, idx);
+      g = e.g;
+      for (int k = 0; k < tc; ++k) {
+        const nqa_metric_term* __restrict__ t = terms + k;
+        if (t->ignore_nan && e.tnan) continue;  // masked on the TARGET, as the reference
+        m |= 1u << k;
+        vals[k * 256 + tid] = mt_value(t, e.d, e.norm);
+      }
+    }
+    msk[tid] = m;
+    grp[tid] = g;
+  }
+  __device__ __forceinline__ void fold(int part, int sl, int k, int gg, int i0, int share) {
+    const bool grouped = terms[k].n_groups > 1, mx = is_max(k);
+    double v = acc_val[part * a.lay.lmax + sl];
+    int64_t c = acc_cnt[part * a.lay.lmax + sl];
+    // every load is unconditional (so that the LDS reads of an unrolled block are in flight together) and a value that
+    // does not belong to the slot -- possibly a stale one -- is dropped by a select, never by arithmetic
+#pragma unroll 8
+    for (int i = i0; i < i0 + share; ++i) {
+      const bool hit = ((msk[i] >> k) & 1u) && (!grouped || grp[i] == gg);
+      const double x = vals[k * 256 + i];
+      const double vn = mx ? sr_nanmax(v, x) : v + x;
+      v = hit ? vn : v;
+      c += hit ? 1 : 0;
+    }
+    acc_val[part * a.lay.lmax + sl] = v;
+    acc_cnt[part * a.lay.lmax + sl] = c;
+  }
+  __device__ __forceinline__ MtAcc load(int part, int sl) const {
+    return {acc_val[part * a.lay.lmax + sl], acc_cnt[part * a.lay.lmax + sl]};
+  }
+  __device__ __forceinline__ MtAcc merge(const MtAcc& x, const MtAcc& y, int k) const {
+    return MtAcc{is_max(k) ? sr_nanmax(x.v, y.v) : x.v + y.v, x.c + y.c};
+  }
+  __device__ __forceinline__ void store(int64_t o, const MtAcc& r, int k) {
+    part_sum[o] = is_max(k) ? 0.0 : r.v;
+    part_max[o] = is_max(k) ? r.v : -INFINITY;
+    part_cnt[o] = r.c;
+  }
+};
+
 __global__ __launch_bounds__(256) void metrics_partial_kernel(const MetricsArgs a, double* __restrict__ part_sum,
                                                               int64_t* __restrict__ part_cnt,
                                                               double* __restrict__ part_max) {
   extern __shared__ __attribute__((aligned(16))) char mt_smem[];
-  double* __restrict__ vals = reinterpret_cast<double*>(mt_smem);
-  double* __restrict__ acc_val = vals + (size_t)a.kmax * 256;
-  int64_t* __restrict__ acc_cnt = reinterpret_cast<int64_t*>(acc_val + (size_t)MT_PARTS * a.lmax);
-  int32_t* __restrict__ slot_term = reinterpret_cast<int32_t*>(acc_cnt + (size_t)MT_PARTS * a.lmax);
-  int32_t* __restrict__ slot_group = slot_term + a.lmax;
-  int32_t* __restrict__ grp = slot_group + a.lmax;
-  uint32_t* __restrict__ msk = reinterpret_cast<uint32_t*>(grp + 256);
-  const int tid = threadIdx.x;
-
-  for (int s = 0; s < a.n_streams; ++s) {
-    const nqa_metric_stream& st = a.st[s];
-    const int tb = a.term_begin[s], tc = a.term_count[s], sb = a.slot_begin[s], sc = a.slot_count[s];
-    const bool need_norm = a.need_norm[s] != 0;
-    for (int k = tid; k < tc; k += 256) {
-      const nqa_metric_term* __restrict__ t = a.terms + tb + k;
-      for (int g = 0; g < t->n_groups; ++g) {
-        slot_term[t->slot0 - sb + g] = k;
-        slot_group[t->slot0 - sb + g] = g;
-      }
-    }
-    __syncthreads();
-    for (int o = tid; o < MT_PARTS * sc; o += 256) {
-      const int part = o / sc, sl = o - part * sc;
-      const bool is_max = a.terms[tb + slot_term[sl]].kind == NQA_METRIC_MAXABS;
-      acc_val[part * a.lmax + sl] = is_max ? -INFINITY : 0.0;
-      acc_cnt[part * a.lmax + sl] = 0;
-    }
-    // (the loop's barrier, or the one behind it, orders the initialisation before the first read)
-    const int64_t total = st.rows * st.cols;
-    for (int64_t base = (int64_t)blockIdx.x * 256; base < total; base += (int64_t)gridDim.x * 256) {  // uniform trip count
-      const int64_t idx = base + tid;
-      uint32_t m = 0;
-      int g = 0;
-      if (idx < total) {
-        const MtElement e = mt_element(st, need_norm, idx);
-        g = e.g;
-        for (int k = 0; k < tc; ++k) {
-          const nqa_metric_term* __restrict__ t = a.terms + tb + k;
-          if (t->ignore_nan && e.tnan) continue;  // masked on the TARGET, as the reference
-          m |= 1u << k;
-          vals[k * 256 + tid] = mt_value(t, e.d, e.norm);
-        }
-      }
-      msk[tid] = m;
-      grp[tid] = g;
-      __syncthreads();
-      for (int o = tid; o < MT_PARTS * sc; o += 256) {
-        const int part = o / sc, sl = o - part * sc;
-        const int k = slot_term[sl], gg = slot_group[sl];
-        const nqa_metric_term* __restrict__ t = a.terms + tb + k;
-        const bool grouped = t->n_groups > 1, is_max = t->kind == NQA_METRIC_MAXABS;
-        double v = acc_val[part * a.lmax + sl];
-        int64_t c = acc_cnt[part * a.lmax + sl];
-        const int i0 = part * (256 / MT_PARTS);
-        // every load is unconditional (so that the LDS reads of an unrolled block are in flight together) and a value that
-        // does not belong to the slot -- possibly a stale one -- is dropped by a select, never by arithmetic
-#pragma unroll 8
-        for (int i = i0; i < i0 + 256 / MT_PARTS; ++i) {
-          const bool hit = ((msk[i] >> k) & 1u) && (!grouped || grp[i] == gg);
-          const double x = vals[k * 256 + i];
-          const double vn = is_max ? mt_nanmax(v, x) : v + x;
-          v = hit ? vn : v;
-          c += hit ? 1 : 0;
-        }
-        acc_val[part * a.lmax + sl] = v;
-        acc_cnt[part * a.lmax + sl] = c;
-      }
-      __syncthreads();
-    }
-    __syncthreads();
-    for (int sl = tid; sl < sc; sl += 256) {  // the parts in a fixed order: one row of partials per workgroup
-      const bool is_max = a.terms[tb + slot_term[sl]].kind == NQA_METRIC_MAXABS;
-      double v = acc_val[sl];
-      int64_t c = acc_cnt[sl];
-      for (int part = 1; part < MT_PARTS; ++part) {
-        const double x = acc_val[part * a.lmax + sl];
-        v = is_max ? mt_nanmax(v, x) : v + x;
-        c += acc_cnt[part * a.lmax + sl];
-      }
-      const int64_t o = (int64_t)blockIdx.x * a.n_slots + sb + sl;
-      part_sum[o] = is_max ? 0.0 : v;
-      part_max[o] = is_max ? v : -INFINITY;
-      part_cnt[o] = c;
-    }
-    __syncthreads();  // the next stream reuses the LDS
-  }
+  MtSweep p(a, mt_smem + (size_t)a.lay.lmax * 8, part_sum, part_cnt, part_max);
+  slot_sweep(a.lay, reinterpret_cast<int32_t*>(mt_smem), p);
 }
 
 // ---- forward, second stage: one workgroup -----------------------------------------------------------------------------------
@@ -301,7 +288,7 @@ __global__ __launch_bounds__(256) void metrics_final_kernel(const MetricsFinalAr
     for (int b = 0; b < f.groups; ++b) {  // row order
       sum += __shfl(ps, b);
       cnt += __shfl(pc, b);
-      mx = mt_nanmax(mx, __shfl(pm, b));
+      mx = sr_nanmax(mx, __shfl(pm, b));
     }
     if (lane != 0) continue;
     f.saved_sum[s] = sum;
@@ -309,7 +296,7 @@ __global__ __launch_bounds__(256) void metrics_final_kernel(const MetricsFinalAr
     if (f.state_sum != nullptr) {
       f.state_sum[s] += sum;
       f.state_cnt[s] += cnt;
-      f.state_max[s] = mt_nanmax(f.state_max[s], mx);
+      f.state_max[s] = sr_nanmax(f.state_max[s], mx);
     }
     const double v = mt_slot_value(t, sum, cnt, mx);
     slot_val[s] = v;
@@ -361,7 +348,7 @@ __global__ __launch_bounds__(256) void metrics_bwd_kernel(const MetricsArgs a, c
   // every workgroup forms all the slot weights for itself from the device table and the saved sums: at most 512 slots of
   // a few operations each, cheaper than a launch of its own that would write them once
   const int tid = threadIdx.x;
-  for (int k = tid; k < a.n_terms; k += 256) {
+  for (int k = tid; k < a.lay.n_terms; k += 256) {
     const nqa_metric_term* __restrict__ t = a.terms + k;
     const int ng = t->n_groups;
     const double gws = (a.ws_index >= 0 && t->has_coeff) ? gout[a.ws_index] * t->coeff : 0.0;
@@ -397,10 +384,10 @@ __global__ __launch_bounds__(256) void metrics_bwd_kernel(const MetricsArgs a, c
     }
   }
   __syncthreads();
-  for (int s = 0; s < a.n_streams; ++s) {
+  for (int s = 0; s < a.lay.n_streams; ++s) {
     const nqa_metric_stream& st = a.st[s];
     if (st.grad_pred == nullptr) continue;
-    const int tb = a.term_begin[s], tc = a.term_count[s];
+    const int tb = a.lay.term_begin[s], tc = a.lay.term_count[s];
     const bool need_norm = a.need_norm[s] != 0;
     const int64_t total = st.rows * st.cols;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + tid; idx < total; idx += (int64_t)gridDim.x * 256) {
@@ -427,64 +414,36 @@ __global__ __launch_bounds__(256) void metrics_bwd_kernel(const MetricsArgs a, c
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-static std::string mt_range(int lo, int hi, const char* what) {
-  return std::to_string(lo) + " to " + std::to_string(hi) + " " + what;
-}
-static int mt_fail(const char* name, const std::string& what) {
-  set_error(std::string(name) + ": " + what);
-  return NQA_ERR_INVALID;
-}
-
 // checks the descriptors and fills the launch arguments; `terms` is the HOST copy of the device table
 static int mt_prepare(const char* name, const nqa_metric_stream* streams, int32_t n_streams, const nqa_metric_term* terms,
                       const nqa_metric_term* terms_device, int32_t n_terms, int32_t n_values, int32_t ws_index,
                       MetricsArgs& a) {
-  if (n_streams < 1 || n_streams > MT_MAX_STREAMS) return mt_fail(name, mt_range(1, MT_MAX_STREAMS, "streams"));
-  if (n_terms < 1 || n_terms > MT_MAX_TERMS) return mt_fail(name, mt_range(1, MT_MAX_TERMS, "terms"));
-  if (!streams || !terms || !terms_device) return mt_fail(name, "null descriptor table");
-  if (n_values < 1 || ws_index < -1 || ws_index >= n_values) return mt_fail(name, "weighted_sum index outside the values");
+  int rc = slot_limits(name, n_streams, MT_MAX_STREAMS, n_terms, MT_MAX_TERMS, streams && terms && terms_device);
+  if (rc != NQA_OK) return rc;
+  if (n_values < 1 || ws_index < -1 || ws_index >= n_values) return slot_fail(name, "weighted_sum index outside the values");
   a = MetricsArgs{};
   for (int s = 0; s < n_streams; ++s) {
     const nqa_metric_stream& st = streams[s];
     if (st.rows < 0 || st.cols < 1 || (st.pred_dtype != NQA_F32 && st.pred_dtype != NQA_F64) ||
         (st.target_dtype != NQA_F32 && st.target_dtype != NQA_F64) || (st.rows > 0 && (!st.pred || !st.target)))
-      return mt_fail(name, "invalid stream (rows >= 0, cols >= 1, float32 / float64 data)");
+      return slot_fail(name, "invalid stream (rows >= 0, cols >= 1, float32 / float64 data)");
     a.st[s] = st;
-    a.term_begin[s] = -1;
   }
-  int slot = 0, prev_stream = -1;
-  for (int k = 0; k < n_terms; ++k) {
-    const nqa_metric_term& t = terms[k];
-    if (t.stream < 0 || t.stream >= n_streams || t.stream < prev_stream)
-      return mt_fail(name, "terms must be ordered by stream");
-    if (t.kind < NQA_METRIC_MSE || t.kind > NQA_METRIC_STRATIFIED_HUBER) return mt_fail(name, "unknown metric kind");
-    if (t.n_groups < 1 || t.n_groups > MT_MAX_TYPES) return mt_fail(name, mt_range(1, MT_MAX_TYPES, "groups per term"));
+  rc = slot_layout_fill(name, terms, n_streams, n_terms, a.lay, [&](const nqa_metric_term& t, int) {
+    if (t.kind < NQA_METRIC_MSE || t.kind > NQA_METRIC_STRATIFIED_HUBER) return slot_fail(name, "unknown metric kind");
+    if (t.n_groups < 1 || t.n_groups > MT_MAX_TYPES) return slot_fail(name, slot_range(1, MT_MAX_TYPES, "groups per term"));
     if (t.n_groups > 1 && streams[t.stream].group == nullptr && streams[t.stream].rows > 0)
-      return mt_fail(name, "a grouped term needs the stream's group index");
+      return slot_fail(name, "a grouped term needs the stream's group index");
     if (t.kind == NQA_METRIC_STRATIFIED_HUBER && (t.n_strata < 2 || t.n_strata > MT_MAX_STRATA))
-      return mt_fail(name, mt_range(2, MT_MAX_STRATA, "strata"));
-    if (t.slot0 != slot) return mt_fail(name, "slots must be contiguous in term order");
+      return slot_fail(name, slot_range(2, MT_MAX_STRATA, "strata"));
     const int outs = t.n_groups > 1 ? t.n_groups + 1 : 1;
-    if (t.out0 < 0 || t.out0 + outs > n_values) return mt_fail(name, "value index outside the values");
-    if (t.stream != prev_stream) {
-      a.term_begin[t.stream] = k;
-      a.slot_begin[t.stream] = slot;
-      prev_stream = t.stream;
-    }
-    a.term_count[t.stream] += 1;
-    a.slot_count[t.stream] += t.n_groups;
+    if (t.out0 < 0 || t.out0 + outs > n_values) return slot_fail(name, "value index outside the values");
     if (t.kind == NQA_METRIC_STRATIFIED_HUBER) a.need_norm[t.stream] = 1;
-    slot += t.n_groups;
-  }
-  for (int s = 0; s < n_streams; ++s) {
-    if (a.term_begin[s] < 0) return mt_fail(name, "a stream without terms");
-    a.kmax = a.term_count[s] > a.kmax ? a.term_count[s] : a.kmax;
-    a.lmax = a.slot_count[s] > a.lmax ? a.slot_count[s] : a.lmax;
-  }
+    return (int)NQA_OK;
+  });
+  if (rc != NQA_OK) return rc;
+  for (int s = 0; s < n_streams; ++s) a.kmax = a.lay.term_count[s] > a.kmax ? a.lay.term_count[s] : a.kmax;
   a.terms = terms_device;
-  a.n_streams = n_streams;
-  a.n_terms = n_terms;
-  a.n_slots = slot;
   a.n_values = n_values;
   a.ws_index = ws_index;
   return NQA_OK;
@@ -509,22 +468,22 @@ int nqa_metrics_fwd(const nqa_metric_stream* streams, int32_t n_streams, const n
   MetricsArgs a;
   const int rc = mt_prepare(name, streams, n_streams, terms, terms_device, n_terms, n_values, weighted_sum_index, a);
   if (rc != NQA_OK) return rc;
-  if (!workspace || workspace_bytes < nqa_metrics_workspace_bytes(a.n_slots) || !saved || !values) {
+  if (!workspace || workspace_bytes < nqa_metrics_workspace_bytes(a.lay.n_slots) || !saved || !values) {
     set_error(std::string(name) + ": workspace of nqa_metrics_workspace_bytes, `saved` and `values` are required");
     return NQA_ERR_WORKSPACE;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int64_t gs = (int64_t)MT_GROUPS * a.n_slots;
+  const int64_t gs = (int64_t)MT_GROUPS * a.lay.n_slots;
   double* part_sum = static_cast<double*>(workspace);
   int64_t* part_cnt = reinterpret_cast<int64_t*>(part_sum + gs);
   double* part_max = reinterpret_cast<double*>(part_cnt + gs);
-  const size_t lds = (size_t)a.kmax * 256 * 8 + (size_t)MT_PARTS * a.lmax * 16 + (size_t)a.lmax * 8 + 256 * 8;
+  const size_t lds = (size_t)a.kmax * 256 * 8 + (size_t)MT_PARTS * a.lay.lmax * 16 + (size_t)a.lay.lmax * 8 + 256 * 8;
   if (lds > 64 * 1024) {  // (set at every such call: cheap, and right on every device and from every thread)
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&metrics_partial_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
       (void)hipGetLastError();
       set_error(std::string(name) + ": the first stage needs " + std::to_string(lds) + " bytes of LDS for " +
-                std::to_string(a.kmax) + " terms / " + std::to_string(a.lmax) +
+                std::to_string(a.kmax) + " terms / " + std::to_string(a.lay.lmax) +
                 " slots on one stream, which this device does not grant");
       return NQA_ERR_LAUNCH;
     }
@@ -537,14 +496,14 @@ int nqa_metrics_fwd(const nqa_metric_stream* streams, int32_t n_streams, const n
   f.part_max = part_max;
   if (state != nullptr) {
     f.state_sum = static_cast<double*>(state);
-    f.state_cnt = reinterpret_cast<int64_t*>(f.state_sum + a.n_slots);
-    f.state_max = reinterpret_cast<double*>(f.state_cnt + a.n_slots);
+    f.state_cnt = reinterpret_cast<int64_t*>(f.state_sum + a.lay.n_slots);
+    f.state_max = reinterpret_cast<double*>(f.state_cnt + a.lay.n_slots);
   }
   f.saved_sum = static_cast<double*>(saved);
-  f.saved_cnt = reinterpret_cast<int64_t*>(f.saved_sum + a.n_slots);
+  f.saved_cnt = reinterpret_cast<int64_t*>(f.saved_sum + a.lay.n_slots);
   f.values = values;
-  f.n_terms = a.n_terms;
-  f.n_slots = a.n_slots;
+  f.n_terms = a.lay.n_terms;
+  f.n_slots = a.lay.n_slots;
   f.groups = MT_GROUPS;
   f.ws_index = weighted_sum_index;
   hipLaunchKernelGGL(metrics_final_kernel, dim3(1), dim3(256), 0, s, f);
@@ -559,16 +518,16 @@ int nqa_metrics_bwd(const nqa_metric_stream* streams, int32_t n_streams, const n
   MetricsArgs a;
   const int rc = mt_prepare(name, streams, n_streams, terms, terms_device, n_terms, n_values, weighted_sum_index, a);
   if (rc != NQA_OK) return rc;
-  if (!saved || !grad_values) return mt_fail(name, "`saved` and `grad_values` are required");
+  if (!saved || !grad_values) return slot_fail(name, "`saved` and `grad_values` are required");
   int64_t most = 0;
   for (int s = 0; s < n_streams; ++s)
     if (streams[s].grad_pred != nullptr && streams[s].rows * streams[s].cols > most) most = streams[s].rows * streams[s].cols;
   if (most == 0) return NQA_OK;
   const int64_t blocks = (most + 255) / 256;
   const double* saved_sum = static_cast<const double*>(saved);
-  const int64_t* saved_cnt = reinterpret_cast<const int64_t*>(saved_sum + a.n_slots);
+  const int64_t* saved_cnt = reinterpret_cast<const int64_t*>(saved_sum + a.lay.n_slots);
   hipLaunchKernelGGL(metrics_bwd_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256),
-                     (size_t)a.n_slots * 8, static_cast<hipStream_t>(stream), a, saved_sum, saved_cnt, grad_values);
+                     (size_t)a.lay.n_slots * 8, static_cast<hipStream_t>(stream), a, saved_sum, saved_cnt, grad_values);
   return launch_status(name);
 }
 

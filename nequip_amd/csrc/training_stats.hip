@@ -11,8 +11,8 @@
 // without reading anything else.
 //   tstats_partial_kernel  one workgroup per chunk.  Every lane folds its elements y = f(x), promoted to double, by Welford
 //                          updates into (count, mean, M2, sum of squares, min, max, absmin, absmax); the lanes of a wavefront are
-//                          merged by a fixed shuffle tree, the four wavefronts in wavefront order (Chan's formula); one workspace
-//                          row per chunk.
+//                          merged by a fixed shuffle tree (wave_merge_ordered, slot_reduce.h), the four wavefronts in wavefront
+//                          order (Chan's formula); one workspace row per chunk.
 //   tstats_final_kernel    one wavefront per tensor.  Lane b merges a contiguous run of the tensor's chunk rows in ascending
 //                          order, the lanes are merged by the same tree (lane l takes lane l + off BEHIND itself, so the chunks
 //                          stay in ascending order), lane 0 writes [min, max, mean, std, absmin, absmax, rms, count] and, for
@@ -27,11 +27,8 @@
 // LDS: the four wavefront states of the first stage only.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdint>
-#include <string>
-
 #include "multi_tensor.h"
+#include "slot_reduce.h"
 
 namespace nqa {
 
@@ -45,9 +42,6 @@ struct TsAcc {
   double n, mean, m2, ss, mn, mx, amn, amx;  // (n as a double: exact below 2^53)
 };
 
-__device__ __forceinline__ double ts_nanmin(double a, double b) { return (a != a || b != b) ? (a + b) : fmin(a, b); }
-__device__ __forceinline__ double ts_nanmax(double a, double b) { return (a != a || b != b) ? (a + b) : fmax(a, b); }
-
 __device__ __forceinline__ TsAcc ts_empty() { return TsAcc{0.0, 0.0, 0.0, 0.0, INFINITY, -INFINITY, INFINITY, -INFINITY}; }
 
 // one more element (Welford)
@@ -58,10 +52,10 @@ __device__ __forceinline__ void ts_push(TsAcc& a, double y) {
   a.m2 += d * (y - a.mean);
   a.ss += y * y;
   const double ay = fabs(y);
-  a.mn = ts_nanmin(a.mn, y);
-  a.mx = ts_nanmax(a.mx, y);
-  a.amn = ts_nanmin(a.amn, ay);
-  a.amx = ts_nanmax(a.amx, ay);
+  a.mn = sr_nanmin(a.mn, y);
+  a.mx = sr_nanmax(a.mx, y);
+  a.amn = sr_nanmin(a.amn, ay);
+  a.amx = sr_nanmax(a.amx, ay);
 }
 
 // a followed by b (Chan); an empty side leaves the other one bit for bit
@@ -75,29 +69,11 @@ __device__ __forceinline__ TsAcc ts_merge(const TsAcc& a, const TsAcc& b) {
   r.mean = a.mean + delta * w;
   r.m2 = a.m2 + b.m2 + delta * delta * (a.n * w);
   r.ss = a.ss + b.ss;
-  r.mn = ts_nanmin(a.mn, b.mn);
-  r.mx = ts_nanmax(a.mx, b.mx);
-  r.amn = ts_nanmin(a.amn, b.amn);
-  r.amx = ts_nanmax(a.amx, b.amx);
+  r.mn = sr_nanmin(a.mn, b.mn);
+  r.mx = sr_nanmax(a.mx, b.mx);
+  r.amn = sr_nanmin(a.amn, b.amn);
+  r.amx = sr_nanmax(a.amx, b.amx);
   return r;
-}
-
-// the lanes of a wavefront by a fixed tree: lane l takes lane l + off behind itself; lane 0 ends with all 64 in lane order
-__device__ __forceinline__ TsAcc ts_wave_merge(TsAcc v, int lane) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    TsAcc w;
-    w.n = __shfl_down(v.n, off);
-    w.mean = __shfl_down(v.mean, off);
-    w.m2 = __shfl_down(v.m2, off);
-    w.ss = __shfl_down(v.ss, off);
-    w.mn = __shfl_down(v.mn, off);
-    w.mx = __shfl_down(v.mx, off);
-    w.amn = __shfl_down(v.amn, off);
-    w.amx = __shfl_down(v.amx, off);
-    if (lane < off) v = ts_merge(v, w);
-  }
-  return v;
 }
 
 __device__ __forceinline__ void ts_store(double* __restrict__ row, const TsAcc& v) {
@@ -174,7 +150,7 @@ __global__ __launch_bounds__(TS_THREADS) void tstats_partial_kernel(const nqa_ts
     }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  acc = ts_wave_merge(acc, lane);
+  acc = wave_merge_ordered(acc, lane, ts_merge);
   if (lane == 0) ts_store(waves[wave], acc);
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -203,7 +179,7 @@ __global__ __launch_bounds__(64) void tstats_final_kernel(const nqa_tstats_tenso
   const int64_t lo = lane * per, hi = lo + per < n_chunks ? lo + per : n_chunks;
   TsAcc v = ts_empty();
   for (int64_t k = lo; k < hi; ++k) v = ts_merge(v, ts_load(workspace + ((int64_t)t.chunk0 + k) * TS_ROW));
-  v = ts_wave_merge(v, lane);
+  v = wave_merge_ordered(v, lane, ts_merge);
   if (lane != 0) return;
   double* __restrict__ out = table + (int64_t)blockIdx.x * TS_ROW;
   out[0] = v.mn;

@@ -25,11 +25,12 @@ from __future__ import annotations
 
 import dataclasses
 import math
-from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from .. import _lib
+from ..utils._slot_plan import SlotPlan, canonical_row_scale, canonical_rows, membership
 
 IDENTITY, ABS, SQUARE = _lib.NQA_STATS_MOD_IDENTITY, _lib.NQA_STATS_MOD_ABS, _lib.NQA_STATS_MOD_SQUARE
 GROUP_NONE, GROUP_NODE, GROUP_EDGE = _lib.NQA_STATS_GROUP_NONE, _lib.NQA_STATS_GROUP_NODE, _lib.NQA_STATS_GROUP_EDGE
@@ -58,19 +59,24 @@ class TermSpec:
     slot0: int = 0
 
 
-class StatsPlan:
+class StatsPlan(SlotPlan):
     """Terms in the caller's order; the table handed to the kernels is ordered by stream.  ``group_kinds[s]`` says how the
     per-type terms of stream ``s`` are grouped (``GROUP_NONE`` / ``GROUP_NODE`` / ``GROUP_EDGE``)."""
 
+    MAX_STREAMS, MAX_TERMS, MAX_SLOTS = MAX_STREAMS, MAX_TERMS, MAX_SLOTS
+    TOO_MANY_STREAMS = "{n} distinct fields: the statistics kernels take at most {max} (NQA_STATS_MAX_STREAMS)"
+    TOO_MANY_TERMS = "{n} statistics entries: the statistics kernels take at most {max} (NQA_STATS_MAX_TERMS)"
+    TOO_MANY_SLOTS = "{n} groups over all entries: the statistics kernels take at most {max} (NQA_STATS_MAX_SLOTS)"
+    TERM_STRUCT, WORKSPACE_BYTES = _lib.StatsTerm, "nqa_stats_workspace_bytes"
+    PLANES = (("count", torch.int64, 0), ("mean", torch.float64, 0.0), ("mean_lo", torch.float64, 0.0),
+              ("m2", torch.float64, 0.0), ("min", torch.float64, math.inf), ("max", torch.float64, -math.inf))
+
     def __init__(self, terms: Sequence[TermSpec], group_kinds: Sequence[int], num_types: int = 0):
-        n_streams = len(group_kinds)
-        if n_streams > MAX_STREAMS:
-            raise ValueError(f"{n_streams} distinct fields: the statistics kernels take at most {MAX_STREAMS} "
-                             "(NQA_STATS_MAX_STREAMS)")
-        if len(terms) > MAX_TERMS:
-            raise ValueError(f"{len(terms)} statistics entries: the statistics kernels take at most {MAX_TERMS} "
-                             "(NQA_STATS_MAX_TERMS)")
-        self.terms, self.group_kinds, self.num_types = list(terms), list(group_kinds), int(num_types)
+        self.group_kinds, self.num_types = list(group_kinds), int(num_types)
+        super().__init__(terms, len(self.group_kinds))
+
+    def check_terms(self) -> None:
+        num_types = self.num_types
         for t in self.terms:
             kind = self.group_kinds[t.stream]
             if t.per_type:
@@ -84,59 +90,13 @@ class StatsPlan:
                 t.n_groups = num_types if kind == GROUP_NODE else num_types * num_types
             else:
                 t.n_groups = 1
-        self.table_order = sorted(range(len(self.terms)), key=lambda i: self.terms[i].stream)  # (stable)
-        slot = 0
-        for i in self.table_order:
-            self.terms[i].slot0 = slot
-            slot += self.terms[i].n_groups
-        if slot > MAX_SLOTS:
-            raise ValueError(f"{slot} groups over all entries: the statistics kernels take at most {MAX_SLOTS} "
-                             "(NQA_STATS_MAX_SLOTS)")
-        self.n_slots = slot
-        self._dev: Dict[torch.device, dict] = {}
-        self._host_table = None
 
-    def __getstate__(self):  # (device buffers and the ctypes table are rebuilt on demand; a copy starts with an empty state)
-        d = dict(self.__dict__)
-        d["_dev"], d["_host_table"] = {}, None
-        return d
+    @staticmethod
+    def fill_row(c, t: TermSpec) -> None:
+        c.stream, c.mod, c.n_groups, c.ignore_nan, c.slot0 = t.stream, t.mod, t.n_groups, int(t.ignore_nan), t.slot0
 
-    def host_table(self):
-        if self._host_table is None:
-            arr = (_lib.StatsTerm * len(self.terms))()
-            for row, i in enumerate(self.table_order):
-                t, c = self.terms[i], arr[row]
-                c.stream, c.mod, c.n_groups, c.ignore_nan, c.slot0 = t.stream, t.mod, t.n_groups, int(t.ignore_nan), t.slot0
-            self._host_table = arr
-        return self._host_table
-
-    # ---- per-device buffers ------------------------------------------------------------------------------------------------
-    def buffers(self, device: torch.device) -> dict:
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        bufs = self._dev.get(device)
-        if bufs is None:
-            S = self.n_slots
-            state = torch.zeros(6 * S, dtype=torch.int64, device=device)  # [6, S]: count (i64), then five float64 planes
-            f = state[S:].view(torch.float64)
-            bufs = {"state": state, "count": state[:S], "mean": f[:S], "mean_lo": f[S:2 * S], "m2": f[2 * S:3 * S],
-                    "min": f[3 * S:4 * S], "max": f[4 * S:]}
-            bufs["min"].fill_(math.inf)
-            bufs["max"].fill_(-math.inf)
-            if device.type == "cuda":
-                nbytes = int(_lib.load().nqa_stats_workspace_bytes(S))
-                bufs["workspace"] = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
-                bufs["workspace_bytes"] = nbytes
-                bufs["counts"] = torch.empty(0, dtype=torch.int32, device=device)
-            self._dev[device] = bufs
-        return bufs
-
-    def reset(self) -> None:
-        for bufs in self._dev.values():
-            bufs["state"].zero_()
-            bufs["min"].fill_(math.inf)
-            bufs["max"].fill_(-math.inf)
+    def device_buffers(self, bufs: dict, device: torch.device) -> None:
+        bufs["counts"] = torch.empty(0, dtype=torch.int32, device=device)
 
     def device_state(self, device) -> State:
         """Views of the running state on one device (no copy)."""
@@ -208,20 +168,9 @@ _DT = {torch.float32: _lib.NQA_STATS_F32, torch.float64: _lib.NQA_STATS_F64, tor
 
 def _canonical(s: StreamInput, kind: int, num_types: int) -> StreamInput:
     """[rows, cols] contiguous float32 / float64 / int32 / int64 data, float64 scale, int64 types and edge index."""
-    data = s.data.detach()
-    if data.dtype not in _DT:
-        if data.is_floating_point():
-            data = data.to(torch.float32 if data.dtype in (torch.float16, torch.bfloat16) else torch.float64)
-        else:
-            data = data.to(torch.int64)
-    rows = data.shape[0] if data.dim() > 0 else 1
-    data = data.reshape(rows, -1) if rows > 0 else data.reshape(0, max(1, math.prod(data.shape[1:])))
-    data = data.contiguous()
-    dev = data.device
-    scale = s.row_scale
-    if scale is not None:
-        scale = scale.detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
-        assert scale.numel() == rows, "one scale per row"
+    data = canonical_rows(s.data.detach(), keep=tuple(_DT), integers=torch.int64)
+    rows, dev = data.shape[0], data.device
+    scale = canonical_row_scale(s.row_scale, rows, dev)
     types = edge_index = None
     if kind != GROUP_NONE and s.atom_types is not None:
         types = s.atom_types.detach().to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
@@ -290,11 +239,7 @@ def _aten_update(plan: StatsPlan, streams: Sequence[StreamInput], device: torch.
             x = x * s.row_scale[:, None]
         y = x.abs() if t.mod == ABS else (x * x if t.mod == SQUARE else x)
         contrib = ~torch.isnan(x) if t.ignore_nan else torch.ones_like(x, dtype=torch.bool)
-        if t.per_type:
-            g = _groups(s, kind, plan.num_types)
-            member = (g[None, :] == torch.arange(t.n_groups, device=device)[:, None])[:, :, None] & contrib[None]
-        else:
-            member = contrib[None]
+        member = membership(_groups(s, kind, plan.num_types) if t.per_type else None, t.n_groups, contrib)
         yb = y[None]
         cnt = member.sum((1, 2))
         safe = cnt.clamp(min=1).to(torch.float64)

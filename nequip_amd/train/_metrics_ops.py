@@ -18,11 +18,12 @@ from __future__ import annotations
 
 import dataclasses
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from .. import _lib
+from ..utils._slot_plan import SlotPlan, canonical_row_scale, canonical_rows, membership
 
 MSE, MAE, RMSE, MAXABS, HUBER, STRATIFIED_HUBER = range(6)
 MAX_STREAMS, MAX_TERMS = _lib.NQA_METRICS_MAX_STREAMS, _lib.NQA_METRICS_MAX_TERMS
@@ -57,41 +58,31 @@ class TermSpec:
         return self.out0 + (self.n_groups if self.n_groups > 1 else 0)
 
 
-class FusedPlan:
+class FusedPlan(SlotPlan):
     """Terms in the caller's order (= order of the returned values); the device table is ordered by stream."""
 
+    MAX_STREAMS, MAX_TERMS = MAX_STREAMS, MAX_TERMS
+    TOO_MANY_STREAMS = "{n} distinct prediction/target pairs: the fused metric kernels take at most {max}"
+    TOO_MANY_TERMS = "{n} metric terms: the fused metric kernels take at most {max}"
+    TERM_STRUCT, WORKSPACE_BYTES = _lib.MetricTerm, "nqa_metrics_workspace_bytes"
+    PLANES = (("sum", torch.float64, 0.0), ("count", torch.int64, 0), ("max", torch.float64, -math.inf))
+
     def __init__(self, terms: Sequence[TermSpec], n_streams: int):
-        if n_streams > MAX_STREAMS:
-            raise ValueError(f"{n_streams} distinct prediction/target pairs: the fused metric kernels take at most {MAX_STREAMS}")
-        if len(terms) > MAX_TERMS:
-            raise ValueError(f"{len(terms)} metric terms: the fused metric kernels take at most {MAX_TERMS}")
-        for t in terms:
-            if t.n_groups > MAX_TYPES:
-                raise ValueError(f"{t.n_groups} atom types: per-type metrics take at most {MAX_TYPES}")
-            if t.kind == STRATIFIED_HUBER and not 2 <= len(t.strata) <= MAX_STRATA:
-                raise ValueError(f"{len(t.strata)} strata: the stratified Huber loss takes 2 to {MAX_STRATA}")
-        self.terms = list(terms)
-        self.n_streams = n_streams
+        super().__init__(terms, n_streams)
         out = 0
         for t in self.terms:
             t.out0 = out
             out += t.n_values
-        self.table_order = sorted(range(len(self.terms)), key=lambda i: self.terms[i].stream)  # (stable)
-        slot = 0
-        for i in self.table_order:
-            self.terms[i].slot0 = slot
-            slot += self.terms[i].n_groups
-        self.n_slots = slot
         self.n_term_values = out
-        self._dev: Dict[torch.device, dict] = {}
-        self._host_table = None
         self.table_version = 0  # counts coeffs_changed: a backward must see the table its forward saw
         self.last_device: Optional[torch.device] = None
 
-    def __getstate__(self):  # (device buffers and the ctypes table are rebuilt on demand; a copy starts with an empty state)
-        d = dict(self.__dict__)
-        d["_dev"], d["_host_table"] = {}, None
-        return d
+    def check_terms(self) -> None:
+        for t in self.terms:
+            if t.n_groups > MAX_TYPES:
+                raise ValueError(f"{t.n_groups} atom types: per-type metrics take at most {MAX_TYPES}")
+            if t.kind == STRATIFIED_HUBER and not 2 <= len(t.strata) <= MAX_STRATA:
+                raise ValueError(f"{len(t.strata)} strata: the stratified Huber loss takes 2 to {MAX_STRATA}")
 
     # ---- what depends on the coefficients --------------------------------------------------------------------------------
     @property
@@ -110,54 +101,26 @@ class FusedPlan:
             if dev.type == "cuda":
                 bufs["table"].copy_(self._table_tensor())
 
-    def host_table(self):
-        if self._host_table is None:
-            arr = (_lib.MetricTerm * len(self.terms))()
-            for row, i in enumerate(self.table_order):
-                t, c = self.terms[i], arr[row]
-                c.stream, c.kind, c.n_groups, c.ignore_nan = t.stream, t.kind, t.n_groups, int(t.ignore_nan)
-                c.reduce_sum, c.slot0, c.out0 = int(t.reduce_sum), t.slot0, t.out0
-                c.has_coeff, c.coeff = int(t.coeff is not None), float(t.coeff or 0.0)
-                c.delta = float(t.delta)
-                strata = t.strata or []
-                c.n_strata = len(strata)
-                for j, (b, d) in enumerate(strata):
-                    c.bound[j], c.stratum_delta[j] = float(b), float(d)
-                c.has_group_coeffs = int(t.group_coeffs is not None)
-                for j, g in enumerate(t.group_coeffs or []):
-                    c.group_coeff[j] = float(g)
-            self._host_table = arr
-        return self._host_table
+    @staticmethod
+    def fill_row(c, t: TermSpec) -> None:
+        c.stream, c.kind, c.n_groups, c.ignore_nan = t.stream, t.kind, t.n_groups, int(t.ignore_nan)
+        c.reduce_sum, c.slot0, c.out0 = int(t.reduce_sum), t.slot0, t.out0
+        c.has_coeff, c.coeff = int(t.coeff is not None), float(t.coeff or 0.0)
+        c.delta = float(t.delta)
+        strata = t.strata or []
+        c.n_strata = len(strata)
+        for j, (b, d) in enumerate(strata):
+            c.bound[j], c.stratum_delta[j] = float(b), float(d)
+        c.has_group_coeffs = int(t.group_coeffs is not None)
+        for j, g in enumerate(t.group_coeffs or []):
+            c.group_coeff[j] = float(g)
 
     def _table_tensor(self) -> torch.Tensor:
         raw = bytes(memoryview(self.host_table()).cast("B"))
         return torch.frombuffer(bytearray(raw), dtype=torch.uint8)
 
-    # ---- per-device buffers ------------------------------------------------------------------------------------------------
-    def buffers(self, device: torch.device) -> dict:
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        bufs = self._dev.get(device)
-        if bufs is None:
-            S = self.n_slots
-            state = torch.zeros(3 * S, dtype=torch.int64, device=device)  # [3, S]: sum (f64), count (i64), max (f64)
-            bufs = {"state": state, "sum": state[:S].view(torch.float64), "count": state[S:2 * S],
-                    "max": state[2 * S:].view(torch.float64)}
-            bufs["max"].fill_(-math.inf)
-            if device.type == "cuda":
-                nbytes = int(_lib.load().nqa_metrics_workspace_bytes(S))
-                bufs["workspace"] = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
-                bufs["workspace_bytes"] = nbytes
-                bufs["table"] = self._table_tensor().to(device)
-            self._dev[device] = bufs
-        return bufs
-
-    def reset(self) -> None:
-        for bufs in self._dev.values():
-            bufs["sum"].zero_()
-            bufs["count"].zero_()
-            bufs["max"].fill_(-math.inf)
+    def device_buffers(self, bufs: dict, device: torch.device) -> None:
+        bufs["table"] = self._table_tensor().to(device)
 
     def state(self, device=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Copies of the running (sum, count, max) per slot, over every device this plan has run on."""
@@ -222,19 +185,9 @@ def _canonical(pred, target, row_scale, group) -> StreamInput:
     """[rows, cols] contiguous float32 / float64 on both sides, float64 scale, int64 groups."""
     if pred.shape != target.shape:
         pred, target = torch.broadcast_tensors(pred, target)
-    if pred.dtype not in (torch.float32, torch.float64):
-        pred = pred.to(torch.float32 if pred.dtype in (torch.float16, torch.bfloat16) else torch.float64)
-    if target.dtype not in (torch.float32, torch.float64):
-        target = target.to(torch.float32 if target.dtype in (torch.float16, torch.bfloat16) else torch.float64)
-    target = target.detach().to(pred.device)
-    rows = pred.shape[0] if pred.dim() > 0 else 1
-    cols = 1
-    for d in pred.shape[1:]:
-        cols *= d
-    pred, target = pred.reshape(rows, cols).contiguous(), target.reshape(rows, cols).contiguous()
-    if row_scale is not None:
-        row_scale = row_scale.detach().to(device=pred.device, dtype=torch.float64).reshape(-1).contiguous()
-        assert row_scale.numel() == rows, "one scale per row"
+    pred, target = canonical_rows(pred), canonical_rows(target.detach().to(pred.device))
+    rows = pred.shape[0]
+    row_scale = canonical_row_scale(row_scale, rows, pred.device)
     if group is not None:
         group = group.detach().to(device=pred.device, dtype=torch.int64).reshape(-1).contiguous()
         assert group.numel() == rows, "one group index per row (per-type metrics are for per-atom fields)"
@@ -353,10 +306,7 @@ def _aten_forward(plan: FusedPlan, streams: Sequence[StreamInput], accumulate: b
         if t.ignore_nan:  # a masked element must not reach the modifier: its derivative there could be NaN
             d = torch.where(contrib, d, torch.zeros_like(d))
         v = _element_values(t, d, tg)
-        if t.n_groups > 1:
-            member = (group[None, :] == torch.arange(t.n_groups, device=dev)[:, None])[:, :, None] & contrib[None]
-        else:
-            member = contrib[None]
+        member = membership(group if t.n_groups > 1 else None, t.n_groups, contrib)
         cnt = member.sum((1, 2))
         if t.kind == MAXABS:
             mx = torch.where(member, v[None], torch.full_like(v, -math.inf)[None]).flatten(1)

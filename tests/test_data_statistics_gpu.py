@@ -6,7 +6,9 @@ installed -- so there are no reference-generated fixtures for this feature.
 
 Tolerance: rtol 1e-10, atol 0, NaN equal to NaN (float64 reductions of fewer than 1e5 well-conditioned terms in another order
 differ by about n * 2^-53).  Element counts: 1, 63, 64, 65 (a wavefront), 255, 256, 257 (a sweep of a workgroup) and
-``G * 256 + 1`` with ``G`` the workgroup count of the first launch (the grid stride wraps once).
+``G * 256 + 1`` with ``G`` the workgroup count of the first launch (the grid stride wraps once).  T = 3 leaves every stream
+with few slots, i.e. 16 owner threads per slot; ``test_owners_per_slot_boundaries`` builds the plans on which the first stage
+takes 16, 8 and 1 owners.
 """
 import math
 
@@ -189,3 +191,31 @@ def test_cpu_tensors_after_gpu_tensors_keep_a_state_of_their_own(device):
         mixed({k: v.to(device) for k, v in b.items()} if i < 2 else dict(b))
     assert sorted(d.type for d in mixed._plan._dev) == ["cpu", "cuda"]
     sc.assert_stats_close(mixed.compute(), single.compute())
+
+
+@pytest.mark.parametrize("rows", [1, 257, G * 256 + 1])
+@pytest.mark.parametrize("num_types,plain,slots", [(16, False, 16), (16, True, 17), (128, True, 129)])
+def test_owners_per_slot_boundaries(device, rows, num_types, plain, slots):
+    """The first stage gives a slot 16 owner threads, halved until owners * slots <= 256: one per-type term at T = 16 is the
+    last plan with 16 owners (16 slots), one plain term more the first with 8 (17 slots), and T = 128 plus a plain term
+    (129 slots) has one owner, which folds the whole sweep of 256 elements.  One [rows, 1] node stream, two batches, against
+    the CPU form of the same plan at this file's tolerance; two runs end with the same bits."""
+    def plan():
+        terms = [_stats_ops.TermSpec(0, _stats_ops.IDENTITY, per_type=True)]
+        terms += [_stats_ops.TermSpec(0, _stats_ops.ABS)] if plain else []
+        return _stats_ops.StatsPlan(terms, [_stats_ops.GROUP_NODE], num_types=num_types)
+
+    g = torch.Generator().manual_seed(1000 * slots + rows)
+    batches = [_stats_ops.StreamInput(0.5 + torch.randn(rows, 1, generator=g, dtype=F64), None,
+                                      torch.randint(0, num_types, (rows,), generator=g)) for _ in range(2)]
+    cpu, gpu, again = plan(), plan(), plan()
+    assert cpu.n_slots == slots
+    for b in batches:
+        cpu.update([b])
+        for p in (gpu, again):
+            p.update([_stats_ops.StreamInput(b.data.to(device), None, b.atom_types.to(device))])
+    assert torch.equal(gpu.buffers(device)["state"], again.buffers(device)["state"])
+    (n_g, hi_g, lo_g, *rest_g), (n_c, hi_c, lo_c, *rest_c) = gpu.state(), cpu.state()
+    assert torch.equal(n_g, n_c) and int(n_g[:num_types].sum()) == 2 * rows and (not plain or int(n_g[-1]) == 2 * rows)
+    for name, a, b in zip(("mean", "M2", "min", "max"), [hi_g + lo_g] + rest_g, [hi_c + lo_c] + rest_c):
+        torch.testing.assert_close(a, b, rtol=1e-10, atol=0.0, equal_nan=True, msg=lambda m, name=name: f"{name}: {m}")

@@ -8,13 +8,15 @@ Tolerances.  Values: rtol 1e-10 (float64 sums of fewer than 1e5 terms in another
 ``grad_pred``, compared in float64: float64 predictions 1e-10 * max|ref|; float32 predictions 1e-6 * max|ref| (one rounding
 to float32, 6e-8, under the project's usual 2e-6 bar).  Elements masked by ``ignore_nan``: exactly 0.0.
 """
+import ctypes
 import math
 
 import pytest
 import torch
 
 import metrics_restatement as mr
-from nequip_amd.data import PerAtomModifier, register_fields
+from nequip_amd import _lib
+from nequip_amd.data import PerAtomModifier, _stats_ops, register_fields
 from nequip_amd.train import (EnergyForceLoss, EnergyForceStressLoss, EnergyForceStressMetrics, HuberLoss,
                               MaximumAbsoluteError, MeanAbsoluteError, MeanSquaredError, MetricsManager,
                               RootMeanSquaredError, StratifiedHuberForceLoss, _metrics_ops)
@@ -338,3 +340,47 @@ def test_coefficients_changed_between_forward_and_backward_are_refused(device):
     close(out["weighted_sum"], ref["weighted_sum"], "weighted_sum")
     (g_ref,) = torch.autograd.grad(ref["weighted_sum"], [p_ref["forces"]])
     torch.testing.assert_close(p["forces"].grad.cpu().double(), g_ref.double(), rtol=0.0, atol=1e-6 * float(g_ref.abs().max()))
+
+
+# (term streams, term slot0s, number of streams) that break one rule of the term table each, and the rule's message
+BAD_LAYOUTS = {"terms out of stream order": ([1, 0], [0, 1], 2, "terms must be ordered by stream"),
+               "a gap in slot0": ([0, 1], [0, 2], 2, "slots must be contiguous in term order"),
+               "a stream without terms": ([0, 2], [0, 1], 3, "a stream without terms"),
+               "nine streams": ([0, 8], [0, 1], 9, "1 to 8 streams")}
+
+
+@pytest.mark.parametrize("rule", list(BAD_LAYOUTS))
+def test_layout_checks_of_both_entry_points(device, rule):
+    """``nqa_metrics_fwd`` and ``nqa_stats_update`` check the term table by the same code (csrc/slot_reduce.h): each refuses
+    the table with ``NQA_ERR_INVALID`` and the rule's message under its own name, before any launch -- the streams hold four
+    rows each, so a launch would write the workspace, the state and the values."""
+    term_streams, slot0s, n_streams, message = BAD_LAYOUTS[rule]
+    lib, n_terms = _lib.load(), len(term_streams)
+    x = torch.randn(4, 1, dtype=F64, device=device)
+    sentinel = lambda n: torch.full((n,), -12345, dtype=torch.int64, device=device)
+    workspace, state, saved, values = sentinel(4096), sentinel(64), sentinel(64), sentinel(64).double()
+    before = [t.clone() for t in (workspace, state, saved, values)]
+
+    m_streams, m_terms = (_lib.MetricStream * n_streams)(), (_lib.MetricTerm * n_terms)()
+    for c in m_streams:
+        c.pred, c.target, c.rows, c.cols = x.data_ptr(), x.data_ptr(), 4, 1
+        c.pred_dtype, c.target_dtype = _lib.NQA_F64, _lib.NQA_F64
+    for k, c in enumerate(m_terms):
+        c.stream, c.kind, c.n_groups, c.slot0, c.out0 = term_streams[k], _metrics_ops.MSE, 1, slot0s[k], k
+    table = torch.zeros(ctypes.sizeof(m_terms), dtype=torch.uint8, device=device)
+    rc = lib.nqa_metrics_fwd(m_streams, n_streams, m_terms, _lib.ptr(table), n_terms, n_terms + 1, n_terms, _lib.ptr(workspace),
+                             workspace.numel() * 8, _lib.ptr(state), _lib.ptr(saved), _lib.ptr(values), _lib.stream_ptr(device))
+    assert rc == -1 and lib.nqa_last_error().decode() == f"nqa_metrics_fwd: {message}"  # NQA_ERR_INVALID
+
+    s_streams, s_terms = (_lib.StatsStream * n_streams)(), (_lib.StatsTerm * n_terms)()
+    for c in s_streams:
+        c.data, c.rows, c.cols, c.dtype, c.group_kind = x.data_ptr(), 4, 1, _lib.NQA_STATS_F64, _stats_ops.GROUP_NONE
+    for k, c in enumerate(s_terms):
+        c.stream, c.mod, c.n_groups, c.slot0 = term_streams[k], _stats_ops.IDENTITY, 1, slot0s[k]
+    rc = lib.nqa_stats_update(s_streams, n_streams, s_terms, n_terms, _lib.ptr(workspace), workspace.numel() * 8,
+                              _lib.ptr(state), _lib.stream_ptr(device))
+    assert rc == -1 and lib.nqa_last_error().decode() == f"nqa_stats_update: {message}"
+
+    torch.cuda.synchronize(device)
+    for t, b in zip((workspace, state, saved, values), before):
+        assert torch.equal(t, b)
