@@ -229,7 +229,7 @@ int nqa_edge_vectors_bwd(const double* g_edge_vec, const double* edge_cell_shift
 int nqa_virial_finalize(const double* per_atom, const int64_t* batch, const double* cell, int64_t num_nodes,
                         int64_t num_frames, double* virial, double* stress, nqa_stream stream) {
   if (num_nodes < 0 || num_frames < 0 || (num_frames > 0 && !virial) || (num_nodes > 0 && !per_atom) ||
-      (stress != nullptr && cell == nullptr) || (num_frames > 1 && batch == nullptr)) {
+      (stress != nullptr && cell == nullptr) || (num_frames > 1 && num_nodes > 0 && batch == nullptr)) {
     set_error("nqa_virial_finalize: invalid argument");
     return NQA_ERR_INVALID;
   }
@@ -248,7 +248,7 @@ int nqa_virial_finalize(const double* per_atom, const int64_t* batch, const doub
 int nqa_frame_sum(const double* rows, const int64_t* batch, int64_t num_nodes, int32_t width, int64_t num_frames,
                   double* out, nqa_stream stream) {
   if (num_nodes < 0 || num_frames < 0 || width < 1 || width > 16 || (num_frames > 0 && !out) ||
-      (num_nodes > 0 && !rows) || (num_frames > 1 && batch == nullptr)) {
+      (num_nodes > 0 && !rows) || (num_frames > 1 && num_nodes > 0 && batch == nullptr)) {
     set_error("nqa_frame_sum: invalid argument (1 <= width <= 16; batch is required for more than one frame)");
     return NQA_ERR_INVALID;
   }

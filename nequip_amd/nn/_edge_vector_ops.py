@@ -73,14 +73,18 @@ torch.library.register_autograd(f"{_NS}::edge_vectors", _fwd_backward, setup_con
 def _adj_setup(ctx, inputs, output):
     g_vec, edge_index, shift, batch, num_nodes, num_frames, need_cell = inputs
     ctx.edge_index, ctx.shift, ctx.batch, ctx.need_cell = edge_index, shift, batch, need_cell
+    ctx.num_nodes, ctx.device = num_nodes, g_vec.device
     ctx.set_materialize_grads(False)
 
 
 def _adj_backward(ctx, c_pos, c_cell):
     # adjoint of the adjoint = the (linear) forward map applied to the cotangents
-    if c_pos is None:
-        raise RuntimeError("double backward through edge vectors needs a position cotangent")
     cell = c_cell if (ctx.need_cell and c_cell is not None) else None
+    if c_pos is None:
+        if cell is None:
+            return None, None, None, None, None, None, None
+        # only the cell gradient carries a cotangent (a stress-only loss): vec_e = shift_e @ c_cell[frame(dst_e)]
+        c_pos = torch.zeros((ctx.num_nodes, 3), dtype=torch.float64, device=ctx.device)
     vec = torch.ops.nequip_amd.edge_vectors(c_pos, cell, ctx.edge_index, ctx.shift if cell is not None else None,
                                             ctx.batch)
     return vec, None, None, None, None, None, None

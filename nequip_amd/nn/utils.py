@@ -42,7 +42,9 @@ class _FrameSumFn(torch.autograd.Function):
         from ._topology import _ptr, current_stream_ptr
 
         rows_c = rows.contiguous()
-        width = rows_c.numel() // max(rows_c.shape[0], 1)
+        width = 1  # (from the row shape, not numel // N: an empty system still has its row width)
+        for d in rows_c.shape[1:]:
+            width *= d
         out = torch.empty((num_frames,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
         with torch.cuda.device(rows.device):
             rc = _lib.load().nqa_frame_sum(_ptr(rows_c), _ptr(batch), rows_c.shape[0], width, num_frames, _ptr(out),
@@ -176,9 +178,8 @@ class _EdgeVectorsAdjFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, c_pos, c_cell):
-        # adjoint of the adjoint = the (linear) forward map applied to the cotangents
-        if c_pos is None:
-            raise RuntimeError("double backward through edge vectors needs a position cotangent")
+        # adjoint of the adjoint = the (linear) forward map applied to the cotangents (autograd materialises a missing
+        # cotangent of the tensor output g_pos as zeros: a cell-only cotangent gives shift @ c_cell[frame])
         cell = c_cell if (ctx.has_cell and c_cell is not None) else None
         vec = _EdgeVectorsFn.apply(c_pos, cell, ctx.edge_index, ctx.shift if cell is not None else None, ctx.batch)
         return vec, None, None, None, None, None

@@ -18,17 +18,22 @@ def test_edge_vectors_any_dtype(device, pos_dtype, shift_dtype):
     ref = with_edge_vectors_(dict(data))  # CPU: the reference's ATen formulation in float64
     d = K.to_device(dict(data), device)
     d[K.POSITIONS_KEY] = d[K.POSITIONS_KEY].to(pos_dtype).requires_grad_(True)
-    d[K.CELL_KEY] = d[K.CELL_KEY].to(pos_dtype)
+    d[K.CELL_KEY] = d[K.CELL_KEY].to(pos_dtype).requires_grad_(True)
     d[K.EDGE_CELL_SHIFT_KEY] = d[K.EDGE_CELL_SHIFT_KEY].to(shift_dtype)
     out = with_edge_vectors_(d)
     tol = 1e-12 if pos_dtype == torch.float64 else 2e-5
     torch.testing.assert_close(out[K.EDGE_VECTORS_KEY].detach().cpu(), ref[K.EDGE_VECTORS_KEY], atol=tol, rtol=0)
     g = torch.randn(ref[K.EDGE_VECTORS_KEY].shape, dtype=torch.float64, generator=torch.Generator().manual_seed(0))
-    (gp,) = torch.autograd.grad(out[K.EDGE_VECTORS_KEY], d[K.POSITIONS_KEY], g.to(device))
+    gp, gc = torch.autograd.grad(out[K.EDGE_VECTORS_KEY], [d[K.POSITIONS_KEY], d[K.CELL_KEY]], g.to(device))
     assert gp.dtype == pos_dtype
     ei = data[K.EDGE_INDEX_KEY]
     gp_ref = torch.zeros(len(pos), 3, dtype=torch.float64).index_add_(0, ei[1], g).index_add_(0, ei[0], -g)
     torch.testing.assert_close(gp.cpu().double(), gp_ref, atol=1e-12 if pos_dtype == torch.float64 else 1e-5, rtol=0)
+    # the cell gradient: sum_e shift_e^T g_e into the one frame
+    assert gc.dtype == pos_dtype and gc.shape == d[K.CELL_KEY].shape
+    outer = data[K.EDGE_CELL_SHIFT_KEY][:, :, None] * g[:, None, :]
+    gc_ref = torch.zeros(1, 3, 3, dtype=torch.float64).index_add_(0, torch.zeros(len(g), dtype=torch.long), outer)
+    torch.testing.assert_close(gc.cpu().double(), gc_ref, atol=1e-12 if pos_dtype == torch.float64 else 1e-5, rtol=0)
 
 
 @pytest.mark.gpu
