@@ -893,8 +893,8 @@ int nqa_metrics_bwd(const nqa_metric_stream* streams, int32_t n_streams, const n
                     const void* saved, const double* grad_values, nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
- * The multi-tensor chunk layout of the four sections that follow (weight averaging, schedule-free AdamW, ConFIG, per-tensor
- *   statistics): launches over device-resident tables.  `tensors` [n] is the tensor table, one record per tensor (or per set of
+ * The multi-tensor chunk layout of the five sections that follow (weight averaging, schedule-free AdamW, Adam, ConFIG,
+ *   per-tensor statistics): launches over device-resident tables.  `tensors` [n] is the tensor table, one record per tensor (or per set of
  *   tensors of one shape that are walked together), float32 or float64, dense.  `chunks` [chunk_capacity] is the chunk map: the
  *   tensor a chunk belongs to and the element offset at which it starts.  A chunk is NQA_EMA_CHUNK elements (nqa_ema_chunk_elems;
  *   NQA_TSTATS_CHUNK, nqa_tstats_chunk_elems, for the statistics), the last one of a tensor shorter; a tensor without elements
@@ -974,6 +974,80 @@ int nqa_sfree_step(const nqa_sfree_tensor* tensors, const nqa_mt_chunk* chunks, 
                    nqa_sfree_group* groups, int32_t n_groups, nqa_stream stream);
 int nqa_sfree_swap(const nqa_sfree_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* n_chunks,
                    const nqa_sfree_group* groups, int32_t n_groups, int32_t to_eval, nqa_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Adam / AdamW (torch.optim.Adam, torch.optim.AdamW) with gradient clipping, and ReduceLROnPlateau
+ *   (torch.optim.lr_scheduler.ReduceLROnPlateau): the optimizer and scheduler of the reference's default training recipe, as
+ *   multi-tensor launches over the chunk layout above.  A table entry is (parameter, .grad, exp_avg, exp_avg_sq, max_exp_avg_sq,
+ *   step), the tensors of one dtype and `step` a 0-d float32 in device memory, the count of steps THIS parameter has taken (as
+ *   torch's capturable and fused Adam keep it); `group` indexes `groups` [n_groups]: the hyper-parameters of every parameter
+ *   group, in device memory, so that a captured launch sees a rewritten lr.  A chunk whose `group` is outside [0, n_groups) is
+ *   skipped.  `counts` [2] (device memory, int64) = {chunks in use, tensors in use}; `tensor_capacity` is the length of `tensors`.
+ * nqa_adam_step: per tensor whose `grad` is not null (the others are skipped, their state and step untouched), from the OLD
+ *   *step, in double (each scalar rounded once to float for float32 tensors):
+ *       s = *step + 1,  bc1 = 1 - beta1^s,  bc2 = 1 - beta2^s,  step_size = lr / bc1,  bc2_sqrt = sqrt(bc2)
+ *   and per element, torch's _single_tensor_adam with p the parameter, m = exp_avg, v = exp_avg_sq:
+ *       g = grad;  factor != 1: g = g factor;  g = clamp(g, -clip_value, clip_value) (a NaN passes);  maximize: g = -g
+ *       weight_decay != 0:  decoupled: p = p (1 - lr weight_decay),  otherwise: g = g + weight_decay p
+ *       m = lerp(m, g, 1 - beta1)  (ATen's lerp, nqa_ema_update),  v = beta2 v + (1 - beta2) g g
+ *       amsgrad: max_exp_avg_sq = max(max_exp_avg_sq, v) (a NaN of either stays) and v' = max_exp_avg_sq, otherwise v' = v
+ *       p = p - step_size m / (sqrt(v') / bc2_sqrt + eps)
+ *   `grad` is only read.  `clip` is the clipping record: factor is exactly 1 and clip_value +inf without clipping.  Then
+ *   *step += 1 for every entry with a `grad`, by a second launch with one thread per table entry on the same stream (no
+ *   workgroup of the first sees the advanced count).  chunk_capacity == 0: only the counts move.
+ * nqa_adam_grad_norm: two launches.  (1) One wavefront per chunk sums the squares of the chunk's `grad` elements in double (a
+ *   lane its elements in ascending order, the lanes by a fixed tree) into partials [chunk_capacity]; a chunk without `grad` gives
+ *   0.  (2) One wavefront adds the partials in use (lane l a contiguous run in index order, then the 64 lane sums in lane order)
+ *   and writes clip->norm = sqrt(sum) and clip->factor = min(1, max_norm / (norm + 1e-6)) (clip_grad_norm_'s; a NaN stays, as
+ *   with error_if_nonfinite=False).  No floating-point atomics: the same inputs give the same bits.
+ * nqa_adam_plateau: one launch of one thread, torch's ReduceLROnPlateau.step(metric) with the metric (float32 or float64) read
+ *   through a device pointer: last_epoch += 1; the metric is better than `best` when (min, rel) metric < best (1 - threshold),
+ *   (min, abs) metric < best - threshold, (max, rel) metric > best (threshold + 1), (max, abs) metric > best + threshold; then
+ *   best = metric, num_bad_epochs = 0, otherwise num_bad_epochs += 1; cooldown_counter > 0: cooldown_counter -= 1,
+ *   num_bad_epochs = 0; num_bad_epochs > patience: for every group new_lr = max(lr factor, min_lr) and lr = new_lr where
+ *   lr - new_lr > eps, cooldown_counter = cooldown, num_bad_epochs = 0.  Double arithmetic without contraction: every
+ *   comparison is the IEEE operation of torch's Python.
+ *   No allocation, no host synchronisation: all three capture into a hipGraph.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct nqa_adam_tensor {
+  void* param;
+  const void* grad; /* null: skipped */
+  void* exp_avg;
+  void* exp_avg_sq;
+  void* max_exp_avg_sq; /* null without amsgrad */
+  float* step;          /* 0-d float32: the steps this parameter has taken */
+  int64_t numel;
+  int32_t dtype, group; /* nqa_dtype, index into the group records */
+} nqa_adam_tensor;
+
+typedef struct nqa_adam_group {
+  double lr, beta1, beta2, eps, weight_decay;
+  int32_t amsgrad, maximize, decoupled, pad;
+  double min_lr; /* of the scheduler */
+} nqa_adam_group;
+
+typedef struct nqa_adam_clip {
+  double norm;       /* written by nqa_adam_grad_norm: the norm of all gradients before clipping */
+  double factor;     /* written by nqa_adam_grad_norm; exactly 1 when clipping by norm is off */
+  double max_norm;   /* the bound of clipping by norm */
+  double clip_value; /* the bound of clipping by value; +inf when off */
+} nqa_adam_clip;
+
+typedef struct nqa_adam_plateau_state {
+  double best;
+  int64_t num_bad_epochs, cooldown_counter, last_epoch;
+  double factor, threshold, eps;
+  int64_t patience, cooldown;
+  int32_t mode_max, threshold_abs; /* 0: "min" / "rel" */
+} nqa_adam_plateau_state;
+
+int nqa_adam_step(const nqa_adam_tensor* tensors, int64_t tensor_capacity, const nqa_mt_chunk* chunks, int64_t chunk_capacity,
+                  const int64_t* counts, const nqa_adam_group* groups, int32_t n_groups, const nqa_adam_clip* clip,
+                  nqa_stream stream);
+int nqa_adam_grad_norm(const nqa_adam_tensor* tensors, const nqa_mt_chunk* chunks, int64_t chunk_capacity, const int64_t* counts,
+                       double* partials, nqa_adam_clip* clip, nqa_stream stream);
+int nqa_adam_plateau(const void* metric, int32_t metric_dtype, nqa_adam_plateau_state* state, nqa_adam_group* groups,
+                     int32_t n_groups, nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Conflict-free inverse gradients, ConFIG (nequip/train/config.py::ConFIGLightningModule._ConFIG_backwards) as multi-tensor

@@ -379,6 +379,9 @@ SIGNATURES = {
     "nqa_ema_swap": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "nqa_sfree_step": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
     "nqa_sfree_swap": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    "nqa_adam_step": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "nqa_adam_grad_norm": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nqa_adam_plateau": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "nqa_config_gram_chunk_elems": (c_int32, []),
     "nqa_config_collect": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int64, c_int32, c_void_p]),
     "nqa_config_gram": (

@@ -1,4 +1,4 @@
-// The multi-tensor chunk layer of ema.hip, schedulefree.hip, config.hip and training_stats.hip (internal; the public side is the
+// The multi-tensor chunk layer of ema.hip, schedulefree.hip, adam.hip, config.hip and training_stats.hip (internal; the public side is the
 // "multi-tensor chunk layout" section of include/nequip_amd.h).
 //
 // Layout: a device table of TENSORS (one record per tensor, or per set of tensors of one shape that are walked together:

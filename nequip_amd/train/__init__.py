@@ -3,6 +3,7 @@ from .ema import EMAWeights  # noqa: F401
 from .config import ConFIGGradients  # noqa: F401
 from .training_stats import TrainingStatsMonitor  # noqa: F401
 from .schedulefree import AdamWScheduleFree, ScheduleFreeHooks  # noqa: F401
+from .adam import Adam, AdamW, ReduceLROnPlateau  # noqa: F401
 from .metrics import (  # noqa: F401
     HuberLoss,
     MaximumAbsoluteError,
