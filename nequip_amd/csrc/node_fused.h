@@ -108,9 +108,13 @@ struct NFStage {  // one (instruction, atom type, 32-channel K slab) step of a c
   bool valid;
 };
 
-template <int D>
+// TWO: two 32-column tiles; XAL: every slab of the unit is 16-byte aligned; GATED: the unit has stages whose operand is
+// multiplied by activated gate scalars.  Wave-uniform and fixed for the unit, they decide which vector loads a stage issues:
+// as template parameters they leave the stage loop without a branch around a load (see node_linear_wave_bf16_unit).
+template <int D, bool TWO, bool XAL, bool GATED>
 __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NFChunk& ch, int64_t g,
                                                 float* __restrict__ xs, float* __restrict__ gs) {
+  static_assert(D > 1 || !GATED, "gated blocks have d >= 3");
   constexpr int NZT = 32 / D;
   constexpr int P = D == 1 ? 1 : ((D + 3) / 4) * 4;
   constexpr int S = kNLK3 * D + P;
@@ -145,7 +149,7 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
   }
   const int nct = (ch.mul_out + 31) / 32;
   const int ct0 = ch.c0 / 32;
-  const bool two_tiles = cw > 32;
+  constexpr bool two_tiles = TWO;  // cw > 32
 
   int xz[XV4], xo[XV4];
 #pragma unroll
@@ -218,7 +222,7 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
   auto load_x = [&](float4 (&xr)[XV4], const NFStage& st) __attribute__((always_inline)) {
     const int kk = min(kNLK3, st.mul_in - st.k0) * D;
     const float* __restrict__ xb0 = st.xp + st.x_off + st.k0 * D;
-    if (((st.din | st.x_off | kk) & 3) == 0) {
+    if constexpr (XAL) {
 #pragma unroll
       for (int v = 0; v < XV4; ++v) {
         const int64_t zg = zrow_x[v];
@@ -270,23 +274,24 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
   };
   // gate scalars of a stage's channels: [NZT atoms][32 channels], activated once when they go to LDS.  (The host only asks
   // for gated blocks with d >= 3, multiplicities and offsets that are multiples of 4.)
+  // (unconditional loads: a stage without gates in a unit that has gated ones reads the first floats of the operand rows)
   auto load_g = [&](float4 (&gr)[XG4], const NFStage& st) __attribute__((always_inline)) {
-    if constexpr (D > 1) {
-      if (st.gate_off >= 0) {
-        const int kc = min(kNLK3, st.mul_in - st.k0);
-        const float* __restrict__ gb0 = st.xp + st.gate_off + st.k0;
+    if constexpr (GATED) {
+      const bool gated = st.gate_off >= 0;
+      const int kc = min(kNLK3, st.mul_in - st.k0);
+      const float* __restrict__ gb0 = st.xp + (gated ? st.gate_off + st.k0 : 0);
+      const int64_t gdin = gated ? st.din : 0;
 #pragma unroll
-        for (int v = 0; v < XG4; ++v) {
-          const int idx = lane + v * 64;
-          const int gz = idx / GQ, go = (idx - gz * GQ) * 4;
-          const int64_t zg = zrow_g[v];
-          gr[v] = *reinterpret_cast<const float4*>(gb0 + zg * st.din + min(go, kc - 4));
-        }
+      for (int v = 0; v < XG4; ++v) {
+        const int idx = lane + v * 64;
+        const int gz = idx / GQ, go = (idx - gz * GQ) * 4;
+        const int64_t zg = zrow_g[v];
+        gr[v] = *reinterpret_cast<const float4*>(gb0 + zg * gdin + (gated ? min(go, kc - 4) : 0));
       }
     }
   };
   auto store_g = [&](const float4 (&gr)[XG4], const NFStage& st) __attribute__((always_inline)) {
-    if constexpr (D > 1) {
+    if constexpr (GATED) {
       if (st.gate_off >= 0) {
         const int kc = min(kNLK3, st.mul_in - st.k0);
 #pragma unroll
@@ -307,25 +312,25 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
     }
   };
 
-  u32x4 Af[2][2];  // [tile][plane]
-  int we_blk = 0;
-  auto load_a = [&](const NFStage& st, int k16) __attribute__((always_inline)) {
+  u32x4 Af[2][2][2];  // [K block of the stage][tile][plane]
+  int we_blk[2] = {};
+  auto load_a = [&](int buf, const NFStage& st, int k16) __attribute__((always_inline)) {
     const NFSet& s = a.sets[__builtin_amdgcn_readfirstlane(st.set)];
     const u32x4* __restrict__ p = s.wf + (int64_t)st.t * s.frag_stride + st.frag_off + lane +
                                      ((int64_t)(k16 * nct + ct0) * 2) * 64;
-    Af[0][0] = p[0]; Af[0][1] = p[64];
-    if (two_tiles) { Af[1][0] = p[128]; Af[1][1] = p[192]; }
-    we_blk = s.wexp[st.t * s.exp_stride + st.exp_off + k16];
+    Af[buf][0][0] = p[0]; Af[buf][0][1] = p[64];
+    if (two_tiles) { Af[buf][1][0] = p[128]; Af[buf][1][1] = p[192]; }
+    we_blk[buf] = s.wexp[st.t * s.exp_stride + st.exp_off + k16];
   };
   f32x16 acc0 = {0}, acc1 = {0};
   constexpr int kUnset = 1 << 20;
   int Scol = kUnset;
-  auto block = [&](int s, bool on, bool gated, bool masked) __attribute__((always_inline)) {
+  auto block = [&](int buf, int s, bool on, bool gated, bool masked) __attribute__((always_inline)) {
     const float* __restrict__ xb = xs + zl * S + m;
     float bq[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) bq[e] = xb[(16 * s + 8 * half + e) * D];
-    if constexpr (D > 1) {
+    if constexpr (GATED) {
       if (gated) {  // (wave-uniform) act(gate[u]) of this lane's atom, channels 16 s + 8 half + e
         const float4 g0 = *reinterpret_cast<const float4*>(gs + zl * GS + 16 * s + 8 * half);
         const float4 g1 = *reinterpret_cast<const float4*>(gs + zl * GS + 16 * s + 8 * half + 4);
@@ -340,7 +345,7 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
 #pragma unroll
       for (int e = 0; e < 8; ++e) bq[e] = on ? bq[e] : 0.f;
     }
-    const int we = we_blk;
+    const int we = we_blk[buf];
     float mx = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(bq[e]));
@@ -376,47 +381,62 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
       Bh[e] = x; Bl[e] = y;
     }
     if (two_tiles) {
-      acc0 = mfma_f16(Af[0][1], Bh, acc0);
-      acc1 = mfma_f16(Af[1][1], Bh, acc1);
-      acc0 = mfma_f16(Af[0][0], Bl, acc0);
-      acc1 = mfma_f16(Af[1][0], Bl, acc1);
-      acc0 = mfma_f16(Af[0][0], Bh, acc0);
-      acc1 = mfma_f16(Af[1][0], Bh, acc1);
+      acc0 = mfma_f16(Af[buf][0][1], Bh, acc0);
+      acc1 = mfma_f16(Af[buf][1][1], Bh, acc1);
+      acc0 = mfma_f16(Af[buf][0][0], Bl, acc0);
+      acc1 = mfma_f16(Af[buf][1][0], Bl, acc1);
+      acc0 = mfma_f16(Af[buf][0][0], Bh, acc0);
+      acc1 = mfma_f16(Af[buf][1][0], Bh, acc1);
     } else {
-      acc0 = mfma_f16(Af[0][1], Bh, acc0);
-      acc0 = mfma_f16(Af[0][0], Bl, acc0);
-      acc0 = mfma_f16(Af[0][0], Bh, acc0);
+      acc0 = mfma_f16(Af[buf][0][1], Bh, acc0);
+      acc0 = mfma_f16(Af[buf][0][0], Bl, acc0);
+      acc0 = mfma_f16(Af[buf][0][0], Bh, acc0);
     }
   };
 
+  // The stage loop, in the order of node_linear_wave_bf16_unit's: requests in the order of their use, none inside a branch,
+  // the stage behind the last one is the last one again.
+  //   in flight at the top of stage s: x(s), g(s), A0(s), A1(s)
+  //   slab(s), gates(s) -> LDS | request x(s+1), g(s+1) | block 0 | request A0(s+1) | block 1 | request A1(s+1)
+  static_assert(kNLK3 == 32, "two K blocks per stage");
+  auto kblk = [&](const NFStage& st, int s16) __attribute__((always_inline)) {  // (a missing second K block: the first again)
+    return (st.k0 >> 4) + ((s16 > 0 && st.k0 + 16 * s16 < st.mul_in) ? s16 : 0);
+  };
   float4 xr0[XV4];
   float4 gr0[XG4];
   NFStage cur = first_stage();
-  NFStage ld = cur;
-  if (ld.valid) { load_x(xr0, ld); load_g(gr0, ld); ld = next_stage(ld); }
-  while (cur.valid) {
-    store_x(xr0, cur);
-    store_g(gr0, cur);
-    const int k16a = cur.k0 >> 4;
-    load_a(cur, k16a);
-    __builtin_amdgcn_sched_barrier(0);
-    if (ld.valid) { load_x(xr0, ld); load_g(gr0, ld); ld = next_stage(ld); }
-    __builtin_amdgcn_sched_barrier(0);
-    const bool bsel = col_ok && (cur.n_types == 1 || tzj == cur.t);
-    const bool gated = cur.gate_off >= 0;
-#pragma unroll
-    for (int s16 = 0; s16 < kNLK3 / 16; ++s16) {
-      const bool exists = cur.k0 + 16 * s16 < cur.mul_in;
-      (void)exists;
-      block(s16, bsel, gated, cur.n_types > 1);
-      if (s16 + 1 < kNLK3 / 16) {
-        __builtin_amdgcn_sched_barrier(0);
-        const bool nexists = cur.k0 + 16 * (s16 + 1) < cur.mul_in;
-        load_a(cur, nexists ? k16a + s16 + 1 : k16a);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+  if (cur.valid) {
+    NFStage nx = next_stage(cur);
+    bool more = nx.valid;
+    if (!more) nx = cur;
+    load_x(xr0, cur);
+    load_g(gr0, cur);
+    load_a(0, cur, kblk(cur, 0));
+    load_a(1, cur, kblk(cur, 1));
+    for (;;) {
+      __builtin_amdgcn_sched_barrier(0);
+      store_x(xr0, cur);
+      store_g(gr0, cur);
+      const bool bsel = col_ok && (cur.n_types == 1 || tzj == cur.t);
+      const bool gated = cur.gate_off >= 0;
+      const bool masked = cur.n_types > 1;
+      __builtin_amdgcn_sched_barrier(0);
+      load_x(xr0, nx);
+      load_g(gr0, nx);
+      __builtin_amdgcn_sched_barrier(0);
+      block(0, 0, bsel, gated, masked);
+      __builtin_amdgcn_sched_barrier(0);
+      load_a(0, nx, kblk(nx, 0));  // (the MFMAs above have read these registers)
+      __builtin_amdgcn_sched_barrier(0);
+      block(1, 1, bsel, gated, masked);
+      __builtin_amdgcn_sched_barrier(0);
+      load_a(1, nx, kblk(nx, 1));
+      if (!more) break;
+      cur = nx;
+      nx = next_stage(cur);
+      more = nx.valid;
+      if (!more) nx = cur;
     }
-    cur = next_stage(cur);
   }
 
   // ---- epilogue: accumulators -> the wavefront's slab -> contiguous runs per atom, through the chunk's epilogue
@@ -560,6 +580,39 @@ __device__ __forceinline__ void node_fused_unit(const NodeFusedArgs& a, const NF
   }
 }
 
+// the unit's wave-uniform properties that decide which loads its stages issue -> template parameters of the unit
+template <int D, bool TWO, bool XAL>
+__device__ __forceinline__ void node_fused_dispatch_g(const NodeFusedArgs& a, const NFChunk& ch, int64_t g, float* __restrict__ xs,
+                                                      float* __restrict__ gs, bool gated) {
+  if constexpr (D > 1) {
+    if (gated) {
+      node_fused_unit<D, TWO, XAL, true>(a, ch, g, xs, gs);
+      return;
+    }
+  }
+  node_fused_unit<D, TWO, XAL, false>(a, ch, g, xs, gs);
+}
+template <int D>
+__device__ __forceinline__ void node_fused_dispatch(const NodeFusedArgs& a, const NFChunk& ch, int64_t g, float* __restrict__ xs,
+                                                    float* __restrict__ gs) {
+  const bool two = min(kNLW, ch.mul_out - ch.c0) > 32;
+  // a slab is 16-byte aligned when its offset, mul_in d and its rows' stride are multiples of 4 floats; a unit with one slab
+  // that is not takes the element-wise loads for all of them (same values)
+  bool xal = true, gated = false;
+  for (int q = ch.instr_begin; q < ch.instr_end; ++q) {
+    const NFInstr& in = a.instr[q];
+    xal = xal && ((a.sets[in.set].din | in.x_off | (in.mul_in * D)) & 3) == 0;
+    gated = gated || in.gate_off >= 0;
+  }
+  if (two) {
+    if (xal) node_fused_dispatch_g<D, true, true>(a, ch, g, xs, gs, gated);
+    else node_fused_dispatch_g<D, true, false>(a, ch, g, xs, gs, gated);
+  } else {
+    if (xal) node_fused_dispatch_g<D, false, true>(a, ch, g, xs, gs, gated);
+    else node_fused_dispatch_g<D, false, false>(a, ch, g, xs, gs, gated);
+  }
+}
+
 __global__ __launch_bounds__(64 * kNLWavesPerWG, 3) void node_fused_kernel(const NodeFusedArgs a_kernarg) {
   __shared__ __align__(16) float xs_all[kNLWavesPerWG * (kNLXS + kNFGS)];
   // The tables are read where the dispatch packet put them (the kernel-argument segment; this kernel's only argument sits at
@@ -578,11 +631,11 @@ __global__ __launch_bounds__(64 * kNLWavesPerWG, 3) void node_fused_kernel(const
   const NFChunk ch = a.chunks[a.grp_chunk0[gi] + local % n];
   const int64_t g = (int64_t)(local / n);
   switch (ch.d) {
-    case 1: node_fused_unit<1>(a, ch, g, xs, gs); break;
-    case 3: node_fused_unit<3>(a, ch, g, xs, gs); break;
-    case 5: node_fused_unit<5>(a, ch, g, xs, gs); break;
-    case 7: node_fused_unit<7>(a, ch, g, xs, gs); break;
-    case 9: node_fused_unit<9>(a, ch, g, xs, gs); break;
+    case 1: node_fused_dispatch<1>(a, ch, g, xs, gs); break;
+    case 3: node_fused_dispatch<3>(a, ch, g, xs, gs); break;
+    case 5: node_fused_dispatch<5>(a, ch, g, xs, gs); break;
+    case 7: node_fused_dispatch<7>(a, ch, g, xs, gs); break;
+    case 9: node_fused_dispatch<9>(a, ch, g, xs, gs); break;
     default: break;
   }
 }

@@ -607,10 +607,14 @@ struct NodeStage {  // one (instruction, atom type, 32-channel K slab) step of a
   bool valid;
 };
 
-template <int D, bool F16>
+// TWO: the chunk has two 32-column tiles; XAL: every slab of the unit is 16-byte aligned.  Both are wave-uniform and fixed
+// for the unit, and both decide which vector loads a stage issues: as template parameters they leave the stage loop without
+// a branch around a load, so that the compiler counts its waits (vmcnt(k), k > 0) instead of draining the queue.
+template <int D, bool F16, bool TWO, bool XAL>
 __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPackedArgs& pa, const NodeChunk& ch, int64_t g,
                                                            float* __restrict__ xs) {
   constexpr int NPL = F16 ? 2 : 3;  // operand planes
+  constexpr int NBUF = 2;           // fragment buffers: one per K block of a stage (16 registers each, three planes: 24)
   const NodeLinearArgs<float>& a = pa.base;
   constexpr int NZT = 32 / D;
   constexpr int P = D == 1 ? 1 : ((D + 3) / 4) * 4;
@@ -639,7 +643,7 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
   }
   const int nct = (ch.mul_out + 31) / 32;   // column tiles of the whole output block
   const int ct0 = ch.c0 / 32;               // first tile of this chunk (c0 is a multiple of 64)
-  const bool two_tiles = cw > 32;           // wave-uniform
+  constexpr bool two_tiles = TWO;           // cw > 32
 
   int xz[XV4], xo[XV4], zrow[XV4];
 #pragma unroll
@@ -695,15 +699,13 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
   };
 
   // x slab of a stage: XV4 UNCONDITIONAL loads per lane from clamped (always valid) addresses; what lies outside the
-  // slab is zeroed when the registers go to LDS.  TWO slabs are kept in flight per wavefront (the stage being computed is
-  // in LDS, the next two are on their way): the loaded latency of these 128 d-byte row pieces is 2-6 us (timeline:
-  // first slab in LDS 7 k cycles after the unit starts), and with one 4 KiB slab in flight per wavefront the whole
-  // kernel ran at latency x occupancy = 2.4 TB/s.
-  const bool xal_all = (a.din & 3) == 0;
+  // slab is zeroed when the registers go to LDS.  The stage being computed is in LDS, the next one is on its way for a
+  // whole stage (the loaded latency of these 128 d-byte row pieces is 2-6 us); a second slab in flight does not fit the
+  // 168 registers of three wavefronts per SIMD.
   auto load_x = [&](float4 (&xr)[XV4], const NodeStage& st) {
     const int kk = min(kNLK3, st.mul_in - st.k0) * D;
     const float* __restrict__ xb0 = a.x + st.x_off + st.k0 * D;
-    if (xal_all && ((st.x_off | kk) & 3) == 0) {
+    if constexpr (XAL) {
 #pragma unroll
       for (int v = 0; v < XV4; ++v) {
         const int64_t zg = zrow[v];
@@ -747,20 +749,19 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
     }
   };
 
-  // A fragments of one 16-row K block for the two column tiles of this chunk (3 planes each): requested for the first K
-  // block of the slab at the top of the stage, for the second one right after the MFMAs of the first have been issued
-  // (a stage whose slab holds 16 channels or fewer -- multiplicities that are not multiples of 32 -- repeats its block
-  // with B = 0: branch-free, wasted work only for such shapes).  They come out of the L2 (all wavefronts of a chunk read
-  // the same 12 KiB per stage) and land behind the LDS write / B split; double-buffering them (measured) buys nothing.
-  u32x4 Af[1][2][NPL];
-  int we_blk = 0;  // F16: exponent of the K block whose fragments are in Af
+  // A fragments of one 16-row K block for the column tiles of this chunk (NPL planes each); when they are requested is
+  // the stage loop's business (below).  A stage whose slab holds 16 channels or fewer -- multiplicities that are not
+  // multiples of 32 -- repeats its block with B = 0: branch-free, wasted work only for such shapes.  They come out of the
+  // L2: all wavefronts of a chunk read the same 12 KiB per stage.
+  u32x4 Af[NBUF][2][NPL];
+  int we_blk[NBUF] = {};  // F16: exponent of the K block whose fragments are in Af[buf]
   auto load_a = [&](int buf, const NodeStage& st, int k16) {
     const u32x4* __restrict__ p = pa.wf + (int64_t)st.t * pa.frag_stride + pa.frag_off[st.q] + lane +
                                      ((int64_t)(k16 * nct + ct0) * NPL) * 64;
     if constexpr (F16) {
       Af[buf][0][0] = p[0]; Af[buf][0][1] = p[64];
       if (two_tiles) { Af[buf][1][0] = p[128]; Af[buf][1][1] = p[192]; }
-      we_blk = pa.wexp[st.t * pa.exp_stride + a.instr[st.q].pad + k16];
+      we_blk[buf] = pa.wexp[st.t * pa.exp_stride + a.instr[st.q].pad + k16];
     } else {
       Af[buf][0][0] = p[0]; Af[buf][0][1] = p[64]; Af[buf][0][2] = p[128];
       if (two_tiles) { Af[buf][1][0] = p[192]; Af[buf][1][1] = p[256]; Af[buf][1][2] = p[320]; }
@@ -783,7 +784,7 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
       for (int e = 0; e < 8; ++e) bq[e] = on ? bq[e] : 0.f;
     }
     if constexpr (F16) {
-      const int we = we_blk;
+      const int we = we_blk[buf];
       float mx = 0.f;  // the column's largest magnitude in this K block (its other 8 values sit in lane ^ 32)
 #pragma unroll
       for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(bq[e]));
@@ -866,31 +867,46 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
     }
   };
 
-  // one stage: slab registers -> LDS, request the next slab into the same registers, then the K blocks of the slab
+  // The stage loop.  Vector loads return in order, so a wait for one load is a wait for everything requested before it:
+  // the loop requests in the order it consumes, and no load sits inside a branch (TWO / XAL are template parameters; the
+  // stage behind the last one is the last one again, its loads hit the cache and nobody reads them), so every wait in front
+  // of a K block's MFMAs is a counted one that leaves the next stage's slab on its way.
+  //   in flight at the top of stage s: x(s), A0(s), A1(s), requested in this order a stage to half a stage ago
+  //   slab(s) -> LDS | request x(s+1) | block 0 | request A0(s+1) | block 1 | request A1(s+1)
+  static_assert(kNLK3 == 32 && NBUF == 2, "two K blocks per stage, one fragment buffer each");
+  auto kblk = [&](const NodeStage& st, int s16) {  // K block s16 of the stage's slab (a missing second block: the first again)
+    return (st.k0 >> 4) + ((s16 > 0 && st.k0 + 16 * s16 < st.mul_in) ? s16 : 0);
+  };
   float4 xr0[XV4];
   NodeStage cur = first_stage();
-  NodeStage ld = cur;  // the stage whose slab is requested next
-  if (ld.valid) { load_x(xr0, ld); ld = next_stage(ld); }
-  while (cur.valid) {
-    store_x(xr0, cur);
-    const int k16a = cur.k0 >> 4;
-    load_a(0, cur, k16a);
-    __builtin_amdgcn_sched_barrier(0);
-    if (ld.valid) { load_x(xr0, ld); ld = next_stage(ld); }
-    __builtin_amdgcn_sched_barrier(0);
-    const bool bsel = col_ok && (a.n_types == 1 || tzj == cur.t);
-#pragma unroll
-    for (int s16 = 0; s16 < kNLK3 / 16; ++s16) {
-      const bool exists = cur.k0 + 16 * s16 < cur.mul_in;  // (wave-uniform; a missing block repeats the last one with B = 0)
-      block(0, s16, bsel && exists);
-      if (s16 + 1 < kNLK3 / 16) {
-        __builtin_amdgcn_sched_barrier(0);
-        const bool nexists = cur.k0 + 16 * (s16 + 1) < cur.mul_in;
-        load_a(0, cur, nexists ? k16a + s16 + 1 : k16a);  // (same registers: the MFMAs above have read them)
-        __builtin_amdgcn_sched_barrier(0);
-      }
+  if (cur.valid) {
+    NodeStage nx = next_stage(cur);
+    bool more = nx.valid;
+    if (!more) nx = cur;
+    load_x(xr0, cur);
+    load_a(0, cur, kblk(cur, 0));
+    load_a(1, cur, kblk(cur, 1));
+    for (;;) {
+      __builtin_amdgcn_sched_barrier(0);
+      store_x(xr0, cur);
+      const bool bsel = col_ok && (a.n_types == 1 || tzj == cur.t);
+      const bool exists1 = cur.k0 + 16 < cur.mul_in;  // (wave-uniform; a missing block repeats the first one with B = 0)
+      __builtin_amdgcn_sched_barrier(0);
+      load_x(xr0, nx);
+      __builtin_amdgcn_sched_barrier(0);
+      block(0, 0, bsel);
+      __builtin_amdgcn_sched_barrier(0);
+      load_a(0, nx, kblk(nx, 0));  // (the MFMAs above have read these registers)
+      __builtin_amdgcn_sched_barrier(0);
+      block(1, 1, bsel && exists1);
+      __builtin_amdgcn_sched_barrier(0);
+      load_a(1, nx, kblk(nx, 1));
+      if (!more) break;
+      cur = nx;
+      nx = next_stage(cur);
+      more = nx.valid;
+      if (!more) nx = cur;
     }
-    cur = next_stage(cur);
   }
   // ---- epilogue (as in node_linear_wave_unit)
   constexpr int SE = kNLW * D + P;
@@ -960,9 +976,30 @@ __device__ __forceinline__ void node_linear_wave_bf16_unit(const NodeLinearPacke
 
 constexpr int kNLWavesPerWG = 4;  // independent wavefronts (units) per workgroup: no barrier, only fewer dispatches
 
+// the unit's two wave-uniform properties that decide which loads its stages issue -> template parameters of the unit
+template <int D, bool F16>
+__device__ __forceinline__ void node_linear_wave_bf16_dispatch(const NodeLinearPackedArgs& pa, const NodeChunk& ch, int64_t g,
+                                                               float* __restrict__ xs) {
+  const NodeLinearArgs<float>& a = pa.base;
+  const bool two = min(kNLW, ch.mul_out - ch.c0) > 32;
+  // a slab [x_off + k0 d, + min(32, mul_in - k0) d) of a row is 16-byte aligned when x_off, mul_in d and the row stride are
+  // multiples of 4 floats; a unit with one slab that is not takes the element-wise loads for all of them (same values)
+  bool xal = (a.din & 3) == 0;
+  for (int q = ch.instr_begin; q < ch.instr_end; ++q) xal = xal && ((a.instr[q].x_off | (a.instr[q].mul_in * D)) & 3) == 0;
+  if (two) {
+    if (xal) node_linear_wave_bf16_unit<D, F16, true, true>(pa, ch, g, xs);
+    else node_linear_wave_bf16_unit<D, F16, true, false>(pa, ch, g, xs);
+  } else {
+    if (xal) node_linear_wave_bf16_unit<D, F16, false, true>(pa, ch, g, xs);
+    else node_linear_wave_bf16_unit<D, F16, false, false>(pa, ch, g, xs);
+  }
+}
+
 template <bool F16>
-__global__ __launch_bounds__(64 * kNLWavesPerWG, 3) void node_linear_wave_bf16_kernel(const NodeLinearPackedArgs pa) {
+__global__ __launch_bounds__(64 * kNLWavesPerWG, 3) void node_linear_wave_bf16_kernel(const NodeLinearPackedArgs pa_kernarg) {
   __shared__ __align__(16) float xs_all[kNLWavesPerWG * kNLXS];
+  // the tables are read where the dispatch packet put them (see node_fused_kernel): no private copy of the struct
+  const NodeLinearPackedArgs& pa = *(const NodeLinearPackedArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   const NodeLinearArgs<float>& a = pa.base;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int unit = (int)blockIdx.x * kNLWavesPerWG + wv;
@@ -975,11 +1012,11 @@ __global__ __launch_bounds__(64 * kNLWavesPerWG, 3) void node_linear_wave_bf16_k
   const NodeChunk ch = a.chunks[pa.grp_chunk0[gi] + local % n];
   const int64_t g = (int64_t)(local / n);
   switch (ch.d) {
-    case 1: node_linear_wave_bf16_unit<1, F16>(pa, ch, g, xs); break;
-    case 3: node_linear_wave_bf16_unit<3, F16>(pa, ch, g, xs); break;
-    case 5: node_linear_wave_bf16_unit<5, F16>(pa, ch, g, xs); break;
-    case 7: node_linear_wave_bf16_unit<7, F16>(pa, ch, g, xs); break;
-    case 9: node_linear_wave_bf16_unit<9, F16>(pa, ch, g, xs); break;
+    case 1: node_linear_wave_bf16_dispatch<1, F16>(pa, ch, g, xs); break;
+    case 3: node_linear_wave_bf16_dispatch<3, F16>(pa, ch, g, xs); break;
+    case 5: node_linear_wave_bf16_dispatch<5, F16>(pa, ch, g, xs); break;
+    case 7: node_linear_wave_bf16_dispatch<7, F16>(pa, ch, g, xs); break;
+    case 9: node_linear_wave_bf16_dispatch<9, F16>(pa, ch, g, xs); break;
     default: break;
   }
 }

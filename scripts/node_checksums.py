@@ -9,7 +9,8 @@ fp16 split only).  Every map runs untyped and typed with one atom type that no a
 launches run three times: in the caller's own atom order, grouped by type, and in a fixed random permutation -- the three
 must give the same bits, and so must the two builds.  Shapes: the layer shapes of ``tests/test_node_fused.py`` (the last one
 has more merged chunks than one fused launch holds) and the 43-chunk map of ``tests/test_node_kernels.py`` (more chunks than one
-linear launch holds).  Run it once per build in separate processes and compare the lines that do not start with ``#``."""
+linear launch holds), and the stage-loop edge shapes of ``tests/test_node_stage_loop.py`` (units of 1 to 5 stages, partial K
+slabs, one and two column tiles, d = 1 .. 9, 1 / 31 / 33 / 37 atoms, with an addend, unaligned slabs).  Run it once per build in separate processes and compare the lines that do not start with ``#``."""
 import hashlib, os, sys
 tree, out_path = os.path.abspath(sys.argv[1]), sys.argv[2]
 label = sys.argv[3] if len(sys.argv) > 3 else ""
@@ -123,6 +124,31 @@ for mname, env in MODES.items():
     os.environ.update(env)
     for T, absent in ((1, None), (3, 2)):
         linear(f"{mname} 43chunks N=37", meta, 37, T, absent, g, torch.float64 if mname == "f64" else torch.float32)
+
+# the shapes of tests/test_node_stage_loop.py: units of 1, 2, 3 and 5 stages, last K slabs of 8 and 16 channels, one and two
+# column tiles, d = 1 .. 9, slabs that are not 16-byte aligned; atom groups with one row, one short of and one past a full
+# d = 1 group; with an addend (forward, untyped); typed with three weight sets of which no atom has the middle one
+EDGE_LINEAR = [("32x0e+64x1o+72x2e+144x3o+40x4e", "32x0e+64x1o+32x2e+64x3o+32x4e"), ("144x0e+32x1o+64x2e", "64x0e+32x1o+64x2e"),
+               ("72x0e+16x0e+72x1o+16x2e", "32x0e+64x1o+32x2e"), ("7x0e+13x1o+5x2e", "7x0e+13x1o+5x2e")]
+EDGE_FUSED = ["32x0e+32x1o+32x2e", "40x0e+72x1o+48x2e"]
+EDGE_ATOMS = (1, 31, 33, 37)
+g = torch.Generator().manual_seed(97)
+for mname in ("f16", "bf16"):
+    os.environ.update(MODES[mname])
+    for ir_in, ir_out in EDGE_LINEAR:
+        meta = Linear(Irreps(ir_in), Irreps(ir_out))._meta
+        for N in EDGE_ATOMS:
+            tag = f"{mname} edge {ir_in}->{ir_out} N={N}"
+            for T, absent in ((1, None), (3, 1)):
+                linear(tag, meta, N, T, absent, g, torch.float32)
+            x, wp, add = (torch.randn(*s, generator=g).to(dev) for s in ((N, meta.din), (1, meta.wstride), (N, meta.dout)))
+            rec(tag + " addend fwd", nk._launch_linear(x, wp, add, None, meta, "fwd", 0.37))
+os.environ.update(MODES["f16"])
+for hidden in EDGE_FUSED:
+    gm, m1, ms = layer(hidden)
+    for N in EDGE_ATOMS:
+        for T, absent in ((1, None), (3, 1)):
+            fused(f"f16 edge {hidden} N={N}", gm, m1, ms, N, T, absent, g)
 
 open(out_path, "w").write(f"# {label}: python scripts/node_checksums.py <tree> <out> on {torch.cuda.get_device_name(0)}\n" + "\n".join(lines) + "\n")
 print("wrote", len(lines), "checksums to", out_path, "from", _lib.LIB_PATH)
