@@ -1220,6 +1220,43 @@ int nqa_md_step(int32_t force_dtype, const void* forces, const double* masses, d
                 double* vel_out, int64_t num_atoms, const nqa_md_state* state, double* partials, int32_t mode, nqa_stream stream);
 int nqa_md_bath(const double* partials, int64_t num_partials, nqa_md_state* state, int32_t mode, nqa_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Langevin dynamics, BAOAB splitting (Leimkuhler-Matthews), on the same state: positions, velocities, masses, the nqa_md_state
+ *   record (its dt, nsteps, fresh and the two kinetic energies; g, q and xi are unused) and the parameter record below.  One MD
+ *   step is nqa_md_langevin_step followed by nqa_md_bath WITHOUT NQA_MD_THERMOSTAT on the same stream, then one force evaluation
+ *   at the new positions by the caller.  With F the force at the current positions, hdt = dt / 2:
+ * nqa_md_langevin_step: flat over the 3N components as nqa_md_step, one launch.
+ *   (1) unless state->fresh: v = v + hdt F/m, which completes the PREVIOUS step (between two steps `velocities` holds v2);
+ *   (2) B  v1 = v + hdt F/m;   A  x += hdt v1;   O  v2 = c1 v1 + (c2 sqrt(kT/m)) z;   A  x += hdt v2;   v2 written to `velocities`.
+ *   c1 = exp(-friction dt) and c2 = sqrt(1 - c1^2) are the host's, in float64 (friction = 0: c1 = 1, c2 = 0, velocity Verlet).
+ *   The noise z of component i at step s = state->nsteps (before nqa_md_bath increments it) with the 64-bit seed:
+ *     (w0, w1, w2, w3) = Philox4x32-10(counter = (i & 0xffffffff, i >> 32, s & 0xffffffff, s >> 32), key = (seed & 0xffffffff, seed >> 32))
+ *       multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85; ten rounds, the key bumped between rounds
+ *     u1 = ((w0 >> 5) * 67108864.0 + (w1 >> 6) + 1.0) * 2^-53   in (0, 1]
+ *     u2 = ((w2 >> 5) * 67108864.0 + (w3 >> 6)) * 2^-53         in [0, 1)
+ *     z  = sqrt(-2 log(u1)) * cos(6.283185307179586 * u2)       (the second Box-Muller value is dropped)
+ *   and of nothing else: not the grid, not the number of atoms, not what was read in between.
+ *   Workgroup b writes partials[2b] = sum m v^2 over the completed velocities of (1) and partials[2b + 1] = sum m v2^2, summed in
+ *   the order of nqa_md_step.
+ *   NQA_MD_FINISH_ONLY: only (1), written to `vel_out` ([N, 3], required in this mode); positions, velocities and the records are
+ *   not written, partials[2b + 1] = 0.  NQA_MD_THERMOSTAT is not a mode of this entry.
+ * nqa_md_bath (without the thermostat bit): kinetic_energy = S / 2, nsteps += 1, fresh = 0; finish-only: observed_kinetic_energy.
+ *   The record is rewritten by that second launch, so no workgroup of the step sees the incremented nsteps.  The host may rewrite
+ *   dt, c1, c2, kT and seed in place between steps; a captured pair of launches draws fresh noise at every replay.
+ * nqa_md_noise: the generator alone, through the same device function: for components 0 .. count - 1 of (seed, step) the four
+ *   Philox words (`words`, [count, 4]) and / or z (`normals`, [count]); either may be NULL, not both.
+ *   No atomics, no FMA contraction, no allocation, no host synchronisation: captures into a hipGraph.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct nqa_md_langevin_params {
+  double c1, c2, kT; /* exp(-friction dt), sqrt(1 - c1^2), kB T */
+  uint64_t seed;
+} nqa_md_langevin_params;
+
+int nqa_md_langevin_step(int32_t force_dtype, const void* forces, const double* masses, double* positions, double* velocities,
+                         double* vel_out, int64_t num_atoms, const nqa_md_state* state, const nqa_md_langevin_params* params,
+                         double* partials, int32_t mode, nqa_stream stream);
+int nqa_md_noise(uint64_t seed, uint64_t step, int64_t count, uint32_t* words, double* normals, nqa_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import POINTER, c_char_p, c_double, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_int32, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libnequip_amd.so")
@@ -402,6 +402,10 @@ SIGNATURES = {
     "nqa_md_step": (
         c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
     "nqa_md_bath": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
+    "nqa_md_langevin_step": (
+        c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
+                  c_void_p]),
+    "nqa_md_noise": (c_int32, [c_uint64, c_uint64, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 # nqa_tp_scatter_<family>_paired: the family's arguments with (weight_rows, num_pairs) before the stream

@@ -27,6 +27,9 @@
 // multiply-adds either, so that the finish of a velocity is the same arithmetic in both modes (a saved and reloaded run
 // continues bit for bit) and the steps are the ones a float64 restatement takes.
 // LDS: the eight wavefront sums of md_step_kernel.  Nothing is read by the host.
+//
+// Langevin (BAOAB) dynamics, further down, takes the same two launches: md_langevin_step_kernel, with its noise made on the
+// device from a counter-based generator, then md_bath_kernel with the thermostat off.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -127,6 +130,114 @@ __global__ __launch_bounds__(64) void md_bath_kernel(const double* __restrict__ 
 
 inline int64_t md_num_partials(int64_t num_atoms) { return (3 * num_atoms + MD_THREADS - 1) / MD_THREADS; }
 
+// ---- Langevin dynamics: BAOAB (Leimkuhler-Matthews) with one force evaluation per step ------------------------------------------
+//   B  v1 = v + dt/2 F/m;   A  x += dt/2 v1;   O  v2 = c1 v1 + (c2 sqrt(kT/m)) z;   A  x += dt/2 v2;   B  v' = v2 + dt/2 F'/m
+// with c1 = exp(-friction dt) and c2 = sqrt(1 - c1^2) from the host's parameter record and z a standard normal per component.
+// The closing B needs the next step's force and is deferred exactly as above: the velocity buffer holds v2 between two steps.
+// The noise is a pure function of (seed, step, component): Philox4x32-10 with counter (i, step) and key seed, one call per
+// component, Box-Muller on two 53-bit uniforms, the second normal dropped.  `step` is the record's nsteps, which md_bath_kernel
+// increments in the second launch (no workgroup here sees the incremented count: the hazard argument of xi), so a captured pair of
+// launches draws fresh noise at every replay.  Nothing depends on the grid: a run of N atoms and the noise entry draw the same z.
+static_assert(sizeof(nqa_md_langevin_params) == 32, "the host writes the parameters as four 8-byte words");
+
+constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
+
+// Philox4x32-10 (Salmon et al., Random123): counter (i lo, i hi, step lo, step hi), key (seed lo, seed hi)
+__device__ __forceinline__ void md_philox(uint64_t seed, uint64_t step, uint64_t i, uint32_t w[4]) {
+  uint32_t c0 = (uint32_t)i, c1 = (uint32_t)(i >> 32), c2 = (uint32_t)step, c3 = (uint32_t)(step >> 32);
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
+    const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += PHILOX_W0;
+    k1 += PHILOX_W1;
+  }
+  w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
+}
+
+// u1 in (0, 1] and u2 in [0, 1) from 53 bits each (every operation up to the product with 2 pi is exact), then Box-Muller
+__device__ __forceinline__ double md_normal(const uint32_t w[4]) {
+  const double u1 = ((double)(w[0] >> 5) * 67108864.0 + (double)(w[1] >> 6) + 1.0) * 0x1p-53;
+  const double u2 = ((double)(w[2] >> 5) * 67108864.0 + (double)(w[3] >> 6)) * 0x1p-53;
+  return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+// The layout, the partial rows and the order of every sum are md_step_kernel's.  partials[2b] = sum m v^2 over the completed
+// velocities, partials[2b + 1] = sum m v2^2 (0 in the finish-only mode); md_bath_kernel without the thermostat bit reads only
+// the first.
+template <typename F>
+__global__ __launch_bounds__(MD_THREADS) void md_langevin_step_kernel(
+    const F* __restrict__ forces, const double* __restrict__ masses, double* __restrict__ positions,
+    double* __restrict__ velocities, double* __restrict__ vel_out, int64_t n3, const nqa_md_state* __restrict__ state,
+    const nqa_md_langevin_params* __restrict__ params, double* __restrict__ partials, int finish_only) {
+  __shared__ double waves[MD_WAVES][2];
+  const int64_t i = (int64_t)blockIdx.x * MD_THREADS + threadIdx.x;
+  const double dt = state->dt;
+  const bool fresh = state->fresh != 0;
+  const uint64_t step = (uint64_t)state->nsteps;
+  const double hdt = 0.5 * dt;
+  double s_full = 0.0, s_half = 0.0;
+  if (i < n3) {
+    const double m = masses[i / 3];
+    const double fm = (double)forces[i] / m;
+    double v = velocities[i];
+    if (!fresh) v = v + hdt * fm;
+    s_full = m * v * v;
+    if (finish_only) {
+      vel_out[i] = v;
+    } else {
+      const double c1 = params->c1, c2 = params->c2, kT = params->kT;
+      uint32_t w[4];
+      md_philox(params->seed, step, (uint64_t)i, w);
+      const double z = md_normal(w);
+      const double v1 = v + hdt * fm;
+      double x = positions[i] + hdt * v1;
+      const double v2 = c1 * v1 + (c2 * sqrt(kT / m)) * z;
+      x = x + hdt * v2;
+      positions[i] = x;
+      velocities[i] = v2;
+      s_half = m * v2 * v2;
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  s_full = md_wave_sum(s_full);
+  s_half = md_wave_sum(s_half);
+  if (lane == 0) {
+    waves[wave][0] = s_full;
+    waves[wave][1] = s_half;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = waves[0][0], b = waves[0][1];
+#pragma unroll
+    for (int k = 1; k < MD_WAVES; ++k) {
+      a += waves[k][0];
+      b += waves[k][1];
+    }
+    partials[2 * (int64_t)blockIdx.x] = a;
+    partials[2 * (int64_t)blockIdx.x + 1] = b;
+  }
+}
+
+// the generator on its own: the Philox words and / or the normal of components 0 .. count - 1
+__global__ __launch_bounds__(MD_THREADS) void md_noise_kernel(uint64_t seed, uint64_t step, int64_t count,
+                                                               uint32_t* __restrict__ words, double* __restrict__ normals) {
+  const int64_t i = (int64_t)blockIdx.x * MD_THREADS + threadIdx.x;
+  if (i >= count) return;
+  uint32_t w[4];
+  md_philox(seed, step, (uint64_t)i, w);
+  if (words) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) words[4 * i + k] = w[k];
+  }
+  if (normals) normals[i] = md_normal(w);
+}
+
 }  // namespace nqa
 
 extern "C" {
@@ -176,6 +287,58 @@ int nqa_md_bath(const double* partials, int64_t num_partials, nqa_md_state* stat
   }
   hipLaunchKernelGGL(md_bath_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), partials, num_partials, state,
                      (int)((mode & NQA_MD_FINISH_ONLY) != 0), (int)((mode & NQA_MD_THERMOSTAT) != 0));
+  return launch_status(name);
+}
+
+int nqa_md_langevin_step(int32_t force_dtype, const void* forces, const double* masses, double* positions, double* velocities,
+                         double* vel_out, int64_t num_atoms, const nqa_md_state* state, const nqa_md_langevin_params* params,
+                         double* partials, int32_t mode, nqa_stream stream) {
+  using namespace nqa;
+  const char* name = "nqa_md_langevin_step";
+  const bool finish_only = (mode & NQA_MD_FINISH_ONLY) != 0;
+  if (num_atoms <= 0 || num_atoms > INT32_MAX) {
+    set_error(std::string(name) + ": 0 < num_atoms < 2^31");
+    return NQA_ERR_INVALID;
+  }
+  if (force_dtype != NQA_F32 && force_dtype != NQA_F64) {
+    set_error(std::string(name) + ": forces are float32 or float64");
+    return NQA_ERR_UNSUPPORTED;
+  }
+  if ((mode & ~NQA_MD_FINISH_ONLY) != 0) {
+    set_error(std::string(name) + ": unknown mode bits (the thermostat bit belongs to nqa_md_step)");
+    return NQA_ERR_INVALID;
+  }
+  if (!forces || !masses || !velocities || !state || !params || !partials || (finish_only ? !vel_out : !positions)) {
+    set_error(std::string(name) + ": forces, masses, velocities, state, params and partials are required, and positions (or, in "
+                                  "the finish-only mode, the output buffer)");
+    return NQA_ERR_INVALID;
+  }
+  const int64_t n3 = 3 * num_atoms;
+  const dim3 grid((unsigned)md_num_partials(num_atoms));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (force_dtype == NQA_F64)
+    hipLaunchKernelGGL(md_langevin_step_kernel<double>, grid, dim3(MD_THREADS), 0, s, (const double*)forces, masses, positions,
+                       velocities, vel_out, n3, state, params, partials, (int)finish_only);
+  else
+    hipLaunchKernelGGL(md_langevin_step_kernel<float>, grid, dim3(MD_THREADS), 0, s, (const float*)forces, masses, positions,
+                       velocities, vel_out, n3, state, params, partials, (int)finish_only);
+  return launch_status(name);
+}
+
+int nqa_md_noise(uint64_t seed, uint64_t step, int64_t count, uint32_t* words, double* normals, nqa_stream stream) {
+  using namespace nqa;
+  const char* name = "nqa_md_noise";
+  if (count <= 0 || count > 3 * (int64_t)INT32_MAX) {
+    set_error(std::string(name) + ": 0 < count <= 3 (2^31 - 1), the components of nqa_md_langevin_step");
+    return NQA_ERR_INVALID;
+  }
+  if (!words && !normals) {
+    set_error(std::string(name) + ": words or normals (or both) are required");
+    return NQA_ERR_INVALID;
+  }
+  const dim3 grid((unsigned)((count + MD_THREADS - 1) / MD_THREADS));
+  hipLaunchKernelGGL(md_noise_kernel, grid, dim3(MD_THREADS), 0, static_cast<hipStream_t>(stream), seed, step, count, words,
+                     normals);
   return launch_status(name);
 }
 

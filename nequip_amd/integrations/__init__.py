@@ -1,3 +1,3 @@
-from .md import NoseHoover, VelocityVerlet, maxwell_boltzmann_velocities, units
+from .md import Langevin, NoseHoover, VelocityVerlet, langevin_noise, maxwell_boltzmann_velocities, units
 
-__all__ = ["NoseHoover", "VelocityVerlet", "maxwell_boltzmann_velocities", "units"]
+__all__ = ["Langevin", "NoseHoover", "VelocityVerlet", "langevin_noise", "maxwell_boltzmann_velocities", "units"]

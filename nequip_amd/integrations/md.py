@@ -23,6 +23,11 @@ Units are ASE's (eV, Angstrom, amu; time in ``units.fs``), so the model must giv
 into the cell, as in the reference: the device neighbour list wraps internally.
 
 CPU tensors (and ``backend="aten"``) take an ATen form of the same equations, for any callable ``force_step``.
+
+``Langevin`` is the stochastic NVT ensemble on the same state and the same two-launch step (``nqa_md_langevin_step`` +
+``nqa_md_bath``): BAOAB with its noise made on the device by a counter-based generator, a function of (seed, step count,
+component) alone (``langevin_noise``), so that a run is reproducible bit for bit, survives a checkpoint and captures into a
+hipGraph.  Not provided: NPT, a centre-of-mass constraint during the run, an ``ase.md.MolecularDynamics`` subclass.
 """
 
 from __future__ import annotations
@@ -97,23 +102,12 @@ def _graphed_step_for(atoms, model, device, r_max, chemical_symbols):
     return GraphedStep(model, torch.as_tensor(types).to(device), torch.as_tensor(cell).to(device), pbc, float(r_max))
 
 
-class NoseHoover:
-    """Nose-Hoover NVT dynamics of a fixed set of atoms, state on the device of ``positions``.
+class _DeviceMD:
+    """What the drivers share: the checks of the constructor's arguments, the buffers, the force evaluation and the interface.
+    A driver adds its record (``_write_state``), the two forms of its step (``_launch``, ``_aten_finished`` + ``_aten_step``)
+    and its checkpoints."""
 
-    ``force_step``: a ``GraphedStep`` or any callable ``pos [N, 3] -> {"forces": [N, 3], "total_energy": ...}`` (float32 or
-    float64 forces, eV/Angstrom; all tensors on the device of ``positions``).  ``masses`` ``[N]`` in amu, ``timestep`` in ASE's
-    time unit (``0.5 * units.fs``), ``temperature`` in K, ``nvt_q`` the bath's inertia ``Q``.  ``velocities`` default to zero.
-    ``remove_drift``: once, here, centre-of-mass momentum and angular momentum are set to zero (the reference does this in its
-    constructor).  ``thermostat=False``: the bath variable stays 0, i.e. velocity Verlet.
-    ``backend``: ``"hip"`` (the kernels; the default on the GPU), ``"aten"`` (the default on the CPU).
-
-    ``positions`` and ``forces`` are the live tensors (``forces`` is what ``force_step`` returned last: a ``GraphedStep``
-    overwrites it at the next step).  ``velocities`` are the completed ``v(t)`` in a buffer that the next read overwrites.
-    The scalar properties copy one value to the host; ``step`` and ``run`` read nothing themselves."""
-
-    def __init__(self, force_step: Callable[[torch.Tensor], Dict[str, torch.Tensor]], masses: torch.Tensor, timestep: float,
-                 temperature: float, nvt_q: float, positions: torch.Tensor, velocities: Optional[torch.Tensor] = None,
-                 thermostat: bool = True, remove_drift: bool = True, backend: str = "auto"):
+    def _check_system(self, force_step, masses, positions, velocities, timestep) -> None:
         if not callable(force_step):
             raise TypeError("force_step must be callable: positions [N, 3] -> {'forces', 'total_energy'}")
         if not (isinstance(masses, torch.Tensor) and isinstance(positions, torch.Tensor)):
@@ -138,8 +132,10 @@ class NoseHoover:
             raise ValueError("masses must be positive and finite")
         if not (timestep > 0.0 and math.isfinite(timestep)):
             raise ValueError("timestep must be positive")
-        if thermostat and not (nvt_q > 0.0 and temperature >= 0.0):
-            raise ValueError("the thermostat needs nvt_q > 0 and temperature >= 0")
+
+    def _setup(self, force_step, masses, positions, velocities, remove_drift, backend) -> None:
+        """The backend, the buffers and, on the kernel path, the partial sums and the ``nqa_md_state`` record."""
+        device, n = positions.device, int(positions.shape[0])
         if backend not in ("auto", "hip", "aten"):
             raise ValueError(f"backend must be 'auto', 'hip' or 'aten', got {backend!r}")
         if backend == "hip" and device.type != "cuda":
@@ -148,16 +144,13 @@ class NoseHoover:
         self.force_step = force_step
         self.device = device
         self.num_atoms = n
-        self.thermostat = bool(thermostat)
         self._m = masses.detach().to(torch.float64).contiguous().clone()
         self._pos = positions.detach().to(torch.float64).contiguous().clone()
         vel = torch.zeros_like(self._pos) if velocities is None else velocities.detach().to(torch.float64)
         if remove_drift:
             vel = _remove_drift(self._pos, vel, self._m)
-        self._vel = vel.contiguous().clone()  # v(t) while `fresh`, v_half between two steps
+        self._vel = vel.contiguous().clone()  # v(t) while `fresh`, the half-step velocities between two steps
         self._vel_out = torch.empty_like(self._vel)
-        self._temperature = float(temperature)
-        self._dt, self._q = float(timestep), float(nvt_q)
         self._out: Dict[str, torch.Tensor] = {}
         self._forces: Optional[torch.Tensor] = None
         if self._hip:
@@ -170,12 +163,141 @@ class NoseHoover:
             self._partials_observed = torch.zeros_like(self._partials)
             self._rec = torch.zeros(8, dtype=torch.float64, device=device)
             self._rec_i = self._rec.view(torch.int64)
-            self._mode = _MD_THERMOSTAT if self.thermostat else 0
         else:
-            self._xi = torch.zeros((), dtype=torch.float64, device=device)
             self._ekin = torch.zeros((), dtype=torch.float64, device=device)
             self._fresh = True
             self._nsteps = 0
+
+    def _evaluate(self) -> None:
+        out = self.force_step(self._pos)
+        f = out[AtomicDataDict.FORCE_KEY].detach()
+        if tuple(f.shape) != (self.num_atoms, 3) or f.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"force_step must return float32 or float64 forces [{self.num_atoms}, 3], got {f.dtype} "
+                             f"{tuple(f.shape)}")
+        if f.device != self.device:
+            raise ValueError(f"mixed devices: positions on {self.device}, forces on {f.device}")
+        self._out, self._forces = out, f.contiguous()
+
+    def set_timestep(self, timestep: float) -> None:
+        """The time step from the next step on.  The step that is under way is completed with the step it began with."""
+        if not (timestep > 0.0 and math.isfinite(timestep)):
+            raise ValueError("timestep must be positive")
+        self._vel.copy_(self.velocities)
+        self._dt = float(timestep)
+        if self._hip:
+            self._rec_i[_FRESH:_FRESH + 1].fill_(1)
+            self._rec[_DT:_DT + 1].fill_(self._dt)
+        else:
+            self._fresh = True
+
+    # ---- interface ----------------------------------------------------------------------------------------------------------
+    def step(self) -> None:
+        """One MD step: two launches, then one force evaluation at the new positions."""
+        if self._hip:
+            self._launch(finish_only=False)
+        else:
+            self._aten_step()
+        self._evaluate()
+
+    def run(self, n: int) -> None:
+        for _ in range(int(n)):
+            self.step()
+
+    @property
+    def positions(self) -> torch.Tensor:
+        return self._pos
+
+    @property
+    def forces(self) -> torch.Tensor:
+        return self._forces
+
+    @property
+    def masses(self) -> torch.Tensor:
+        return self._m
+
+    @property
+    def velocities(self) -> torch.Tensor:
+        """The completed velocities ``v(t)`` at the current positions; leaves the trajectory alone."""
+        if self._hip:
+            self._launch(finish_only=True, bath=False)
+        else:
+            self._vel_out.copy_(self._aten_finished())
+        return self._vel_out
+
+    @property
+    def kinetic_energy(self) -> float:
+        """``1/2 sum m v(t)^2`` of the completed velocities at the current positions (eV)."""
+        if self._hip:
+            self._launch(finish_only=True)
+            return float(self._rec[_EKIN_OBSERVED])
+        v = self._aten_finished()
+        return float(0.5 * (self._m[:, None] * v * v).sum())
+
+    @property
+    def temperature(self) -> float:
+        return 2.0 * self.kinetic_energy / (3 * self.num_atoms * units.kB)
+
+    @property
+    def potential_energy(self) -> float:
+        return float(self._out[AtomicDataDict.TOTAL_ENERGY_KEY].detach().reshape(-1)[0])
+
+    @property
+    def nsteps(self) -> int:
+        return int(self._rec_i[_NSTEPS]) if self._hip else self._nsteps
+
+    # ---- Atoms --------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_atoms(cls, atoms, model_or_step, *args, device="cuda", r_max: Optional[float] = None, chemical_symbols=None,
+                   **kwargs):
+        """The driver for an ``Atoms`` object (positions, velocities, masses, cell, periodicity, species); ``args`` and
+        ``kwargs`` are the constructor's between ``masses`` and ``positions`` (``timestep, temperature, nvt_q``, or ``friction``
+        for ``Langevin``) and after ``velocities``.  ``model_or_step``: an eval-mode model (``torch.nn.Module`` with ``type_names``; a ``GraphedStep`` is
+        built around it, which needs a periodic cell and ``r_max``) or a ready ``force_step``.  ``chemical_symbols``: as for
+        ``NequIPCalculator``."""
+        device = torch.device(device)
+        pos = torch.as_tensor(np.asarray(atoms.get_positions(), dtype=np.float64)).to(device)
+        vel = atoms.get_velocities()
+        vel = None if vel is None else torch.as_tensor(np.asarray(vel, dtype=np.float64)).to(device)
+        masses = torch.as_tensor(np.asarray(atoms.get_masses(), dtype=np.float64)).to(device)
+        step = model_or_step
+        if isinstance(model_or_step, torch.nn.Module):
+            step = _graphed_step_for(atoms, model_or_step, device, r_max, chemical_symbols)
+        return cls(step, masses, *args, positions=pos, velocities=vel, **kwargs)
+
+    def write_back(self, atoms) -> None:
+        """Positions and completed velocities into ``atoms`` (one copy each)."""
+        atoms.set_positions(self._pos.detach().cpu().numpy())
+        atoms.set_velocities(self.velocities.detach().cpu().numpy())
+
+
+class NoseHoover(_DeviceMD):
+    """Nose-Hoover NVT dynamics of a fixed set of atoms, state on the device of ``positions``.
+
+    ``force_step``: a ``GraphedStep`` or any callable ``pos [N, 3] -> {"forces": [N, 3], "total_energy": ...}`` (float32 or
+    float64 forces, eV/Angstrom; all tensors on the device of ``positions``).  ``masses`` ``[N]`` in amu, ``timestep`` in ASE's
+    time unit (``0.5 * units.fs``), ``temperature`` in K, ``nvt_q`` the bath's inertia ``Q``.  ``velocities`` default to zero.
+    ``remove_drift``: once, here, centre-of-mass momentum and angular momentum are set to zero (the reference does this in its
+    constructor).  ``thermostat=False``: the bath variable stays 0, i.e. velocity Verlet.
+    ``backend``: ``"hip"`` (the kernels; the default on the GPU), ``"aten"`` (the default on the CPU).
+
+    ``positions`` and ``forces`` are the live tensors (``forces`` is what ``force_step`` returned last: a ``GraphedStep``
+    overwrites it at the next step).  ``velocities`` are the completed ``v(t)`` in a buffer that the next read overwrites.
+    The scalar properties copy one value to the host; ``step`` and ``run`` read nothing themselves."""
+
+    def __init__(self, force_step: Callable[[torch.Tensor], Dict[str, torch.Tensor]], masses: torch.Tensor, timestep: float,
+                 temperature: float, nvt_q: float, positions: torch.Tensor, velocities: Optional[torch.Tensor] = None,
+                 thermostat: bool = True, remove_drift: bool = True, backend: str = "auto"):
+        self._check_system(force_step, masses, positions, velocities, timestep)
+        if thermostat and not (nvt_q > 0.0 and temperature >= 0.0):
+            raise ValueError("the thermostat needs nvt_q > 0 and temperature >= 0")
+        self.thermostat = bool(thermostat)
+        self._temperature = float(temperature)
+        self._dt, self._q = float(timestep), float(nvt_q)
+        self._setup(force_step, masses, positions, velocities, remove_drift, backend)
+        if self._hip:
+            self._mode = _MD_THERMOSTAT if self.thermostat else 0
+        else:
+            self._xi = torch.zeros((), dtype=torch.float64, device=self.device)
         self._write_state(xi=0.0, nsteps=0)
         self._evaluate()
 
@@ -194,33 +316,11 @@ class NoseHoover:
             self._xi.fill_(float(xi))
             self._fresh, self._nsteps = True, int(nsteps)
 
-    def _evaluate(self) -> None:
-        out = self.force_step(self._pos)
-        f = out[AtomicDataDict.FORCE_KEY].detach()
-        if tuple(f.shape) != (self.num_atoms, 3) or f.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"force_step must return float32 or float64 forces [{self.num_atoms}, 3], got {f.dtype} "
-                             f"{tuple(f.shape)}")
-        if f.device != self.device:
-            raise ValueError(f"mixed devices: positions on {self.device}, forces on {f.device}")
-        self._out, self._forces = out, f.contiguous()
-
     def set_temperature(self, temperature: float) -> None:
         """The bath's target from the next step on; written in place, nothing is read back."""
         self._temperature = float(temperature)
         if self._hip:
             self._rec[_G:_G + 1].fill_(self._g())
-
-    def set_timestep(self, timestep: float) -> None:
-        """The time step from the next step on.  The step that is under way is completed with the step it began with."""
-        if not (timestep > 0.0 and math.isfinite(timestep)):
-            raise ValueError("timestep must be positive")
-        self._vel.copy_(self.velocities)
-        self._dt = float(timestep)
-        if self._hip:
-            self._rec_i[_FRESH:_FRESH + 1].fill_(1)
-            self._rec[_DT:_DT + 1].fill_(self._dt)
-        else:
-            self._fresh = True
 
     # ---- the two forms of a step --------------------------------------------------------------------------------------------
     def _launch(self, finish_only: bool, bath: bool = True) -> None:
@@ -258,64 +358,9 @@ class NoseHoover:
         self._fresh = False
         self._nsteps += 1
 
-    # ---- interface ----------------------------------------------------------------------------------------------------------
-    def step(self) -> None:
-        """One MD step: two launches, then one force evaluation at the new positions."""
-        if self._hip:
-            self._launch(finish_only=False)
-        else:
-            self._aten_step()
-        self._evaluate()
-
-    def run(self, n: int) -> None:
-        for _ in range(int(n)):
-            self.step()
-
-    @property
-    def positions(self) -> torch.Tensor:
-        return self._pos
-
-    @property
-    def forces(self) -> torch.Tensor:
-        return self._forces
-
-    @property
-    def masses(self) -> torch.Tensor:
-        return self._m
-
-    @property
-    def velocities(self) -> torch.Tensor:
-        """The completed velocities ``v(t)`` at the current positions; leaves the trajectory alone."""
-        if self._hip:
-            self._launch(finish_only=True, bath=False)
-        else:
-            self._vel_out.copy_(self._aten_finished())
-        return self._vel_out
-
     @property
     def nvt_bath(self) -> float:
         return float(self._rec[_XI]) if self._hip else float(self._xi)
-
-    @property
-    def kinetic_energy(self) -> float:
-        """``1/2 sum m v(t)^2`` of the completed velocities at the current positions (eV)."""
-        if self._hip:
-            self._launch(finish_only=True)
-            return float(self._rec[_EKIN_OBSERVED])
-        v = self._aten_finished()
-        return float(0.5 * (self._m[:, None] * v * v).sum())
-
-    @property
-    def temperature(self) -> float:
-        return 2.0 * self.kinetic_energy / (3 * self.num_atoms * units.kB)
-
-    @property
-    def potential_energy(self) -> float:
-        return float(self._out[AtomicDataDict.TOTAL_ENERGY_KEY].detach().reshape(-1)[0])
-
-    @property
-    def nsteps(self) -> int:
-        return int(self._rec_i[_NSTEPS]) if self._hip else self._nsteps
 
     # ---- checkpoints --------------------------------------------------------------------------------------------------------
     def state_dict(self) -> Dict[str, object]:
@@ -328,6 +373,8 @@ class NoseHoover:
         if tuple(pos.shape) != (self.num_atoms, 3) or tuple(vel.shape) != (self.num_atoms, 3):
             raise ValueError(f"the state holds {tuple(pos.shape)} positions and {tuple(vel.shape)} velocities, this run has "
                              f"{self.num_atoms} atoms")
+        if "nvt_bath" not in state or "friction" in state:
+            raise ValueError("the state was not saved by a Nose-Hoover / velocity-Verlet run (a Langevin state has no nvt_bath)")
         if bool(state["thermostat"]) != self.thermostat:
             raise ValueError("the state was saved with the thermostat " + ("on" if state["thermostat"] else "off"))
         self._pos.copy_(pos)
@@ -335,30 +382,6 @@ class NoseHoover:
         self._dt, self._temperature, self._q = float(state["timestep"]), float(state["temperature"]), float(state["nvt_q"])
         self._write_state(xi=float(state["nvt_bath"]), nsteps=int(state["nsteps"]))
         self._evaluate()
-
-    # ---- Atoms --------------------------------------------------------------------------------------------------------------
-    @classmethod
-    def from_atoms(cls, atoms, model_or_step, *args, device="cuda", r_max: Optional[float] = None, chemical_symbols=None,
-                   **kwargs):
-        """The driver for an ``Atoms`` object (positions, velocities, masses, cell, periodicity, species); ``args`` and
-        ``kwargs`` are the constructor's between ``masses`` and ``positions`` (``timestep, temperature, nvt_q``) and after
-        ``velocities``.  ``model_or_step``: an eval-mode model (``torch.nn.Module`` with ``type_names``; a ``GraphedStep`` is
-        built around it, which needs a periodic cell and ``r_max``) or a ready ``force_step``.  ``chemical_symbols``: as for
-        ``NequIPCalculator``."""
-        device = torch.device(device)
-        pos = torch.as_tensor(np.asarray(atoms.get_positions(), dtype=np.float64)).to(device)
-        vel = atoms.get_velocities()
-        vel = None if vel is None else torch.as_tensor(np.asarray(vel, dtype=np.float64)).to(device)
-        masses = torch.as_tensor(np.asarray(atoms.get_masses(), dtype=np.float64)).to(device)
-        step = model_or_step
-        if isinstance(model_or_step, torch.nn.Module):
-            step = _graphed_step_for(atoms, model_or_step, device, r_max, chemical_symbols)
-        return cls(step, masses, *args, positions=pos, velocities=vel, **kwargs)
-
-    def write_back(self, atoms) -> None:
-        """Positions and completed velocities into ``atoms`` (one copy each)."""
-        atoms.set_positions(self._pos.detach().cpu().numpy())
-        atoms.set_velocities(self.velocities.detach().cpu().numpy())
 
 
 class VelocityVerlet(NoseHoover):
@@ -368,3 +391,221 @@ class VelocityVerlet(NoseHoover):
                  velocities: Optional[torch.Tensor] = None, remove_drift: bool = True, backend: str = "auto"):
         super().__init__(force_step, masses, timestep, 0.0, 1.0, positions, velocities, thermostat=False,
                          remove_drift=remove_drift, backend=backend)
+
+
+# ---- Langevin dynamics ---------------------------------------------------------------------------------------------------------
+# the 8-byte words of nqa_md_langevin_params (include/nequip_amd.h)
+_C1, _C2, _KT, _SEED = range(4)
+_M32 = 0xFFFFFFFF
+
+
+def _check_u64(name: str, value) -> int:
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not (0 <= int(value) < 2 ** 64):
+        raise ValueError(f"{name} must be an integer in [0, 2^64), got {value!r}")
+    return int(value)
+
+
+def _philox_numpy(seed: int, step: int, count: int) -> np.ndarray:
+    """Philox4x32-10 in uint64 arithmetic (a product of two 32-bit words fits): the words ``[count, 4]`` of components
+    ``0 .. count - 1`` at ``step``, counter ``(i lo, i hi, step lo, step hi)``, key ``(seed lo, seed hi)``."""
+    u = np.uint64
+    mask, s32 = u(_M32), u(32)
+    i = np.arange(count, dtype=np.uint64)
+    c0, c1 = i & mask, i >> s32
+    c2, c3 = np.full(count, step & _M32, dtype=np.uint64), np.full(count, step >> 32, dtype=np.uint64)
+    k0, k1 = seed & _M32, seed >> 32
+    for _ in range(10):
+        p0, p1 = u(0xD2511F53) * c0, u(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ u(k0), p1 & mask, (p0 >> s32) ^ c3 ^ u(k1), p0 & mask
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return np.stack([c0, c1, c2, c3], axis=1)
+
+
+def _normals_numpy(words: np.ndarray) -> np.ndarray:
+    """Box-Muller on two 53-bit uniforms, ``u1`` in (0, 1] and ``u2`` in [0, 1); the second normal is dropped."""
+    w = [(words[:, k] >> np.uint64(5 + k % 2)).astype(np.float64) for k in range(4)]
+    u1 = (w[0] * 67108864.0 + w[1] + 1.0) * 2.0 ** -53
+    u2 = (w[2] * 67108864.0 + w[3]) * 2.0 ** -53
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)
+
+
+def langevin_noise(seed: int, step: int, count: int, device="cpu", *, backend: str = "auto", return_words: bool = False):
+    """The standard normals ``[count]`` (float64, on ``device``) that ``Langevin`` with ``seed`` draws at step ``step`` for the
+    flat components ``0 .. count - 1`` (component ``i`` of atom ``i // 3``), a function of these three numbers alone::
+
+        (w0, w1, w2, w3) = philox4x32_10(counter=(i & 0xffffffff, i >> 32, step & 0xffffffff, step >> 32),
+                                         key=(seed & 0xffffffff, seed >> 32))
+        u1 = ((w0 >> 5) * 2^26 + (w1 >> 6) + 1) * 2^-53;  u2 = ((w2 >> 5) * 2^26 + (w3 >> 6)) * 2^-53
+        z  = sqrt(-2 log(u1)) * cos(6.283185307179586 * u2)
+
+    ``backend``: ``"hip"`` (``nqa_md_noise``, the default on the GPU) or ``"aten"`` (numpy ``uint64`` on the host, uploaded).
+    The Philox words of the two are the same bits; the normals differ by the ``log`` and ``cos`` of the two libraries, a few
+    ulp.  ``return_words``: also the words, ``[count, 4]`` int64 with values below 2^32."""
+    seed, step = _check_u64("seed", seed), _check_u64("step", step)
+    count, device = int(count), torch.device(device)
+    if count < 0:
+        raise ValueError(f"count must not be negative, got {count}")
+    if backend not in ("auto", "hip", "aten"):
+        raise ValueError(f"backend must be 'auto', 'hip' or 'aten', got {backend!r}")
+    if backend == "hip" and device.type != "cuda":
+        raise ValueError("backend='hip' needs a GPU device: the kernel runs there")
+    if count > 0 and (backend == "hip" or (backend == "auto" and device.type == "cuda")):
+        from .. import _lib as L
+
+        z = torch.empty(count, dtype=torch.float64, device=device)
+        w = torch.empty(count, 4, dtype=torch.int32, device=device) if return_words else None
+        with torch.cuda.device(device):
+            L.check(L.load().nqa_md_noise(seed, step, count, L.ptr(w), L.ptr(z), L.stream_ptr(device)), "nqa_md_noise")
+        return (z, w.to(torch.int64) & _M32) if return_words else z
+    words = _philox_numpy(seed, step, count)
+    z = torch.from_numpy(_normals_numpy(words)).to(device)
+    return (z, torch.from_numpy(words.astype(np.int64)).to(device)) if return_words else z
+
+
+class Langevin(_DeviceMD):
+    """Langevin NVT dynamics of a fixed set of atoms, state on the device of ``positions``: the BAOAB splitting of Leimkuhler
+    and Matthews with one force evaluation per step.  With ``F`` the force at the start of the step, ``F'`` the one at the new
+    positions and ``hdt = dt / 2``::
+
+        B   v1 = v + hdt F/m
+        A   x  = x + hdt v1
+        O   v2 = c1 v1 + (c2 sqrt(kB T / m)) z      c1 = exp(-friction dt),  c2 = sqrt(1 - c1^2),  z ~ N(0, 1) per component
+        A   x  = x + hdt v2
+        B   v' = v2 + hdt F'/m
+
+    The last line is carried out by the launch of the next step, as in ``NoseHoover``.  The noise is made on the device and is a
+    function of ``(seed, step count, component)`` alone (``langevin_noise``): the same seed gives the same trajectory bit for
+    bit, whatever is read in between, a reloaded ``state_dict`` continues bit for bit, and a captured pair of launches draws
+    fresh noise at every replay, since the step count lives in the device record.
+
+    ``force_step``, ``masses``, ``timestep``, ``temperature``, ``positions``, ``velocities``, ``backend`` and the properties: as
+    for ``NoseHoover``.  ``friction`` in 1/time (``0.01 / units.fs``); ``friction=0`` is velocity Verlet.  ``seed``: an integer
+    in [0, 2^64).  ``remove_drift``: once, here, centre-of-mass momentum and angular momentum are set to zero.  The centre of
+    mass is NOT held fixed during the run (ASE's ``fixcm``): the noise moves it like any other degree of freedom."""
+
+    def __init__(self, force_step: Callable[[torch.Tensor], Dict[str, torch.Tensor]], masses: torch.Tensor, timestep: float,
+                 temperature: float, friction: float, positions: torch.Tensor, velocities: Optional[torch.Tensor] = None,
+                 seed: int = 0, remove_drift: bool = False, backend: str = "auto"):
+        self._check_system(force_step, masses, positions, velocities, timestep)
+        self._check_temperature(temperature)
+        self._check_friction(friction)
+        self.seed = _check_u64("seed", seed)
+        self.friction = float(friction)
+        self._temperature = float(temperature)
+        self._dt = float(timestep)
+        self._setup(force_step, masses, positions, velocities, remove_drift, backend)
+        if self._hip:
+            self._par = torch.zeros(4, dtype=torch.float64, device=self.device)
+            self._par_i = self._par.view(torch.int64)
+        self._write_state(nsteps=0)
+        self._evaluate()
+
+    # ---- state -------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_temperature(temperature) -> None:
+        if not (temperature >= 0.0 and math.isfinite(temperature)):
+            raise ValueError(f"temperature must be non-negative and finite, got {temperature!r}")
+
+    @staticmethod
+    def _check_friction(friction) -> None:
+        if not (friction >= 0.0 and math.isfinite(friction)):
+            raise ValueError(f"friction must be non-negative and finite, got {friction!r}")
+
+    def _coefficients(self):
+        """``c1`` and ``c2`` in the host's float64: the bits a restatement with ``math.exp`` and ``math.sqrt`` holds."""
+        c1 = math.exp(-self.friction * self._dt)
+        return c1, math.sqrt(1.0 - c1 * c1)
+
+    def _write_params(self) -> None:
+        self._c1, self._c2 = self._coefficients()
+        self._kt = units.kB * self._temperature
+        if self._hip:
+            self._par[_C1:_C1 + 1].fill_(self._c1)
+            self._par[_C2:_C2 + 1].fill_(self._c2)
+            self._par[_KT:_KT + 1].fill_(self._kt)
+            self._par_i[_SEED:_SEED + 1].fill_(self.seed - 2 ** 64 if self.seed >= 2 ** 63 else self.seed)  # (the same 64 bits)
+
+    def _write_state(self, nsteps: int) -> None:
+        """Both records, with ``velocities`` taken as completed."""
+        if self._hip:
+            words = torch.zeros(8, dtype=torch.float64)
+            words[_DT] = self._dt
+            words.view(torch.int64)[_NSTEPS] = int(nsteps)
+            words.view(torch.int64)[_FRESH] = 1
+            self._rec.copy_(words)
+        else:
+            self._fresh, self._nsteps = True, int(nsteps)
+        self._write_params()
+
+    def set_temperature(self, temperature: float) -> None:
+        """The target from the next step on; ``kB T`` is written in place, nothing is read back."""
+        self._check_temperature(temperature)
+        self._temperature = float(temperature)
+        self._write_params()
+
+    def set_friction(self, friction: float) -> None:
+        """The friction (1/time) from the next step on; ``c1`` and ``c2`` are written in place."""
+        self._check_friction(friction)
+        self.friction = float(friction)
+        self._write_params()
+
+    def set_timestep(self, timestep: float) -> None:
+        """The time step from the next step on, ``c1`` and ``c2`` with it.  The step that is under way is completed with the
+        step it began with."""
+        super().set_timestep(timestep)
+        self._write_params()
+
+    # ---- the two forms of a step --------------------------------------------------------------------------------------------
+    def _launch(self, finish_only: bool, bath: bool = True) -> None:
+        lib, L = self._lib.load(), self._lib
+        f = self._forces
+        mode = _MD_FINISH_ONLY if finish_only else 0
+        partials = self._partials_observed if finish_only else self._partials
+        stream = L.stream_ptr(self.device)
+        L.check(lib.nqa_md_langevin_step(L.NQA_F64 if f.dtype == torch.float64 else L.NQA_F32, L.ptr(f), L.ptr(self._m),
+                                         L.ptr(self._pos), L.ptr(self._vel), L.ptr(self._vel_out), self.num_atoms,
+                                         L.ptr(self._rec), L.ptr(self._par), L.ptr(partials), mode, stream),
+                "nqa_md_langevin_step")
+        if bath:
+            L.check(lib.nqa_md_bath(L.ptr(partials), self._n_partials, L.ptr(self._rec), mode, stream), "nqa_md_bath")
+
+    def _aten_finished(self) -> torch.Tensor:
+        if self._fresh:
+            return self._vel
+        hdt = 0.5 * self._dt
+        fm = self._forces.to(torch.float64) / self._m[:, None]
+        return self._vel + hdt * fm
+
+    def _aten_step(self) -> None:
+        hdt, mc = 0.5 * self._dt, self._m[:, None]
+        v = self._aten_finished()
+        fm = self._forces.to(torch.float64) / mc
+        z = langevin_noise(self.seed, self._nsteps, 3 * self.num_atoms, self.device, backend="aten").reshape(-1, 3)
+        v1 = v + hdt * fm
+        x = self._pos + hdt * v1
+        # (a true division: `float / tensor` is the tensor's reciprocal times the float, which rounds twice)
+        v2 = self._c1 * v1 + (self._c2 * torch.sqrt(torch.full_like(mc, self._kt) / mc)) * z
+        self._pos.copy_(x + hdt * v2)
+        self._ekin = 0.5 * (mc * v * v).sum()
+        self._vel.copy_(v2)
+        self._fresh = False
+        self._nsteps += 1
+
+    # ---- checkpoints --------------------------------------------------------------------------------------------------------
+    def state_dict(self) -> Dict[str, object]:
+        return {"positions": self._pos.detach().clone(), "velocities": self.velocities.detach().clone(), "nsteps": self.nsteps,
+                "timestep": self._dt, "temperature": self._temperature, "friction": self.friction, "seed": self.seed}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        pos, vel = state["positions"], state["velocities"]
+        if tuple(pos.shape) != (self.num_atoms, 3) or tuple(vel.shape) != (self.num_atoms, 3):
+            raise ValueError(f"the state holds {tuple(pos.shape)} positions and {tuple(vel.shape)} velocities, this run has "
+                             f"{self.num_atoms} atoms")
+        if "friction" not in state or "seed" not in state or "nvt_bath" in state:
+            raise ValueError("the state was not saved by a Langevin run (a Nose-Hoover state has no friction and no seed)")
+        self._pos.copy_(pos)
+        self._vel.copy_(vel)
+        self._dt, self._temperature = float(state["timestep"]), float(state["temperature"])
+        self.friction, self.seed = float(state["friction"]), _check_u64("seed", state["seed"])
+        self._write_state(nsteps=int(state["nsteps"]))
+        self._evaluate()
