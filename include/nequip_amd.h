@@ -1257,6 +1257,65 @@ int nqa_md_langevin_step(int32_t force_dtype, const void* forces, const double* 
                          double* partials, int32_t mode, nqa_stream stream);
 int nqa_md_noise(uint64_t seed, uint64_t step, int64_t count, uint32_t* words, double* normals, nqa_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * FIRE structural relaxation (Bitzek et al. 2006; ASE's defaults and step cap; massless dynamics, fixed cell) with the state in
+ *   device memory: positions and velocities (float64, [N, 3]) and one nqa_fire_system record per system.  A batch of independent
+ *   systems is concatenated along the atom axis; the atoms are cut into chunks of at most NQA_FIRE_CHUNK atoms, none of which
+ *   straddles two systems (nqa_fire_chunk; chunk_begin[s] .. chunk_begin[s + 1] are the chunks of system s, in atom order).
+ *   One step is nqa_fire_reduce, nqa_fire_decide, nqa_fire_move on the same stream, then one force evaluation at the new
+ *   positions by the caller.  F is the force at the current positions (float32 or float64, promoted on load); the components
+ *   of atoms with fixed[i] != 0 count as zero everywhere (`fixed` may be NULL: no atom is fixed).
+ * nqa_fire_reduce: one workgroup per chunk, one atom per lane.  Row b of `partials` (4 doubles per chunk) = over the atoms of
+ *   chunk b:  sum F.v,  sum F.F,  sum v.v,  max (Fx^2 + Fy^2 + Fz^2)   (a NaN is kept by the max).
+ * nqa_fire_decide: one wavefront per system; merges the rows of its chunks in a fixed order to P, FF, VV, M.  Then lane 0:
+ *     fmax = sqrt(M);  converged = M < fmax_target^2            (both always written)
+ *     if converged: nothing else changes (nsteps included)
+ *     else if nsteps == 0:  cv = 0, cf = 0                      (the velocities are zero by construction: no branch is taken)
+ *     else if P > 0:        cv = 1 - a;  cf = a sqrt(VV) / sqrt(FF)   (the old a)
+ *                           if npos > nmin: dt = min(dt finc, dtmax), a = a fa
+ *                           npos += 1
+ *     else (NaN included):  cv = 0, cf = 0, a = astart, dt = dt fdec, npos = 0
+ *     then, with the new dt:  c = cf + dt;  VVn = cv cv VV + 2 cv c P + c c FF;  normdr = dt sqrt(VVn)
+ *                           scale = normdr > maxstep ? maxstep / normdr : 1;   nsteps += 1
+ *   VVn is the squared norm of the velocities the move is about to form, from the sums of the old ones (every term is
+ *   non-negative in both branches): it differs from a direct norm by rounding only and spares a third reduction.
+ * nqa_fire_move: one workgroup per chunk, flat over its components; for systems that are not converged and atoms that are not
+ *   fixed:  v = cv v + cf F;  v = v + dt F;  x = x + scale (dt v).
+ *   The record is rewritten by the second launch and read by the third, so that no workgroup sees a half-written record
+ *   (launches of one stream run in order).  The host may rewrite the parameter words in place between steps.
+ *   No floating-point atomics, no fused multiply-adds, a fixed order of every sum: the same inputs give the same bits, and a
+ *   system takes the same steps alone and inside a batch.  No allocation, no host synchronisation: the three capture into a
+ *   hipGraph.
+ * The record, sixteen 8-byte words:
+ *   0 dt  1 a  2 npos  3 nsteps                                         state (decide advances it)
+ *   4 dtmax  5 maxstep  6 finc  7 fdec  8 astart  9 fa  10 fmax_target   parameters (the host's)
+ *   11 nmin (low 32 bits, the host's) and converged (high 32 bits, written by decide)
+ *   12 cv  13 cf  14 scale  15 fmax                                      written by decide
+ * ------------------------------------------------------------------------------------------- */
+#define NQA_FIRE_CHUNK 256
+
+typedef struct nqa_fire_system {
+  double dt, a;
+  int64_t npos, nsteps;
+  double dtmax, maxstep, finc, fdec, astart, fa, fmax_target;
+  int32_t nmin, converged;
+  double cv, cf, scale, fmax;
+} nqa_fire_system;
+
+typedef struct nqa_fire_chunk {
+  int64_t atom0;
+  int32_t count, system; /* atoms atom0 .. atom0 + count - 1 (count <= NQA_FIRE_CHUNK) of system `system` */
+} nqa_fire_chunk;
+
+int32_t nqa_fire_chunk_atoms(void);
+int nqa_fire_reduce(int32_t force_dtype, const void* forces, const double* velocities, const uint8_t* fixed /* [N] or NULL */,
+                    const nqa_fire_chunk* chunks, int64_t n_chunks, double* partials /* 4 doubles per chunk */,
+                    nqa_stream stream);
+int nqa_fire_decide(const double* partials, const int64_t* chunk_begin /* [n_systems + 1] */, nqa_fire_system* systems,
+                    int64_t n_systems, nqa_stream stream);
+int nqa_fire_move(int32_t force_dtype, const void* forces, double* positions, double* velocities, const uint8_t* fixed,
+                  const nqa_fire_chunk* chunks, int64_t n_chunks, const nqa_fire_system* systems, nqa_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
