@@ -1316,6 +1316,62 @@ int nqa_fire_decide(const double* partials, const int64_t* chunk_begin /* [n_sys
 int nqa_fire_move(int32_t force_dtype, const void* forces, double* positions, double* velocities, const uint8_t* fixed,
                   const nqa_fire_chunk* chunks, int64_t n_chunks, const nqa_fire_system* systems, nqa_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Variable-cell FIRE: the FIRE above over the atoms and the cell together, as ASE's UnitCellFilter under opt.fire.FIRE, with the
+ *   state in device memory.  Per system: n atoms, the reference cell C0 (rows = lattice vectors, taken at construction), the
+ *   current cell C, the deformation gradient D = (C0^-1 C)^T, i.e. C = C0 D^T (D = I at the start), cell_factor (ASE: n).
+ *   Generalised coordinates, n + 3 rows of 3:  q_i = x_i D^-T for the atoms (carried as state, never re-solved),
+ *   Q = cell_factor D for the cell.  Generalised forces, with F the force and sigma the stress ([S, 3, 3], float32 or float64,
+ *   sigma = (1/V) dE/d(strain), V = |det C|) at (x, C):
+ *     atoms  g_i = F_i D  (row vector times matrix; the rows of atoms with fixed[i] != 0 count as zero; a fixed atom keeps its
+ *            q_i, so its x_i = q_i D^T follows the cell)
+ *     cell   W = -V (sigma + pressure I);  G = W D^-T;  then, in this order:
+ *            hydrostatic:      G = (tr G / 3) I
+ *            mask:             G = G * mask elementwise (nine doubles, 0 or 1)
+ *            constant_volume:  tr G / 3 is subtracted from the diagonal
+ *            finally           G = G / cell_factor
+ * One step is nqa_cellfire_reduce, nqa_cellfire_decide, nqa_cellfire_move on the same stream, then one force evaluation at
+ *   (x, C) by the caller.  Chunks, chunk_begin and `partials` are those of the fixed-cell kernels.
+ * nqa_cellfire_reduce: one workgroup per chunk, one atom per lane; g is formed with the D of the record (d_new: the D at which F
+ *   was evaluated).  Row b of `partials` = over the atoms of chunk b:  sum g.v,  sum g.g,  sum v.v,  max |g_i|^2.
+ * nqa_cellfire_decide: one wavefront per system; merges the rows of its chunks in the fixed order.  Then lane 0, in plain C++:
+ *     forms G (det and D^-T by cofactors), adds its nine components to P, FF, VV (against the cell velocity vd, row-major order)
+ *     and its three row norms to M;  fmax = sqrt(M);  converged = M < fmax_target^2  (both always written; a NaN in a force or
+ *     in the stress reaches fmax);  if converged nothing else changes;  else the FIRE branch of nqa_fire_decide, word for word,
+ *     which gives cv, cf, dt, a, npos, scale, nsteps += 1;  then the cell move:
+ *       d_old = d_new;  vd = cv vd + cf G;  vd = vd + dt G;  Q = cell_factor d_old;  Q = Q + scale (dt vd)
+ *       d_new = Q / cell_factor;  C = C0 d_new^T, written to row s of `cell` ([S, 3, 3] float64: the buffer the force step reads)
+ * nqa_cellfire_move: one workgroup per chunk, one atom per lane; for systems that are not converged:
+ *       g = F d_old;  v = cv v + cf g;  v = v + dt g;  q = q + scale (dt v)    (skipped for fixed atoms)
+ *       x = q d_new^T                                                          (fixed atoms included)
+ *   The record hazards are those of the fixed-cell kernels: three launches of one stream.  No floating-point atomics, no fused
+ *   multiply-adds, a fixed order of every sum, no allocation, no host synchronisation.
+ * The record, sixty-four 8-byte words: 0 .. 15 are the words of nqa_fire_system, then
+ *   16 cell_factor  17 pressure  18 hydrostatic (low 32 bits) and constant_volume (high 32 bits)      parameters (the host's)
+ *   19 .. 27 mask  28 .. 36 c0                                                      parameters, 3 x 3 row-major
+ *   37 .. 45 d_old  46 .. 54 d_new  55 .. 63 vd                                     state (decide advances it), 3 x 3 row-major
+ * ------------------------------------------------------------------------------------------- */
+typedef struct nqa_cellfire_system {
+  double dt, a;
+  int64_t npos, nsteps;
+  double dtmax, maxstep, finc, fdec, astart, fa, fmax_target;
+  int32_t nmin, converged;
+  double cv, cf, scale, fmax;
+  double cell_factor, pressure;
+  int32_t hydrostatic, constant_volume;
+  double mask[9], c0[9], d_old[9], d_new[9], vd[9];
+} nqa_cellfire_system;
+
+int nqa_cellfire_reduce(int32_t force_dtype, const void* forces, const double* velocities, const uint8_t* fixed /* [N] or NULL */,
+                        const nqa_fire_chunk* chunks, int64_t n_chunks, const nqa_cellfire_system* systems,
+                        double* partials /* 4 doubles per chunk */, nqa_stream stream);
+int nqa_cellfire_decide(const double* partials, const int64_t* chunk_begin /* [n_systems + 1] */, int32_t stress_dtype,
+                        const void* stress /* [n_systems, 3, 3] */, nqa_cellfire_system* systems, double* cell /* [n_systems, 3, 3] */,
+                        int64_t n_systems, nqa_stream stream);
+int nqa_cellfire_move(int32_t force_dtype, const void* forces, double* positions, double* coords /* q, [N, 3] */,
+                      double* velocities, const uint8_t* fixed, const nqa_fire_chunk* chunks, int64_t n_chunks,
+                      const nqa_cellfire_system* systems, nqa_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

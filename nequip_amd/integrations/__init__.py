@@ -1,4 +1,5 @@
 from .md import Langevin, NoseHoover, VelocityVerlet, langevin_noise, maxwell_boltzmann_velocities, units
-from .relax import FIRE
+from .relax import FIRE, CellFIRE
 
-__all__ = ["FIRE", "Langevin", "NoseHoover", "VelocityVerlet", "langevin_noise", "maxwell_boltzmann_velocities", "units"]
+__all__ = ["CellFIRE", "FIRE", "Langevin", "NoseHoover", "VelocityVerlet", "langevin_noise", "maxwell_boltzmann_velocities",
+           "units"]

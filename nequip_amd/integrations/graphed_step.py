@@ -163,6 +163,21 @@ class GraphedStep:
         if self._nl is not None:
             self._nl.set_cell(self._cell[0])
 
+    def set_cell_from_device(self, cell: torch.Tensor) -> None:
+        """New lattice vectors from a device tensor (variable-cell relaxation with the cell on the device): device-to-device
+        copies into the buffers the captured launches read, no host read, no new capture.  ``set_cell`` completes the lattice
+        vectors of non-periodic directions on the host; with all three directions periodic there is nothing to complete, and
+        this refuses any other cell."""
+        if not all(self._pbc):
+            raise ValueError(f"set_cell_from_device needs all three directions periodic (pbc is {self._pbc}): the lattice vectors "
+                             "of a non-periodic direction are completed on the host, use set_cell")
+        if not (isinstance(cell, torch.Tensor) and cell.is_cuda and cell.numel() == 9):
+            raise ValueError("cell must be a device tensor of nine elements ([3, 3] or [1, 3, 3])")
+        src = cell.detach().reshape(1, 3, 3)
+        self._cell.copy_(src)
+        if self._nl is not None:
+            self._nl.cell64.copy_(src[0])
+
     @property
     def edge_capacity(self) -> Optional[int]:
         return self._capacity

@@ -77,8 +77,9 @@ def _remove_drift(pos: torch.Tensor, vel: torch.Tensor, m: torch.Tensor) -> torc
     return vel - torch.linalg.cross(omega.expand_as(r), r)
 
 
-def _graphed_step_for(atoms, model, device, r_max, chemical_symbols):
-    """A ``GraphedStep`` for the species, cell and periodicity of ``atoms`` (the species mapping of ``NequIPCalculator``)."""
+def _graphed_step_for(atoms, model, device, r_max, chemical_symbols, outputs=None):
+    """A ``GraphedStep`` for the species, cell and periodicity of ``atoms`` (the species mapping of ``NequIPCalculator``);
+    ``outputs``: the fields it keeps (default: its own, energy and forces)."""
     from .graphed_step import GraphedStep
 
     if r_max is None:
@@ -99,7 +100,8 @@ def _graphed_step_for(atoms, model, device, r_max, chemical_symbols):
     except KeyError as e:
         raise ValueError(f"chemical species {e.args[0]!r} is not among the model's types {sorted(type_of)}") from None
     cell = np.asarray(atoms.get_cell(), dtype=np.float64).reshape(3, 3)
-    return GraphedStep(model, torch.as_tensor(types).to(device), torch.as_tensor(cell).to(device), pbc, float(r_max))
+    kwargs = {} if outputs is None else {"outputs": tuple(outputs)}
+    return GraphedStep(model, torch.as_tensor(types).to(device), torch.as_tensor(cell).to(device), pbc, float(r_max), **kwargs)
 
 
 class _DeviceMD:

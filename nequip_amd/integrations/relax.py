@@ -24,8 +24,10 @@ displacements directly.  The two differ by rounding only, and a third reduction 
 The verdict is taken at the start of a step, from the forces that step is handed: ``fmax`` and ``converged`` describe the
 positions BEFORE the last step's move, and a converged system is left alone by every later step.
 
-CPU tensors (and ``backend="aten"``) take an ATen form of the same equations.  Not provided: variable-cell relaxation, other
-optimizers (the quasi-Newton ones need a Hessian estimate and a line search), an ``ase.optimize.Optimizer`` subclass.
+CPU tensors (and ``backend="aten"``) take an ATen form of the same equations.  ``CellFIRE`` (below) relaxes the cell together
+with the atoms: the same FIRE over ASE's ``UnitCellFilter`` coordinates, three launches of ``csrc/relax_cell.hip``.  Not
+provided: other optimizers (the quasi-Newton ones need a Hessian estimate and a line search), an ``ase.optimize.Optimizer``
+subclass, the exponential cell filters.
 """
 
 from __future__ import annotations
@@ -83,6 +85,17 @@ class FIRE:
                  system_idx: Optional[torch.Tensor] = None, fixed: Optional[torch.Tensor] = None, dt: float = 0.1,
                  maxstep: float = 0.2, dtmax: float = 1.0, nmin: int = 5, finc: float = 1.1, fdec: float = 0.5,
                  astart: float = 0.1, fa: float = 0.99, backend: str = "auto"):
+        self._setup(force_step, positions, system_idx, fixed, dict(dt=dt, maxstep=maxstep, dtmax=dtmax, nmin=nmin, finc=finc,
+                                                                   fdec=fdec, astart=astart, fa=fa), backend, _WORDS)
+        S = self.num_systems
+        self._write_state(torch.full((S,), self._params["dt"], dtype=torch.float64),
+                          torch.full((S,), self._params["astart"], dtype=torch.float64),
+                          torch.zeros(S, dtype=torch.int64), torch.zeros(S, dtype=torch.int64))
+        self._evaluate()
+
+    def _setup(self, force_step, positions, system_idx, fixed, params, backend, words) -> None:
+        """The checks of the arguments, the systems, the buffers and, on the kernel path, the chunk table, the partial sums and
+        the record of ``words`` 8-byte words per system."""
         if not callable(force_step):
             raise TypeError("force_step must be callable: positions [N, 3] -> {'forces', 'total_energy'}")
         if not isinstance(positions, torch.Tensor):
@@ -104,8 +117,7 @@ class FIRE:
         step_device = getattr(force_step, "device", None)
         if isinstance(step_device, torch.device) and step_device != device:
             raise ValueError(f"mixed devices: positions on {device}, force_step on {step_device}")
-        self._params = self._check_params(dict(dt=dt, maxstep=maxstep, dtmax=dtmax, nmin=nmin, finc=finc, fdec=fdec,
-                                               astart=astart, fa=fa))
+        self._params = self._check_params(params)
         if backend not in ("auto", "hip", "aten"):
             raise ValueError(f"backend must be 'auto', 'hip' or 'aten', got {backend!r}")
         if backend == "hip" and device.type != "cuda":
@@ -147,7 +159,7 @@ class FIRE:
             self._chunks = torch.from_numpy(chunks.view(np.int64).reshape(-1, 2).copy()).to(device)
             self._chunk_begin = torch.from_numpy(chunk_begin).to(device)
             self._partials = torch.zeros(self._n_chunks, 4, dtype=torch.float64, device=device)
-            self._rec = torch.zeros(S, _WORDS, dtype=torch.float64, device=device)
+            self._rec = torch.zeros(S, words, dtype=torch.float64, device=device)
             self._rec_i = self._rec.view(torch.int64)
             self._rec_h = self._rec.view(torch.int32)  # [S, 32]: nmin at 2 * 11, converged at 2 * 11 + 1
         else:
@@ -157,10 +169,6 @@ class FIRE:
             k = np.arange(width)[None, :]
             self._pad_mask = torch.from_numpy(k < counts[:, None]).to(device)
             self._pad_idx = torch.from_numpy(np.where(k < counts[:, None], begin[:, None] + k, 0)).to(device)
-        self._write_state(torch.full((S,), self._params["dt"], dtype=torch.float64),
-                          torch.full((S,), self._params["astart"], dtype=torch.float64),
-                          torch.zeros(S, dtype=torch.int64), torch.zeros(S, dtype=torch.int64))
-        self._evaluate()
 
     # ---- state -------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -416,3 +424,392 @@ class FIRE:
             return {AtomicDataDict.FORCE_KEY: res["forces"], AtomicDataDict.TOTAL_ENERGY_KEY: res["energy"]}
 
         return cls(force_step, positions, system_idx=system_idx, **kwargs)
+
+
+# ---- variable cell -------------------------------------------------------------------------------------------------------------
+# the 8-byte words of nqa_cellfire_system behind the sixteen of nqa_fire_system; word 18 is two 32-bit halves: hydrostatic,
+# constant_volume; the five matrices are 3 x 3 row-major
+_CELL_FACTOR, _PRESSURE, _HYDROSTATIC_CONSTVOL, _MASK, _C0, _D_OLD, _D_NEW, _VD = 16, 17, 18, 19, 28, 37, 46, 55
+_CELL_WORDS = 64
+
+
+def _mul_rows(a: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
+    """``a [..., 3]`` times ``m [..., 3, 3]`` (row vector times matrix), the three products added left to right."""
+    return a[..., 0:1] * m[..., 0, :] + a[..., 1:2] * m[..., 1, :] + a[..., 2:3] * m[..., 2, :]
+
+
+def _mul_rows_t(a: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
+    """``a [..., 3]`` times the transpose of ``m [..., 3, 3]``, the three products added left to right."""
+    return a[..., 0:1] * m[..., :, 0] + a[..., 1:2] * m[..., :, 1] + a[..., 2:3] * m[..., :, 2]
+
+
+def _cofactors(m: torch.Tensor) -> torch.Tensor:
+    """``[S, 3, 3]``: the cofactor of every element of ``m`` (``m^-T = cofactors / det``)."""
+    c = [[None] * 3 for _ in range(3)]
+    for i in range(3):
+        for j in range(3):
+            i1, i2, j1, j2 = (i + 1) % 3, (i + 2) % 3, (j + 1) % 3, (j + 2) % 3
+            c[i][j] = m[:, i1, j1] * m[:, i2, j2] - m[:, i1, j2] * m[:, i2, j1]
+    return torch.stack([torch.stack(row, dim=-1) for row in c], dim=-2)
+
+
+def _det(m: torch.Tensor, cof: Optional[torch.Tensor] = None) -> torch.Tensor:
+    cof = _cofactors(m) if cof is None else cof
+    return m[:, 0, 0] * cof[:, 0, 0] + m[:, 0, 1] * cof[:, 0, 1] + m[:, 0, 2] * cof[:, 0, 2]
+
+
+class CellFIRE(FIRE):
+    """FIRE over the atoms and the cell together, state on the device of ``positions``: ASE's ``UnitCellFilter`` under
+    ``ase.optimize.FIRE``, for one system or a batch of independent systems concatenated along the atom axis.
+
+    Per system: ``n`` atoms, the reference cell ``C0`` (rows are the lattice vectors, taken at construction), the current cell
+    ``C``, the deformation gradient ``D = (C0^-1 C)^T`` (``C = C0 D^T``, ``D = I`` at the start), ``cell_factor`` (default ``n``,
+    as in ASE).  Generalised coordinates, ``n + 3`` rows of 3: ``q_i = x_i D^-T`` for the atoms (carried as state, never
+    re-solved) and ``Q = cell_factor D`` for the cell.  Generalised forces, with ``F`` the force and ``sigma`` the stress that
+    ``force_step`` returns (``sigma = (1/V) dE/d(strain)``, ASE's sign; ``V = |det C|``)::
+
+        atoms   g_i = F_i D                          (rows of ``fixed`` atoms count as zero; a fixed atom keeps its q_i, so its
+                                                      x_i = q_i D^T follows the cell, as a filter over FixAtoms does)
+        cell    W = -V (sigma + scalar_pressure I);  G = W D^-T;  then, in this order:
+                hydrostatic_strain: G = (tr G / 3) I;  mask: G = G * mask;  constant_volume: tr G / 3 off the diagonal
+                finally G = G / cell_factor
+
+    FIRE is the fixed-cell definition of this module word for word, over all ``n + 3`` rows::
+
+        reduce   with the D at which F was evaluated:  P = sum g.v,  FF = sum g.g,  VV = sum v.v,  M = max |g_i|^2
+        decide   G is formed; its 9 components are added to P, FF, VV (against the cell velocity vD), its three row norms to M
+                 fmax = sqrt(M);  converged = M < fmax_target^2;  if converged nothing changes; else the FIRE branch gives
+                 cv, cf, dt, a, npos, scale, nsteps += 1, and the cell moves:
+                   vD = cv vD + cf G;  vD = vD + dt G;  Q = cell_factor D + scale (dt vD);  D_new = Q / cell_factor;  C = C0 D_new^T
+        move     g = F D_old;  v = cv v + cf g;  v = v + dt g;  q = q + scale (dt v);  x = q D_new^T
+
+    Three HIP launches (``csrc/relax_cell.hip``: ``nqa_cellfire_reduce`` + ``nqa_cellfire_decide`` + ``nqa_cellfire_move``), then
+    one force evaluation at ``(x, C)``.  ``C`` is written by the deciding launch into ``cell``, the ``[S, 3, 3]`` float64 buffer
+    that ``force_step`` is handed at every call, so nothing of a step passes through the host.
+
+    ``fmax`` is taken over the generalised rows, as an ASE optimizer sees them through the filter: the largest of ``|g_i|`` and of
+    the three row norms of ``G``.  It is NOT the atoms' own ``|F_i|``; ``stress`` holds the last stress for a pressure criterion.
+
+    ``force_step``: ``(positions [N, 3], cell [S, 3, 3]) -> {"forces", "total_energy", "stress" [S, 3, 3]}`` (float32 or float64
+    forces and stress), or a ``GraphedStep`` built with ``outputs=(total_energy, forces, stress)`` for one system in a fully
+    periodic cell (its cell is set by ``set_cell_from_device``).  ``cell``: ``[3, 3]`` or ``[S, 3, 3]``; ``cell_factor``: a float or
+    ``[S]``; ``mask``: ``[3, 3]`` of 0/1.  The other arguments are those of ``FIRE``.
+
+    Not provided: ``FrechetCellFilter`` / ``ExpCellFilter`` (they need a matrix exponential and its derivative), other
+    optimizers, an ``ase.optimize`` shell, reading an ``Atoms`` object's constraints, cells with non-periodic directions on the
+    ``GraphedStep`` route."""
+
+    def __init__(self, force_step, positions: torch.Tensor, cell: torch.Tensor, system_idx: Optional[torch.Tensor] = None,
+                 fixed: Optional[torch.Tensor] = None, cell_factor=None, scalar_pressure: float = 0.0,
+                 hydrostatic_strain: bool = False, constant_volume: bool = False, mask=None, dt: float = 0.1,
+                 maxstep: float = 0.2, dtmax: float = 1.0, nmin: int = 5, finc: float = 1.1, fdec: float = 0.5,
+                 astart: float = 0.1, fa: float = 0.99, backend: str = "auto"):
+        if hasattr(force_step, "set_cell_from_device"):  # a GraphedStep: the cell goes in through its own buffers
+            graphed = force_step
+            if AtomicDataDict.STRESS_KEY not in getattr(graphed, "outputs", ()):
+                raise ValueError("stress: the GraphedStep must be built with outputs=(total_energy, forces, stress)")
+
+            def force_step(pos, cell_buffer, _step=graphed):
+                _step.set_cell_from_device(cell_buffer)
+                return _step(pos)
+
+            force_step.device = getattr(graphed, "device", None)
+        self._setup(force_step, positions, system_idx, fixed, dict(dt=dt, maxstep=maxstep, dtmax=dtmax, nmin=nmin, finc=finc,
+                                                                   fdec=fdec, astart=astart, fa=fa), backend, _CELL_WORDS)
+        S, device = self.num_systems, self.device
+        if not isinstance(cell, torch.Tensor) or tuple(cell.shape) not in ((3, 3), (S, 3, 3)):
+            raise ValueError(f"cell must be a tensor of shape [3, 3] or [{S}, 3, 3], got "
+                             f"{tuple(cell.shape) if isinstance(cell, torch.Tensor) else type(cell).__name__}")
+        if cell.device != device:
+            raise ValueError(f"mixed devices: positions on {device}, cell on {cell.device}")
+        c0 = cell.detach().to(torch.float64).reshape(-1, 3, 3).expand(S, 3, 3).contiguous().clone()
+        c0_host = c0.cpu().numpy()
+        for s in range(S):
+            scale = float(np.prod(np.linalg.norm(c0_host[s], axis=1)))
+            if not np.isfinite(c0_host[s]).all() or not abs(float(np.linalg.det(c0_host[s]))) > 1e-12 * max(scale, 1e-300):
+                raise ValueError(f"cell of system {s} is singular: its lattice vectors do not span a volume")
+        if cell_factor is None:
+            factor = torch.from_numpy(self._counts.astype(np.float64))
+        else:
+            factor = torch.as_tensor(cell_factor, dtype=torch.float64).detach().cpu().reshape(-1)
+            if factor.numel() not in (1, S):
+                raise ValueError(f"cell_factor must be a number or hold one per system ([{S}]), got {factor.numel()} values")
+            factor = factor.expand(S).clone()
+        if not bool((torch.isfinite(factor) & (factor > 0.0)).all()):
+            raise ValueError("cell_factor must be positive and finite")
+        if not (isinstance(scalar_pressure, (int, float)) and math.isfinite(scalar_pressure)):
+            raise ValueError(f"scalar_pressure must be finite, got {scalar_pressure!r}")
+        if mask is None:
+            mask_t = torch.ones(3, 3, dtype=torch.float64)
+        else:
+            mask_t = torch.as_tensor(mask).detach().cpu()
+            if tuple(mask_t.shape) != (3, 3):
+                raise ValueError(f"mask must have shape [3, 3], got {tuple(mask_t.shape)}")
+            mask_t = mask_t.to(torch.float64)
+            if not bool(((mask_t == 0.0) | (mask_t == 1.0)).all()):
+                raise ValueError("mask must hold zeros and ones")
+        self._cell_params = {"cell_factor": factor, "scalar_pressure": float(scalar_pressure),
+                             "hydrostatic_strain": bool(hydrostatic_strain), "constant_volume": bool(constant_volume),
+                             "mask": mask_t}
+        self._c0 = c0
+        self._cell = c0.clone()
+        self._q = self._pos.clone()
+        self._stress: Optional[torch.Tensor] = None
+        eye = torch.eye(3, dtype=torch.float64).expand(S, 3, 3)
+        self._write_state(torch.full((S,), self._params["dt"], dtype=torch.float64),
+                          torch.full((S,), self._params["astart"], dtype=torch.float64),
+                          torch.zeros(S, dtype=torch.int64), torch.zeros(S, dtype=torch.int64),
+                          eye, eye, torch.zeros(S, 3, 3, dtype=torch.float64))
+        self._evaluate()
+
+    # ---- state -------------------------------------------------------------------------------------------------------------
+    def _write_state(self, dt, a, npos, nsteps, d_old=None, d_new=None, vd=None) -> None:
+        """The whole record of every system: the FIRE state, ``D`` and ``vD`` (``[S, 3, 3]``), the parameters, the verdict
+        cleared."""
+        S, p, c = self.num_systems, self._params, self._cell_params
+        if self._hip:
+            words = torch.zeros(S, _CELL_WORDS, dtype=torch.float64)
+            words[:, _DT], words[:, _A] = dt.cpu().double(), a.cpu().double()
+            words.view(torch.int64)[:, _NPOS], words.view(torch.int64)[:, _NSTEPS] = npos.cpu().long(), nsteps.cpu().long()
+            for word, key in ((_DTMAX, "dtmax"), (_MAXSTEP, "maxstep"), (_FINC, "finc"), (_FDEC, "fdec"), (_ASTART, "astart"),
+                              (_FA, "fa")):
+                words[:, word] = p[key]
+            words[:, _TARGET] = self._fmax_target
+            words.view(torch.int32)[:, 2 * _NMIN_CONVERGED] = p["nmin"]
+            words[:, _CELL_FACTOR] = c["cell_factor"]
+            words[:, _PRESSURE] = c["scalar_pressure"]
+            words.view(torch.int32)[:, 2 * _HYDROSTATIC_CONSTVOL] = int(c["hydrostatic_strain"])
+            words.view(torch.int32)[:, 2 * _HYDROSTATIC_CONSTVOL + 1] = int(c["constant_volume"])
+            words[:, _MASK:_MASK + 9] = c["mask"].reshape(1, 9)
+            words[:, _C0:_C0 + 9] = self._c0.cpu().reshape(S, 9)
+            words[:, _D_OLD:_D_OLD + 9] = d_old.cpu().double().reshape(S, 9)
+            words[:, _D_NEW:_D_NEW + 9] = d_new.cpu().double().reshape(S, 9)
+            words[:, _VD:_VD + 9] = vd.cpu().double().reshape(S, 9)
+            self._rec.copy_(words)
+        else:
+            FIRE._write_state(self, dt, a, npos, nsteps)
+            dev = self.device
+            self._d_old_s = d_old.to(dev).double().reshape(S, 3, 3).clone()
+            self._d_s = d_new.to(dev).double().reshape(S, 3, 3).clone()
+            self._vd_s = vd.to(dev).double().reshape(S, 3, 3).clone()
+
+    def _evaluate(self) -> None:
+        out = self.force_step(self._pos, self._cell)
+        S = self.num_systems
+        stress = out.get(AtomicDataDict.STRESS_KEY) if hasattr(out, "get") else None
+        if stress is None:
+            raise ValueError("stress: force_step must return it ([S, 3, 3]) next to the forces for a variable-cell relaxation")
+        stress = stress.detach()
+        if S == 1 and tuple(stress.shape) == (3, 3):
+            stress = stress.reshape(1, 3, 3)
+        if tuple(stress.shape) != (S, 3, 3) or stress.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"stress: force_step must return float32 or float64 [{S}, 3, 3], got {stress.dtype} "
+                             f"{tuple(stress.shape)}")
+        if stress.device != self.device:
+            raise ValueError(f"mixed devices: positions on {self.device}, stress on {stress.device}")
+        f = out[AtomicDataDict.FORCE_KEY].detach()
+        if tuple(f.shape) != (self.num_atoms, 3) or f.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"force_step must return float32 or float64 forces [{self.num_atoms}, 3], got {f.dtype} "
+                             f"{tuple(f.shape)}")
+        if f.device != self.device:
+            raise ValueError(f"mixed devices: positions on {self.device}, forces on {f.device}")
+        self._out, self._forces, self._stress = out, f.contiguous(), stress.contiguous()
+
+    # ---- the two forms of a step --------------------------------------------------------------------------------------------
+    def _launch(self) -> None:
+        lib, L = self._lib.load(), self._lib
+        f, sig = self._forces, self._stress
+        dtype = L.NQA_F64 if f.dtype == torch.float64 else L.NQA_F32
+        sdtype = L.NQA_F64 if sig.dtype == torch.float64 else L.NQA_F32
+        stream = L.stream_ptr(self.device)
+        L.check(lib.nqa_cellfire_reduce(dtype, L.ptr(f), L.ptr(self._vel), L.ptr(self._fixed), L.ptr(self._chunks), self._n_chunks,
+                                        L.ptr(self._rec), L.ptr(self._partials), stream), "nqa_cellfire_reduce")
+        L.check(lib.nqa_cellfire_decide(L.ptr(self._partials), L.ptr(self._chunk_begin), sdtype, L.ptr(sig), L.ptr(self._rec),
+                                        L.ptr(self._cell), self.num_systems, stream), "nqa_cellfire_decide")
+        L.check(lib.nqa_cellfire_move(dtype, L.ptr(f), L.ptr(self._pos), L.ptr(self._q), L.ptr(self._vel), L.ptr(self._fixed),
+                                      L.ptr(self._chunks), self._n_chunks, L.ptr(self._rec), stream), "nqa_cellfire_move")
+
+    def _cell_force(self, D: torch.Tensor) -> torch.Tensor:
+        """``G [S, 3, 3]`` from the last stress at the deformation gradients ``D``."""
+        c, dev = self._cell_params, self.device
+        cell = _mul_rows_t(self._c0, D[:, None, :, :])  # C = C0 D^T, row by row
+        V = _det(cell).abs()
+        cof = _cofactors(D)
+        d_inv_t = cof / _det(D, cof)[:, None, None]
+        W = self._stress.to(torch.float64) + c["scalar_pressure"] * torch.eye(3, dtype=torch.float64, device=dev)
+        W = -V[:, None, None] * W
+        G = _mul_rows(W, d_inv_t[:, None, :, :])
+        eye = torch.eye(3, dtype=torch.float64, device=dev)
+        if c["hydrostatic_strain"]:
+            G = ((G[:, 0, 0] + G[:, 1, 1] + G[:, 2, 2]) / 3.0)[:, None, None] * eye
+        G = G * c["mask"].to(dev)
+        if c["constant_volume"]:
+            G = G - ((G[:, 0, 0] + G[:, 1, 1] + G[:, 2, 2]) / 3.0)[:, None, None] * eye
+        return G / c["cell_factor"].to(dev)[:, None, None]
+
+    def _aten_step(self) -> None:
+        p = self._params
+        s = self._system_idx
+        f = self._forces.to(torch.float64)
+        v, D, vd = self._vel, self._d_s, self._vd_s
+        if self._fixed is not None:
+            f = torch.where(self._fixed.bool()[:, None], torch.zeros_like(f), f)
+        g = _mul_rows(f, D[s])
+        # reduce
+        gv, gg, vv = g * v, g * g, v * v
+        gg_atom = self._padded(gg[:, 0] + gg[:, 1] + gg[:, 2])
+        P = torch.sum(self._padded(gv[:, 0] + gv[:, 1] + gv[:, 2]), dim=1)
+        FF = torch.sum(gg_atom, dim=1)
+        VV = torch.sum(self._padded(vv[:, 0] + vv[:, 1] + vv[:, 2]), dim=1)
+        M = torch.amax(gg_atom, dim=1)
+        # decide: the cell's rows join the sums
+        G = self._cell_force(D)
+        P = P + (G * vd).reshape(-1, 9).sum(1)
+        FF = FF + (G * G).reshape(-1, 9).sum(1)
+        VV = VV + (vd * vd).reshape(-1, 9).sum(1)
+        M = torch.maximum(M, torch.amax((G * G).sum(2), dim=1))  # (both keep a NaN)
+        dt, a, npos = self._dt_s, self._a_s, self._npos_s
+        converged = M < self._fmax_target * self._fmax_target
+        first = self._nsteps_s == 0
+        up = (P > 0.0) & ~first
+        down = ~up & ~first
+        grow = up & (npos > p["nmin"])
+        zero, one = torch.zeros_like(dt), torch.ones_like(dt)
+        cv = torch.where(up, 1.0 - a, zero)
+        cf = torch.where(up, a * torch.sqrt(VV) / torch.sqrt(FF), zero)
+        grown = dt * p["finc"]
+        dt_new = torch.where(grow, torch.where(grown < p["dtmax"], grown, torch.full_like(dt, p["dtmax"])),
+                             torch.where(down, dt * p["fdec"], dt))
+        a_new = torch.where(grow, a * p["fa"], torch.where(down, torch.full_like(a, p["astart"]), a))
+        npos_new = torch.where(up, npos + 1, torch.where(down, torch.zeros_like(npos), npos))
+        c = cf + dt_new
+        vvn = cv * cv * VV + 2.0 * cv * c * P + c * c * FF
+        normdr = dt_new * torch.sqrt(vvn)
+        scale = torch.where(normdr > p["maxstep"], p["maxstep"] / normdr, one)
+        active = ~converged
+        self._fmax_s, self._converged_s = torch.sqrt(M), converged
+        self._dt_s = torch.where(active, dt_new, dt)
+        self._a_s = torch.where(active, a_new, a)
+        self._npos_s = torch.where(active, npos_new, npos)
+        self._nsteps_s = self._nsteps_s + active.to(torch.int64)
+        # the cell move
+        m3 = lambda t: t[:, None, None]  # noqa: E731
+        factor = m3(self._cell_params["cell_factor"].to(self.device))
+        vd_new = m3(cv) * vd + m3(cf) * G
+        vd_new = vd_new + m3(dt_new) * G
+        Q = factor * D
+        Q = Q + m3(scale) * (m3(dt_new) * vd_new)
+        d_new = Q / factor
+        act3 = m3(active)
+        self._d_old_s = torch.where(act3, D, self._d_old_s)
+        self._d_s = torch.where(act3, d_new, D)
+        self._vd_s = torch.where(act3, vd_new, vd)
+        self._cell.copy_(torch.where(act3, _mul_rows_t(self._c0, d_new[:, None, :, :]), self._cell))
+        # move
+        moves = active[s][:, None]
+        free = moves if self._fixed is None else moves & ~self._fixed.bool()[:, None]
+        v_new = cv[s][:, None] * v + cf[s][:, None] * g
+        v_new = v_new + dt_new[s][:, None] * g
+        q_new = torch.where(free, self._q + scale[s][:, None] * (dt_new[s][:, None] * v_new), self._q)
+        self._vel.copy_(torch.where(free, v_new, v))
+        self._q.copy_(q_new)
+        self._pos.copy_(torch.where(moves, _mul_rows_t(q_new, d_new[s]), self._pos))
+
+    # ---- interface ----------------------------------------------------------------------------------------------------------
+    @property
+    def cell(self) -> torch.Tensor:
+        """``[S, 3, 3]`` float64, rows are the lattice vectors: the live buffer that ``force_step`` reads."""
+        return self._cell
+
+    @property
+    def deform_grad(self) -> torch.Tensor:
+        return self._rec[:, _D_NEW:_D_NEW + 9].view(-1, 3, 3) if self._hip else self._d_s
+
+    @property
+    def cell_velocities(self) -> torch.Tensor:
+        return self._rec[:, _VD:_VD + 9].view(-1, 3, 3) if self._hip else self._vd_s
+
+    @property
+    def _d_old(self) -> torch.Tensor:
+        return self._rec[:, _D_OLD:_D_OLD + 9].view(-1, 3, 3) if self._hip else self._d_old_s
+
+    @property
+    def stress(self) -> torch.Tensor:
+        """``[S, 3, 3]``: the stress ``force_step`` returned last, at the current positions and cell."""
+        return self._stress
+
+    @property
+    def volume(self) -> torch.Tensor:
+        return _det(self._cell).abs()
+
+    @property
+    def reference_cell(self) -> torch.Tensor:
+        return self._c0
+
+    # ---- checkpoints --------------------------------------------------------------------------------------------------------
+    def state_dict(self) -> Dict[str, object]:
+        state = FIRE.state_dict(self)
+        state.update({"q": self._q.detach().clone(), "D": self.deform_grad.detach().clone(), "D_old": self._d_old.detach().clone(),
+                      "vD": self.cell_velocities.detach().clone(), "C0": self._c0.detach().clone(),
+                      "cell": self._cell.detach().clone(),
+                      "cell_parameters": {k: (v.clone() if isinstance(v, torch.Tensor) else v)
+                                          for k, v in self._cell_params.items()}})
+        return state
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        pos, vel = state["positions"], state["velocities"]
+        if tuple(pos.shape) != (self.num_atoms, 3) or tuple(vel.shape) != (self.num_atoms, 3):
+            raise ValueError(f"the state holds {tuple(pos.shape)} positions and {tuple(vel.shape)} velocities, this run has "
+                             f"{self.num_atoms} atoms")
+        if "vD" not in state or "npos" not in state or tuple(state["dt"].shape) != (self.num_systems,):
+            raise ValueError(f"the state was not saved by a CellFIRE run of {self.num_systems} systems")
+        self._params = self._check_params(dict(state["parameters"]))
+        self._cell_params = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in state["cell_parameters"].items()}
+        self._fmax_target = float(state["fmax_target"])
+        self._pos.copy_(pos)
+        self._vel.copy_(vel)
+        self._q.copy_(state["q"])
+        self._c0.copy_(state["C0"])
+        self._cell.copy_(state["cell"])
+        self._write_state(state["dt"], state["a"], state["npos"], state["nsteps"], state["D_old"], state["D"], state["vD"])
+        self._evaluate()
+
+    # ---- Atoms and torch-sim ------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_atoms(cls, atoms, model_or_step, device="cuda", r_max: Optional[float] = None, chemical_symbols=None, **kwargs):
+        """The optimizer for an ``Atoms`` object (positions, cell, periodicity, species; its constraints are NOT read: pass
+        ``fixed``).  ``model_or_step``: an eval-mode model (a ``GraphedStep`` with energy, forces and stress is built around
+        it, which needs ``r_max`` and all three directions periodic) or a ready ``force_step``.  ``kwargs``: the constructor's."""
+        device = torch.device(device)
+        pos = torch.as_tensor(np.asarray(atoms.get_positions(), dtype=np.float64)).to(device)
+        cell = torch.as_tensor(np.asarray(atoms.get_cell(), dtype=np.float64).reshape(3, 3)).to(device)
+        step = model_or_step
+        if isinstance(model_or_step, torch.nn.Module):
+            if not all(bool(b) for b in np.asarray(atoms.get_pbc(), dtype=bool).reshape(3)):
+                raise ValueError("a variable-cell relaxation around a GraphedStep needs all three directions periodic")
+            K = AtomicDataDict
+            step = _graphed_step_for(atoms, model_or_step, device, r_max, chemical_symbols,
+                                     outputs=(K.TOTAL_ENERGY_KEY, K.FORCE_KEY, K.STRESS_KEY))
+        return cls(step, pos, cell, **kwargs)
+
+    def write_back(self, atoms) -> None:
+        """Cell and positions into ``atoms`` (one copy each; the atoms are not rescaled with the cell: the positions follow)."""
+        atoms.set_cell(self._cell[0].detach().cpu().numpy(), scale_atoms=False)
+        atoms.set_positions(self._pos.detach().cpu().numpy())
+
+    @classmethod
+    def from_torchsim(cls, calc, positions, cell, pbc, atomic_numbers, system_idx, **kwargs):
+        """The optimizer of a batch around a ``NequIPTorchSimCalc``: ``force_step`` hands ``calc`` a state with ``positions``,
+        ``row_vector_cell`` (the live cell buffer), ``pbc``, ``atomic_numbers`` and ``system_idx``, and returns its forces,
+        per-system energies and stresses.  ``calc.compute_stress`` is switched on."""
+        calc.compute_stress = True
+        numbers = None if getattr(calc, "atomic_numbers_in_init", False) else atomic_numbers
+        state = SimpleNamespace(positions=None, row_vector_cell=None, pbc=pbc, atomic_numbers=numbers, system_idx=system_idx)
+
+        def force_step(pos, cell_buffer):
+            state.positions, state.row_vector_cell = pos, cell_buffer
+            res = calc(state)
+            return {AtomicDataDict.FORCE_KEY: res["forces"], AtomicDataDict.TOTAL_ENERGY_KEY: res["energy"],
+                    AtomicDataDict.STRESS_KEY: res.get("stress")}
+
+        return cls(force_step, positions, cell, system_idx=system_idx, **kwargs)
