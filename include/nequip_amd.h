@@ -1258,6 +1258,38 @@ int nqa_md_langevin_step(int32_t force_dtype, const void* forces, const double* 
 int nqa_md_noise(uint64_t seed, uint64_t step, int64_t count, uint32_t* words, double* normals, nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Isotropic NPT: the Langevin step above followed by a stochastic cell rescaling barostat (Bernetti and Bussi 2020, first order
+ *   in the volume), for ONE system whose cell (`cell`, [3, 3] float64, rows are the lattice vectors) lives on the device.  One
+ *   step is nqa_md_langevin_step (unchanged), nqa_md_npt_bath IN PLACE OF nqa_md_bath, nqa_md_npt_scale, on the same stream,
+ *   then one force evaluation at the new positions and cell by the caller.  `stress` ([3, 3], float32 or float64, promoted on
+ *   load) is the potential stress at the positions and cell of the start of the step, (1/V) dE/d(strain).
+ * nqa_md_npt_bath: one wavefront; adds the rows of `partials` in the order of nqa_md_bath to S = sum m v^2, then lane 0:
+ *   K = S / 2;  V = |det cell| (cofactors along the first row);  P = (2 K) / (3 V) - (stress_00 + stress_11 + stress_22) / 3
+ *   xi = the normal of nqa_md_langevin_step's generator for component `noise_index` (the host writes 3N: one past the atoms'
+ *        components) at step s = state->nsteps with params->seed
+ *   d_eps = -a (p0 - P) + sqrt((2 kT a) / V) xi;  mu = exp(d_eps / 3)
+ *   mu not finite or not V > 0: mu = 1 and `failed` = 1, which stays set until the host clears it.
+ *   cell = mu cell;  mu, pressure = P, kinetic_energy = K, volume = V (BEFORE the scaling) into the record; and, as nqa_md_bath,
+ *   state->kinetic_energy = K, state->nsteps += 1, state->fresh = 0.
+ *   a = compressibility dt / taup (the host's float64) and p0 (eV/A^3) may be rewritten in place between steps.  a = 0 gives
+ *   mu = 1 exactly: the trajectory of nqa_md_langevin_step + nqa_md_bath bit for bit.
+ * nqa_md_npt_scale: flat over the 3N components as nqa_md_step: x = mu x;  v2 = v2 / mu (a division), with the mu of the record.
+ *   mu is written by the second launch and read by the third, nsteps by the second and read by the first of the next step: no
+ *   launch sees a word that a launch of the same step rewrites after it started.  The finish-only readers are those of the
+ *   Langevin step.  No atomics, no FMA contraction, no allocation, no host synchronisation: the three capture into a hipGraph.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct nqa_md_npt_state {
+  double a, p0;        /* compressibility dt / taup, target pressure: the host's */
+  int64_t noise_index; /* 3N: the host's */
+  double mu, pressure, kinetic_energy, volume;
+  int64_t failed;
+} nqa_md_npt_state;
+
+int nqa_md_npt_bath(const double* partials, int64_t num_partials, nqa_md_state* state, const nqa_md_langevin_params* params,
+                    nqa_md_npt_state* npt, int32_t stress_dtype, const void* stress, double* cell, nqa_stream stream);
+int nqa_md_npt_scale(double* positions, double* velocities, int64_t num_atoms, const nqa_md_npt_state* npt, nqa_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * FIRE structural relaxation (Bitzek et al. 2006; ASE's defaults and step cap; massless dynamics, fixed cell) with the state in
  *   device memory: positions and velocities (float64, [N, 3]) and one nqa_fire_system record per system.  A batch of independent
  *   systems is concatenated along the atom axis; the atoms are cut into chunks of at most NQA_FIRE_CHUNK atoms, none of which

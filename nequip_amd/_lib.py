@@ -406,6 +406,9 @@ SIGNATURES = {
         c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
                   c_void_p]),
     "nqa_md_noise": (c_int32, [c_uint64, c_uint64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nqa_md_npt_bath": (
+        c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "nqa_md_npt_scale": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "nqa_fire_chunk_atoms": (c_int32, []),
     "nqa_fire_reduce": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "nqa_fire_decide": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

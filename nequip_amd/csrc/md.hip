@@ -238,6 +238,65 @@ __global__ __launch_bounds__(MD_THREADS) void md_noise_kernel(uint64_t seed, uin
   if (normals) normals[i] = md_normal(w);
 }
 
+// ---- isotropic NPT: the Langevin step, then stochastic cell rescaling (Bernetti-Bussi, first order in the volume) ---------------
+//   md_langevin_step_kernel (unchanged), md_npt_bath_kernel in place of md_bath_kernel, md_npt_scale_kernel.
+// The bath launch adds the partial rows exactly as md_bath_kernel does (the kinetic energy has the bits of a Langevin run), and
+// lane 0 forms the pressure of the start of the step from it and the stress, draws ONE normal (component 3N of the step's noise,
+// one past the atoms'), scales the cell and leaves mu in the record; the third launch scales positions and stored velocities.
+// mu is written by the second launch and read by the third; nsteps and fresh are written by the second and read by the first
+// of the NEXT step: the ordering argument of the top of this file, no launch sees a word that a launch of its own step rewrites.
+static_assert(sizeof(nqa_md_npt_state) == 64, "the host writes the record as eight 8-byte words");
+
+template <typename S>
+__global__ __launch_bounds__(64) void md_npt_bath_kernel(const double* __restrict__ partials, int64_t num_partials,
+                                                         nqa_md_state* __restrict__ state,
+                                                         const nqa_md_langevin_params* __restrict__ params,
+                                                         nqa_md_npt_state* __restrict__ npt, const S* __restrict__ stress,
+                                                         double* __restrict__ cell) {
+  const int lane = threadIdx.x;
+  const int64_t per = (num_partials + 63) / 64;
+  const int64_t lo = lane * per, hi = lo + per < num_partials ? lo + per : num_partials;
+  double s_full = 0.0;
+  for (int64_t k = lo; k < hi; ++k) s_full += partials[2 * k];
+  s_full = md_wave_sum(s_full);
+  if (lane != 0) return;
+  const double ekin = 0.5 * s_full;
+  double c[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) c[k] = cell[k];
+  const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+  const double vol = fabs(det);
+  const double p = (2.0 * ekin) / (3.0 * vol) - ((double)stress[0] + (double)stress[4] + (double)stress[8]) / 3.0;
+  uint32_t w[4];
+  md_philox(params->seed, (uint64_t)state->nsteps, (uint64_t)npt->noise_index, w);
+  const double xi = md_normal(w);
+  const double a = npt->a;
+  const double d_eps = -a * (npt->p0 - p) + sqrt((2.0 * params->kT * a) / vol) * xi;
+  double mu = exp(d_eps / 3.0);
+  if (!isfinite(mu) || !(vol > 0.0)) {
+    mu = 1.0;
+    npt->failed = 1;
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) cell[k] = mu * c[k];
+  npt->mu = mu;
+  npt->pressure = p;
+  npt->kinetic_energy = ekin;
+  npt->volume = vol;
+  state->kinetic_energy = ekin;
+  state->nsteps += 1;
+  state->fresh = 0;
+}
+
+__global__ __launch_bounds__(MD_THREADS) void md_npt_scale_kernel(double* __restrict__ positions, double* __restrict__ velocities,
+                                                                   int64_t n3, const nqa_md_npt_state* __restrict__ npt) {
+  const int64_t i = (int64_t)blockIdx.x * MD_THREADS + threadIdx.x;
+  if (i >= n3) return;
+  const double mu = npt->mu;
+  positions[i] = mu * positions[i];
+  velocities[i] = velocities[i] / mu;
+}
+
 }  // namespace nqa
 
 extern "C" {
@@ -339,6 +398,49 @@ int nqa_md_noise(uint64_t seed, uint64_t step, int64_t count, uint32_t* words, d
   const dim3 grid((unsigned)((count + MD_THREADS - 1) / MD_THREADS));
   hipLaunchKernelGGL(md_noise_kernel, grid, dim3(MD_THREADS), 0, static_cast<hipStream_t>(stream), seed, step, count, words,
                      normals);
+  return launch_status(name);
+}
+
+int nqa_md_npt_bath(const double* partials, int64_t num_partials, nqa_md_state* state, const nqa_md_langevin_params* params,
+                    nqa_md_npt_state* npt, int32_t stress_dtype, const void* stress, double* cell, nqa_stream stream) {
+  using namespace nqa;
+  const char* name = "nqa_md_npt_bath";
+  if (stress_dtype != NQA_F32 && stress_dtype != NQA_F64) {
+    set_error(std::string(name) + ": the stress is float32 or float64");
+    return NQA_ERR_UNSUPPORTED;
+  }
+  if (num_partials <= 0 || !partials || !state || !params || !npt) {
+    set_error(std::string(name) + ": partials (num_partials > 0), state, params and the npt record are required");
+    return NQA_ERR_INVALID;
+  }
+  if (!stress || !cell) {
+    set_error(std::string(name) + ": stress and cell ([3, 3] each) are required");
+    return NQA_ERR_INVALID;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (stress_dtype == NQA_F64)
+    hipLaunchKernelGGL(md_npt_bath_kernel<double>, dim3(1), dim3(64), 0, s, partials, num_partials, state, params, npt,
+                       (const double*)stress, cell);
+  else
+    hipLaunchKernelGGL(md_npt_bath_kernel<float>, dim3(1), dim3(64), 0, s, partials, num_partials, state, params, npt,
+                       (const float*)stress, cell);
+  return launch_status(name);
+}
+
+int nqa_md_npt_scale(double* positions, double* velocities, int64_t num_atoms, const nqa_md_npt_state* npt, nqa_stream stream) {
+  using namespace nqa;
+  const char* name = "nqa_md_npt_scale";
+  if (num_atoms <= 0 || num_atoms > INT32_MAX) {
+    set_error(std::string(name) + ": 0 < num_atoms < 2^31");
+    return NQA_ERR_INVALID;
+  }
+  if (!positions || !velocities || !npt) {
+    set_error(std::string(name) + ": positions, velocities and the npt record are required");
+    return NQA_ERR_INVALID;
+  }
+  const dim3 grid((unsigned)md_num_partials(num_atoms));
+  hipLaunchKernelGGL(md_npt_scale_kernel, grid, dim3(MD_THREADS), 0, static_cast<hipStream_t>(stream), positions, velocities,
+                     3 * num_atoms, npt);
   return launch_status(name);
 }
 

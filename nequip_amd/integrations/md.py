@@ -27,7 +27,15 @@ CPU tensors (and ``backend="aten"``) take an ATen form of the same equations, fo
 ``Langevin`` is the stochastic NVT ensemble on the same state and the same two-launch step (``nqa_md_langevin_step`` +
 ``nqa_md_bath``): BAOAB with its noise made on the device by a counter-based generator, a function of (seed, step count,
 component) alone (``langevin_noise``), so that a run is reproducible bit for bit, survives a checkpoint and captures into a
-hipGraph.  Not provided: NPT, a centre-of-mass constraint during the run, an ``ase.md.MolecularDynamics`` subclass.
+hipGraph.
+
+``LangevinNPT`` is the isotropic constant-pressure ensemble for one system: the same Langevin launch, then a one-wavefront launch
+that forms the pressure from the kinetic energy and the stress and rescales the cell on the device (stochastic cell rescaling,
+``nqa_md_npt_bath``), then a flat launch that rescales positions and stored velocities (``nqa_md_npt_scale``).  The cell is a
+device buffer that ``force_step(positions, cell)`` reads; a ``GraphedStep`` follows it through ``set_cell_from_device``.
+
+Not provided: anisotropic cells and other barostats, batches of systems under NPT, a centre-of-mass constraint during the run,
+an ``ase.md.MolecularDynamics`` subclass.
 """
 
 from __future__ import annotations
@@ -43,7 +51,7 @@ from ..data import AtomicDataDict
 
 # CODATA 2014, the values behind ase.units
 _e, _amu, _k = 1.6021766208e-19, 1.660539040e-27, 1.38064852e-23
-units = SimpleNamespace(kB=_k / _e, fs=1e-5 * math.sqrt(_e / _amu))
+units = SimpleNamespace(kB=_k / _e, fs=1e-5 * math.sqrt(_e / _amu), GPa=1e-21 / _e, bar=1e-25 / _e)
 
 _MD_FINISH_ONLY, _MD_THERMOSTAT = 1, 2
 # the 8-byte words of nqa_md_state (include/nequip_amd.h)
@@ -102,6 +110,24 @@ def _graphed_step_for(atoms, model, device, r_max, chemical_symbols, outputs=Non
     cell = np.asarray(atoms.get_cell(), dtype=np.float64).reshape(3, 3)
     kwargs = {} if outputs is None else {"outputs": tuple(outputs)}
     return GraphedStep(model, torch.as_tensor(types).to(device), torch.as_tensor(cell).to(device), pbc, float(r_max), **kwargs)
+
+
+def _cell_following_step(force_step):
+    """``force_step`` as a ``(positions, cell buffer)`` callable.  A ``GraphedStep`` takes the cell through its own buffers
+    (``set_cell_from_device``) before every evaluation and must keep the stress; any other callable is returned as it is."""
+    if not hasattr(force_step, "set_cell_from_device"):
+        return force_step
+    graphed = force_step
+    if AtomicDataDict.STRESS_KEY not in getattr(graphed, "outputs", ()):
+        raise ValueError("stress: the GraphedStep must be built with outputs=(total_energy, forces, stress)")
+
+    def step(pos, cell_buffer, _step=graphed):
+        _step.set_cell_from_device(cell_buffer)
+        return _step(pos)
+
+    step.device = getattr(graphed, "device", None)
+    step.graphed_step = graphed
+    return step
 
 
 class _DeviceMD:
@@ -407,12 +433,12 @@ def _check_u64(name: str, value) -> int:
     return int(value)
 
 
-def _philox_numpy(seed: int, step: int, count: int) -> np.ndarray:
+def _philox_numpy(seed: int, step: int, count: int, first: int = 0) -> np.ndarray:
     """Philox4x32-10 in uint64 arithmetic (a product of two 32-bit words fits): the words ``[count, 4]`` of components
-    ``0 .. count - 1`` at ``step``, counter ``(i lo, i hi, step lo, step hi)``, key ``(seed lo, seed hi)``."""
+    ``first .. first + count - 1`` at ``step``, counter ``(i lo, i hi, step lo, step hi)``, key ``(seed lo, seed hi)``."""
     u = np.uint64
     mask, s32 = u(_M32), u(32)
-    i = np.arange(count, dtype=np.uint64)
+    i = np.arange(first, first + count, dtype=np.uint64)
     c0, c1 = i & mask, i >> s32
     c2, c3 = np.full(count, step & _M32, dtype=np.uint64), np.full(count, step >> 32, dtype=np.uint64)
     k0, k1 = seed & _M32, seed >> 32
@@ -611,3 +637,279 @@ class Langevin(_DeviceMD):
         self.friction, self.seed = float(state["friction"]), _check_u64("seed", state["seed"])
         self._write_state(nsteps=int(state["nsteps"]))
         self._evaluate()
+
+
+# ---- constant pressure ---------------------------------------------------------------------------------------------------------
+# the 8-byte words of nqa_md_npt_state (include/nequip_amd.h)
+_NPT_A, _NPT_P0, _NPT_INDEX, _NPT_MU, _NPT_P, _NPT_EKIN, _NPT_VOLUME, _NPT_FAILED = range(8)
+
+
+def _det3(c: torch.Tensor) -> torch.Tensor:
+    """The determinant of ``[3, 3]`` by cofactors along the first row, in the order of the kernel."""
+    return (c[0, 0] * (c[1, 1] * c[2, 2] - c[1, 2] * c[2, 1]) - c[0, 1] * (c[1, 0] * c[2, 2] - c[1, 2] * c[2, 0])
+            + c[0, 2] * (c[1, 0] * c[2, 1] - c[1, 1] * c[2, 0]))
+
+
+class LangevinNPT(Langevin):
+    """Isotropic NPT dynamics of one system, state and cell on the device of ``positions``: the BAOAB step of ``Langevin``
+    followed by a stochastic cell rescaling barostat (Bernetti and Bussi, J. Chem. Phys. 153, 114107, 2020), which is first order
+    in the volume and samples the isothermal-isobaric ensemble.  It shares ``kB T`` and the noise generator with the thermostat.
+    With ``F`` the force and ``sigma`` the stress at the positions ``x`` and the cell ``C`` (rows are the lattice vectors) of the
+    start of the step, ``s`` the count of completed steps and ``a = compressibility dt / taup``::
+
+        x', v2 = the B, A, O, A of ``Langevin`` (the closing B is deferred to the next step, as there)
+        K      = 1/2 sum m v^2 over the completed velocities;  V = |det C|
+        P      = (2 K) / (3 V) - (sigma_00 + sigma_11 + sigma_22) / 3
+        xi     = langevin_noise(seed, s, 3N + 1)[3N]            (one past the atoms' components: independent of their noise)
+        d_eps  = -a (p0 - P) + sqrt((2 kB T a) / V) xi;  mu = exp(d_eps / 3)
+        C      = mu C;  x = mu x';  v2 = v2 / mu
+
+    then ``force_step`` at the new ``(x, C)``.  The pressure that drives a step is the one of its start, applied after the move:
+    the force is evaluated once per step, and ``taup >> dt``.  ``compressibility = 0`` gives ``mu = 1`` exactly, the trajectory of
+    ``Langevin`` with the same seed bit for bit.  A ``mu`` that is not finite or a cell without volume leaves ``mu = 1`` and sets
+    a flag in the device record; the next read of ``nsteps``, ``pressure`` or ``volume`` raises ``RuntimeError``.
+
+    Three HIP launches (``csrc/md.hip``: ``nqa_md_langevin_step`` + ``nqa_md_npt_bath`` + ``nqa_md_npt_scale``); the second writes
+    ``C`` into ``cell``, the ``[1, 3, 3]`` float64 buffer that ``force_step`` is handed at every call, so nothing of a step passes
+    through the host.
+
+    ``force_step``: ``(positions [N, 3], cell [1, 3, 3]) -> {"forces", "total_energy", "stress"}`` (the stress ``[3, 3]`` or
+    ``[1, 3, 3]``, float32 or float64, ``(1/V) dE/d(strain)``: ASE's sign, what ``CellFIRE`` takes), or a ``GraphedStep`` built
+    with ``outputs=(total_energy, forces, stress)`` in a fully periodic cell (its cell is set by ``set_cell_from_device``).
+    ``pressure``: the target ``p0`` in eV/A^3 (``1.0 * units.bar``); ``compressibility`` in A^3/eV (``4.57e-5 / units.bar`` for
+    water); ``taup`` in time units.  The other arguments and the interface are those of ``Langevin``; added are ``cell`` (the
+    live buffer), ``volume``, ``pressure`` (the ``P`` of the last step; 0 before the first), ``stress``, ``target_pressure``,
+    ``set_pressure`` and ``set_barostat``.
+
+    Not provided: anisotropic or semi-isotropic cells, batches of systems, Nose-Hoover / MTK barostats."""
+
+    def __init__(self, force_step, masses: torch.Tensor, timestep: float, temperature: float, friction: float, pressure: float,
+                 compressibility: float, taup: float, positions: torch.Tensor, cell: torch.Tensor,
+                 velocities: Optional[torch.Tensor] = None, seed: int = 0, remove_drift: bool = False, backend: str = "auto"):
+        if hasattr(force_step, "set_cell_from_device") and not all(getattr(force_step, "_pbc", (True,) * 3)):
+            raise ValueError("NPT around a GraphedStep needs all three directions periodic")
+        force_step = _cell_following_step(force_step)
+        self._check_system(force_step, masses, positions, velocities, timestep)
+        self._check_temperature(temperature)
+        self._check_friction(friction)
+        self._check_pressure(pressure)
+        self._check_barostat(compressibility, taup)
+        if not isinstance(cell, torch.Tensor) or tuple(cell.shape) not in ((3, 3), (1, 3, 3)):
+            raise ValueError("cell must be a tensor of shape [3, 3] or [1, 3, 3], got "
+                             f"{tuple(cell.shape) if isinstance(cell, torch.Tensor) else type(cell).__name__}")
+        if cell.device != positions.device:
+            raise ValueError(f"mixed devices: positions on {positions.device}, cell on {cell.device}")
+        self._check_cell(cell)
+        self.seed = _check_u64("seed", seed)
+        self.friction = float(friction)
+        self._temperature = float(temperature)
+        self._dt = float(timestep)
+        self._p0, self.compressibility, self.taup = float(pressure), float(compressibility), float(taup)
+        self._setup(force_step, masses, positions, velocities, remove_drift, backend)
+        self._cell = cell.detach().to(torch.float64).reshape(1, 3, 3).contiguous().clone()
+        self._stress: Optional[torch.Tensor] = None
+        if self._hip:
+            self._par = torch.zeros(4, dtype=torch.float64, device=self.device)
+            self._par_i = self._par.view(torch.int64)
+            self._npt = torch.zeros(8, dtype=torch.float64, device=self.device)
+            self._npt_i = self._npt.view(torch.int64)
+        self._write_state(nsteps=0)
+        self._evaluate()
+
+    # ---- state -------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_pressure(pressure) -> None:
+        if not (isinstance(pressure, (int, float)) and math.isfinite(pressure)):
+            raise ValueError(f"pressure must be finite, got {pressure!r}")
+
+    @staticmethod
+    def _check_barostat(compressibility, taup) -> None:
+        if not (compressibility >= 0.0 and math.isfinite(compressibility)):
+            raise ValueError(f"compressibility must be non-negative and finite, got {compressibility!r}")
+        if not (taup > 0.0 and math.isfinite(taup)):
+            raise ValueError(f"taup must be positive and finite, got {taup!r}")
+
+    @staticmethod
+    def _check_cell(cell: torch.Tensor) -> None:
+        c = cell.detach().to(torch.float64).reshape(3, 3).cpu().numpy()
+        scale = float(np.prod(np.linalg.norm(c, axis=1)))
+        if not np.isfinite(c).all() or not abs(float(np.linalg.det(c))) > 1e-12 * max(scale, 1e-300):
+            raise ValueError("cell is singular: its lattice vectors do not span a volume")
+
+    def _write_params(self) -> None:
+        """The thermostat's record and the two words of the barostat's that the host owns beside the noise index."""
+        super()._write_params()
+        self._a = self.compressibility * self._dt / self.taup
+        if self._hip:
+            self._npt[_NPT_A:_NPT_A + 1].fill_(self._a)
+            self._npt[_NPT_P0:_NPT_P0 + 1].fill_(self._p0)
+
+    def _write_state(self, nsteps: int) -> None:
+        """All three records, with ``velocities`` taken as completed, ``mu = 1`` and the flag cleared."""
+        super()._write_state(nsteps)
+        if self._hip:
+            words = torch.zeros(8, dtype=torch.float64)
+            words[_NPT_A], words[_NPT_P0], words[_NPT_MU] = self._a, self._p0, 1.0
+            words.view(torch.int64)[_NPT_INDEX] = 3 * self.num_atoms
+            self._npt.copy_(words)
+        else:
+            self._mu = torch.ones((), dtype=torch.float64, device=self.device)
+            self._pressure = torch.zeros((), dtype=torch.float64, device=self.device)
+            self._failed = torch.zeros((), dtype=torch.bool, device=self.device)
+
+    def set_pressure(self, pressure: float) -> None:
+        """The target pressure (eV/A^3) from the next step on; written in place, nothing is read back."""
+        self._check_pressure(pressure)
+        self._p0 = float(pressure)
+        self._write_params()
+
+    def set_barostat(self, compressibility: float, taup: float) -> None:
+        """Compressibility (A^3/eV) and relaxation time from the next step on; ``a`` is written in place."""
+        self._check_barostat(compressibility, taup)
+        self.compressibility, self.taup = float(compressibility), float(taup)
+        self._write_params()
+
+    def _evaluate(self) -> None:
+        out = self.force_step(self._pos, self._cell)
+        stress = out.get(AtomicDataDict.STRESS_KEY) if hasattr(out, "get") else None
+        if stress is None:
+            raise ValueError("stress: force_step must return it ([3, 3] or [1, 3, 3]) next to the forces for NPT")
+        stress = stress.detach()
+        if tuple(stress.shape) not in ((3, 3), (1, 3, 3)) or stress.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"stress: force_step must return float32 or float64 [3, 3] or [1, 3, 3], got {stress.dtype} "
+                             f"{tuple(stress.shape)}")
+        if stress.device != self.device:
+            raise ValueError(f"mixed devices: positions on {self.device}, stress on {stress.device}")
+        f = out[AtomicDataDict.FORCE_KEY].detach()
+        if tuple(f.shape) != (self.num_atoms, 3) or f.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"force_step must return float32 or float64 forces [{self.num_atoms}, 3], got {f.dtype} "
+                             f"{tuple(f.shape)}")
+        if f.device != self.device:
+            raise ValueError(f"mixed devices: positions on {self.device}, forces on {f.device}")
+        self._out, self._forces, self._stress = out, f.contiguous(), stress.reshape(3, 3).contiguous()
+
+    # ---- the two forms of a step --------------------------------------------------------------------------------------------
+    def _launch(self, finish_only: bool, bath: bool = True) -> None:
+        if finish_only:
+            return super()._launch(finish_only, bath)
+        super()._launch(False, bath=False)
+        lib, L = self._lib.load(), self._lib
+        sig = self._stress
+        stream = L.stream_ptr(self.device)
+        L.check(lib.nqa_md_npt_bath(L.ptr(self._partials), self._n_partials, L.ptr(self._rec), L.ptr(self._par), L.ptr(self._npt),
+                                    L.NQA_F64 if sig.dtype == torch.float64 else L.NQA_F32, L.ptr(sig), L.ptr(self._cell),
+                                    stream), "nqa_md_npt_bath")
+        L.check(lib.nqa_md_npt_scale(L.ptr(self._pos), L.ptr(self._vel), self.num_atoms, L.ptr(self._npt), stream),
+                "nqa_md_npt_scale")
+
+    def _aten_step(self) -> None:
+        step, sig, n3 = self._nsteps, self._stress.to(torch.float64), 3 * self.num_atoms
+        super()._aten_step()
+        ekin, cell = self._ekin, self._cell[0]
+        vol = _det3(cell).abs()
+        three = torch.full_like(vol, 3.0)  # (tensor divisors: a true division on every device)
+        p = (2.0 * ekin) / (3.0 * vol) - (sig[0, 0] + sig[1, 1] + sig[2, 2]) / three
+        xi = float(_normals_numpy(_philox_numpy(self.seed, step, 1, first=n3))[0])
+        a = self._a
+        d_eps = -a * (self._p0 - p) + torch.sqrt(torch.full_like(vol, 2.0 * self._kt * a) / vol) * xi
+        mu = torch.exp(d_eps / three)
+        bad = ~torch.isfinite(mu) | ~(vol > 0.0)
+        mu = torch.where(bad, torch.ones_like(mu), mu)
+        self._failed = self._failed | bad
+        self._cell.copy_(mu * self._cell)
+        self._pos.copy_(mu * self._pos)
+        self._vel.copy_(self._vel / mu)
+        self._mu, self._pressure = mu, p
+
+    # ---- interface ----------------------------------------------------------------------------------------------------------
+    def _check_failed(self, failed: bool) -> None:
+        if failed:
+            raise RuntimeError("the barostat met a scaling factor that is not finite or a cell without volume: the run is invalid "
+                               "from that step on (smaller compressibility / taup or time step)")
+
+    @property
+    def nsteps(self) -> int:
+        self._check_failed(bool(self._npt_i[_NPT_FAILED]) if self._hip else bool(self._failed))
+        return super().nsteps
+
+    @property
+    def cell(self) -> torch.Tensor:
+        """``[1, 3, 3]`` float64, rows are the lattice vectors: the live buffer that ``force_step`` reads."""
+        return self._cell
+
+    @property
+    def stress(self) -> torch.Tensor:
+        """``[3, 3]``: the stress ``force_step`` returned last, at the current positions and cell."""
+        return self._stress
+
+    @property
+    def target_pressure(self) -> float:
+        return self._p0
+
+    @property
+    def pressure(self) -> float:
+        """The ``P`` that drove the last step (eV/A^3; kinetic plus potential part, at the start of that step); one copy."""
+        if self._hip:
+            words = self._npt[_NPT_P:].cpu()
+            self._check_failed(bool(words.view(torch.int64)[_NPT_FAILED - _NPT_P]))
+            return float(words[0])
+        self._check_failed(bool(self._failed))
+        return float(self._pressure)
+
+    @property
+    def volume(self) -> float:
+        """``|det C|`` of the current cell (A^3)."""
+        self._check_failed(bool(self._npt_i[_NPT_FAILED]) if self._hip else bool(self._failed))
+        return float(_det3(self._cell[0]).abs())
+
+    # ---- checkpoints --------------------------------------------------------------------------------------------------------
+    def state_dict(self) -> Dict[str, object]:
+        state = super().state_dict()
+        state.update({"cell": self._cell.detach().clone(), "pressure": self._p0, "compressibility": self.compressibility,
+                      "taup": self.taup})
+        return state
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        if "compressibility" not in state or "cell" not in state:
+            raise ValueError("the state was not saved by a LangevinNPT run (it holds no cell and no barostat)")
+        cell = state["cell"]
+        if tuple(cell.shape) != (1, 3, 3):
+            raise ValueError(f"the state holds a cell of shape {tuple(cell.shape)}, this run has one system ([1, 3, 3])")
+        if tuple(state["positions"].shape) != (self.num_atoms, 3) or "friction" not in state or "seed" not in state:
+            raise ValueError(f"the state was not saved by a LangevinNPT run of {self.num_atoms} atoms")
+        self._check_pressure(state["pressure"])
+        self._check_barostat(state["compressibility"], state["taup"])
+        self._check_cell(cell)
+        self._cell.copy_(cell)
+        self._p0 = float(state["pressure"])
+        self.compressibility, self.taup = float(state["compressibility"]), float(state["taup"])
+        super().load_state_dict(state)
+
+    # ---- Atoms --------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_atoms(cls, atoms, model_or_step, *args, device="cuda", r_max: Optional[float] = None, chemical_symbols=None,
+                   **kwargs):
+        """The driver for an ``Atoms`` object (positions, velocities, masses, cell, periodicity, species); ``args`` and
+        ``kwargs`` are the constructor's between ``masses`` and ``positions`` (``timestep, temperature, friction, pressure,
+        compressibility, taup``) and after ``velocities``.  ``model_or_step``: an eval-mode model (a ``GraphedStep`` with energy,
+        forces and stress is built around it, which needs ``r_max`` and all three directions periodic) or a ready
+        ``force_step``."""
+        device = torch.device(device)
+        pos = torch.as_tensor(np.asarray(atoms.get_positions(), dtype=np.float64)).to(device)
+        vel = atoms.get_velocities()
+        vel = None if vel is None else torch.as_tensor(np.asarray(vel, dtype=np.float64)).to(device)
+        masses = torch.as_tensor(np.asarray(atoms.get_masses(), dtype=np.float64)).to(device)
+        cell = torch.as_tensor(np.asarray(atoms.get_cell(), dtype=np.float64).reshape(3, 3)).to(device)
+        step = model_or_step
+        if isinstance(model_or_step, torch.nn.Module):
+            if not all(bool(b) for b in np.asarray(atoms.get_pbc(), dtype=bool).reshape(3)):
+                raise ValueError("NPT around a GraphedStep needs all three directions periodic")
+            K = AtomicDataDict
+            step = _graphed_step_for(atoms, model_or_step, device, r_max, chemical_symbols,
+                                     outputs=(K.TOTAL_ENERGY_KEY, K.FORCE_KEY, K.STRESS_KEY))
+        return cls(step, masses, *args, positions=pos, cell=cell, velocities=vel, **kwargs)
+
+    def write_back(self, atoms) -> None:
+        """Cell, positions and completed velocities into ``atoms`` (one copy each; the positions are already the scaled ones)."""
+        atoms.set_cell(self._cell[0].detach().cpu().numpy(), scale_atoms=False)
+        super().write_back(atoms)

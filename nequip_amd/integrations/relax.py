@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from ..data import AtomicDataDict
-from .md import _DeviceMD, _graphed_step_for
+from .md import _cell_following_step, _DeviceMD, _graphed_step_for
 
 # the 8-byte words of nqa_fire_system (include/nequip_amd.h); word 11 is two 32-bit halves: nmin, converged
 _DT, _A, _NPOS, _NSTEPS, _DTMAX, _MAXSTEP, _FINC, _FDEC, _ASTART, _FA, _TARGET, _NMIN_CONVERGED, _CV, _CF, _SCALE, _FMAX = range(16)
@@ -504,16 +504,7 @@ class CellFIRE(FIRE):
                  hydrostatic_strain: bool = False, constant_volume: bool = False, mask=None, dt: float = 0.1,
                  maxstep: float = 0.2, dtmax: float = 1.0, nmin: int = 5, finc: float = 1.1, fdec: float = 0.5,
                  astart: float = 0.1, fa: float = 0.99, backend: str = "auto"):
-        if hasattr(force_step, "set_cell_from_device"):  # a GraphedStep: the cell goes in through its own buffers
-            graphed = force_step
-            if AtomicDataDict.STRESS_KEY not in getattr(graphed, "outputs", ()):
-                raise ValueError("stress: the GraphedStep must be built with outputs=(total_energy, forces, stress)")
-
-            def force_step(pos, cell_buffer, _step=graphed):
-                _step.set_cell_from_device(cell_buffer)
-                return _step(pos)
-
-            force_step.device = getattr(graphed, "device", None)
+        force_step = _cell_following_step(force_step)
         self._setup(force_step, positions, system_idx, fixed, dict(dt=dt, maxstep=maxstep, dtmax=dtmax, nmin=nmin, finc=finc,
                                                                    fdec=fdec, astart=astart, fa=fa), backend, _CELL_WORDS)
         S, device = self.num_systems, self.device
