@@ -1290,6 +1290,52 @@ int nqa_md_npt_bath(const double* partials, int64_t num_partials, nqa_md_state* 
 int nqa_md_npt_scale(double* positions, double* velocities, int64_t num_atoms, const nqa_md_npt_state* npt, nqa_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batched Langevin NVT and NPT: S independent systems concatenated along the atom axis (system s has n_s atoms, contiguous),
+ *   each with its own records, as arrays: nqa_md_state[S], nqa_md_langevin_params[S], nqa_md_npt_state[S] (noise_index = 3 n_s),
+ *   cells and stresses [S, 3, 3].  One step of the whole batch is nqa_md_batched_langevin_step + nqa_md_batched_bath (NVT), or
+ *   nqa_md_batched_langevin_step + nqa_md_batched_npt_bath + nqa_md_batched_npt_scale (NPT), on the same stream, then one force
+ *   evaluation by the caller.  System s takes, BIT FOR BIT, the steps that nqa_md_langevin_step + nqa_md_bath (or the NPT
+ *   three) take for it alone with the same records, forces and stress: the arithmetic is the same device functions, and
+ *   - the noise of a component is drawn for (seed of its system, nsteps of its system, j) with j the component's index INSIDE
+ *     its system, 0 .. 3 n_s - 1, never the global index;
+ *   - the components are cut into chunks (nqa_md_chunk): chunk k of system s covers its local components
+ *     [NQA_MD_THREADS k, min(NQA_MD_THREADS (k + 1), 3 n_s)): the workgroups of nqa_md_langevin_step for n_s atoms.  A chunk may
+ *     straddle two atoms, never two systems.  chunk_begin[s] .. chunk_begin[s + 1] are the chunks of system s, in order;
+ *     there are nqa_md_num_partials(n_s) of them.  The host builds both tables once.
+ * nqa_md_batched_langevin_step: one workgroup per chunk, one component per lane; (1) and (2) of nqa_md_langevin_step with dt,
+ *   fresh, nsteps, c1, c2, kT and seed of the chunk's system.  Row c of `partials` (2 doubles per chunk) = the sums of chunk c.
+ *   NQA_MD_FINISH_ONLY: only (1), into `vel_out`, as there.
+ * nqa_md_batched_bath: one wavefront per system; lane b adds the contiguous run of ceil(P_s / 64) rows of its system in
+ *   ascending order, the lanes are merged by the tree of nqa_md_bath; then kinetic_energy = S / 2, nsteps += 1, fresh = 0 (or, in
+ *   the finish-only mode, observed_kinetic_energy) in the record of that system.  There is no thermostat bit.
+ * nqa_md_batched_npt_bath: one wavefront per system; the sum as above, then lane 0 as in nqa_md_npt_bath with the records,
+ *   stress and cell of that system.  A mu that is not finite or a cell without volume sets `failed` of that system alone.
+ * nqa_md_batched_npt_scale: one workgroup per chunk: x = mu x;  v2 = v2 / mu with the mu of the chunk's system.
+ *   The records are rewritten only by the second launch; mu is written by the second and read by the third: no launch sees a
+ *   word that a launch of the same step rewrites after it started.  No atomics, no FMA contraction, no allocation, no host
+ *   synchronisation: the launches capture into a hipGraph.  Every entry refuses null pointers, num_systems <= 0,
+ *   num_chunks <= 0, unknown dtypes and unknown mode bits before anything is launched.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct nqa_md_chunk {
+  int64_t component0;    /* the flat (global) component of the chunk's first lane */
+  int64_t local0;        /* the same component counted from the first of its system: NQA_MD_THREADS k */
+  int32_t count, system; /* components component0 .. component0 + count - 1 (count <= NQA_MD_THREADS) of system `system` */
+} nqa_md_chunk;
+
+int nqa_md_batched_langevin_step(int32_t force_dtype, const void* forces, const double* masses, double* positions,
+                                 double* velocities, double* vel_out, const nqa_md_chunk* chunks, int64_t num_chunks,
+                                 const nqa_md_state* states, const nqa_md_langevin_params* params,
+                                 double* partials /* 2 doubles per chunk */, int32_t mode, nqa_stream stream);
+int nqa_md_batched_bath(const double* partials, const int64_t* chunk_begin /* [num_systems + 1] */, nqa_md_state* states,
+                        int64_t num_systems, int32_t mode, nqa_stream stream);
+int nqa_md_batched_npt_bath(const double* partials, const int64_t* chunk_begin, nqa_md_state* states,
+                            const nqa_md_langevin_params* params, nqa_md_npt_state* npt, int32_t stress_dtype,
+                            const void* stress /* [S, 3, 3] */, double* cell /* [S, 3, 3] */, int64_t num_systems,
+                            nqa_stream stream);
+int nqa_md_batched_npt_scale(double* positions, double* velocities, const nqa_md_chunk* chunks, int64_t num_chunks,
+                             const nqa_md_npt_state* npt, nqa_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * FIRE structural relaxation (Bitzek et al. 2006; ASE's defaults and step cap; massless dynamics, fixed cell) with the state in
  *   device memory: positions and velocities (float64, [N, 3]) and one nqa_fire_system record per system.  A batch of independent
  *   systems is concatenated along the atom axis; the atoms are cut into chunks of at most NQA_FIRE_CHUNK atoms, none of which

@@ -409,6 +409,13 @@ SIGNATURES = {
     "nqa_md_npt_bath": (
         c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "nqa_md_npt_scale": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "nqa_md_batched_langevin_step": (
+        c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                  c_int32, c_void_p]),
+    "nqa_md_batched_bath": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "nqa_md_batched_npt_bath": (
+        c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "nqa_md_batched_npt_scale": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "nqa_fire_chunk_atoms": (c_int32, []),
     "nqa_fire_reduce": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "nqa_fire_decide": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -31,7 +31,8 @@ SPEC_DIR = os.path.join(HERE, "generated_spec")
 SOURCES = ["plan.cpp", "csr.hip", "tp_generic.hip", "edge_embed.hip", "edge_vectors.hip", "radial_mlp.hip", "node_ops.hip",
            "neighbor_list.hip", "wgrad.hip", "edge_pairs.hip", "energy_head.hip",
            "pair_potential.hip", "metrics.hip", "ema.hip", "stats.hip", "config.hip",
-           "training_stats.hip", "schedulefree.hip", "adam.hip", "md.hip", "relax.hip", "relax_cell.hip"]
+           "training_stats.hip", "schedulefree.hip", "adam.hip", "md.hip", "md_batched.hip", "relax.hip",
+           "relax_cell.hip"]
 ARCH = "gfx950"
 
 

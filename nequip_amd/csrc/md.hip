@@ -30,28 +30,24 @@
 //
 // Langevin (BAOAB) dynamics, further down, takes the same two launches: md_langevin_step_kernel, with its noise made on the
 // device from a counter-based generator, then md_bath_kernel with the thermostat off.
+//
+// The generator, the arithmetic of a Langevin component, the partial row of a workgroup, the sum of the rows and the lane-0
+// arithmetic of the bath launches are device functions of md_device.h, which md_batched.hip (a batch of systems) calls too.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
 
 #include "launch_status.h"
+#include "md_device.h"
 #include "nequip_amd.h"
 
 #pragma clang fp contract(off)
 
 namespace nqa {
 
-constexpr int MD_THREADS = NQA_MD_THREADS;
-constexpr int MD_WAVES = MD_THREADS / 64;
+// MD_THREADS, MD_WAVES, md_wave_sum, md_block_partials, md_sum_rows and md_bath_update: md_device.h (shared with md_batched.hip)
 static_assert(sizeof(nqa_md_state) == 64, "the host writes the record as eight 8-byte words");
-
-// lane 0 ends with the 64 values added by a fixed tree
-__device__ __forceinline__ double md_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-  return v;
-}
 
 template <typename F>
 __global__ __launch_bounds__(MD_THREADS) void md_step_kernel(const F* __restrict__ forces, const double* __restrict__ masses,
@@ -59,7 +55,6 @@ __global__ __launch_bounds__(MD_THREADS) void md_step_kernel(const F* __restrict
                                                               double* __restrict__ vel_out, int64_t n3,
                                                               const nqa_md_state* __restrict__ state,
                                                               double* __restrict__ partials, int finish_only) {
-  __shared__ double waves[MD_WAVES][2];
   const int64_t i = (int64_t)blockIdx.x * MD_THREADS + threadIdx.x;
   const double dt = state->dt, xi = state->xi;
   const bool fresh = state->fresh != 0;
@@ -81,51 +76,15 @@ __global__ __launch_bounds__(MD_THREADS) void md_step_kernel(const F* __restrict
       s_half = m * vh * vh;
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  s_full = md_wave_sum(s_full);
-  s_half = md_wave_sum(s_half);
-  if (lane == 0) {
-    waves[wave][0] = s_full;
-    waves[wave][1] = s_half;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = waves[0][0], b = waves[0][1];
-#pragma unroll
-    for (int k = 1; k < MD_WAVES; ++k) {
-      a += waves[k][0];
-      b += waves[k][1];
-    }
-    partials[2 * (int64_t)blockIdx.x] = a;
-    partials[2 * (int64_t)blockIdx.x + 1] = b;
-  }
+  md_block_partials(s_full, s_half, partials + 2 * (int64_t)blockIdx.x);
 }
 
 __global__ __launch_bounds__(64) void md_bath_kernel(const double* __restrict__ partials, int64_t num_partials,
                                                      nqa_md_state* __restrict__ state, int finish_only, int thermostat) {
-  const int lane = threadIdx.x;
-  const int64_t per = (num_partials + 63) / 64;
-  const int64_t lo = lane * per, hi = lo + per < num_partials ? lo + per : num_partials;
-  double s_full = 0.0, s_half = 0.0;
-  for (int64_t k = lo; k < hi; ++k) {
-    s_full += partials[2 * k];
-    s_half += partials[2 * k + 1];
-  }
-  s_full = md_wave_sum(s_full);
-  s_half = md_wave_sum(s_half);
-  if (lane != 0) return;
-  if (finish_only) {
-    state->observed_kinetic_energy = 0.5 * s_full;
-    return;
-  }
-  if (thermostat) {
-    const double hdt = 0.5 * state->dt, g = state->g, q = state->q;
-    const double xi_half = state->xi + hdt * (0.5 * (s_full - g)) / q;
-    state->xi = xi_half + hdt * (0.5 * (s_half - g)) / q;
-  }
-  state->kinetic_energy = 0.5 * s_full;
-  state->nsteps += 1;
-  state->fresh = 0;
+  double s_full, s_half;
+  md_sum_rows(partials, num_partials, true, s_full, s_half);
+  if (threadIdx.x != 0) return;
+  md_bath_update(state, s_full, s_half, finish_only, thermostat);
 }
 
 inline int64_t md_num_partials(int64_t num_atoms) { return (3 * num_atoms + MD_THREADS - 1) / MD_THREADS; }
@@ -140,32 +99,7 @@ inline int64_t md_num_partials(int64_t num_atoms) { return (3 * num_atoms + MD_T
 // launches draws fresh noise at every replay.  Nothing depends on the grid: a run of N atoms and the noise entry draw the same z.
 static_assert(sizeof(nqa_md_langevin_params) == 32, "the host writes the parameters as four 8-byte words");
 
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
-
-// Philox4x32-10 (Salmon et al., Random123): counter (i lo, i hi, step lo, step hi), key (seed lo, seed hi)
-__device__ __forceinline__ void md_philox(uint64_t seed, uint64_t step, uint64_t i, uint32_t w[4]) {
-  uint32_t c0 = (uint32_t)i, c1 = (uint32_t)(i >> 32), c2 = (uint32_t)step, c3 = (uint32_t)(step >> 32);
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
-    const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += PHILOX_W0;
-    k1 += PHILOX_W1;
-  }
-  w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
-}
-
-// u1 in (0, 1] and u2 in [0, 1) from 53 bits each (every operation up to the product with 2 pi is exact), then Box-Muller
-__device__ __forceinline__ double md_normal(const uint32_t w[4]) {
-  const double u1 = ((double)(w[0] >> 5) * 67108864.0 + (double)(w[1] >> 6) + 1.0) * 0x1p-53;
-  const double u2 = ((double)(w[2] >> 5) * 67108864.0 + (double)(w[3] >> 6)) * 0x1p-53;
-  return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-}
+// md_philox, md_normal and md_langevin_component (the arithmetic of one component): md_device.h
 
 // The layout, the partial rows and the order of every sum are md_step_kernel's.  partials[2b] = sum m v^2 over the completed
 // velocities, partials[2b + 1] = sum m v2^2 (0 in the finish-only mode); md_bath_kernel without the thermostat bit reads only
@@ -175,53 +109,12 @@ __global__ __launch_bounds__(MD_THREADS) void md_langevin_step_kernel(
     const F* __restrict__ forces, const double* __restrict__ masses, double* __restrict__ positions,
     double* __restrict__ velocities, double* __restrict__ vel_out, int64_t n3, const nqa_md_state* __restrict__ state,
     const nqa_md_langevin_params* __restrict__ params, double* __restrict__ partials, int finish_only) {
-  __shared__ double waves[MD_WAVES][2];
   const int64_t i = (int64_t)blockIdx.x * MD_THREADS + threadIdx.x;
-  const double dt = state->dt;
-  const bool fresh = state->fresh != 0;
-  const uint64_t step = (uint64_t)state->nsteps;
-  const double hdt = 0.5 * dt;
   double s_full = 0.0, s_half = 0.0;
-  if (i < n3) {
-    const double m = masses[i / 3];
-    const double fm = (double)forces[i] / m;
-    double v = velocities[i];
-    if (!fresh) v = v + hdt * fm;
-    s_full = m * v * v;
-    if (finish_only) {
-      vel_out[i] = v;
-    } else {
-      const double c1 = params->c1, c2 = params->c2, kT = params->kT;
-      uint32_t w[4];
-      md_philox(params->seed, step, (uint64_t)i, w);
-      const double z = md_normal(w);
-      const double v1 = v + hdt * fm;
-      double x = positions[i] + hdt * v1;
-      const double v2 = c1 * v1 + (c2 * sqrt(kT / m)) * z;
-      x = x + hdt * v2;
-      positions[i] = x;
-      velocities[i] = v2;
-      s_half = m * v2 * v2;
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  s_full = md_wave_sum(s_full);
-  s_half = md_wave_sum(s_half);
-  if (lane == 0) {
-    waves[wave][0] = s_full;
-    waves[wave][1] = s_half;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = waves[0][0], b = waves[0][1];
-#pragma unroll
-    for (int k = 1; k < MD_WAVES; ++k) {
-      a += waves[k][0];
-      b += waves[k][1];
-    }
-    partials[2 * (int64_t)blockIdx.x] = a;
-    partials[2 * (int64_t)blockIdx.x + 1] = b;
-  }
+  if (i < n3)
+    md_langevin_component(forces, masses, positions, velocities, vel_out, i, (uint64_t)i, state, params, finish_only, s_full,
+                          s_half);
+  md_block_partials(s_full, s_half, partials + 2 * (int64_t)blockIdx.x);
 }
 
 // the generator on its own: the Philox words and / or the normal of components 0 .. count - 1
@@ -253,39 +146,10 @@ __global__ __launch_bounds__(64) void md_npt_bath_kernel(const double* __restric
                                                          const nqa_md_langevin_params* __restrict__ params,
                                                          nqa_md_npt_state* __restrict__ npt, const S* __restrict__ stress,
                                                          double* __restrict__ cell) {
-  const int lane = threadIdx.x;
-  const int64_t per = (num_partials + 63) / 64;
-  const int64_t lo = lane * per, hi = lo + per < num_partials ? lo + per : num_partials;
-  double s_full = 0.0;
-  for (int64_t k = lo; k < hi; ++k) s_full += partials[2 * k];
-  s_full = md_wave_sum(s_full);
-  if (lane != 0) return;
-  const double ekin = 0.5 * s_full;
-  double c[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) c[k] = cell[k];
-  const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
-  const double vol = fabs(det);
-  const double p = (2.0 * ekin) / (3.0 * vol) - ((double)stress[0] + (double)stress[4] + (double)stress[8]) / 3.0;
-  uint32_t w[4];
-  md_philox(params->seed, (uint64_t)state->nsteps, (uint64_t)npt->noise_index, w);
-  const double xi = md_normal(w);
-  const double a = npt->a;
-  const double d_eps = -a * (npt->p0 - p) + sqrt((2.0 * params->kT * a) / vol) * xi;
-  double mu = exp(d_eps / 3.0);
-  if (!isfinite(mu) || !(vol > 0.0)) {
-    mu = 1.0;
-    npt->failed = 1;
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) cell[k] = mu * c[k];
-  npt->mu = mu;
-  npt->pressure = p;
-  npt->kinetic_energy = ekin;
-  npt->volume = vol;
-  state->kinetic_energy = ekin;
-  state->nsteps += 1;
-  state->fresh = 0;
+  double s_full, s_half;
+  md_sum_rows(partials, num_partials, false, s_full, s_half);
+  if (threadIdx.x != 0) return;
+  md_npt_bath_update(s_full, state, params, npt, stress, cell);
 }
 
 __global__ __launch_bounds__(MD_THREADS) void md_npt_scale_kernel(double* __restrict__ positions, double* __restrict__ velocities,

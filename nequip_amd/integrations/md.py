@@ -34,8 +34,10 @@ that forms the pressure from the kinetic energy and the stress and rescales the 
 ``nqa_md_npt_bath``), then a flat launch that rescales positions and stored velocities (``nqa_md_npt_scale``).  The cell is a
 device buffer that ``force_step(positions, cell)`` reads; a ``GraphedStep`` follows it through ``set_cell_from_device``.
 
-Not provided: anisotropic cells and other barostats, batches of systems under NPT, a centre-of-mass constraint during the run,
-an ``ase.md.MolecularDynamics`` subclass.
+Batches of independent systems: ``BatchedLangevin`` and ``BatchedLangevinNPT`` (``integrations/md_batched.py``).
+
+Not provided: anisotropic cells and other barostats, a centre-of-mass constraint during the run, an
+``ase.md.MolecularDynamics`` subclass.
 """
 
 from __future__ import annotations
@@ -66,6 +68,14 @@ def maxwell_boltzmann_velocities(masses: torch.Tensor, temperature: float,
     where = generator.device if generator is not None else m.device
     xi = torch.randn(m.numel(), 3, dtype=torch.float64, device=where, generator=generator).to(m.device)
     return xi * torch.sqrt(units.kB * float(temperature) / m)[:, None]
+
+
+def _sqrt(t: torch.Tensor) -> torch.Tensor:
+    """The square root, correctly rounded.  ATen's vectorised float64 square root on the CPU is off by an ulp for some
+    arguments; numpy's is IEEE's, as is the device's."""
+    if t.device.type == "cpu":
+        return torch.from_numpy(np.sqrt(t.detach().numpy()))
+    return torch.sqrt(t)
 
 
 def _remove_drift(pos: torch.Tensor, vel: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
@@ -612,7 +622,7 @@ class Langevin(_DeviceMD):
         v1 = v + hdt * fm
         x = self._pos + hdt * v1
         # (a true division: `float / tensor` is the tensor's reciprocal times the float, which rounds twice)
-        v2 = self._c1 * v1 + (self._c2 * torch.sqrt(torch.full_like(mc, self._kt) / mc)) * z
+        v2 = self._c1 * v1 + (self._c2 * _sqrt(torch.full_like(mc, self._kt) / mc)) * z
         self._pos.copy_(x + hdt * v2)
         self._ekin = 0.5 * (mc * v * v).sum()
         self._vel.copy_(v2)
@@ -681,7 +691,8 @@ class LangevinNPT(Langevin):
     live buffer), ``volume``, ``pressure`` (the ``P`` of the last step; 0 before the first), ``stress``, ``target_pressure``,
     ``set_pressure`` and ``set_barostat``.
 
-    Not provided: anisotropic or semi-isotropic cells, batches of systems, Nose-Hoover / MTK barostats."""
+    Not provided: anisotropic or semi-isotropic cells, Nose-Hoover / MTK barostats (batches of systems:
+    ``BatchedLangevinNPT``)."""
 
     def __init__(self, force_step, masses: torch.Tensor, timestep: float, temperature: float, friction: float, pressure: float,
                  compressibility: float, taup: float, positions: torch.Tensor, cell: torch.Tensor,
