@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "nequip_amd.h"
+#include "wave_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -18,12 +19,7 @@ namespace nqa {
 constexpr int MD_THREADS = NQA_MD_THREADS;
 constexpr int MD_WAVES = MD_THREADS / 64;
 
-// lane 0 ends with the 64 values added by a fixed tree
-__device__ __forceinline__ double md_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-  return v;
-}
+__device__ __forceinline__ double md_wave_sum(double v) { return wave_sum(v); }  // (the tree of wave_sum.h)
 
 // The row of a workgroup of MD_THREADS lanes: the lanes of a wavefront by the tree, the four wavefronts in wavefront order.
 // Every lane of the workgroup must call it (it holds a barrier).

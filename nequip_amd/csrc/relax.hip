@@ -17,11 +17,10 @@
 //
 // Layout: the atoms are cut into chunks of at most NQA_FIRE_CHUNK atoms, none of which straddles two systems (the host builds the
 // table once from system_idx).
-//   fire_reduce_kernel   one workgroup per chunk, one atom per lane (so |F|^2 of an atom needs no cross-lane work); the lanes of a
-//                        wavefront are merged by a fixed shuffle tree, the four wavefronts in wavefront order; row b of `partials`
-//                        holds (P, FF, VV, M) of chunk b.
-//   fire_decide_kernel   one wavefront per system: its chunks are dealt to the lanes in contiguous ascending runs and merged by
-//                        the same tree; lane 0 decides and rewrites the record.
+//   fire_reduce_kernel   one workgroup per chunk, one atom per lane (so |F|^2 of an atom needs no cross-lane work); row b of
+//                        `partials` holds (P, FF, VV, M) of chunk b (fire_block_partials).
+//   fire_decide_kernel   one wavefront per system merges its rows (fire_sum_rows); lane 0 decides and rewrites the record
+//                        (fire_decide).  The three are the device functions of fire_device.h, which relax_cell.hip calls too.
 //   fire_move_kernel     one workgroup per chunk, flat over the chunk's 3 * count components.
 // The record hazard is the one md.hip describes: no workgroup of the reduction or of the move may see a half-written record, so
 // the three are three launches on one stream; launches of one stream run in order.  No ticket, no atomics, no fence.
@@ -33,6 +32,7 @@
 #include <cstdint>
 #include <string>
 
+#include "fire_device.h"
 #include "launch_status.h"
 #include "nequip_amd.h"
 
@@ -40,27 +40,9 @@
 
 namespace nqa {
 
-constexpr int FIRE_CHUNK = NQA_FIRE_CHUNK;
-constexpr int FIRE_WAVES = FIRE_CHUNK / 64;
+// FIRE_CHUNK, FIRE_WAVES, fire_block_partials, fire_sum_rows and fire_decide: fire_device.h (shared with relax_cell.hip)
 static_assert(sizeof(nqa_fire_system) == 128, "the host writes the record as sixteen 8-byte words");
 static_assert(sizeof(nqa_fire_chunk) == 16, "the host writes a chunk as two 8-byte words");
-static_assert(FIRE_CHUNK % 64 == 0 && FIRE_CHUNK <= 1024, "one atom per lane of a workgroup of whole wavefronts");
-
-// lane 0 ends with the 64 values added by a fixed tree
-__device__ __forceinline__ double fire_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-  return v;
-}
-
-// the larger of two, a NaN on either side kept (a NaN force must reach fmax, not vanish in a max)
-__device__ __forceinline__ double fire_max(double a, double b) { return (a > b || a != a) ? a : b; }
-
-__device__ __forceinline__ double fire_wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fire_max(v, __shfl_down(v, off));
-  return v;
-}
 
 template <typename F>
 __global__ __launch_bounds__(FIRE_CHUNK) void fire_reduce_kernel(const F* __restrict__ forces,
@@ -68,7 +50,6 @@ __global__ __launch_bounds__(FIRE_CHUNK) void fire_reduce_kernel(const F* __rest
                                                                   const uint8_t* __restrict__ fixed,
                                                                   const nqa_fire_chunk* __restrict__ chunks,
                                                                   double* __restrict__ partials) {
-  __shared__ double waves[FIRE_WAVES][4];
   const nqa_fire_chunk chunk = chunks[blockIdx.x];
   const int count = chunk.count < FIRE_CHUNK ? chunk.count : FIRE_CHUNK;
   double p = 0.0, ff = 0.0, vv = 0.0;
@@ -82,88 +63,15 @@ __global__ __launch_bounds__(FIRE_CHUNK) void fire_reduce_kernel(const F* __rest
       vv = vx * vx + vy * vy + vz * vz;
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double m = fire_wave_max(ff);
-  p = fire_wave_sum(p);
-  ff = fire_wave_sum(ff);
-  vv = fire_wave_sum(vv);
-  if (lane == 0) {
-    waves[wave][0] = p;
-    waves[wave][1] = ff;
-    waves[wave][2] = vv;
-    waves[wave][3] = m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = waves[0][0], b = waves[0][1], c = waves[0][2], d = waves[0][3];
-#pragma unroll
-    for (int k = 1; k < FIRE_WAVES; ++k) {
-      a += waves[k][0];
-      b += waves[k][1];
-      c += waves[k][2];
-      d = fire_max(d, waves[k][3]);
-    }
-    double* row = partials + 4 * (int64_t)blockIdx.x;
-    row[0] = a;
-    row[1] = b;
-    row[2] = c;
-    row[3] = d;
-  }
+  fire_block_partials(p, ff, vv, partials + 4 * (int64_t)blockIdx.x);
 }
 
 __global__ __launch_bounds__(64) void fire_decide_kernel(const double* __restrict__ partials,
                                                          const int64_t* __restrict__ chunk_begin,
                                                          nqa_fire_system* __restrict__ systems) {
-  const int lane = threadIdx.x;
-  const int64_t begin = chunk_begin[blockIdx.x], end = chunk_begin[blockIdx.x + 1];
-  const int64_t n = end > begin ? end - begin : 0;
-  const int64_t per = (n + 63) / 64;
-  const int64_t lo = begin + lane * per, hi = lo + per < begin + n ? lo + per : begin + n;
-  double P = 0.0, FF = 0.0, VV = 0.0, M = 0.0;
-  for (int64_t k = lo; k < hi; ++k) {
-    P += partials[4 * k];
-    FF += partials[4 * k + 1];
-    VV += partials[4 * k + 2];
-    M = fire_max(M, partials[4 * k + 3]);
-  }
-  P = fire_wave_sum(P);
-  FF = fire_wave_sum(FF);
-  VV = fire_wave_sum(VV);
-  M = fire_wave_max(M);
-  if (lane != 0) return;
-  nqa_fire_system* s = systems + blockIdx.x;
-  const bool converged = M < s->fmax_target * s->fmax_target;
-  s->fmax = sqrt(M);
-  s->converged = converged ? 1 : 0;
-  if (converged) return;
-  double dt = s->dt, a = s->a, cv = 0.0, cf = 0.0;
-  int64_t npos = s->npos;
-  if (s->nsteps == 0) {
-    // the first step: the velocities are zero by construction, no branch is taken
-  } else if (P > 0.0) {
-    cv = 1.0 - a;
-    cf = a * sqrt(VV) / sqrt(FF);
-    if (npos > (int64_t)s->nmin) {
-      const double grown = dt * s->finc;
-      dt = grown < s->dtmax ? grown : s->dtmax;
-      a = a * s->fa;
-    }
-    npos += 1;
-  } else {  // downhill no more, or a NaN
-    a = s->astart;
-    dt = dt * s->fdec;
-    npos = 0;
-  }
-  const double c = cf + dt;
-  const double vvn = cv * cv * VV + 2.0 * cv * c * P + c * c * FF;
-  const double normdr = dt * sqrt(vvn);
-  s->scale = normdr > s->maxstep ? s->maxstep / normdr : 1.0;
-  s->cv = cv;
-  s->cf = cf;
-  s->dt = dt;
-  s->a = a;
-  s->npos = npos;
-  s->nsteps += 1;
+  double P, FF, VV, M;
+  fire_sum_rows(partials, chunk_begin[blockIdx.x], chunk_begin[blockIdx.x + 1], P, FF, VV, M);
+  if (threadIdx.x == 0) fire_decide(systems + blockIdx.x, P, FF, VV, M);
 }
 
 template <typename F>

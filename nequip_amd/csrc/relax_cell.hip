@@ -11,8 +11,8 @@
 //   reduce   over the atoms of a chunk, with the D at which F was evaluated (d_new of the record):
 //            P = sum g.v,  FF = sum g.g,  VV = sum v.v,  M = max |g_i|^2
 //   decide   merges the chunks in the fixed order; lane 0 forms G, adds its nine components to P, FF, VV (against the cell velocity
-//            vd) and its three row norms to M;  fmax = sqrt(M), converged = M < fmax_target^2; unless converged: the FIRE branch of
-//            relax.hip word for word (cv, cf, dt, a, npos, scale, nsteps += 1), then the cell move by the same lane:
+//            vd) and its three row norms to M;  then fire_decide of fire_device.h, the decision relax.hip takes (fmax, converged;
+//            unless converged cv, cf, dt, a, npos, scale, nsteps += 1), then the cell move by the same lane:
 //            d_old = d_new;  vd = cv vd + cf G;  vd = vd + dt G;  Q = cell_factor d_old + scale (dt vd);  d_new = Q / cell_factor
 //            C = C0 d_new^T into the [S, 3, 3] float64 cell buffer that the force step reads
 //   move     g = F d_old;  v = cv v + cf g;  v = v + dt g;  q = q + scale (dt v);  x = q d_new^T
@@ -30,6 +30,7 @@
 #include <cstdint>
 #include <string>
 
+#include "fire_device.h"
 #include "launch_status.h"
 #include "nequip_amd.h"
 
@@ -37,28 +38,10 @@
 
 namespace nqa {
 
-constexpr int CELLFIRE_CHUNK = NQA_FIRE_CHUNK;
-constexpr int CELLFIRE_WAVES = CELLFIRE_CHUNK / 64;
+// FIRE_CHUNK, fire_max, fire_block_partials, fire_sum_rows and fire_decide: fire_device.h (shared with relax.hip)
 static_assert(sizeof(nqa_cellfire_system) == 512, "the host writes the record as sixty-four 8-byte words");
 static_assert(sizeof(nqa_cellfire_system) % 8 == 0, "the record is whole 8-byte words");
 static_assert(sizeof(nqa_fire_chunk) == 16, "the host writes a chunk as two 8-byte words");
-static_assert(CELLFIRE_CHUNK % 64 == 0 && CELLFIRE_CHUNK <= 1024, "one atom per lane of a workgroup of whole wavefronts");
-
-// lane 0 ends with the 64 values added by a fixed tree
-__device__ __forceinline__ double cellfire_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-  return v;
-}
-
-// the larger of two, a NaN on either side kept (a NaN force or stress must reach fmax, not vanish in a max)
-__device__ __forceinline__ double cellfire_max(double a, double b) { return (a > b || a != a) ? a : b; }
-
-__device__ __forceinline__ double cellfire_wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = cellfire_max(v, __shfl_down(v, off));
-  return v;
-}
 
 // row vector times matrix: out_j = a_0 m[0][j] + a_1 m[1][j] + a_2 m[2][j], added left to right
 __device__ __forceinline__ void row_times(const double a[3], const double m[9], double out[3]) {
@@ -73,15 +56,14 @@ __device__ __forceinline__ void row_times_transposed(const double a[3], const do
 }
 
 template <typename F>
-__global__ __launch_bounds__(CELLFIRE_CHUNK) void cellfire_reduce_kernel(const F* __restrict__ forces,
+__global__ __launch_bounds__(FIRE_CHUNK) void cellfire_reduce_kernel(const F* __restrict__ forces,
                                                                           const double* __restrict__ velocities,
                                                                           const uint8_t* __restrict__ fixed,
                                                                           const nqa_fire_chunk* __restrict__ chunks,
                                                                           const nqa_cellfire_system* __restrict__ systems,
                                                                           double* __restrict__ partials) {
-  __shared__ double waves[CELLFIRE_WAVES][4];
   const nqa_fire_chunk chunk = chunks[blockIdx.x];
-  const int count = chunk.count < CELLFIRE_CHUNK ? chunk.count : CELLFIRE_CHUNK;
+  const int count = chunk.count < FIRE_CHUNK ? chunk.count : FIRE_CHUNK;
   double D[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) D[k] = systems[chunk.system].d_new[k];
@@ -98,33 +80,7 @@ __global__ __launch_bounds__(CELLFIRE_CHUNK) void cellfire_reduce_kernel(const F
       vv = vx * vx + vy * vy + vz * vz;
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double m = cellfire_wave_max(ff);
-  p = cellfire_wave_sum(p);
-  ff = cellfire_wave_sum(ff);
-  vv = cellfire_wave_sum(vv);
-  if (lane == 0) {
-    waves[wave][0] = p;
-    waves[wave][1] = ff;
-    waves[wave][2] = vv;
-    waves[wave][3] = m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = waves[0][0], b = waves[0][1], c = waves[0][2], d = waves[0][3];
-#pragma unroll
-    for (int k = 1; k < CELLFIRE_WAVES; ++k) {
-      a += waves[k][0];
-      b += waves[k][1];
-      c += waves[k][2];
-      d = cellfire_max(d, waves[k][3]);
-    }
-    double* row = partials + 4 * (int64_t)blockIdx.x;
-    row[0] = a;
-    row[1] = b;
-    row[2] = c;
-    row[3] = d;
-  }
+  fire_block_partials(p, ff, vv, partials + 4 * (int64_t)blockIdx.x);
 }
 
 template <typename T>
@@ -133,23 +89,9 @@ __global__ __launch_bounds__(64) void cellfire_decide_kernel(const double* __res
                                                              const T* __restrict__ stress,
                                                              nqa_cellfire_system* __restrict__ systems,
                                                              double* __restrict__ cell) {
-  const int lane = threadIdx.x;
-  const int64_t begin = chunk_begin[blockIdx.x], end = chunk_begin[blockIdx.x + 1];
-  const int64_t n = end > begin ? end - begin : 0;
-  const int64_t per = (n + 63) / 64;
-  const int64_t lo = begin + lane * per, hi = lo + per < begin + n ? lo + per : begin + n;
-  double P = 0.0, FF = 0.0, VV = 0.0, M = 0.0;
-  for (int64_t k = lo; k < hi; ++k) {
-    P += partials[4 * k];
-    FF += partials[4 * k + 1];
-    VV += partials[4 * k + 2];
-    M = cellfire_max(M, partials[4 * k + 3]);
-  }
-  P = cellfire_wave_sum(P);
-  FF = cellfire_wave_sum(FF);
-  VV = cellfire_wave_sum(VV);
-  M = cellfire_wave_max(M);
-  if (lane != 0) return;
+  double P, FF, VV, M;
+  fire_sum_rows(partials, chunk_begin[blockIdx.x], chunk_begin[blockIdx.x + 1], P, FF, VV, M);
+  if (threadIdx.x != 0) return;
   nqa_cellfire_system* s = systems + blockIdx.x;
 
   // the generalised force of the cell, at the D the stress was evaluated at
@@ -215,43 +157,12 @@ __global__ __launch_bounds__(64) void cellfire_decide_kernel(const double* __res
     VV += vd[k] * vd[k];
   }
 #pragma unroll
-  for (int i = 0; i < 3; ++i) M = cellfire_max(M, G[3 * i] * G[3 * i] + G[3 * i + 1] * G[3 * i + 1] + G[3 * i + 2] * G[3 * i + 2]);
+  for (int i = 0; i < 3; ++i) M = fire_max(M, G[3 * i] * G[3 * i] + G[3 * i + 1] * G[3 * i + 1] + G[3 * i + 2] * G[3 * i + 2]);
 
-  const bool converged = M < s->fmax_target * s->fmax_target;
-  s->fmax = sqrt(M);
-  s->converged = converged ? 1 : 0;
-  if (converged) return;
-  double dt = s->dt, a = s->a, cv = 0.0, cf = 0.0;
-  int64_t npos = s->npos;
-  if (s->nsteps == 0) {
-    // the first step: the velocities are zero by construction, no branch is taken
-  } else if (P > 0.0) {
-    cv = 1.0 - a;
-    cf = a * sqrt(VV) / sqrt(FF);
-    if (npos > (int64_t)s->nmin) {
-      const double grown = dt * s->finc;
-      dt = grown < s->dtmax ? grown : s->dtmax;
-      a = a * s->fa;
-    }
-    npos += 1;
-  } else {  // downhill no more, or a NaN
-    a = s->astart;
-    dt = dt * s->fdec;
-    npos = 0;
-  }
-  const double c = cf + dt;
-  const double vvn = cv * cv * VV + 2.0 * cv * c * P + c * c * FF;
-  const double normdr = dt * sqrt(vvn);
-  const double scale = normdr > s->maxstep ? s->maxstep / normdr : 1.0;
-  s->scale = scale;
-  s->cv = cv;
-  s->cf = cf;
-  s->dt = dt;
-  s->a = a;
-  s->npos = npos;
-  s->nsteps += 1;
+  if (!fire_decide(s, P, FF, VV, M)) return;
 
-  // the cell move
+  // the cell move, with the coefficients the decision just left in the record
+  const double cv = s->cv, cf = s->cf, dt = s->dt, scale = s->scale;
   double Dn[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
@@ -276,7 +187,7 @@ __global__ __launch_bounds__(64) void cellfire_decide_kernel(const double* __res
 }
 
 template <typename F>
-__global__ __launch_bounds__(CELLFIRE_CHUNK) void cellfire_move_kernel(const F* __restrict__ forces, double* __restrict__ positions,
+__global__ __launch_bounds__(FIRE_CHUNK) void cellfire_move_kernel(const F* __restrict__ forces, double* __restrict__ positions,
                                                                         double* __restrict__ coords,
                                                                         double* __restrict__ velocities,
                                                                         const uint8_t* __restrict__ fixed,
@@ -285,7 +196,7 @@ __global__ __launch_bounds__(CELLFIRE_CHUNK) void cellfire_move_kernel(const F* 
   const nqa_fire_chunk chunk = chunks[blockIdx.x];
   const nqa_cellfire_system* s = systems + chunk.system;
   if (s->converged != 0) return;
-  const int count = chunk.count < CELLFIRE_CHUNK ? chunk.count : CELLFIRE_CHUNK;
+  const int count = chunk.count < FIRE_CHUNK ? chunk.count : FIRE_CHUNK;
   if ((int)threadIdx.x >= count) return;
   const double cv = s->cv, cf = s->cf, dt = s->dt, scale = s->scale;
   double Do[9], Dn[9];
@@ -340,10 +251,10 @@ int nqa_cellfire_reduce(int32_t force_dtype, const void* forces, const double* v
   const dim3 grid((unsigned)n_chunks);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (force_dtype == NQA_F64)
-    hipLaunchKernelGGL(cellfire_reduce_kernel<double>, grid, dim3(CELLFIRE_CHUNK), 0, s, (const double*)forces, velocities, fixed,
+    hipLaunchKernelGGL(cellfire_reduce_kernel<double>, grid, dim3(FIRE_CHUNK), 0, s, (const double*)forces, velocities, fixed,
                        chunks, systems, partials);
   else
-    hipLaunchKernelGGL(cellfire_reduce_kernel<float>, grid, dim3(CELLFIRE_CHUNK), 0, s, (const float*)forces, velocities, fixed,
+    hipLaunchKernelGGL(cellfire_reduce_kernel<float>, grid, dim3(FIRE_CHUNK), 0, s, (const float*)forces, velocities, fixed,
                        chunks, systems, partials);
   return launch_status(name);
 }
@@ -395,10 +306,10 @@ int nqa_cellfire_move(int32_t force_dtype, const void* forces, double* positions
   const dim3 grid((unsigned)n_chunks);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (force_dtype == NQA_F64)
-    hipLaunchKernelGGL(cellfire_move_kernel<double>, grid, dim3(CELLFIRE_CHUNK), 0, s, (const double*)forces, positions, coords,
+    hipLaunchKernelGGL(cellfire_move_kernel<double>, grid, dim3(FIRE_CHUNK), 0, s, (const double*)forces, positions, coords,
                        velocities, fixed, chunks, systems);
   else
-    hipLaunchKernelGGL(cellfire_move_kernel<float>, grid, dim3(CELLFIRE_CHUNK), 0, s, (const float*)forces, positions, coords,
+    hipLaunchKernelGGL(cellfire_move_kernel<float>, grid, dim3(FIRE_CHUNK), 0, s, (const float*)forces, positions, coords,
                        velocities, fixed, chunks, systems);
   return launch_status(name);
 }

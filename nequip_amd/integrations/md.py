@@ -50,6 +50,8 @@ import numpy as np
 import torch
 
 from ..data import AtomicDataDict
+from ._driver import (_M32, _det3, _philox_numpy, atoms_tensors, check_cells, checked_forces, checked_stress, select_backend,
+                      state_arrays)
 
 # CODATA 2014, the values behind ase.units
 _e, _amu, _k = 1.6021766208e-19, 1.660539040e-27, 1.38064852e-23
@@ -174,11 +176,7 @@ class _DeviceMD:
     def _setup(self, force_step, masses, positions, velocities, remove_drift, backend) -> None:
         """The backend, the buffers and, on the kernel path, the partial sums and the ``nqa_md_state`` record."""
         device, n = positions.device, int(positions.shape[0])
-        if backend not in ("auto", "hip", "aten"):
-            raise ValueError(f"backend must be 'auto', 'hip' or 'aten', got {backend!r}")
-        if backend == "hip" and device.type != "cuda":
-            raise ValueError("backend='hip' needs device tensors: the kernels run on the GPU")
-        self._hip = backend == "hip" or (backend == "auto" and device.type == "cuda")
+        self._hip = select_backend(backend, device)
         self.force_step = force_step
         self.device = device
         self.num_atoms = n
@@ -208,13 +206,7 @@ class _DeviceMD:
 
     def _evaluate(self) -> None:
         out = self.force_step(self._pos)
-        f = out[AtomicDataDict.FORCE_KEY].detach()
-        if tuple(f.shape) != (self.num_atoms, 3) or f.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"force_step must return float32 or float64 forces [{self.num_atoms}, 3], got {f.dtype} "
-                             f"{tuple(f.shape)}")
-        if f.device != self.device:
-            raise ValueError(f"mixed devices: positions on {self.device}, forces on {f.device}")
-        self._out, self._forces = out, f.contiguous()
+        self._out, self._forces = out, checked_forces(out, self.num_atoms, self.device)
 
     def set_timestep(self, timestep: float) -> None:
         """The time step from the next step on.  The step that is under way is completed with the step it began with."""
@@ -293,10 +285,7 @@ class _DeviceMD:
         built around it, which needs a periodic cell and ``r_max``) or a ready ``force_step``.  ``chemical_symbols``: as for
         ``NequIPCalculator``."""
         device = torch.device(device)
-        pos = torch.as_tensor(np.asarray(atoms.get_positions(), dtype=np.float64)).to(device)
-        vel = atoms.get_velocities()
-        vel = None if vel is None else torch.as_tensor(np.asarray(vel, dtype=np.float64)).to(device)
-        masses = torch.as_tensor(np.asarray(atoms.get_masses(), dtype=np.float64)).to(device)
+        pos, vel, masses = atoms_tensors(atoms, device, "positions", "velocities", "masses")
         step = model_or_step
         if isinstance(model_or_step, torch.nn.Module):
             step = _graphed_step_for(atoms, model_or_step, device, r_max, chemical_symbols)
@@ -407,10 +396,7 @@ class NoseHoover(_DeviceMD):
                 "thermostat": self.thermostat}
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
-        pos, vel = state["positions"], state["velocities"]
-        if tuple(pos.shape) != (self.num_atoms, 3) or tuple(vel.shape) != (self.num_atoms, 3):
-            raise ValueError(f"the state holds {tuple(pos.shape)} positions and {tuple(vel.shape)} velocities, this run has "
-                             f"{self.num_atoms} atoms")
+        pos, vel = state_arrays(state, self.num_atoms)
         if "nvt_bath" not in state or "friction" in state:
             raise ValueError("the state was not saved by a Nose-Hoover / velocity-Verlet run (a Langevin state has no nvt_bath)")
         if bool(state["thermostat"]) != self.thermostat:
@@ -434,29 +420,12 @@ class VelocityVerlet(NoseHoover):
 # ---- Langevin dynamics ---------------------------------------------------------------------------------------------------------
 # the 8-byte words of nqa_md_langevin_params (include/nequip_amd.h)
 _C1, _C2, _KT, _SEED = range(4)
-_M32 = 0xFFFFFFFF
 
 
 def _check_u64(name: str, value) -> int:
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not (0 <= int(value) < 2 ** 64):
         raise ValueError(f"{name} must be an integer in [0, 2^64), got {value!r}")
     return int(value)
-
-
-def _philox_numpy(seed: int, step: int, count: int, first: int = 0) -> np.ndarray:
-    """Philox4x32-10 in uint64 arithmetic (a product of two 32-bit words fits): the words ``[count, 4]`` of components
-    ``first .. first + count - 1`` at ``step``, counter ``(i lo, i hi, step lo, step hi)``, key ``(seed lo, seed hi)``."""
-    u = np.uint64
-    mask, s32 = u(_M32), u(32)
-    i = np.arange(first, first + count, dtype=np.uint64)
-    c0, c1 = i & mask, i >> s32
-    c2, c3 = np.full(count, step & _M32, dtype=np.uint64), np.full(count, step >> 32, dtype=np.uint64)
-    k0, k1 = seed & _M32, seed >> 32
-    for _ in range(10):
-        p0, p1 = u(0xD2511F53) * c0, u(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ u(k0), p1 & mask, (p0 >> s32) ^ c3 ^ u(k1), p0 & mask
-        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
-    return np.stack([c0, c1, c2, c3], axis=1)
 
 
 def _normals_numpy(words: np.ndarray) -> np.ndarray:
@@ -495,7 +464,7 @@ def langevin_noise(seed: int, step: int, count: int, device="cpu", *, backend: s
         with torch.cuda.device(device):
             L.check(L.load().nqa_md_noise(seed, step, count, L.ptr(w), L.ptr(z), L.stream_ptr(device)), "nqa_md_noise")
         return (z, w.to(torch.int64) & _M32) if return_words else z
-    words = _philox_numpy(seed, step, count)
+    words = _philox_numpy(seed, step, np.arange(count, dtype=np.uint64))
     z = torch.from_numpy(_normals_numpy(words)).to(device)
     return (z, torch.from_numpy(words.astype(np.int64)).to(device)) if return_words else z
 
@@ -635,10 +604,7 @@ class Langevin(_DeviceMD):
                 "timestep": self._dt, "temperature": self._temperature, "friction": self.friction, "seed": self.seed}
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
-        pos, vel = state["positions"], state["velocities"]
-        if tuple(pos.shape) != (self.num_atoms, 3) or tuple(vel.shape) != (self.num_atoms, 3):
-            raise ValueError(f"the state holds {tuple(pos.shape)} positions and {tuple(vel.shape)} velocities, this run has "
-                             f"{self.num_atoms} atoms")
+        pos, vel = state_arrays(state, self.num_atoms)
         if "friction" not in state or "seed" not in state or "nvt_bath" in state:
             raise ValueError("the state was not saved by a Langevin run (a Nose-Hoover state has no friction and no seed)")
         self._pos.copy_(pos)
@@ -654,10 +620,16 @@ class Langevin(_DeviceMD):
 _NPT_A, _NPT_P0, _NPT_INDEX, _NPT_MU, _NPT_P, _NPT_EKIN, _NPT_VOLUME, _NPT_FAILED = range(8)
 
 
-def _det3(c: torch.Tensor) -> torch.Tensor:
-    """The determinant of ``[3, 3]`` by cofactors along the first row, in the order of the kernel."""
-    return (c[0, 0] * (c[1, 1] * c[2, 2] - c[1, 2] * c[2, 1]) - c[0, 1] * (c[1, 0] * c[2, 2] - c[1, 2] * c[2, 0])
-            + c[0, 2] * (c[1, 0] * c[2, 1] - c[1, 1] * c[2, 0]))
+def _aten_barostat(ekin, cell, stress, xi, a, p0, kT):
+    """The stochastic cell rescaling of ``LangevinNPT`` over ``[S]`` systems in ATen: ``(mu, p, bad)`` from the kinetic
+    energies, the cells and stresses ``[S, 3, 3]``, one normal each and the ``[S]`` float64 tensors ``a``, ``p0``, ``kB T``."""
+    vol = _det3(cell).abs()
+    three = torch.full_like(vol, 3.0)  # (tensor divisors: a true division on every device)
+    p = (2.0 * ekin) / (3.0 * vol) - (stress[:, 0, 0] + stress[:, 1, 1] + stress[:, 2, 2]) / three
+    d_eps = -a * (p0 - p) + torch.sqrt((2.0 * kT * a) / vol) * xi
+    mu = torch.exp(d_eps / three)
+    bad = ~torch.isfinite(mu) | ~(vol > 0.0)
+    return torch.where(bad, torch.ones_like(mu), mu), p, bad
 
 
 class LangevinNPT(Langevin):
@@ -710,7 +682,7 @@ class LangevinNPT(Langevin):
                              f"{tuple(cell.shape) if isinstance(cell, torch.Tensor) else type(cell).__name__}")
         if cell.device != positions.device:
             raise ValueError(f"mixed devices: positions on {positions.device}, cell on {cell.device}")
-        self._check_cell(cell)
+        check_cells(cell, single=True)
         self.seed = _check_u64("seed", seed)
         self.friction = float(friction)
         self._temperature = float(temperature)
@@ -739,13 +711,6 @@ class LangevinNPT(Langevin):
             raise ValueError(f"compressibility must be non-negative and finite, got {compressibility!r}")
         if not (taup > 0.0 and math.isfinite(taup)):
             raise ValueError(f"taup must be positive and finite, got {taup!r}")
-
-    @staticmethod
-    def _check_cell(cell: torch.Tensor) -> None:
-        c = cell.detach().to(torch.float64).reshape(3, 3).cpu().numpy()
-        scale = float(np.prod(np.linalg.norm(c, axis=1)))
-        if not np.isfinite(c).all() or not abs(float(np.linalg.det(c))) > 1e-12 * max(scale, 1e-300):
-            raise ValueError("cell is singular: its lattice vectors do not span a volume")
 
     def _write_params(self) -> None:
         """The thermostat's record and the two words of the barostat's that the host owns beside the noise index."""
@@ -782,22 +747,8 @@ class LangevinNPT(Langevin):
 
     def _evaluate(self) -> None:
         out = self.force_step(self._pos, self._cell)
-        stress = out.get(AtomicDataDict.STRESS_KEY) if hasattr(out, "get") else None
-        if stress is None:
-            raise ValueError("stress: force_step must return it ([3, 3] or [1, 3, 3]) next to the forces for NPT")
-        stress = stress.detach()
-        if tuple(stress.shape) not in ((3, 3), (1, 3, 3)) or stress.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"stress: force_step must return float32 or float64 [3, 3] or [1, 3, 3], got {stress.dtype} "
-                             f"{tuple(stress.shape)}")
-        if stress.device != self.device:
-            raise ValueError(f"mixed devices: positions on {self.device}, stress on {stress.device}")
-        f = out[AtomicDataDict.FORCE_KEY].detach()
-        if tuple(f.shape) != (self.num_atoms, 3) or f.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"force_step must return float32 or float64 forces [{self.num_atoms}, 3], got {f.dtype} "
-                             f"{tuple(f.shape)}")
-        if f.device != self.device:
-            raise ValueError(f"mixed devices: positions on {self.device}, forces on {f.device}")
-        self._out, self._forces, self._stress = out, f.contiguous(), stress.reshape(3, 3).contiguous()
+        stress = checked_stress(out, 1, self.device, "[3, 3] or [1, 3, 3]", "([3, 3] or [1, 3, 3]) next to the forces for NPT")
+        self._out, self._forces, self._stress = out, checked_forces(out, self.num_atoms, self.device), stress.reshape(3, 3)
 
     # ---- the two forms of a step --------------------------------------------------------------------------------------------
     def _launch(self, finish_only: bool, bath: bool = True) -> None:
@@ -816,16 +767,10 @@ class LangevinNPT(Langevin):
     def _aten_step(self) -> None:
         step, sig, n3 = self._nsteps, self._stress.to(torch.float64), 3 * self.num_atoms
         super()._aten_step()
-        ekin, cell = self._ekin, self._cell[0]
-        vol = _det3(cell).abs()
-        three = torch.full_like(vol, 3.0)  # (tensor divisors: a true division on every device)
-        p = (2.0 * ekin) / (3.0 * vol) - (sig[0, 0] + sig[1, 1] + sig[2, 2]) / three
-        xi = float(_normals_numpy(_philox_numpy(self.seed, step, 1, first=n3))[0])
-        a = self._a
-        d_eps = -a * (self._p0 - p) + torch.sqrt(torch.full_like(vol, 2.0 * self._kt * a) / vol) * xi
-        mu = torch.exp(d_eps / three)
-        bad = ~torch.isfinite(mu) | ~(vol > 0.0)
-        mu = torch.where(bad, torch.ones_like(mu), mu)
+        xi = _normals_numpy(_philox_numpy(self.seed, step, n3))
+        one = lambda value: torch.as_tensor(value, dtype=torch.float64).reshape(1).to(self.device)  # noqa: E731
+        mu, p, bad = (t[0] for t in _aten_barostat(self._ekin.reshape(1), self._cell, sig.reshape(1, 3, 3), one(xi), one(self._a),
+                                                   one(self._p0), one(self._kt)))
         self._failed = self._failed | bad
         self._cell.copy_(mu * self._cell)
         self._pos.copy_(mu * self._pos)
@@ -871,7 +816,7 @@ class LangevinNPT(Langevin):
     def volume(self) -> float:
         """``|det C|`` of the current cell (A^3)."""
         self._check_failed(bool(self._npt_i[_NPT_FAILED]) if self._hip else bool(self._failed))
-        return float(_det3(self._cell[0]).abs())
+        return float(_det3(self._cell).abs())
 
     # ---- checkpoints --------------------------------------------------------------------------------------------------------
     def state_dict(self) -> Dict[str, object]:
@@ -890,7 +835,7 @@ class LangevinNPT(Langevin):
             raise ValueError(f"the state was not saved by a LangevinNPT run of {self.num_atoms} atoms")
         self._check_pressure(state["pressure"])
         self._check_barostat(state["compressibility"], state["taup"])
-        self._check_cell(cell)
+        check_cells(cell, single=True)
         self._cell.copy_(cell)
         self._p0 = float(state["pressure"])
         self.compressibility, self.taup = float(state["compressibility"]), float(state["taup"])
@@ -906,11 +851,7 @@ class LangevinNPT(Langevin):
         forces and stress is built around it, which needs ``r_max`` and all three directions periodic) or a ready
         ``force_step``."""
         device = torch.device(device)
-        pos = torch.as_tensor(np.asarray(atoms.get_positions(), dtype=np.float64)).to(device)
-        vel = atoms.get_velocities()
-        vel = None if vel is None else torch.as_tensor(np.asarray(vel, dtype=np.float64)).to(device)
-        masses = torch.as_tensor(np.asarray(atoms.get_masses(), dtype=np.float64)).to(device)
-        cell = torch.as_tensor(np.asarray(atoms.get_cell(), dtype=np.float64).reshape(3, 3)).to(device)
+        pos, vel, masses, cell = atoms_tensors(atoms, device, "positions", "velocities", "masses", "cell")
         step = model_or_step
         if isinstance(model_or_step, torch.nn.Module):
             if not all(bool(b) for b in np.asarray(atoms.get_pbc(), dtype=bool).reshape(3)):

@@ -21,15 +21,16 @@ active mask, a batched ``GraphedStep``.
 from __future__ import annotations
 
 import math
-from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
 from ..data import AtomicDataDict
-from .md import (_C1, _C2, _DT, _EKIN, _EKIN_OBSERVED, _FRESH, _KT, _M32, _MD_FINISH_ONLY, _NPT_A, _NPT_FAILED, _NPT_INDEX,
-                 _NPT_MU, _NPT_P, _NPT_P0, _NSTEPS, _SEED, _check_u64, _DeviceMD, _normals_numpy, _remove_drift, _sqrt, units)
+from ._driver import (_det3, _philox_numpy, check_cells, checked_forces, checked_stress, padded, padded_layout, select_backend,
+                      state_arrays, torchsim_force_step)
+from .md import (_C1, _C2, _DT, _EKIN_OBSERVED, _FRESH, _KT, _MD_FINISH_ONLY, _NPT_A, _NPT_FAILED, _NPT_INDEX, _NPT_MU, _NPT_P,
+                 _NPT_P0, _NSTEPS, _SEED, _aten_barostat, _check_u64, _DeviceMD, _normals_numpy, _remove_drift, _sqrt, units)
 
 MD_THREADS = 256  # NQA_MD_THREADS (include/nequip_amd.h)
 _CHUNK_DTYPE = np.dtype([("component0", "<i8"), ("local0", "<i8"), ("count", "<i4"), ("system", "<i4")])  # nqa_md_chunk
@@ -72,20 +73,6 @@ def batch_seeds(seed, num_systems: int) -> List[int]:
     return [_check_u64(f"seed of system {s}", v) for s, v in enumerate(seeds)]
 
 
-def _philox_numpy_each(seeds: np.ndarray, steps: np.ndarray, index: np.ndarray) -> np.ndarray:
-    """Philox4x32-10 as ``md._philox_numpy`` with a seed, a step and a component index per element (``uint64`` arrays of one
-    length): the words ``[count, 4]``."""
-    u = np.uint64
-    mask, s32 = u(_M32), u(32)
-    c0, c1, c2, c3 = index & mask, index >> s32, steps & mask, steps >> s32
-    k0, k1 = seeds & mask, seeds >> s32
-    for _ in range(10):
-        p0, p1 = u(0xD2511F53) * c0, u(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & mask, (p0 >> s32) ^ c3 ^ k1, p0 & mask
-        k0, k1 = (k0 + u(0x9E3779B9)) & mask, (k1 + u(0xBB67AE85)) & mask
-    return np.stack([c0, c1, c2, c3], axis=1)
-
-
 def _per_system(name: str, value, num_systems: int) -> np.ndarray:
     """``value`` (a number, or a sequence / array / tensor of one value per system) as float64 ``[S]``."""
     if isinstance(value, torch.Tensor):
@@ -99,13 +86,6 @@ def _per_system(name: str, value, num_systems: int) -> np.ndarray:
     if arr.size != num_systems:
         raise ValueError(f"{name} must be a number or hold one value per system ([{num_systems}]), got {arr.size} values")
     return arr.copy()
-
-
-def _det3(c: torch.Tensor) -> torch.Tensor:
-    """``[S]`` determinants of ``[S, 3, 3]`` by cofactors along the first row, in the order of the kernel."""
-    return (c[:, 0, 0] * (c[:, 1, 1] * c[:, 2, 2] - c[:, 1, 2] * c[:, 2, 1])
-            - c[:, 0, 1] * (c[:, 1, 0] * c[:, 2, 2] - c[:, 1, 2] * c[:, 2, 0])
-            + c[:, 0, 2] * (c[:, 1, 0] * c[:, 2, 1] - c[:, 1, 1] * c[:, 2, 0]))
 
 
 class BatchedLangevin:
@@ -162,11 +142,7 @@ class BatchedLangevin:
         self._friction_h = self._checked("friction", friction)
         self.seeds = batch_seeds(seed, S)
 
-        if backend not in ("auto", "hip", "aten"):
-            raise ValueError(f"backend must be 'auto', 'hip' or 'aten', got {backend!r}")
-        if backend == "hip" and device.type != "cuda":
-            raise ValueError("backend='hip' needs device tensors: the kernels run on the GPU")
-        self._hip = backend == "hip" or (backend == "auto" and device.type == "cuda")
+        self._hip = select_backend(backend, device)
         self.force_step, self.device = force_step, device
         self._system_idx = system_idx.detach().to(torch.long).contiguous().clone()
         self._m = masses.detach().to(torch.float64).contiguous().clone()
@@ -196,10 +172,7 @@ class BatchedLangevin:
             self._rec_i = self._rec.view(torch.int64)
             self._par = torch.zeros(S, 4, dtype=torch.float64, device=device)  # nqa_md_langevin_params[S]
         else:
-            # atom (s, k) of the padded [S, max count] layout that the per-system sums are taken over
-            k = np.arange(int(counts.max()))[None, :]
-            self._pad_mask = torch.from_numpy(k < counts[:, None]).to(device)
-            self._pad_idx = torch.from_numpy(np.where(k < counts[:, None], self._atom_begin[:-1, None] + k, 0)).to(device)
+            self._pad_mask, self._pad_idx = padded_layout(counts, device)
             # the system and the local index of every flat component: what the noise is drawn for
             self._component_system = np.repeat(np.arange(S), 3 * counts)
             self._component_local = (np.arange(3 * n) - 3 * self._atom_begin[self._component_system]).astype(np.uint64)
@@ -305,8 +278,7 @@ class BatchedLangevin:
 
     def _per_system_sum(self, per_atom: torch.Tensor) -> torch.Tensor:
         """``[S]``: the sum of ``per_atom [N]`` over the atoms of every system (the padded layout of ``FIRE``)."""
-        zero = torch.zeros((), dtype=per_atom.dtype, device=per_atom.device)
-        return torch.sum(torch.where(self._pad_mask, per_atom[self._pad_idx], zero), dim=1)
+        return torch.sum(padded(per_atom, self._pad_mask, self._pad_idx), dim=1)
 
     def _kinetic(self, v: torch.Tensor) -> torch.Tensor:
         mvv = self._m[:, None] * v * v
@@ -322,7 +294,7 @@ class BatchedLangevin:
         """The normals of the components ``index`` (local to their systems ``system``) at the step counts of those systems."""
         seeds = np.array(self.seeds, dtype=np.uint64)[system]
         steps = self._nsteps_h.astype(np.uint64)[system]
-        return _normals_numpy(_philox_numpy_each(seeds, steps, index))
+        return _normals_numpy(_philox_numpy(seeds, steps, index))
 
     def _aten_step(self) -> None:
         mc, hdt = self._m[:, None], self._hdt_a
@@ -419,10 +391,7 @@ class BatchedLangevin:
                 "temperature": self._temperature_h.copy(), "friction": self._friction_h.copy(), "seeds": list(self.seeds)}
 
     def _load_common(self, state: Dict[str, object]) -> np.ndarray:
-        pos, vel = state["positions"], state["velocities"]
-        if tuple(pos.shape) != (self.num_atoms, 3) or tuple(vel.shape) != (self.num_atoms, 3):
-            raise ValueError(f"the state holds {tuple(pos.shape)} positions and {tuple(vel.shape)} velocities, this run has "
-                             f"{self.num_atoms} atoms")
+        pos, vel = state_arrays(state, self.num_atoms)
         if "friction" not in state or "seeds" not in state or len(state["seeds"]) != self.num_systems:
             raise ValueError(f"the state was not saved by a batched Langevin run of {self.num_systems} systems")
         nsteps = np.asarray(torch.as_tensor(state["nsteps"]).cpu().numpy(), dtype=np.int64).reshape(-1)
@@ -452,14 +421,7 @@ class BatchedLangevin:
         per-system energies.  A calculator that was given the atomic numbers itself is not given them again.  The driver reads
         forces and energies only: set ``calc.compute_stress = False`` first where the stress is not needed.  ``kwargs``: the
         constructor's (``velocities``, ``seed``, ``remove_drift``, ``backend``)."""
-        numbers = None if getattr(calc, "atomic_numbers_in_init", False) else atomic_numbers
-        state = SimpleNamespace(positions=None, row_vector_cell=cell, pbc=pbc, atomic_numbers=numbers, system_idx=system_idx)
-
-        def force_step(pos):
-            state.positions = pos
-            res = calc(state)
-            return {AtomicDataDict.FORCE_KEY: res["forces"], AtomicDataDict.TOTAL_ENERGY_KEY: res["energy"]}
-
+        force_step = torchsim_force_step(calc, cell, pbc, atomic_numbers, system_idx, with_stress=False)
         return cls(force_step, masses, timestep, temperature, friction, positions, system_idx, **kwargs)
 
 
@@ -495,11 +457,7 @@ class BatchedLangevinNPT(BatchedLangevin):
         if cell.device != device:
             raise ValueError(f"mixed devices: positions on {device}, cell on {cell.device}")
         self._cell = cell.detach().to(torch.float64).reshape(S, 3, 3).contiguous().clone()
-        host = self._cell.cpu().numpy()
-        for s in range(S):
-            scale = float(np.prod(np.linalg.norm(host[s], axis=1)))
-            if not np.isfinite(host[s]).all() or not abs(float(np.linalg.det(host[s]))) > 1e-12 * max(scale, 1e-300):
-                raise ValueError(f"cell of system {s} is singular: its lattice vectors do not span a volume")
+        check_cells(self._cell, single=False)
         self._stress: Optional[torch.Tensor] = None
         if self._hip:
             self._npt = torch.zeros(S, 8, dtype=torch.float64, device=device)  # nqa_md_npt_state[S]
@@ -549,24 +507,8 @@ class BatchedLangevinNPT(BatchedLangevin):
     def _evaluate(self) -> None:
         out = self.force_step(self._pos, self._cell)
         S = self.num_systems
-        stress = out.get(AtomicDataDict.STRESS_KEY) if hasattr(out, "get") else None
-        if stress is None:
-            raise ValueError(f"stress: force_step must return it ([{S}, 3, 3]) next to the forces for NPT")
-        stress = stress.detach()
-        if S == 1 and tuple(stress.shape) == (3, 3):
-            stress = stress.reshape(1, 3, 3)
-        if tuple(stress.shape) != (S, 3, 3) or stress.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"stress: force_step must return float32 or float64 [{S}, 3, 3], got {stress.dtype} "
-                             f"{tuple(stress.shape)}")
-        if stress.device != self.device:
-            raise ValueError(f"mixed devices: positions on {self.device}, stress on {stress.device}")
-        f = out[AtomicDataDict.FORCE_KEY].detach()
-        if tuple(f.shape) != (self.num_atoms, 3) or f.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"force_step must return float32 or float64 forces [{self.num_atoms}, 3], got {f.dtype} "
-                             f"{tuple(f.shape)}")
-        if f.device != self.device:
-            raise ValueError(f"mixed devices: positions on {self.device}, forces on {f.device}")
-        self._out, self._forces, self._stress = out, f.contiguous(), stress.contiguous()
+        self._stress = checked_stress(out, S, self.device, f"[{S}, 3, 3]", f"([{S}, 3, 3]) next to the forces for NPT")
+        self._out, self._forces = out, checked_forces(out, self.num_atoms, self.device)
 
     # ---- the two forms of a step --------------------------------------------------------------------------------------------
     def _launch(self, finish_only: bool, bath: bool = True) -> None:
@@ -586,18 +528,10 @@ class BatchedLangevinNPT(BatchedLangevin):
         xi = torch.from_numpy(self._aten_noise((3 * self._counts).astype(np.uint64), systems)).to(self.device)
         sig = self._stress.to(torch.float64)
         super()._aten_step()
-        ekin, cell = self._ekin, self._cell
-        vol = _det3(cell).abs()
-        three = torch.full_like(vol, 3.0)  # (tensor divisors: a true division on every device)
-        p = (2.0 * ekin) / (3.0 * vol) - (sig[:, 0, 0] + sig[:, 1, 1] + sig[:, 2, 2]) / three
-        a = self._a_t
-        d_eps = -a * (self._p0_t - p) + torch.sqrt((2.0 * self._kt_t * a) / vol) * xi
-        mu = torch.exp(d_eps / three)
-        bad = ~torch.isfinite(mu) | ~(vol > 0.0)
-        mu = torch.where(bad, torch.ones_like(mu), mu)
+        mu, p, bad = _aten_barostat(self._ekin, self._cell, sig, xi, self._a_t, self._p0_t, self._kt_t)
         self._failed = self._failed | bad
         mu_atom = mu[self._system_idx][:, None]
-        self._cell.copy_(mu[:, None, None] * cell)
+        self._cell.copy_(mu[:, None, None] * self._cell)
         self._pos.copy_(mu_atom * self._pos)
         self._vel.copy_(self._vel / mu_atom)
         self._mu, self._pressure = mu, p
@@ -688,15 +622,6 @@ class BatchedLangevinNPT(BatchedLangevin):
         ``row_vector_cell`` (the live cell buffer), ``pbc``, ``atomic_numbers`` and ``system_idx``, and returns its forces,
         per-system energies and stresses (ASE's sign, as ``CellFIRE.from_torchsim`` takes them).  ``calc.compute_stress`` is
         switched on."""
-        calc.compute_stress = True
-        numbers = None if getattr(calc, "atomic_numbers_in_init", False) else atomic_numbers
-        state = SimpleNamespace(positions=None, row_vector_cell=None, pbc=pbc, atomic_numbers=numbers, system_idx=system_idx)
-
-        def force_step(pos, cell_buffer):
-            state.positions, state.row_vector_cell = pos, cell_buffer
-            res = calc(state)
-            return {AtomicDataDict.FORCE_KEY: res["forces"], AtomicDataDict.TOTAL_ENERGY_KEY: res["energy"],
-                    AtomicDataDict.STRESS_KEY: res.get("stress")}
-
+        force_step = torchsim_force_step(calc, cell, pbc, atomic_numbers, system_idx, with_stress=True)
         return cls(force_step, masses, timestep, temperature, friction, pressure, compressibility, taup, positions, cell,
                    system_idx, **kwargs)

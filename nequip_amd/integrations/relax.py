@@ -33,13 +33,14 @@ subclass, the exponential cell filters.
 from __future__ import annotations
 
 import math
-from types import SimpleNamespace
 from typing import Callable, Dict, Optional
 
 import numpy as np
 import torch
 
 from ..data import AtomicDataDict
+from ._driver import (atoms_tensors, check_cells, checked_forces, checked_stress, padded, padded_layout, select_backend,
+                      state_arrays, torchsim_force_step)
 from .md import _cell_following_step, _DeviceMD, _graphed_step_for
 
 # the 8-byte words of nqa_fire_system (include/nequip_amd.h); word 11 is two 32-bit halves: nmin, converged
@@ -118,11 +119,7 @@ class FIRE:
         if isinstance(step_device, torch.device) and step_device != device:
             raise ValueError(f"mixed devices: positions on {device}, force_step on {step_device}")
         self._params = self._check_params(params)
-        if backend not in ("auto", "hip", "aten"):
-            raise ValueError(f"backend must be 'auto', 'hip' or 'aten', got {backend!r}")
-        if backend == "hip" and device.type != "cuda":
-            raise ValueError("backend='hip' needs device tensors: the kernels run on the GPU")
-        self._hip = backend == "hip" or (backend == "auto" and device.type == "cuda")
+        self._hip = select_backend(backend, device)
 
         # the systems: one host read, here (the chunk table is built once)
         if system_idx is None:
@@ -163,12 +160,7 @@ class FIRE:
             self._rec_i = self._rec.view(torch.int64)
             self._rec_h = self._rec.view(torch.int32)  # [S, 32]: nmin at 2 * 11, converged at 2 * 11 + 1
         else:
-            # atom (s, k) of the padded [S, max count] layout that the per-system sums are taken over
-            width = max(int(counts.max()), 1)
-            begin = np.concatenate([[0], np.cumsum(counts)])[:-1]
-            k = np.arange(width)[None, :]
-            self._pad_mask = torch.from_numpy(k < counts[:, None]).to(device)
-            self._pad_idx = torch.from_numpy(np.where(k < counts[:, None], begin[:, None] + k, 0)).to(device)
+            self._pad_mask, self._pad_idx = padded_layout(counts, device)  # (a system may have no atoms)
 
     # ---- state -------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -194,19 +186,25 @@ class FIRE:
         out["nmin"] = int(p["nmin"])
         return out
 
+    def _record(self, dt, a, npos, nsteps) -> torch.Tensor:
+        """The record of every system on the host, as wide as the device's: words 0 .. 15 (``nqa_fire_system``) filled with the
+        state given (``[S]`` each) and the parameters, the verdict cleared, zeros behind them."""
+        p = self._params
+        words = torch.zeros(self.num_systems, self._rec.shape[1], dtype=torch.float64)
+        words[:, _DT], words[:, _A] = dt.cpu().double(), a.cpu().double()
+        words.view(torch.int64)[:, _NPOS], words.view(torch.int64)[:, _NSTEPS] = npos.cpu().long(), nsteps.cpu().long()
+        for word, key in ((_DTMAX, "dtmax"), (_MAXSTEP, "maxstep"), (_FINC, "finc"), (_FDEC, "fdec"), (_ASTART, "astart"),
+                          (_FA, "fa")):
+            words[:, word] = p[key]
+        words[:, _TARGET] = self._fmax_target
+        words.view(torch.int32)[:, 2 * _NMIN_CONVERGED] = p["nmin"]
+        return words
+
     def _write_state(self, dt, a, npos, nsteps) -> None:
         """The whole record of every system: the state given (``[S]`` each), the parameters, the verdict cleared."""
-        S, p = self.num_systems, self._params
+        S = self.num_systems
         if self._hip:
-            words = torch.zeros(S, _WORDS, dtype=torch.float64)
-            words[:, _DT], words[:, _A] = dt.cpu().double(), a.cpu().double()
-            words.view(torch.int64)[:, _NPOS], words.view(torch.int64)[:, _NSTEPS] = npos.cpu().long(), nsteps.cpu().long()
-            for word, key in ((_DTMAX, "dtmax"), (_MAXSTEP, "maxstep"), (_FINC, "finc"), (_FDEC, "fdec"), (_ASTART, "astart"),
-                              (_FA, "fa")):
-                words[:, word] = p[key]
-            words[:, _TARGET] = self._fmax_target
-            words.view(torch.int32)[:, 2 * _NMIN_CONVERGED] = p["nmin"]
-            self._rec.copy_(words)
+            self._rec.copy_(self._record(dt, a, npos, nsteps))
         else:
             dev = self.device
             self._dt_s, self._a_s = dt.to(dev).double().clone(), a.to(dev).double().clone()
@@ -229,23 +227,13 @@ class FIRE:
 
     def _padded(self, per_atom: torch.Tensor) -> torch.Tensor:
         """``[S, max count]``: the values of every system's atoms in a row of their own, zeros behind them."""
-        zero = torch.zeros((), dtype=per_atom.dtype, device=per_atom.device)
-        return torch.where(self._pad_mask, per_atom[self._pad_idx], zero)
+        return padded(per_atom, self._pad_mask, self._pad_idx)
 
-    def _aten_step(self) -> None:
+    def _decide(self, P, FF, VV, M):
+        """The decision of every system from its four ``[S]`` sums: ``fmax`` and the verdict; for a system that has not
+        converged the FIRE branch, with ``dt``, ``a``, ``npos`` and ``nsteps`` updated.  Returns ``(active, cv, cf, dt, scale)``,
+        the coefficients of this step's move (``active``: not converged)."""
         p = self._params
-        f = self._forces.to(torch.float64)
-        v = self._vel
-        if self._fixed is not None:
-            f = torch.where(self._fixed.bool()[:, None], torch.zeros_like(f), f)
-        # reduce
-        fv, ff, vv = f * v, f * f, v * v
-        ff_atom = self._padded(ff[:, 0] + ff[:, 1] + ff[:, 2])
-        P = torch.sum(self._padded(fv[:, 0] + fv[:, 1] + fv[:, 2]), dim=1)
-        FF = torch.sum(ff_atom, dim=1)
-        VV = torch.sum(self._padded(vv[:, 0] + vv[:, 1] + vv[:, 2]), dim=1)
-        M = torch.amax(ff_atom, dim=1)
-        # decide
         dt, a, npos = self._dt_s, self._a_s, self._npos_s
         converged = M < self._fmax_target * self._fmax_target
         first = self._nsteps_s == 0
@@ -270,6 +258,21 @@ class FIRE:
         self._a_s = torch.where(active, a_new, a)
         self._npos_s = torch.where(active, npos_new, npos)
         self._nsteps_s = self._nsteps_s + active.to(torch.int64)
+        return active, cv, cf, dt_new, scale
+
+    def _aten_step(self) -> None:
+        f = self._forces.to(torch.float64)
+        v = self._vel
+        if self._fixed is not None:
+            f = torch.where(self._fixed.bool()[:, None], torch.zeros_like(f), f)
+        # reduce
+        fv, ff, vv = f * v, f * f, v * v
+        ff_atom = self._padded(ff[:, 0] + ff[:, 1] + ff[:, 2])
+        P = torch.sum(self._padded(fv[:, 0] + fv[:, 1] + fv[:, 2]), dim=1)
+        FF = torch.sum(ff_atom, dim=1)
+        VV = torch.sum(self._padded(vv[:, 0] + vv[:, 1] + vv[:, 2]), dim=1)
+        M = torch.amax(ff_atom, dim=1)
+        active, cv, cf, dt_new, scale = self._decide(P, FF, VV, M)
         # move
         s = self._system_idx
         moves = active[s]
@@ -379,10 +382,7 @@ class FIRE:
                 "fmax_target": self._fmax_target, "parameters": dict(self._params)}
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
-        pos, vel = state["positions"], state["velocities"]
-        if tuple(pos.shape) != (self.num_atoms, 3) or tuple(vel.shape) != (self.num_atoms, 3):
-            raise ValueError(f"the state holds {tuple(pos.shape)} positions and {tuple(vel.shape)} velocities, this run has "
-                             f"{self.num_atoms} atoms")
+        pos, vel = state_arrays(state, self.num_atoms)
         if "npos" not in state or tuple(state["dt"].shape) != (self.num_systems,):
             raise ValueError(f"the state was not saved by a FIRE run of {self.num_systems} systems")
         self._params = self._check_params(dict(state["parameters"]))
@@ -399,7 +399,7 @@ class FIRE:
         ``fixed``).  ``model_or_step``: an eval-mode model (a ``GraphedStep`` is built around it, which needs a periodic cell and
         ``r_max``) or a ready ``force_step``.  ``chemical_symbols``: as for ``NequIPCalculator``.  ``kwargs``: the constructor's."""
         device = torch.device(device)
-        pos = torch.as_tensor(np.asarray(atoms.get_positions(), dtype=np.float64)).to(device)
+        pos = atoms_tensors(atoms, device, "positions")
         step = model_or_step
         if isinstance(model_or_step, torch.nn.Module):
             step = _graphed_step_for(atoms, model_or_step, device, r_max, chemical_symbols)
@@ -415,14 +415,7 @@ class FIRE:
         ``row_vector_cell`` (``cell``, ``[S, 3, 3]``), ``pbc``, ``atomic_numbers`` and ``system_idx``, and returns its forces and
         per-system energies.  A calculator that was given the atomic numbers itself is not given them again.  The optimizer
         reads forces and energies only: set ``calc.compute_stress = False`` first where the stress is not needed."""
-        numbers = None if getattr(calc, "atomic_numbers_in_init", False) else atomic_numbers
-        state = SimpleNamespace(positions=None, row_vector_cell=cell, pbc=pbc, atomic_numbers=numbers, system_idx=system_idx)
-
-        def force_step(pos):
-            state.positions = pos
-            res = calc(state)
-            return {AtomicDataDict.FORCE_KEY: res["forces"], AtomicDataDict.TOTAL_ENERGY_KEY: res["energy"]}
-
+        force_step = torchsim_force_step(calc, cell, pbc, atomic_numbers, system_idx, with_stress=False)
         return cls(force_step, positions, system_idx=system_idx, **kwargs)
 
 
@@ -514,11 +507,7 @@ class CellFIRE(FIRE):
         if cell.device != device:
             raise ValueError(f"mixed devices: positions on {device}, cell on {cell.device}")
         c0 = cell.detach().to(torch.float64).reshape(-1, 3, 3).expand(S, 3, 3).contiguous().clone()
-        c0_host = c0.cpu().numpy()
-        for s in range(S):
-            scale = float(np.prod(np.linalg.norm(c0_host[s], axis=1)))
-            if not np.isfinite(c0_host[s]).all() or not abs(float(np.linalg.det(c0_host[s]))) > 1e-12 * max(scale, 1e-300):
-                raise ValueError(f"cell of system {s} is singular: its lattice vectors do not span a volume")
+        check_cells(c0, single=False)
         if cell_factor is None:
             factor = torch.from_numpy(self._counts.astype(np.float64))
         else:
@@ -557,16 +546,9 @@ class CellFIRE(FIRE):
     def _write_state(self, dt, a, npos, nsteps, d_old=None, d_new=None, vd=None) -> None:
         """The whole record of every system: the FIRE state, ``D`` and ``vD`` (``[S, 3, 3]``), the parameters, the verdict
         cleared."""
-        S, p, c = self.num_systems, self._params, self._cell_params
+        S, c = self.num_systems, self._cell_params
         if self._hip:
-            words = torch.zeros(S, _CELL_WORDS, dtype=torch.float64)
-            words[:, _DT], words[:, _A] = dt.cpu().double(), a.cpu().double()
-            words.view(torch.int64)[:, _NPOS], words.view(torch.int64)[:, _NSTEPS] = npos.cpu().long(), nsteps.cpu().long()
-            for word, key in ((_DTMAX, "dtmax"), (_MAXSTEP, "maxstep"), (_FINC, "finc"), (_FDEC, "fdec"), (_ASTART, "astart"),
-                              (_FA, "fa")):
-                words[:, word] = p[key]
-            words[:, _TARGET] = self._fmax_target
-            words.view(torch.int32)[:, 2 * _NMIN_CONVERGED] = p["nmin"]
+            words = self._record(dt, a, npos, nsteps)
             words[:, _CELL_FACTOR] = c["cell_factor"]
             words[:, _PRESSURE] = c["scalar_pressure"]
             words.view(torch.int32)[:, 2 * _HYDROSTATIC_CONSTVOL] = int(c["hydrostatic_strain"])
@@ -586,25 +568,9 @@ class CellFIRE(FIRE):
 
     def _evaluate(self) -> None:
         out = self.force_step(self._pos, self._cell)
-        S = self.num_systems
-        stress = out.get(AtomicDataDict.STRESS_KEY) if hasattr(out, "get") else None
-        if stress is None:
-            raise ValueError("stress: force_step must return it ([S, 3, 3]) next to the forces for a variable-cell relaxation")
-        stress = stress.detach()
-        if S == 1 and tuple(stress.shape) == (3, 3):
-            stress = stress.reshape(1, 3, 3)
-        if tuple(stress.shape) != (S, 3, 3) or stress.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"stress: force_step must return float32 or float64 [{S}, 3, 3], got {stress.dtype} "
-                             f"{tuple(stress.shape)}")
-        if stress.device != self.device:
-            raise ValueError(f"mixed devices: positions on {self.device}, stress on {stress.device}")
-        f = out[AtomicDataDict.FORCE_KEY].detach()
-        if tuple(f.shape) != (self.num_atoms, 3) or f.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"force_step must return float32 or float64 forces [{self.num_atoms}, 3], got {f.dtype} "
-                             f"{tuple(f.shape)}")
-        if f.device != self.device:
-            raise ValueError(f"mixed devices: positions on {self.device}, forces on {f.device}")
-        self._out, self._forces, self._stress = out, f.contiguous(), stress.contiguous()
+        self._stress = checked_stress(out, self.num_systems, self.device, f"[{self.num_systems}, 3, 3]",
+                                      "([S, 3, 3]) next to the forces for a variable-cell relaxation")
+        self._out, self._forces = out, checked_forces(out, self.num_atoms, self.device)
 
     # ---- the two forms of a step --------------------------------------------------------------------------------------------
     def _launch(self) -> None:
@@ -639,7 +605,6 @@ class CellFIRE(FIRE):
         return G / c["cell_factor"].to(dev)[:, None, None]
 
     def _aten_step(self) -> None:
-        p = self._params
         s = self._system_idx
         f = self._forces.to(torch.float64)
         v, D, vd = self._vel, self._d_s, self._vd_s
@@ -659,30 +624,7 @@ class CellFIRE(FIRE):
         FF = FF + (G * G).reshape(-1, 9).sum(1)
         VV = VV + (vd * vd).reshape(-1, 9).sum(1)
         M = torch.maximum(M, torch.amax((G * G).sum(2), dim=1))  # (both keep a NaN)
-        dt, a, npos = self._dt_s, self._a_s, self._npos_s
-        converged = M < self._fmax_target * self._fmax_target
-        first = self._nsteps_s == 0
-        up = (P > 0.0) & ~first
-        down = ~up & ~first
-        grow = up & (npos > p["nmin"])
-        zero, one = torch.zeros_like(dt), torch.ones_like(dt)
-        cv = torch.where(up, 1.0 - a, zero)
-        cf = torch.where(up, a * torch.sqrt(VV) / torch.sqrt(FF), zero)
-        grown = dt * p["finc"]
-        dt_new = torch.where(grow, torch.where(grown < p["dtmax"], grown, torch.full_like(dt, p["dtmax"])),
-                             torch.where(down, dt * p["fdec"], dt))
-        a_new = torch.where(grow, a * p["fa"], torch.where(down, torch.full_like(a, p["astart"]), a))
-        npos_new = torch.where(up, npos + 1, torch.where(down, torch.zeros_like(npos), npos))
-        c = cf + dt_new
-        vvn = cv * cv * VV + 2.0 * cv * c * P + c * c * FF
-        normdr = dt_new * torch.sqrt(vvn)
-        scale = torch.where(normdr > p["maxstep"], p["maxstep"] / normdr, one)
-        active = ~converged
-        self._fmax_s, self._converged_s = torch.sqrt(M), converged
-        self._dt_s = torch.where(active, dt_new, dt)
-        self._a_s = torch.where(active, a_new, a)
-        self._npos_s = torch.where(active, npos_new, npos)
-        self._nsteps_s = self._nsteps_s + active.to(torch.int64)
+        active, cv, cf, dt_new, scale = self._decide(P, FF, VV, M)
         # the cell move
         m3 = lambda t: t[:, None, None]  # noqa: E731
         factor = m3(self._cell_params["cell_factor"].to(self.device))
@@ -748,10 +690,7 @@ class CellFIRE(FIRE):
         return state
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
-        pos, vel = state["positions"], state["velocities"]
-        if tuple(pos.shape) != (self.num_atoms, 3) or tuple(vel.shape) != (self.num_atoms, 3):
-            raise ValueError(f"the state holds {tuple(pos.shape)} positions and {tuple(vel.shape)} velocities, this run has "
-                             f"{self.num_atoms} atoms")
+        pos, vel = state_arrays(state, self.num_atoms)
         if "vD" not in state or "npos" not in state or tuple(state["dt"].shape) != (self.num_systems,):
             raise ValueError(f"the state was not saved by a CellFIRE run of {self.num_systems} systems")
         self._params = self._check_params(dict(state["parameters"]))
@@ -772,8 +711,7 @@ class CellFIRE(FIRE):
         ``fixed``).  ``model_or_step``: an eval-mode model (a ``GraphedStep`` with energy, forces and stress is built around
         it, which needs ``r_max`` and all three directions periodic) or a ready ``force_step``.  ``kwargs``: the constructor's."""
         device = torch.device(device)
-        pos = torch.as_tensor(np.asarray(atoms.get_positions(), dtype=np.float64)).to(device)
-        cell = torch.as_tensor(np.asarray(atoms.get_cell(), dtype=np.float64).reshape(3, 3)).to(device)
+        pos, cell = atoms_tensors(atoms, device, "positions", "cell")
         step = model_or_step
         if isinstance(model_or_step, torch.nn.Module):
             if not all(bool(b) for b in np.asarray(atoms.get_pbc(), dtype=bool).reshape(3)):
@@ -793,14 +731,5 @@ class CellFIRE(FIRE):
         """The optimizer of a batch around a ``NequIPTorchSimCalc``: ``force_step`` hands ``calc`` a state with ``positions``,
         ``row_vector_cell`` (the live cell buffer), ``pbc``, ``atomic_numbers`` and ``system_idx``, and returns its forces,
         per-system energies and stresses.  ``calc.compute_stress`` is switched on."""
-        calc.compute_stress = True
-        numbers = None if getattr(calc, "atomic_numbers_in_init", False) else atomic_numbers
-        state = SimpleNamespace(positions=None, row_vector_cell=None, pbc=pbc, atomic_numbers=numbers, system_idx=system_idx)
-
-        def force_step(pos, cell_buffer):
-            state.positions, state.row_vector_cell = pos, cell_buffer
-            res = calc(state)
-            return {AtomicDataDict.FORCE_KEY: res["forces"], AtomicDataDict.TOTAL_ENERGY_KEY: res["energy"],
-                    AtomicDataDict.STRESS_KEY: res.get("stress")}
-
+        force_step = torchsim_force_step(calc, cell, pbc, atomic_numbers, system_idx, with_stress=True)
         return cls(force_step, positions, cell, system_idx=system_idx, **kwargs)

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import cell_fire_restatement as R
-from nequip_amd.integrations import CellFIRE
+from nequip_amd.integrations import FIRE, CellFIRE
 from nequip_amd.integrations import relax as relax_module
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -241,6 +241,46 @@ def test_state_dict_round_trip_continues_bit_for_bit():
         assert torch.equal(getattr(second, name), getattr(whole, name)), name
     with pytest.raises(ValueError, match="atoms"):
         make([R.site_system(5, seed=5)])[0].load_state_dict(state)
+
+
+FROZEN_SIZES = (1, 40, 7, 257)  # 257: one atom past a chunk of NQA_FIRE_CHUNK = 256, so a system with two rows to merge
+
+
+def frozen_cell_pair(device, fdtype, backend):
+    """``(CellFIRE, FIRE, C0)`` over one batch of ``FROZEN_SIZES`` atoms with every fifth atom from atom 2 fixed: ``CellFIRE``
+    with ``mask = 0``, ``FIRE`` around the same potential evaluated at the constant initial cells ``C0``."""
+    parts = [R.site_system(n, seed=n) for n in FROZEN_SIZES]
+    c = R.concatenated(parts)
+    on = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+    step = R.torch_force_step(parts, device, fdtype)
+    fixed = np.zeros(len(c["x"]), dtype=bool)
+    fixed[2::5] = True
+    c0 = on(c["c0"])
+    cell_fire = CellFIRE(step, on(c["x"]), c0, system_idx=on(c["sidx"]), fixed=on(fixed), mask=torch.zeros(3, 3), backend=backend)
+    fire = FIRE(lambda pos: step(pos, c0), on(c["x"]), system_idx=on(c["sidx"]), fixed=on(fixed), backend=backend)
+    return cell_fire, fire, c0
+
+
+def assert_frozen_cell_is_fire(cell_fire, fire, c0, steps=40):
+    """``steps`` steps of both towards ``fmax = 1e-9`` (nothing converges except by the dynamics), then the whole FIRE state bit
+    for bit and the cell where it was."""
+    for drv in (cell_fire, fire):
+        drv._set_target(1e-9)
+        for _ in range(steps):
+            drv.step()
+    assert fire.nsteps.tolist() == [steps] * len(FROZEN_SIZES) and bool((fire.dt != 0.1).all())  # (every system took branches)
+    for name in ("positions", "velocities", "dt", "a", "fmax", "nsteps", "_npos"):
+        assert torch.equal(getattr(cell_fire, name), getattr(fire, name)), name
+    assert torch.equal(cell_fire.cell, c0)
+
+
+@pytest.mark.parametrize("fname, fdtype", [("f32", torch.float32), ("f64", torch.float64)])
+def test_cell_fire_with_a_frozen_cell_is_fire_bit_for_bit(fname, fdtype):
+    """With ``mask = 0`` the cell's force is ``G = +-0``: ``D`` stays the identity, ``g = F I = F`` and ``x = q I = q`` exactly,
+    and the cell's rows add ``+-0`` to ``P, FF, VV`` and 0 to the max.  What is left is the decision both optimizers share."""
+    cell_fire, fire, c0 = frozen_cell_pair("cpu", fdtype, "aten")
+    assert not cell_fire._hip and not fire._hip
+    assert_frozen_cell_is_fire(cell_fire, fire, c0)
 
 
 def test_a_nan_stress_is_reported():

@@ -15,6 +15,7 @@ import torch
 
 import cell_fire_restatement as R
 from nequip_amd.integrations import CellFIRE
+from test_cell_fire import assert_frozen_cell_is_fire, frozen_cell_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -129,6 +130,15 @@ def test_seventy_small_systems_match_the_restatement(device):
         drv.step()
     R.assert_close(drv, _run(refs, 24), "70 systems after 25 steps")
     assert drv.nsteps.tolist() == [25] * 70
+
+
+@pytest.mark.parametrize("fname", sorted(DTYPES))
+def test_cell_fire_with_a_frozen_cell_is_fire_bit_for_bit(device, fname):
+    """The kernels of relax_cell.hip against those of relax.hip (the argument is that of the ATen form in test_cell_fire.py): with
+    ``mask = 0`` only the decision both files call is left, over systems of 1, 40, 7 and 257 atoms (two rows to merge)."""
+    cell_fire, fire, c0 = frozen_cell_pair(device, DTYPES[fname], "hip")
+    assert cell_fire._hip and fire._hip and fire._n_chunks == cell_fire._n_chunks == 5
+    assert_frozen_cell_is_fire(cell_fire, fire, c0)
 
 
 def test_fixed_atoms_on_the_kernel_path(device):
